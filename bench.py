@@ -9,6 +9,10 @@ A step = one training step of the reference's hot loop (trainer/trainer.py:34-38
 synthetic frames already resident in HBM: zero_grad, forward, smooth-L1 loss, backward (with the
 bucketed RCCL gradient all-reduce when N>1), Adam step.  Metric: 16384-sample frames per second,
 whole job.  Prints ONE JSON line on rank 0.
+
+A plain run measures the headline only: set-up, --warmup steps, --steps timed steps, the result line.  --full adds everything
+else (per-step event timings, gradient-exchange record, per-kernel roofline, the extras, the CPU baseline); --dump-outputs DIR
+writes what the last timed step computed as .npy files, for comparing two builds output for output.
 """
 import argparse
 import ctypes
@@ -242,6 +246,36 @@ def synthetic_batch(batch, device, seed, frame=FRAME):
     return noisy.to(device), clean.to(device)
 
 
+DUMP_CAPS = {"output": 1 << 22, "parameters": 10 << 20, "gradients": 1 << 20, "buffers": 1 << 16}      # float32 elements: < 64 MB together
+
+
+def _flat_sample(tensors, cap, seed):
+    """The tensors flattened and concatenated in order, as float32 on the host; above `cap` elements a fixed, seeded sample of `cap` of
+    them (ascending positions), so that two builds given the same arguments write the same positions."""
+    import numpy as np
+    a = torch.cat([t.detach().reshape(-1).float() for t in tensors]).cpu().numpy()
+    if a.size > cap:
+        a = a[np.sort(np.random.default_rng(seed).choice(a.size, cap, replace=False))]
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def dump_outputs(path, out, loss, model, mode):
+    """--dump-outputs: what the last timed step handed its caller.  forward: the output.  train: the output, the loss, the parameters
+    after the optimiser step, the step's gradients and the BatchNorm running statistics (named_parameters / named_buffers order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"output": _flat_sample([out], DUMP_CAPS["output"], 1).reshape(out.shape) if out.numel() <= DUMP_CAPS["output"]
+              else _flat_sample([out], DUMP_CAPS["output"], 1)}
+    if mode == "train":
+        params = [p for _, p in model.named_parameters()]
+        arrays["loss"] = np.array(float(loss.item()), np.float64)
+        arrays["parameters"] = _flat_sample(params, DUMP_CAPS["parameters"], 2)
+        arrays["gradients"] = _flat_sample([p.grad if p.grad is not None else torch.zeros_like(p) for p in params], DUMP_CAPS["gradients"], 3)
+        arrays["buffers"] = _flat_sample([b for _, b in model.named_buffers()], DUMP_CAPS["buffers"], 4)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def cpu_model_string():
     try:
         for line in open("/proc/cpuinfo"):
@@ -374,10 +408,20 @@ def main():
                          "backward's streams, capturable with --graph on) instead of torch.distributed's process group; at --gpus 1 the "
                          "bucketed collectives are issued anyway (world size 1), so their cost inside the step can be measured on one GPU")
     ap.add_argument("--seed", type=int, default=0, help="extra measurements only: seed of the initial weights and of the synthetic batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the exact-fp32 and eval-forward side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, everything else this file measures: the per-step event-timed pass, the gradient-exchange "
+                         "record, the per-kernel roofline, the extras (200-step window, eval forward, exact fp32, deep16 bf16) and the CPU "
+                         "baseline.  Off by default: a plain run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, < 64 MB "
+                         "in all; arrays above their cap are a fixed, seeded sample): output, loss, parameters after the optimiser "
+                         "step, gradients, BatchNorm buffers (train); output (forward)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the per-kernel roofline passes")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the exact-fp32 and eval-forward side measurements")
     args = ap.parse_args()
+    if not args.full:
+        args.no_roofline = args.no_extras = args.no_cpu_baseline = True
     # the contract: rank 0 prints ONE JSON line.  Libraries write to the C-level stdout behind Python's back (RCCL prints a version
     # banner when a communicator is created): everything but the result line goes to stderr
     sys.stdout.flush()
@@ -445,13 +489,19 @@ def main():
 
     if args.mode == "forward":
         model.eval()
+    last = {} if args.dump_outputs else None       # --dump-outputs: the last eager step's output, detached
 
     def step():
         if args.mode == "forward":
             with torch.no_grad():
-                return model(noisy).sum()
+                out = model(noisy)
+                if last is not None:
+                    last["out"] = out
+                return out.sum()
         opt.zero_grad(set_to_none=True)
         out = model(noisy)
+        if last is not None:
+            last["out"] = out.detach()           # (no reference to the autograd graph: a graph kept alive breaks the capture below)
         loss = crit(clean, out)
         loss.backward()
         opt.step()
@@ -507,6 +557,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        # before anything else runs a step: the state the last timed step left (a graph replay writes its static tensors)
+        dump_outputs(args.dump_outputs, out_g if use_graph else last["out"], loss, model, args.mode)
     if os.environ.get("WUNET_STAMP") and not emu and args.mode == "train":
         # measurement hook (csrc/wunet_backward.cpp, WUNET_STAMP): when the backward's two chains ran inside the LAST step above - device wall clock,
         # 100 MHz - written to stderr, layer by layer in backward order: start of the data gradient, start of the weight gradient, relative to the first stamp
@@ -523,7 +576,7 @@ def main():
     # a second pass of the same K steps timed one by one with device events: the median is robust against a clock ramp or a
     # hiccup inside the short timed region above (which stays the headline, as the contract defines it)
     step_ms = []
-    for _ in range(0 if (os.environ.get("WUNET_BENCH_NO_MEDIAN") or emu) else args.steps):      # (switch: the PMC passes count launches per step)
+    for _ in range(0 if (not args.full or os.environ.get("WUNET_BENCH_NO_MEDIAN") or emu) else args.steps):      # (switch: the PMC passes count launches per step)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         step()
@@ -540,7 +593,7 @@ def main():
     # around the join of a few extra steps), the buckets, the world size the transport reports
     exchange = None
     sync = getattr(model, "grad_sync", None)
-    if sync is not None and args.mode == "train":
+    if sync is not None and args.mode == "train" and args.full:
         sync.measure = True
         for _ in range(1 if emu else 5):
             eager_step()

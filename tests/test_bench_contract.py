@@ -90,7 +90,7 @@ def test_bench_multi_rank_branches_run_on_gloo_and_the_emulator(tmp_path, world)
     env = dict(os.environ, WUNET_BENCH_EMU="1", OMP_NUM_THREADS="1" if world > 2 else "2")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-                        "--layers", "3", "--frame", "256", "--batch", "2"], env=env, capture_output=True, text=True, timeout=1200)
+                        "--layers", "3", "--frame", "256", "--batch", "2", "--full"], env=env, capture_output=True, text=True, timeout=1200)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]                         # rank 0 prints ONE line
@@ -117,3 +117,95 @@ def test_bench_multi_rank_branches_run_on_gloo_and_the_emulator(tmp_path, world)
     numels += [25, 1]
     rs = parallel.bucket_ranges(numels, 25, 4)
     assert len(rs) == 4 and abs(sum(4 * (fe - fb) for _, _, fb, fe in rs) / 1e6 - 40.53) < 0.01
+
+
+# ---- a plain run against --full, and --dump-outputs (bench.py's result line and .npy files)
+def _run_bench(args, env=None, timeout=600):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=timeout)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def _load_dump(d):
+    import numpy as np
+    files = sorted(os.listdir(d))
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) < 64e6
+    out = {f[:-4]: np.load(os.path.join(d, f), allow_pickle=False) for f in files}
+    assert all(f.endswith(".npy") for f in files) and all(a.dtype in (np.float32, np.float64) for a in out.values())
+    return out
+
+
+def _assert_plain(j, steps):
+    assert j["steps"] == steps and j["ms_per_step"] > 0 and j["value"] > 0 and j["higher_is_better"] is True
+    for k in ("roofline", "cpu_baseline", "extras", "gradient_exchange", "ms_per_step_median"):
+        assert j[k] is None, k                    # a plain run measures the headline only; the rest is --full's
+
+
+def test_dump_caps_stay_under_64_mb_and_sample_fixed_positions():
+    import numpy as np
+    import torch
+    assert 4 * sum(bench.DUMP_CAPS.values()) + 1024 < 64e6
+    t = [torch.arange(1000, dtype=torch.float32), torch.arange(1000, 1500, dtype=torch.float64)]      # value == flat position
+    a, b = bench._flat_sample(t, 100, 7), bench._flat_sample(t, 100, 7)
+    assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b) and np.all(np.diff(a) > 0)
+    assert not np.array_equal(a, bench._flat_sample(t, 100, 8))
+    assert np.array_equal(bench._flat_sample(t, 1500, 7), np.arange(1500, dtype=np.float32))
+
+
+def test_plain_run_and_dump_outputs_on_the_emulator(tmp_path):
+    """WUNET_BENCH_EMU (CPU emulator, eager steps): a plain run's line carries the headline only, and two runs with the same arguments
+    write the same files - output, loss, parameters after the step, gradients, BatchNorm buffers - in float32 / float64, < 64 MB."""
+    import importlib
+    from conftest import PKG_NAME
+    env = dict(os.environ, WUNET_BENCH_EMU="1", OMP_NUM_THREADS="2")
+    args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--layers", "3", "--frame", "256", "--batch", "2"]
+    runs = []
+    for d in ("a", "b"):
+        j = _run_bench(args + ["--dump-outputs", str(tmp_path / d)], env)
+        _assert_plain(j, 2)
+        runs.append(_load_dump(tmp_path / d))
+    a, b = runs
+    assert sorted(a) == ["buffers", "gradients", "loss", "output", "parameters"]
+    for k in a:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k
+    plan = importlib.import_module(PKG_NAME + ".plan")
+    numel = sum(co * ci_ * k + 3 * co for ci_, co, k in plan.conv_layer_shapes(3, 24)) + 24 + 1 + 1
+    assert a["output"].shape == (2, 1, 256) and a["loss"].shape == () and a["parameters"].shape == a["gradients"].shape == (numel,)
+    assert float(a["loss"]) == j["final_loss"]
+
+
+def test_plain_multi_rank_run_leaves_the_exchange_record_to_full():
+    """The same torchrun as test_bench_multi_rank_branches_run_on_gloo_and_the_emulator without --full: no gradient_exchange pass."""
+    import socket
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ, WUNET_BENCH_EMU="1", OMP_NUM_THREADS="2")
+    p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
+                        "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--layers", "3", "--frame", "256", "--batch", "2"], env=env, capture_output=True, text=True, timeout=1200)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    j = json.loads(lines[0])
+    assert j["n_gpus"] == 2
+    _assert_plain(j, 2)
+
+
+@pytest.mark.gpu
+def test_plain_run_and_dump_outputs_on_the_gpu(tmp_path):
+    """The headline path on the MI355X (one captured hipGraph per step): a plain run's line carries the headline only, and two runs
+    with the same arguments write bit-identical files within the 64 MB budget."""
+    runs = []
+    for d in ("a", "b"):
+        j = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / d)], timeout=300)
+        _assert_plain(j, 3)
+        assert j["step_launch"] == "one hipGraph replay per step"
+        runs.append(_load_dump(tmp_path / d))
+    a, b = runs
+    assert sorted(a) == ["buffers", "gradients", "loss", "output", "parameters"]
+    assert a["output"].shape == (64, 1, 16384) and a["parameters"].shape == (10132802,) and a["gradients"].shape == (1 << 20,)
+    for k in a:
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes(), k

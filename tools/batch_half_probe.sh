@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd /tmp; export TMPDIR=/tmp
 for b in 64 32; do
   rm -rf /tmp/bh_$b
-  WUNET_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/bh_$b -o s -- python $R/bench.py --batch $b --no-cpu-baseline --no-extras --no-roofline --steps 40 --warmup 10 > /tmp/bh_$b.json 2>/dev/null
+  WUNET_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/bh_$b -o s -- python $R/bench.py --full --batch $b --no-cpu-baseline --no-extras --no-roofline --steps 40 --warmup 10 > $TMPDIR/bh_$b.json 2>/dev/null
 done
 python - <<'PY'
 import csv, glob, json

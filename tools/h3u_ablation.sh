@@ -27,7 +27,7 @@ fi
 mkdir -p gpurun_out
 for a in 0 $VARIANTS; do
     if [ $a = 0 ]; then unset WUNET_LIB_PATH; else export WUNET_LIB_PATH=$PWD/tools/_lib_u$a.so; fi
-    WUNET_H3U=${H3U:-4096,0} python bench.py --mode forward --no-cpu-baseline --no-extras --steps 20 --warmup 5 2>/dev/null | python -c "
+    WUNET_H3U=${H3U:-4096,0} python bench.py --full --mode forward --no-cpu-baseline --no-extras --steps 20 --warmup 5 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j['roofline']
 print('abl %3d' % $a, ' '.join('%s %.1f us x%g' % (t['kernel'][5:], 1e3*t['ms_per_step']/t['launches_per_step'], t['launches_per_step']) for t in r['top5'] if 'h3u' in t['kernel']))

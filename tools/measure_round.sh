@@ -20,7 +20,7 @@ pmc_pass() {   # <name> <bench args...>: FETCH_SIZE and WRITE_SIZE passes of 3 s
     local name=$1; shift
     for ctr in FETCH_SIZE WRITE_SIZE; do
         WUNET_BENCH_NO_MEDIAN=1 timeout 400 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $O/pmc_${name}_$ctr -o p -- \
-            python $R/bench.py --steps 2 --warmup 1 --graph off --no-cpu-baseline --no-roofline --no-extras "$@" > /dev/null 2>&1
+            python $R/bench.py --full --steps 2 --warmup 1 --graph off --no-cpu-baseline --no-roofline --no-extras "$@" > /dev/null 2>&1
     done
     python - <<PY
 import collections, csv, glob, json
@@ -49,28 +49,28 @@ cd $R; python tools/collect_round.py $TAG --pmc-only
 cd /tmp
 WUNET_NO_SIDE_STREAM=1 WUNET_BENCH_NO_MEDIAN=1 timeout 400 rocprofv3 --kernel-trace \
     --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_MFMA_MOPS_F16 \
-    --output-format csv -d $O/pmc_sq -o s -- python $R/bench.py --steps 2 --warmup 1 --graph off --no-cpu-baseline --no-roofline --no-extras > /dev/null 2>&1
+    --output-format csv -d $O/pmc_sq -o s -- python $R/bench.py --full --steps 2 --warmup 1 --graph off --no-cpu-baseline --no-roofline --no-extras > /dev/null 2>&1
 WUNET_NO_SIDE_STREAM=1 WUNET_BENCH_NO_MEDIAN=1 timeout 400 rocprofv3 --kernel-trace \
     --pmc GRBM_GUI_ACTIVE GRBM_COUNT SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_SALU \
-    --output-format csv -d $O/pmc_grbm -o g -- python $R/bench.py --steps 2 --warmup 1 --graph off --no-cpu-baseline --no-roofline --no-extras > /dev/null 2>&1
+    --output-format csv -d $O/pmc_grbm -o g -- python $R/bench.py --full --steps 2 --warmup 1 --graph off --no-cpu-baseline --no-roofline --no-extras > /dev/null 2>&1
 python $R/tools/pmc_sq.py $O/pmc_sq $O/pmc_grbm > $O/pmc_sq.txt 2> $O/pmc_sq.err
 rm -rf $O/pmc_sq $O/pmc_grbm
 cd $R
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json; echo
-WUNET_BENCH_ALL=1 timeout 200 python bench.py --no-cpu-baseline --no-extras > $O/bench_all_kernels.json 2>/dev/null
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json; echo
+WUNET_BENCH_ALL=1 timeout 200 python bench.py --full --no-cpu-baseline --no-extras > $O/bench_all_kernels.json 2>/dev/null
 python tools/traffic_table.py $O/bench_all_kernels.json > $O/traffic_by_family.txt 2>&1
-timeout 200 python bench.py --gemm bf16 --no-cpu-baseline --no-extras > $O/bench_bf16.json 2>/dev/null
+timeout 200 python bench.py --full --gemm bf16 --no-cpu-baseline --no-extras > $O/bench_bf16.json 2>/dev/null
 # the collectives' cost inside the step on one GPU (world size 1 through the library's RCCL entry), eager and as one captured graph
-timeout 200 python bench.py --native-rccl --graph off --no-cpu-baseline --no-extras --no-roofline > $O/bench_native_rccl_eager.json 2>/dev/null
-timeout 200 python bench.py --native-rccl --graph on --no-cpu-baseline --no-extras --no-roofline > $O/bench_native_rccl_graph.json 2>/dev/null
-timeout 200 python bench.py --graph on --no-cpu-baseline --no-extras --no-roofline --steps 100 > $O/bench_graph.json 2>/dev/null
-timeout 200 python bench.py --graph off --no-cpu-baseline --no-extras --no-roofline --steps 100 > $O/bench_eager.json 2>/dev/null
+timeout 200 python bench.py --full --native-rccl --graph off --no-cpu-baseline --no-extras --no-roofline > $O/bench_native_rccl_eager.json 2>/dev/null
+timeout 200 python bench.py --full --native-rccl --graph on --no-cpu-baseline --no-extras --no-roofline > $O/bench_native_rccl_graph.json 2>/dev/null
+timeout 200 python bench.py --full --graph on --no-cpu-baseline --no-extras --no-roofline --steps 100 > $O/bench_graph.json 2>/dev/null
+timeout 200 python bench.py --full --graph off --no-cpu-baseline --no-extras --no-roofline --steps 100 > $O/bench_eager.json 2>/dev/null
 # (the training soak - three seeds, 100 / 300 / 600 steps, split against exact fp32 and the summation-order control - is profiles/r3_training_soak.txt,
 #  measured by its own calls: bench.py --seed S --steps N --warmup 0 [--gemm fp32] with WUNET_BENCH_NO_MEDIAN=1)
 cd /tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/conc -o conc -- python $R/bench.py --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2>/dev/null
-WUNET_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -o serial -- python $R/bench.py --no-cpu-baseline --no-extras > $O/serial_bench.json 2>/dev/null
-WUNET_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fwd -o fwd -- python $R/bench.py --mode forward --no-cpu-baseline --no-roofline > $O/forward_bench.json 2>/dev/null
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/conc -o conc -- python $R/bench.py --full --no-cpu-baseline --no-extras > $O/bench_under_rocprof.json 2>/dev/null
+WUNET_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/serial -o serial -- python $R/bench.py --full --no-cpu-baseline --no-extras > $O/serial_bench.json 2>/dev/null
+WUNET_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/fwd -o fwd -- python $R/bench.py --full --mode forward --no-cpu-baseline --no-roofline > $O/forward_bench.json 2>/dev/null
 # keep what collect_round.py needs, drop the bulky traces
 for d in conc serial fwd; do f=$(find $O/$d -name "${d}_kernel_stats.csv" | head -1); cp $f $O/${d}_kernel_stats.csv; g=$(find $O/$d -name "${d}_kernel_trace.csv" | head -1); [ "$d" = serial ] && cp $g $O/serial_kernel_trace.csv; rm -rf $O/$d; done
 python $R/tools/timeline.py $O/serial_kernel_trace.csv > $O/step_timeline.txt 2>/dev/null
@@ -91,7 +91,7 @@ fi
 timeout 300 bash tools/upt_ab.sh > $O/upt_ab.txt 2>&1
 timeout 300 bash tools/env_ab.sh WUNET_WGRAD_XCD 0 > $O/wgrad_xcd_ab.txt 2>&1
 [ -n "$H3U_SET" ] && { for rep in 1 2; do for v in "" 1; do if [ -z "$v" ]; then unset WUNET_NO_EVOP; else export WUNET_NO_EVOP=1; fi
-    python bench.py --mode forward --no-cpu-baseline --no-extras --no-roofline --steps 50 --warmup 10 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('WUNET_NO_EVOP=$v eval forward ms %.4f median %.4f' % (j['ms_per_step'], j['ms_per_step_median']))"; done; done; unset WUNET_NO_EVOP; } > $O/evop_ab.txt 2>&1
+    python bench.py --full --mode forward --no-cpu-baseline --no-extras --no-roofline --steps 50 --warmup 10 2>/dev/null | python -c "import json,sys; j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('WUNET_NO_EVOP=$v eval forward ms %.4f median %.4f' % (j['ms_per_step'], j['ms_per_step_median']))"; done; done; unset WUNET_NO_EVOP; } > $O/evop_ab.txt 2>&1
 ls tools/_lib_abl2.so > /dev/null 2>&1 && timeout 300 bash tools/conv_ablation.sh run > /dev/null 2>&1 && cp gpurun_out/conv_ablation.txt $O/conv_ablation.txt
 [ -x tools/microbench/_dma_issue ] && timeout 60 tools/microbench/_dma_issue > $O/dma_issue_microbench.txt
 ls -la $O

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; T=$(mktemp -d /tmp/pmcf.XXXX)
 cd /tmp; export TMPDIR=/tmp
 for ctr in FETCH_SIZE WRITE_SIZE; do
   env "$@" WUNET_BENCH_NO_MEDIAN=1 timeout 400 rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d $T/$ctr -o p -- \
-      python $R/bench.py --steps 2 --warmup 1 --graph off --no-cpu-baseline --no-roofline --no-extras > /dev/null 2>&1
+      python $R/bench.py --full --steps 2 --warmup 1 --graph off --no-cpu-baseline --no-roofline --no-extras > /dev/null 2>&1
 done
 python - <<PY > $OUT
 import collections, csv, glob

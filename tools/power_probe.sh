@@ -28,7 +28,7 @@ sample "LDS-DMA only, source in L2" 1.5 tools/microbench/_dma_issue 4000000 1
 sample "LDS-DMA only, source in HBM" 1.5 tools/microbench/_dma_issue 800000 2
 sample "DMA burst from L2 + MFMAs" 1.5 tools/microbench/_dma_issue 1200000 3
 sample "DMA burst from HBM + MFMAs" 1.5 tools/microbench/_dma_issue 800000 4
-sample "bench.py training steps (split GEMMs)" 6 python bench.py --steps 1500 --warmup 5 --no-cpu-baseline --no-extras --no-roofline
-sample "bench.py --gemm fp32 training steps" 6 python bench.py --gemm fp32 --steps 700 --warmup 5 --no-cpu-baseline --no-extras --no-roofline
-sample "bench.py --mode forward (eval)" 6 python bench.py --mode forward --steps 4000 --warmup 5 --no-cpu-baseline --no-extras --no-roofline
+sample "bench.py training steps (split GEMMs)" 6 python bench.py --full --steps 1500 --warmup 5 --no-cpu-baseline --no-extras --no-roofline
+sample "bench.py --gemm fp32 training steps" 6 python bench.py --full --gemm fp32 --steps 700 --warmup 5 --no-cpu-baseline --no-extras --no-roofline
+sample "bench.py --mode forward (eval)" 6 python bench.py --full --mode forward --steps 4000 --warmup 5 --no-cpu-baseline --no-extras --no-roofline
 cat $OUT

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; tag=$1; shift
 O=$R/gpurun_out; mkdir -p $O; rm -rf /tmp/prof_$tag
 cd /tmp; export TMPDIR=/tmp
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -o p -- python $R/bench.py --no-cpu-baseline "$@" > $O/${tag}_bench.json 2> $O/${tag}_err.log
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/prof_$tag -o p -- python $R/bench.py --full --no-cpu-baseline "$@" > $O/${tag}_bench.json 2> $O/${tag}_err.log
 f=$(find /tmp/prof_$tag -name 'p_kernel_stats.csv' | head -1)
 cp $f $O/${tag}_kernel_stats.csv
 python - <<PY

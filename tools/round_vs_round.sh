@@ -8,11 +8,11 @@ PKG=wave-u-net-for-speech-enhancement_amd
 PREV=${PREV:-round5}; CUR=${CUR:-round6}
 for rep in 1 2 3; do for lib in $PREV $CUR; do
   if [ $lib = $PREV ]; then export WUNET_LIB_PATH=$PWD/tools/_lib_$PREV.so; else export WUNET_LIB_PATH=$PWD/$PKG/csrc/libwunet_hip.so; fi
-  python bench.py --no-cpu-baseline --no-extras --no-roofline --steps 100 --warmup 10 2>/dev/null | python -c "
+  python bench.py --full --no-cpu-baseline --no-extras --no-roofline --steps 100 --warmup 10 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib training step ms %.4f (median %.4f) = %.0f frames/s  loss %.7f' % (j['ms_per_step'], j['ms_per_step_median'], j['value'], j['final_loss']))
 "
-  python bench.py --mode forward --no-cpu-baseline --no-extras --no-roofline --steps 50 --warmup 10 2>/dev/null | python -c "
+  python bench.py --full --mode forward --no-cpu-baseline --no-extras --no-roofline --steps 50 --warmup 10 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$lib eval forward  ms %.4f (median %.4f) = %.0f frames/s' % (j['ms_per_step'], j['ms_per_step_median'], j['value']))
 "

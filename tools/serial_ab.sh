@@ -6,7 +6,7 @@ PKG=wave-u-net-for-speech-enhancement_amd
 for lib in base new; do
   if [ $lib = base ]; then export WUNET_LIB_PATH=$R/${BASE:-tools/_lib_base.so}; else export WUNET_LIB_PATH=$R/$PKG/csrc/libwunet_hip.so; fi
   rm -rf /tmp/sab_$lib
-  WUNET_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/sab_$lib -o s -- python $R/bench.py --no-cpu-baseline --no-extras --no-roofline --steps 40 --warmup 10 > /dev/null 2>&1
+  WUNET_NO_SIDE_STREAM=1 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/sab_$lib -o s -- python $R/bench.py --full --no-cpu-baseline --no-extras --no-roofline --steps 40 --warmup 10 > /dev/null 2>&1
 done
 python - "$1" <<'PY'
 import csv, glob, sys

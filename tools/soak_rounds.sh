@@ -1,6 +1,6 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 export WUNET_BENCH_NO_MEDIAN=1
-run() { python bench.py --seed $1 --steps $2 --warmup 0 $3 --no-cpu-baseline --no-extras --no-roofline 2>/dev/null | python -c "import sys,json; print('%.7f' % json.loads(sys.stdin.read().strip().splitlines()[-1])['final_loss'])"; }
+run() { python bench.py --full --seed $1 --steps $2 --warmup 0 $3 --no-cpu-baseline --no-extras --no-roofline 2>/dev/null | python -c "import sys,json; print('%.7f' % json.loads(sys.stdin.read().strip().splitlines()[-1])['final_loss'])"; }
 for seed in 1 2 3; do
   steps=100
   a=$(run $seed $steps ""); b=$(run $seed $steps "--gemm fp32"); c=$(WUNET_H3_KTAIL=0 run $seed $steps "")
