@@ -60,6 +60,13 @@ void wunet_destroy(wunet_ctx* ctx);
  * WUNET_H3 says otherwise.  Changes the workspace size: call before wunet_workspace_bytes.  No reference counterpart. */
 int wunet_set_h3(wunet_ctx* ctx, int enable);
 
+/* Per-layer BatchNorm mode for the following wunet_forward (training != 0) and wunet_backward* calls on this ctx.
+ * frozen: host array of wunet_num_conv_layers(ctx) bytes, non-zero = that layer's BatchNorm uses the running statistics
+ * (nn.BatchNorm1d in eval mode) and leaves them untouched; NULL = none (the default).  Host-side only, capture-safe:
+ * the values become kernel arguments at enqueue time.  A backward must run under the mask of its forward.
+ * Does not change wunet_workspace_bytes. */
+int wunet_set_bn_frozen(wunet_ctx* ctx, const unsigned char* frozen, int count);
+
 /* Bytes of device workspace the caller must provide to wunet_forward (with_backward=0: inference;
  * with_backward=1: also holds everything wunet_backward needs). */
 size_t wunet_workspace_bytes(const wunet_ctx* ctx, int with_backward);
@@ -82,7 +89,8 @@ int wunet_forward(wunet_ctx* ctx, const float* noisy, const float* const* params
 /* Replaces autograd's backward of Model.forward (trainer/trainer.py:37 loss.backward()).
  * Must follow a training-mode wunet_forward on the same ctx/workspace/params/noisy.
  * grad_enhanced: dL/d(enhanced) [B,1,T].  grads: same shapes/order as params; every tensor is
- * overwritten (conv biases feeding training-mode BatchNorm get an exact 0).  No input gradient. */
+ * overwritten (conv biases feeding a batch-statistics BatchNorm get an exact 0; a layer frozen by wunet_set_bn_frozen gets
+ * its true bias gradient).  No input gradient. */
 int wunet_backward(wunet_ctx* ctx, const float* noisy, const float* const* params,
                    const float* enhanced, const float* grad_enhanced, void* workspace,
                    float* const* grads, void* stream);

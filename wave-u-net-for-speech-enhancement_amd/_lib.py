@@ -18,7 +18,7 @@ EXPORTS = [
     "wunet_adam_step", "wunet_set_h3", "wunet_op_conv1d_split", "wunet_op_conv1d_dgrad_split", "wunet_op_conv1d_wgrad_split",
     "wunet_backward_range_async", "wunet_backward_join", "wunet_debug_set_conv_trace", "wunet_crop_windows",
     "wunet_comm_unique_id", "wunet_comm_create", "wunet_comm_allreduce_sum", "wunet_comm_world", "wunet_comm_destroy",
-    "wunet_debug_stamps",
+    "wunet_debug_stamps", "wunet_set_bn_frozen",
 ]
 
 _vp = ctypes.c_void_p
@@ -53,6 +53,8 @@ def declare(lib):
     lib.wunet_adam_step.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                     ctypes.c_double, ctypes.c_longlong, ctypes.c_double, _vp, _vp, _vp]
     lib.wunet_set_h3.argtypes = [_vp, _i]
+    if hasattr(lib, "wunet_set_bn_frozen"):      # (saved libraries of earlier versions - tools/lib_ab.sh - do not have it)
+        lib.wunet_set_bn_frozen.argtypes = [_vp, _vp, _i]
     lib.wunet_profile_enable.argtypes = [_i]
     lib.wunet_profile_collect.argtypes = [ctypes.c_char_p, _sz]
     lib.wunet_profile_collect.restype = ctypes.c_longlong

@@ -87,6 +87,9 @@ int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* pa
 
     for (int i = layer_end - 1; i >= layer_begin; --i) {
         const LayerPlan& l = c->ly[i];
+        // a layer frozen by wunet_set_bn_frozen (running statistics in the forward): every finalize below emits g_z = a g (k2 = k3 = 0)
+        // and the conv bias's gradient a sum g
+        const int fz = (c->any_frozen && c->frozen[i]) ? 1 : 0;
         // ---- a layer whose BatchNorm-backward sums came out of its consumers' data-gradient epilogues (conv_h3d_kernel<.., BSUM>, planned by
         // layout_workspace): no pass A; finalize from the per-tile rows; g_z formed by gz_split_h3_kernel from the data gradients themselves
         static const bool no_enc_gz_ = getenv("WUNET_NO_ENC_GZ") != nullptr;
@@ -112,7 +115,7 @@ int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* pa
         const bool e0 = c->e0 && gz_in_wgrad && !fuse && l.cin == 1 && l.taps == 15 && l.L >= 16 && !dx_stays_split(c, 1) && n >= 1;
         if (fuse) {
             p.gamma = params[4 * i + 2]; p.dgamma = grads[4 * i + 2]; p.dbeta = grads[4 * i + 3]; p.dbias = grads[4 * i + 1];
-            p.k1 = ws + l.k1; p.k2 = ws + l.k2; p.k3 = ws + l.k3; p.count = (double)c->B * l.Lt;
+            p.k1 = ws + l.k1; p.k2 = ws + l.k2; p.k3 = ws + l.k3; p.count = (double)c->B * l.Lt; p.frozen = fz;
         }
         // the last layer on the split kernels: its g is recomputed from the head gradient by gz_split_h3_kernel (HEAD mode), not stored
         const bool head_in_gz = i == NL - 1 && i > 0 && l.h3d && !fuse && !tiny;
@@ -171,7 +174,7 @@ int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* pa
             BnBwdArgs b{};
             b.part = ws + c->bpart_off; b.rows = l.a_split; b.gamma = params[4 * i + 2]; b.mean = ws + l.mean; b.rstd = ws + l.rstd;
             b.dgamma = grads[4 * i + 2]; b.dbeta = grads[4 * i + 3]; b.dbias = grads[4 * i + 1]; b.k1 = ws + l.k1; b.k2 = ws + l.k2; b.k3 = ws + l.k3;
-            b.C = l.cout; b.count = (double)c->B * l.Lt;
+            b.C = l.cout; b.count = (double)c->B * l.Lt; b.frozen = fz;
             b.pmax = (i > 0 && l.h3d) ? ws + c->bmax_off : nullptr; b.bound = ws + c->bound_off;
             if (e0) { b.e0rows = ws + c->e0part_off; b.dw0 = grads[0]; }
             // (short levels on the split kernels: the finalize runs in the prologue of gz_split_h3_kernel's blocks instead -
@@ -189,7 +192,7 @@ int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* pa
                     t.tiles1 = (int)(((size_t)c->B * eq.L + 255) / 256); t.part1 = ws + eq.bsp;
                 }
                 t.gamma = b.gamma; t.mean = b.mean; t.rstd = b.rstd; t.dgamma = b.dgamma; t.dbeta = b.dbeta; t.dbias = b.dbias;
-                t.k1 = b.k1; t.k2 = b.k2; t.k3 = b.k3; t.bound = b.bound; t.C = l.cout; t.count = b.count;
+                t.k1 = b.k1; t.k2 = b.k2; t.k3 = b.k3; t.bound = b.bound; t.C = l.cout; t.count = b.count; t.frozen = fz;
                 WUNET_LAUNCH(bn_finalize_bwd_tiles_kernel, dim3(l.cout), dim3(WUNET_THREADS), 0, st, t);
                 WUNET_CHECK_LAUNCH();
             } else if (!fin_in_gz) {

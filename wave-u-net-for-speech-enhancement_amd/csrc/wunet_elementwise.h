@@ -150,7 +150,10 @@ __device__ __forceinline__ void bn_eval_core(const BnFwdArgs& A, int c)
 
 // Eval mode: the BatchNorm scale / shift of EVERY layer in one launch - they only depend on the running statistics, so nothing
 // of it belongs on the layer-to-layer chain (25 launches of ~4 us less per eval forward).  grid = (ceil(maxC / 256), layers).
-struct BnEvalDesc { const float* gamma; const float* beta; const float* running_mean; const float* running_var; float* a; float* s; int C; };
+// Training mode, the layers frozen by wunet_set_bn_frozen (nn.BatchNorm1d in eval mode): the same scale / shift, and mean / rstd (+ cst)
+// = running_mean / 1/sqrt(running_var + eps), from which the backward rebuilds xhat; nullptr in eval mode.
+struct BnEvalDesc { const float* gamma; const float* beta; const float* running_mean; const float* running_var; float* a; float* s; int C;
+                    float* mean; float* rstd; float* cst; };
 struct BnEvalTable { BnEvalDesc d[WUNET_MAX_CONV_LAYERS]; };
 static __global__ __launch_bounds__(WUNET_THREADS) void bn_eval_all_kernel(BnEvalTable T)
 {
@@ -161,6 +164,13 @@ static __global__ __launch_bounds__(WUNET_THREADS) void bn_eval_all_kernel(BnEva
     A.gamma = d.gamma; A.beta = d.beta; A.running_mean = const_cast<float*>(d.running_mean); A.running_var = const_cast<float*>(d.running_var);
     A.a = d.a; A.s = d.s;
     bn_eval_core(A, c);
+    if (d.mean) {
+        const float rstd = (float)(1.0 / sqrt((double)d.running_var[c] + 1e-5)), a = d.gamma[c] * rstd;
+        const float mu = d.running_mean[c], sh = d.beta[c] - mu * a;
+        d.mean[c] = mu;
+        d.rstd[c] = rstd;
+        if (d.cst) { d.cst[4 * c] = a; d.cst[4 * c + 1] = sh; d.cst[4 * c + 2] = mu; d.cst[4 * c + 3] = rstd; }
+    }
 }
 
 static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_fwd_kernel(BnFwdArgs A)
@@ -565,6 +575,7 @@ struct PassAArgs {
     // FUSE (a whole channel in one pass of one block: B*L <= 1024): BatchNorm-backward finalize and g_z in the same launch -
     // gpre receives g_z = k1*g + k2*z + k3 directly, part is not written (bn_finalize_bwd_kernel + gz_materialize_kernel)
     const float* gamma; float* dgamma; float* dbeta; float* dbias; float* k1; float* k2; float* k3; double count;
+    int frozen;          // FUSE: the layer's BatchNorm ran on the running statistics (BnBwdArgs::frozen)
 };
 
 // The pass's closing reduction: two sums (three in HEAD mode) and two maxima over the block behind ONE barrier - butterflies inside each wave, the four
@@ -847,13 +858,13 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
     if (FUSE) {
         // bn_finalize_bwd_kernel's arithmetic on the (float-rounded, as if through part[]) sums, then gz_materialize_kernel's
         const double t1 = (double)(float)s1, t2 = (double)(float)s2;
-        const double m1 = t1 / A.count, m2 = t2 / A.count;
+        const double m1 = A.frozen ? 0.0 : t1 / A.count, m2 = A.frozen ? 0.0 : t2 / A.count;
         const double ar = (double)gam * (double)rstd;
         const float k1 = (float)ar, k2 = (float)(-ar * m2 * (double)rstd), k3 = (float)(ar * m2 * (double)rstd * (double)mu - ar * m1);
         if (threadIdx.x == 0) {
             A.dgamma[c] = (float)t2;
             A.dbeta[c] = (float)t1;
-            A.dbias[c] = 0.0f;
+            A.dbias[c] = A.frozen ? (float)(ar * t1) : 0.0f;
             A.k1[c] = k1; A.k2[c] = k2; A.k3[c] = k3;
         }
         if (have) {
@@ -880,17 +891,20 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
 // ---------------------------------------------------------------------------- BN backward finalize
 // grid = C.  dgamma = sum g*xhat, dbeta = sum g, and the folded coefficients of
 // g_z = gamma*rstd*(g - mean(g) - xhat*mean(g*xhat)) = k1*g + k2*z + k3.
+// A frozen layer (BatchNorm on the running statistics, wunet_set_bn_frozen; mean / rstd hold running_mean / 1/sqrt(running_var + eps)):
+// y = a z + const, so g_z = a g - k1 = a, k2 = k3 = 0 - and the conv bias gets a sum g (batch statistics cancel it).
 struct BnBwdArgs {
     const float* part; int rows;
     const float* gamma; const float* mean; const float* rstd;
     float* dgamma; float* dbeta;
-    float* dbias;        // conv bias feeding training-mode BN: exact zero gradient
+    float* dbias;        // conv bias feeding batch-statistics BN: exact zero gradient; frozen: a sum g
     float* k1; float* k2; float* k3;
     int C; double count;
     const float* pmax;   // nullptr or pass A's [rows][C][2] maxima
     float* bound;        // [C]: |k1| max|g| + |a m2 rstd| max|z - mean| + |a m1|  >=  max |g_z| of the channel
     const float* e0rows; // nullptr, or the first layer's [rows][C][48] partial sums (pass_a_kernel<.., E0>): its weight gradient is finished here
     float* dw0;          // [C][15]: dW[c][k] = k1 sum g x + k2 sum z x + k3 sum x
+    int frozen;          // the layer's BatchNorm ran on the running statistics
 };
 
 static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_kernel(BnBwdArgs A)
@@ -914,11 +928,11 @@ static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_kernel(B
     }
     block_reduce_pass_a(s1, s2, s3, false, mg, mz, red);
     if (tid == 0) {
-        const double m1 = s1 / A.count, m2 = s2 / A.count;
+        const double m1 = A.frozen ? 0.0 : s1 / A.count, m2 = A.frozen ? 0.0 : s2 / A.count;
         const double a = (double)gam * (double)rs;
         A.dgamma[c] = (float)s2;
         A.dbeta[c] = (float)s1;
-        A.dbias[c] = 0.0f;
+        A.dbias[c] = A.frozen ? (float)(a * s1) : 0.0f;
         A.k1[c] = (float)a;
         A.k2[c] = (float)(-a * m2 * (double)rs);
         A.k3[c] = (float)(a * m2 * (double)rs * (double)mu - a * m1);
@@ -941,7 +955,7 @@ static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_kernel(B
         }
         __syncthreads();
         if (tid < 15) {
-            const double m1 = s1 / A.count, m2 = s2 / A.count;
+            const double m1 = A.frozen ? 0.0 : s1 / A.count, m2 = A.frozen ? 0.0 : s2 / A.count;
             const double a = (double)gam * (double)rs;
             const float k1 = (float)a, k2 = (float)(-a * m2 * (double)rs), k3 = (float)(a * m2 * (double)rs * (double)mu - a * m1);
             A.dw0[c * 15 + tid] = (float)((double)k1 * e0s[tid] + (double)k2 * e0s[15 + tid] + (double)k3 * e0s[30 + tid]);      // (e0s[30 ..]: channel 0's rows)
@@ -959,6 +973,7 @@ struct BnBwdTilesArgs {
     const float* gamma; const float* mean; const float* rstd;
     float* dgamma; float* dbeta; float* dbias; float* k1; float* k2; float* k3; float* bound;
     int C; double count;
+    int frozen;                          // BnBwdArgs::frozen
 };
 static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_tiles_kernel(BnBwdTilesArgs A)
 {
@@ -996,11 +1011,11 @@ static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_tiles_ke
     float dummy = 0.0f;
     block_max2(mz, dummy, red);
     if (tid == 0) {
+        const double m1 = A.frozen ? 0.0 : s1 / A.count, m2 = A.frozen ? 0.0 : s2 / A.count;
+        const double a = (double)A.gamma[c] * (double)A.rstd[c];
         A.dgamma[c] = (float)s2;
         A.dbeta[c] = (float)s1;
-        A.dbias[c] = 0.0f;
-        const double m1 = s1 / A.count, m2 = s2 / A.count;
-        const double a = (double)A.gamma[c] * (double)A.rstd[c];
+        A.dbias[c] = A.frozen ? (float)(a * s1) : 0.0f;
         A.k1[c] = (float)a;
         A.k2[c] = (float)(-a * m2 * (double)A.rstd[c]);
         A.k3[c] = (float)(a * m2 * (double)A.rstd[c] * (double)A.mean[c] - a * m1);

@@ -22,6 +22,12 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
     // L2/HBM bandwidth and CU slots from the encoder GEMMs), so it stays on the caller's stream.
     hipStream_t sd = st;
     float* const fslot = ws + c->fslot_off;
+    // wunet_set_bn_frozen: a frozen layer of a training forward normalises with the running statistics (scale / shift, mean / rstd
+    // ahead of the chain, no statistics partials, running statistics untouched) and, as nothing bounds its activation then, its
+    // consumers' operand scale comes from the measured maximum, as in eval mode.  With no layer frozen nothing below changes.
+    auto frozen = [&](int i) { return training && c->any_frozen && i >= 0 && c->frozen[i] != 0; };
+    // a decoder layer's skip half can only be written by the encoder-side operand pass when both sources' bounds are known that early
+    auto skip_early = [&](const LayerPlan& dl) { return !frozen(dl.src0) && !frozen(dl.src1); };
     float* const enhanced_user = enhanced;
     if (c->padded) {
         // the caller's [B][1][Tt] rows into zero-padded rows of T floats; the result is cropped back at the end
@@ -38,7 +44,7 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
     // (WUNET_NO_EARLY_FPACK=1: A/B switch).  Order on the side stream: scales, split pack (first needed by layer 1), fp32 pack (the
     // levels of <= 8 samples), then the backward's packs.
     wunet_ctx::Side* fside = nullptr;
-    if (training && c->NL > 1 && c->ly[0].first && !g_prof_on) {
+    if (training && c->NL > 1 && c->ly[0].first && !g_prof_on && !frozen(0)) {      // (a frozen first layer measures its bound before layer 1)
         static const bool no_side = getenv("WUNET_NO_SIDE_STREAM") != nullptr;       // (profiling switch: everything on the caller's stream)
         if (!no_side) fside = side_for_current_device(c);
         if (fside && (hipEventRecord(fside->ev_fork, st) != hipSuccess || hipStreamWaitEvent(fside->stream, fside->ev_fork, 0) != hipSuccess))
@@ -80,6 +86,7 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
                 d.w = (l.h3f || l.h3d) ? params[4 * i] : nullptr; d.wn = (unsigned)((size_t)l.cout * l.cin * l.taps);
                 d.gamma = params[4 * i + 2]; d.beta = params[4 * i + 3]; d.C = l.cout;
                 d.sqrtn = sqrtf((float)((double)c->B * l.Lt));
+                d.frozen = frozen(i) ? 1 : 0;
                 d.zp0 = l.h3f ? ws + l.xzp : nullptr;
                 d.zp1 = (l.h3d && training && save_for_backward) ? ws + l.gzp : nullptr;      // (the backward segment only exists then)
                 any = any || l.h3f;
@@ -162,9 +169,28 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
         }
         WUNET_LAUNCH(bn_eval_all_kernel, dim3((unsigned)((maxc + WUNET_THREADS - 1) / WUNET_THREADS), (unsigned)c->NL), dim3(WUNET_THREADS), 0, st, T);
         WUNET_CHECK_LAUNCH();
+    } else if (c->any_frozen) {
+        // the frozen layers: scale / shift and the backward's mean / rstd (+ the BSUM constants) from the running statistics, one launch
+        BnEvalTable T{};
+        int nf = 0, maxc = 1;
+        for (int i = 0; i < c->NL; ++i) {
+            if (!frozen(i)) continue;
+            const LayerPlan& l = c->ly[i];
+            BnEvalDesc& d = T.d[nf++];
+            d.gamma = params[4 * i + 2]; d.beta = params[4 * i + 3]; d.running_mean = running[2 * i]; d.running_var = running[2 * i + 1];
+            d.a = ws + l.a; d.s = ws + l.s; d.C = l.cout;
+            d.mean = ws + l.mean; d.rstd = ws + l.rstd; d.cst = l.bsum ? ws + l.cst : nullptr;
+            if (l.cout > maxc) maxc = l.cout;
+        }
+        if (nf > 0) {
+            WUNET_LAUNCH(bn_eval_all_kernel, dim3((unsigned)((maxc + WUNET_THREADS - 1) / WUNET_THREADS), (unsigned)nf), dim3(WUNET_THREADS), 0, st, T);
+            WUNET_CHECK_LAUNCH();
+        }
     }
     for (int i = 0; i < c->NL; ++i) {
         const LayerPlan& l = c->ly[i];
+        const bool fz = frozen(i);
+        const bool bstats = training && !fz;         // this layer's BatchNorm takes batch statistics
         // (packs on the side stream: the operand scales and the split pack are first read by layer 1, the fp32 pack by the first
         // layer on the fp32 kernels)
         if (!fpack_joined && i >= 1) {
@@ -197,14 +223,14 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
                 ph.kind = l.kind == LK_UPCAT ? 1 : 0;
                 // the encoder-side pass can only write the decoder's skip half when the decoder's x scale is known that early:
                 // training mode (data-independent activation bounds); in eval mode the decoder-side pass reads the skip itself
-                ph.up_only = (l.kind == LK_UPCAT && l.skip_from > 0 && training) ? 1 : 0;
+                ph.up_only = (l.kind == LK_UPCAT && l.skip_from > 0 && training && skip_early(l)) ? 1 : 0;
                 ph.xb0 = fslot + (size_t)WUNET_SLOT_FLOATS * l.src0 + 4;
                 ph.xb1 = l.kind == LK_UPCAT ? fslot + (size_t)WUNET_SLOT_FLOATS * l.src1 + 4 : nullptr;
                 ph.xsc = fslot + (size_t)WUNET_SLOT_FLOATS * i;
                 ph.bf = c->bf;
                 if (l.kind == LK_DECIM && training) {
                     const int dj = 2 * c->n - i + 1;             // the decoder layer that concatenates this pass's producer
-                    if (dj < c->NL && c->ly[dj].skip_from == i && !c->ly[dj].h3u_train) {      // (conv_h3u_kernel writes its whole operand)
+                    if (dj < c->NL && c->ly[dj].skip_from == i && !c->ly[dj].h3u_train && skip_early(c->ly[dj])) {      // (conv_h3u_kernel writes its whole operand)
                         const LayerPlan& dl = c->ly[dj];
                         ph.sh = reinterpret_cast<wunet_half*>(ws + dl.xh); ph.sl = reinterpret_cast<wunet_half*>(ws + dl.xl);
                         ph.SC8 = (dl.cin + 7) / 8; ph.sc8off = dl.c0 / 8;
@@ -264,20 +290,21 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
         b.gamma = params[4 * i + 2]; b.beta = params[4 * i + 3];
         b.running_mean = running[2 * i]; b.running_var = running[2 * i + 1]; b.nbt = nbt[i];
         b.a = ws + l.a; b.s = ws + l.s; b.mean = ws + l.mean; b.rstd = ws + l.rstd;
-        b.cst = (training && l.bsum) ? ws + l.cst : nullptr;      // (read by the consumers' data-gradient epilogues, conv_h3d_kernel<.., BSUM>)
-        b.C = l.cout; b.count = (double)c->B * l.Lt; b.training = training ? 1 : 0;
+        b.cst = (bstats && l.bsum) ? ws + l.cst : nullptr;      // (read by the consumers' data-gradient epilogues, conv_h3d_kernel<.., BSUM>)
+        b.C = l.cout; b.count = (double)c->B * l.Lt; b.training = bstats ? 1 : 0;
         // eval mode, a layer whose activation feeds split operands: its consumers' operand scale comes from the measured maximum
         // of |a z + s| (no batch statistics bound it).  The large producers (conv_first_kernel, un-split conv_h3_kernel) take it
         // in their epilogue - the BatchNorm coefficients only depend on the running statistics, so they are finalised BEFORE the
         // conv - the small ones get a pass of act_max_kernel over z.
-        const bool ev_need = !training && c->h3 && l.feeds_h3;
-        const bool ev_epi = ev_need && (l.first || (l.h3f && !split));
+        // (a frozen layer: a / s are there from the launch ahead of the chain; its bound is measured behind the conv)
+        const bool ev_need = (!training || fz) && c->h3 && l.feeds_h3;
+        const bool ev_epi = ev_need && !training && (l.first || (l.h3f && !split));
         float* const xrows = fslot + (size_t)WUNET_SLOT_FLOATS * i + 4;     // the layer's xb slot (cleared by h3_scales_kernel): blocks fold their maxima into it
         // (eval: a / s of every layer are already there, bn_eval_all_kernel)
         if (l.first) {
             prof_begin(st, "conv_first_kernel<15>", 2.0 * c->B * l.L * l.cout * 15.0, 4.0 * c->B * l.L * (1.0 + l.cout));
             WUNET_LAUNCH(conv_first_kernel<15>, dim3((unsigned)l.f.grid_x), dim3(WUNET_THREADS), 0, st, xin, params[4 * i], params[4 * i + 1],
-                         ws + l.z, training ? ws + c->stats_off : (float*)nullptr, c->B, l.cout, l.L, l.logL,
+                         ws + l.z, bstats ? ws + c->stats_off : (float*)nullptr, c->B, l.cout, l.L, l.logL,
                          ev_epi ? ws + l.a : (const float*)nullptr, ev_epi ? ws + l.s : (const float*)nullptr, ev_epi ? xrows : (float*)nullptr, l.Lt);
             prof_end(st);
         } else if (use_u) {
@@ -291,7 +318,7 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
             u.wh = reinterpret_cast<const wunet_half*>(ws + c->h3_wf_hi) + l.h3f_wpk;
             u.wdelta = (unsigned)((const char*)(ws + c->h3_wf_lo) - (const char*)(ws + c->h3_wf_hi));
             u.bias = params[4 * i + 1]; u.sc2 = fslot + (size_t)WUNET_SLOT_FLOATS * i + 2;
-            u.out = ws + l.z; u.stats = training ? ws + c->stats_off : nullptr;
+            u.out = ws + l.z; u.stats = bstats ? ws + c->stats_off : nullptr;
             u.ev_a = ev_epi ? ws + l.a : nullptr; u.ev_s = ev_epi ? ws + l.s : nullptr; u.xrows = ev_epi ? xrows : nullptr;
             if (training && save_for_backward) {        // the weight gradient reads the split operand
                 u.oxh = reinterpret_cast<wunet_half*>(ws + l.xh); u.oxl = reinterpret_cast<wunet_half*>(ws + l.xl);
@@ -323,7 +350,7 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
                                     // (a result that goes through conv_reduce_bn_kernel gets its bias THERE: an un-split launch into the split
                                     //  buffer - a padded length - added it twice; invisible behind training-mode BatchNorm, 0.03 off in eval mode)
                                     split ? nullptr : params[4 * i + 1], sl, sl + 2,
-                                    split ? ws + c->spart_off : ws + l.z, (training && !split) ? ws + c->stats_off : nullptr, c->B, l.cout,
+                                    split ? ws + c->spart_off : ws + l.z, (bstats && !split) ? ws + c->stats_off : nullptr, c->B, l.cout,
                                     l.cin, l.h3f_nch, l.L, st, ws + l.xzp, ev_epi ? ws + l.a : nullptr, ev_epi ? ws + l.s : nullptr, ev_epi ? xrows : nullptr, c->bf, l.h3f_ntt,
                                     evop ? &opo : nullptr);
             if (rc) return rc;
@@ -333,7 +360,7 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
                          xin, params[4 * i], ws + c->spart_off, c->B, l.cin, l.cout, l.L, l.logL, l.taps, 0);
         } else {
             const ConvArgs a = make_conv_args(xin, l.cin, ws + c->wpkf_off + l.f_wpk, split ? nullptr : params[4 * i + 1],
-                                              split ? ws + c->spart_off : ws + l.z, (training && !split) ? ws + c->stats_off : nullptr,
+                                              split ? ws + c->spart_off : ws + l.z, (bstats && !split) ? ws + c->stats_off : nullptr,
                                               c->B, l.cout, l.L, l.taps, l.f, (size_t)c->B * l.cout * l.L);
             int rc = launch_conv(l.taps, a, l.f, st);
             if (rc) return rc;
@@ -348,18 +375,18 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
             // (eval: every block ends in a block-wide maximum and an atomic on one address - half as many blocks: eval forward 1.470 -> 1.445 ms,
             //  one block per channel the same, twice as many 1.53 -> 1.57; training 2048 / 4096 / 8192 positions per block: 5.166 / 5.152 /
             //  5.148 ms, within the noise and another summation order - left alone; profiles/r5_small_ab.txt)
-            int rs = (int)(pos / (training ? 2048 : 4096));
+            int rs = (int)(pos / (bstats ? 2048 : 4096));
             if (rs < 1) rs = 1;
             if (rs > 64) rs = 64;
             b.rows = rs;
             WUNET_LAUNCH(conv_reduce_bn_kernel, dim3(l.cout, rs), dim3(WUNET_THREADS), 0, st, b, (const float*)(ws + c->spart_off),
                          tiny ? 1 : l.f.ksplit, (size_t)c->B * l.cout * l.L, ws + l.z, c->B, l.L, l.logL, ws + c->stats_off, l.Lt,
                          ev_need ? xrows : (float*)nullptr);
-            if (rs > 1 && training) {
+            if (rs > 1 && bstats) {
                 WUNET_CHECK_LAUNCH();
                 WUNET_LAUNCH(bn_finalize_fwd_kernel, dim3(l.cout), dim3(WUNET_THREADS), 0, st, b);
             }
-        } else if (training) {
+        } else if (bstats) {
             WUNET_LAUNCH(bn_finalize_fwd_kernel, dim3(l.cout), dim3(WUNET_THREADS), 0, st, b);
         }
         WUNET_CHECK_LAUNCH();

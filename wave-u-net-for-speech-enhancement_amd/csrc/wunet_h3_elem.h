@@ -12,20 +12,21 @@
 //            Training mode: max_c |gamma_c| sqrt(N) + |beta_c|, N = B*L positions (batch statistics: (z - mean)^2 <= N var, so
 //            |zhat| <= sqrt(N) - rigorous and data independent, known before the forward starts; measured values sit a factor
 //            sqrt(N)/6 below it, which costs nothing: the error floor of a split value is 2^-25 in scaled units against
-//            actual maxima of 2^5 or more).  Eval mode (running statistics, activations not normalised by the batch): the
-//            measured maximum of |a z + s|, act_max_kernel.
+//            actual maxima of 2^5 or more).  Eval mode and the frozen layers of a training forward (running statistics,
+//            activations not normalised by the batch): the measured maximum of |a z + s|, act_max_kernel.
 #define WUNET_SLOT_FLOATS 8
 #define WUNET_WMAX_PARTS 64
 struct ScaleDesc {
     const float* w; unsigned wn;                  // conv weight (nullptr: no split pack of this layer)
     const float* gamma; const float* beta; int C; // BatchNorm affine parameters of the layer
     float sqrtn;                                  // sqrt(B * L)
+    int frozen;                                   // training mode, BatchNorm on the running statistics (wunet_set_bn_frozen): xb is measured as in eval mode
     float* zp0; float* zp1;                       // nullptr or the 16-byte zero pads behind the layer's split conv input / split g_z: cleared here
 };
 struct ScaleTable { ScaleDesc d[WUNET_MAX_CONV_LAYERS]; float* wmax; float* slots; int training; };
 
 // grid (WUNET_WMAX_PARTS, layers): partial max |W| per layer; block (0, layer) also writes the layer's xb (training) or clears
-// it (eval: act_max_kernel accumulates into it with atomicMax)
+// it (eval, or a frozen layer of a training forward: act_max_kernel accumulates into it with atomicMax)
 static __global__ __launch_bounds__(WUNET_THREADS) void h3_scales_kernel(ScaleTable T)
 {
     __shared__ float red[WUNET_THREADS];
@@ -45,7 +46,7 @@ static __global__ __launch_bounds__(WUNET_THREADS) void h3_scales_kernel(ScaleTa
     }
     if (blockIdx.x == 0) {
         float m = 0.0f;
-        if (T.training)
+        if (T.training && !d.frozen)
             for (int c = tid; c < d.C; c += WUNET_THREADS) m = fmaxf(m, fabsf(d.gamma[c]) * d.sqrtn + fabsf(d.beta[c]));
         red[tid] = m;
         __syncthreads();
@@ -334,7 +335,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void gz_split_h3_kernel(const float*
                     }
                 }
             }
-            const double m1 = s1 / F.count, m2 = s2 / F.count;
+            const double m1 = F.frozen ? 0.0 : s1 / F.count, m2 = F.frozen ? 0.0 : s2 / F.count;
             const double a = (double)gam_ * (double)rs_;
             const float k1c = (float)a, k2c = (float)(-a * m2 * (double)rs_);
             const float k3c = (float)(a * m2 * (double)rs_ * (double)mu_ - a * m1);
@@ -342,7 +343,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void gz_split_h3_kernel(const float*
             ks[c] = k1c; ks[WUNET_GZ_FIN_C + c] = k2c; ks[2 * WUNET_GZ_FIN_C + c] = k3c;
             m = fmaxf(m, bc);
             if (blockIdx.x == 0) {
-                F.dgamma[c] = (float)s2; F.dbeta[c] = (float)s1; F.dbias[c] = 0.0f;
+                F.dgamma[c] = (float)s2; F.dbeta[c] = (float)s1; F.dbias[c] = F.frozen ? (float)(a * s1) : 0.0f;
                 F.k1[c] = k1c; F.k2[c] = k2c; F.k3[c] = k3c; F.bound[c] = bc;
             }
         }

@@ -128,12 +128,16 @@ struct wunet_ctx {
     int head_blocks;
     int h3 = 0;                   // fp16-split GEMMs: 0 off, 1 where the planner wants them, 2 wherever they can run
     int bf = 0;                   // the split kernels run their bf16 mode (one bf16 word per operand value, one MFMA pass)
+    // wunet_set_bn_frozen: per-layer BatchNorm on the running statistics (nn.BatchNorm1d in eval mode) inside a training forward and
+    // its backward; all zero = every layer on batch statistics (the default).  Host state only: read when a call enqueues its launches.
+    std::vector<unsigned char> frozen;
+    bool any_frozen = false;
     size_t h3_wf_hi, h3_wf_lo, h3_wb_hi, h3_wb_lo, h3_slot;   // float offsets
     size_t fslot_off, wmax_off;   // forward segment: WUNET_SLOT_FLOATS per layer (x / weight scales, activation bound), partial max |W|
     size_t h3_wf_halfs, h3_wb_halfs;
     // side stream for the weight-gradient GEMMs (off the backward's critical chain): one per device the ctx is used on, created
     // lazily under the lock and never replaced, so replicas of one shape on several devices (or threads) do not disturb each other.
-    // Everything else in the ctx is immutable after wunet_create / wunet_set_h3.
+    // Everything else in the ctx is immutable after wunet_create / wunet_set_h3 / wunet_set_bn_frozen.
     struct Side {
         hipStream_t stream = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pack = nullptr, ev_fpack = nullptr, ev_fpack2 = nullptr;
         const void* packed_ws = nullptr;      // the workspace whose backward weight packs the last training forward enqueued on `stream`

@@ -654,6 +654,7 @@ int wunet_create(int n_layers, int channels_interval, int batch, int length, wun
     c->n = n; c->ci = ci; c->B = B; c->T = T; c->NL = 2 * n + 1;
     c->Tt = length; c->padded = length != T;
     c->ly.resize(c->NL);
+    c->frozen.assign(c->NL, 0);
     for (int i = 0; i < c->NL; ++i) {
         LayerPlan& l = c->ly[i];
         if (i < n) {            // model/unet_basic.py:38-39
@@ -683,6 +684,18 @@ int wunet_set_h3(wunet_ctx* ctx, int enable)
     ctx->bf = (enable == 3 || enable == 4) ? 1 : 0;
     ctx->h3 = (enable == 2 || enable == 4) ? 2 : (enable ? 1 : 0);
     layout_workspace(ctx);          // sizes and offsets change: call before wunet_workspace_bytes
+    return WUNET_OK;
+}
+
+int wunet_set_bn_frozen(wunet_ctx* ctx, const unsigned char* frozen, int count)
+{
+    if (!ctx) return fail(WUNET_E_ARG, "null ctx");
+    if (frozen && count != ctx->NL) return fail(WUNET_E_ARG, "frozen mask: %d entries for %d conv layers", count, ctx->NL);
+    ctx->any_frozen = false;
+    for (int i = 0; i < ctx->NL; ++i) {
+        ctx->frozen[i] = (frozen && frozen[i]) ? 1 : 0;
+        ctx->any_frozen = ctx->any_frozen || ctx->frozen[i];
+    }
     return WUNET_OK;
 }
 

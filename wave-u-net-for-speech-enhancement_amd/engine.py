@@ -123,7 +123,7 @@ class Engine:
                 self._check(self.lib.wunet_create(n_layers, ci, batch, length, ctypes.byref(h)))
                 if self.h3:
                     self._check(self.lib.wunet_set_h3(h, self.h3))
-                ent = self._ctx[key] = [h, 0]                    # [handle, holders]
+                ent = self._ctx[key] = [h, 0, None]              # [handle, holders, BatchNorm mask set on it (None: none frozen)]
             else:
                 self._ctx.move_to_end(key)
             ent[1] += 1
@@ -138,6 +138,19 @@ class Engine:
 
     def _using(self, n_layers, ci, batch, length, device=None):
         return _CtxHold(self, *self._ctx_for(n_layers, ci, batch, length, device))
+
+    def _set_frozen(self, hold, frozen):
+        """Per-layer BatchNorm mode of the held context (include/wunet_hip.h: wunet_set_bn_frozen) for the call that follows in the
+        same hold: `frozen` - one truthy entry per conv layer for a BatchNorm on the running statistics, or None.  The context is
+        shared by every model of its shape, so each call states its mask; the C call is only made when the mask changes."""
+        ent = hold.ent
+        want = bytes(1 if f else 0 for f in frozen) if frozen is not None and any(frozen) else None
+        if ent[2] != want:
+            if want is None:
+                self._check(self.lib.wunet_set_bn_frozen(ent[0], None, 0))
+            else:
+                self._check(self.lib.wunet_set_bn_frozen(ent[0], ctypes.create_string_buffer(want, len(want)), len(want)))
+            ent[2] = want
 
     def _require(self, t, name):
         if t.dtype != torch.float32 and t.dtype != torch.int64:
@@ -182,8 +195,11 @@ class Engine:
         return torch.cuda.device(device) if not self.host_memory else _NullCtx()
 
     # ------------------------------------------------------------------ network
-    def forward(self, n_layers, ci, noisy, params, running, nbt, training, with_backward):
-        """Returns (enhanced, workspace).  Keep `workspace` alive until backward has been enqueued."""
+    def forward(self, n_layers, ci, noisy, params, running, nbt, training, with_backward, frozen=None):
+        """Returns (enhanced, workspace).  Keep `workspace` alive until backward has been enqueued.  frozen (training mode): per conv
+        layer, True where its BatchNorm uses the running statistics and leaves them untouched (nn.BatchNorm1d in eval mode)."""
+        if not training:
+            frozen = None                    # (eval mode: every layer already runs on the running statistics)
         if noisy.dim() != 3 or noisy.shape[1] != 1:
             raise WunetError(f"input must be [batch, 1, samples], got {tuple(noisy.shape)}")
         # eval mode (enhancement.py:57-69: the same weights over every chunk of every file): the workspace of the previous eval forward
@@ -205,7 +221,9 @@ class Engine:
                 if cache is not None and not cache[1].matches(sig):
                     cache = (cache[0], None)
         if self._fast is not None:
-            with self._using(n_layers, ci, noisy.shape[0], noisy.shape[2], noisy.device) as h:
+            hold = self._using(n_layers, ci, noisy.shape[0], noisy.shape[2], noisy.device)
+            with hold as h:
+                self._set_frozen(hold, frozen)
                 try:
                     out, ws = self._fast.forward(h.value, noisy, params, running, nbt, bool(training), bool(with_backward),
                                                  cache[0] if cache else None, bool(cache and cache[1] is not None))
@@ -219,7 +237,9 @@ class Engine:
         self._require_all(running, "buffer", noisy.device)
         self._require_all(nbt, "buffer", noisy.device)
         B, _, T = noisy.shape
-        with self._using(n_layers, ci, B, T, noisy.device) as h, self._device_guard(noisy.device):
+        hold = self._using(n_layers, ci, B, T, noisy.device)
+        with hold as h, self._device_guard(noisy.device):
+            self._set_frozen(hold, frozen)
             nbytes = self.lib.wunet_workspace_bytes(h, 1 if with_backward else 0)
             reuse = cache is not None and cache[0].numel() * 4 >= nbytes
             ws = cache[0] if reuse else torch.empty(nbytes // 4, dtype=torch.float32, device=noisy.device)
@@ -251,15 +271,18 @@ class Engine:
         with self._lock:
             self._eval_ws.clear()
 
-    def backward(self, n_layers, ci, noisy, params, enhanced, grad_enhanced, ws, grads, layer_range=None, join=True):
+    def backward(self, n_layers, ci, noisy, params, enhanced, grad_enhanced, ws, grads, layer_range=None, join=True, frozen=None):
         """join=False: the caller's stream does not wait for the range's weight gradients (side stream); make a stream see them
-        with `join_weight_gradients` (parallel.GradSync does, on the stream that launches the bucket's all-reduce)."""
+        with `join_weight_gradients` (parallel.GradSync does, on the stream that launches the bucket's all-reduce).
+        frozen: the mask of the training forward that filled `ws` (see `forward`)."""
         B, _, T = noisy.shape
         self._require(grad_enhanced, "grad_output")
         nl = 2 * n_layers + 1
         lb, le = layer_range if layer_range is not None else (0, nl)
         if self._fast is not None and isinstance(grads, FlatGrads):
-            with self._using(n_layers, ci, B, T, noisy.device) as h:
+            hold = self._using(n_layers, ci, B, T, noisy.device)
+            with hold as h:
+                self._set_frozen(hold, frozen)
                 try:
                     self._fast.backward_range(h.value, noisy, params, enhanced, grad_enhanced, ws, grads.flat, grads.offsets, lb, le, bool(join))
                 except RuntimeError as e:
@@ -271,7 +294,9 @@ class Engine:
             gptrs = (ctypes.c_void_p * len(grads.offsets))(*[base + 4 * o for o in grads.offsets])
         else:
             gptrs = self._ptrs(grads)
-        with self._using(n_layers, ci, B, T, noisy.device) as h, self._device_guard(noisy.device):
+        hold = self._using(n_layers, ci, B, T, noisy.device)
+        with hold as h, self._device_guard(noisy.device):
+            self._set_frozen(hold, frozen)
             self._check(fn(h, noisy.data_ptr(), self._ptrs(params), enhanced.data_ptr(), grad_enhanced.data_ptr(), ws.data_ptr(),
                            gptrs, lb, le, self._stream(noisy.device)))
 

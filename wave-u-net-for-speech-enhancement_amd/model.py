@@ -8,7 +8,9 @@ Select it from the reference's config exactly like any other plugin (util/utils.
 same constructor, `forward(input[B,1,T]) -> [B,1,T]`, same 177 state_dict entries
 (`encoder.{i}.main.0.weight`, `encoder.{i}.main.1.running_mean`, `middle.0.*`, `decoder.{i}.main.*`,
 `out.0.*`), same default initialisation under the same seed (the parameter containers are created in
-the reference's order), `.train()/.eval()` switching BatchNorm behaviour, `.to(device)/.cpu()`.
+the reference's order), `.train()/.eval()` switching BatchNorm behaviour, `.to(device)/.cpu()`.  Like the reference's
+nn.BatchNorm1d modules, each layer's BatchNorm obeys its own `.training` flag: a layer put in eval mode inside a training
+model (frozen BatchNorm fine-tuning) normalises with its running statistics, leaves them untouched and back-propagates.
 The arithmetic is not torch's: forward and backward run the hand-written gfx950 kernels behind the
 C ABI of include/wunet_hip.h.  There is no CPU fallback: calling the module on a CPU tensor raises.
 """
@@ -41,28 +43,45 @@ class _WaveUNetFn(torch.autograd.Function):
                                       "(encoder[0] needs no data gradient); detach the input")
         engine = owner._engine()
         running, nbt = owner._wunet_buffers()
-        training = owner.training
+        # Every BatchNorm module obeys its own .training flag.  None frozen: the training forward.  All frozen in an eval-mode model:
+        # the eval forward (inference - enhancement.py's grad-enabled chunks - keeps its path and holds no backward workspace; a
+        # backward runs the forward again first).  Any other mix: the training forward with the frozen layers on their running statistics.
+        frozen = owner._bn_frozen()
+        nfrozen = sum(frozen)
+        training = nfrozen < len(frozen) or owner.training
+        mask = frozen if (training and nfrozen) else None
         # (grad mode is off inside Function.forward and the engine only takes addresses: no detached copies of the 102 parameters)
         out, ws = engine.forward(owner.n_layers, owner.channels_interval, noisy, params, running, nbt,
-                                 training, with_backward=need_grad and training)
-        if training:                      # the kernels updated the running statistics through raw pointers: tell the version counters
+                                 training, with_backward=need_grad and training, frozen=mask)
+        if training and nfrozen < len(frozen):      # the kernels updated running statistics through raw pointers: tell the version counters
             _bump_versions(running + nbt)
         ctx.owner = owner
         ctx.training = training
-        ctx.ws = ws if need_grad else None
+        ctx.frozen = mask if training else frozen
+        ctx.ws = ws if (need_grad and training) else None
         ctx.save_for_backward(noisy, out, *params)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
+        owner = ctx.owner
         if not ctx.training:
-            raise NotImplementedError("backward through eval-mode BatchNorm is not implemented by the HIP path "
-                                      "(the reference only back-propagates in training mode, trainer/trainer.py:34-38)")
+            # eval-mode forward: run it again as a saving training forward with every BatchNorm frozen (the same arithmetic on the
+            # running statistics, which stay untouched), then back-propagate through that
+            noisy, _, *params = ctx.saved_tensors
+            running, nbt = owner._wunet_buffers()
+            out, ws = owner._engine().forward(owner.n_layers, owner.channels_interval, noisy, params, running, nbt, True,
+                                              with_backward=True, frozen=ctx.frozen)
+            return _WaveUNetFn._backward(ctx, grad_out, noisy, out, params, ws)
         if ctx.ws is None:
             raise RuntimeError("backward through this forward has already run: its workspace (the saved activations) was "
                                "released; run the forward again (retain_graph=True cannot keep it)")
-        owner = ctx.owner
         noisy, out, *params = ctx.saved_tensors
+        return _WaveUNetFn._backward(ctx, grad_out, noisy, out, params, ctx.ws)
+
+    @staticmethod
+    def _backward(ctx, grad_out, noisy, out, params, ws):
+        owner = ctx.owner
         engine = owner._engine()
         sizes = [p.numel() for p in params]
         flat = torch.empty(sum(sizes), dtype=torch.float32, device=noisy.device)
@@ -73,10 +92,11 @@ class _WaveUNetFn(torch.autograd.Function):
             offsets.append(off)
             off += n
         fg = FlatGrads(flat, offsets)
+        mask = ctx.frozen if any(ctx.frozen or ()) else None
         if sync is None:
-            engine.backward(owner.n_layers, owner.channels_interval, noisy, params, out, grad_out.contiguous(), ctx.ws, fg)
+            engine.backward(owner.n_layers, owner.channels_interval, noisy, params, out, grad_out.contiguous(), ws, fg, frozen=mask)
         else:
-            sync.run(engine, owner, noisy, params, out, grad_out.contiguous(), ctx.ws, fg, flat)
+            sync.run(engine, owner, noisy, params, out, grad_out.contiguous(), ws, fg, flat, frozen=mask)
         grads = [g.view(p.shape) for g, p in zip(flat.split(sizes), params)]
         owner.last_flat_grad = flat
         ctx.ws = None
@@ -125,6 +145,10 @@ class Model(nn.Module):
         head = self._modules["out"]._modules["0"]
         ps += [P(head, "weight"), P(head, "bias")]
         return ps
+
+    def _bn_frozen(self):
+        """Per conv layer (the C ABI's order): True where its BatchNorm module is in eval mode - what nn.BatchNorm1d obeys."""
+        return tuple(not bn.training for _, bn in self._leaves())
 
     def _wunet_buffers(self):
         running, nbt = [], []

@@ -127,17 +127,17 @@ class GradSync:
             self._launch_streams[device] = torch.cuda.Stream(device=device)
         return self._launch_streams[device]
 
-    def run(self, engine, owner, noisy, params, out, grad_out, ws, grads, flat):
+    def run(self, engine, owner, noisy, params, out, grad_out, ws, grads, flat, frozen=None):
         nl = 2 * owner.n_layers + 1
         world = self.world_size()
         reduce = world > 1 or (self.always_reduce and (dist.is_initialized() or self.comm is not None))
         on_gpu = noisy.is_cuda
         pending = []
         if self.comm is not None and reduce:
-            return self._run_native(engine, owner, noisy, params, out, grad_out, ws, grads, flat, world)
+            return self._run_native(engine, owner, noisy, params, out, grad_out, ws, grads, flat, world, frozen)
         for lb, le, fb, fe in self.ranges_for(params, nl):
             engine.backward(owner.n_layers, owner.channels_interval, noisy, params, out, grad_out, ws, grads,
-                            layer_range=(lb, le), join=not (reduce and on_gpu))
+                            layer_range=(lb, le), join=not (reduce and on_gpu), frozen=frozen)
             if not reduce:
                 continue
             seg = flat[fb:fe]
@@ -158,7 +158,7 @@ class GradSync:
                 seg.mul_(1.0 / world)
         self._mark(noisy, ev)
 
-    def _run_native(self, engine, owner, noisy, params, out, grad_out, ws, grads, flat, world):
+    def _run_native(self, engine, owner, noisy, params, out, grad_out, ws, grads, flat, world, frozen=None):
         """The same schedule with the library's own RCCL entry: every bucket's all-reduce is enqueued on the launch stream C behind
         the events of S (data path) and W (weight gradients); S joins C once at the end.  Nothing here touches a process group
         or a host-side work handle, so the whole backward - collectives included - is capturable in the step's hipGraph."""
@@ -168,7 +168,7 @@ class GradSync:
         launch = self._launch_stream(noisy.device) if on_gpu else None
         for lb, le, fb, fe in self.ranges_for(params, nl):
             engine.backward(owner.n_layers, owner.channels_interval, noisy, params, out, grad_out, ws, grads,
-                            layer_range=(lb, le), join=not on_gpu)
+                            layer_range=(lb, le), join=not on_gpu, frozen=frozen)
             seg = flat[fb:fe]
             if on_gpu:
                 launch.wait_stream(main)

@@ -84,6 +84,7 @@ class Trainer:
             optimizer.device_step = True
         self._graph = None
         self._graph_sig = None
+        self._graph_bn = None          # the BatchNorm modes of the live graph (_bn_signature)
         self._static = None
         self._eager_steps = 0
         self._recaptures = 0          # consecutive graphs, dropped for a changed lr / betas / eps, that did not earn their capture back
@@ -165,12 +166,24 @@ class Trainer:
             self._static_loss = loss.detach()
         self._graph = graph
         self._graph_sig = self.optimizer.hyper_signature()
+        self._graph_bn = self._bn_signature()
         # capture does not execute: undo the host-side count of the captured call; every replay counts itself
         self.optimizer.advance_host_step(-1)
+
+    def _bn_signature(self):
+        """The BatchNorm modes the captured step was enqueued with (which layers are frozen, eval or training forward): part of
+        the launches' arguments, so a change needs a new capture."""
+        m = getattr(self.model, "module", self.model)
+        frozen = getattr(m, "_bn_frozen", None)
+        return (m.training, frozen() if frozen is not None else None)
 
     def _step(self, mixture, clean):
         if not self.use_graph:
             return self._eager_step(mixture, clean)
+        if self._graph is not None and self._bn_signature() != self._graph_bn:
+            # a BatchNorm module changed mode (frozen-BatchNorm fine-tuning): not a hyper-parameter change, capture again
+            self._graph = None
+            self._replays = 0
         if self._graph is not None and self.optimizer.hyper_signature() != self._graph_sig:
             # lr / betas / eps / grad_scale are kernel arguments of the captured Adam step: a scheduler, a manual decay or a
             # load_state_dict with another lr would be ignored by the replay - capture again with the new values.  A schedule that
