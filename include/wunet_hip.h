@@ -90,7 +90,7 @@ int wunet_forward(wunet_ctx* ctx, const float* noisy, const float* const* params
  * Must follow a training-mode wunet_forward on the same ctx/workspace/params/noisy.
  * grad_enhanced: dL/d(enhanced) [B,1,T].  grads: same shapes/order as params; every tensor is
  * overwritten (conv biases feeding a batch-statistics BatchNorm get an exact 0; a layer frozen by wunet_set_bn_frozen gets
- * its true bias gradient).  No input gradient. */
+ * its true bias gradient).  The gradient with respect to `noisy` is a separate call: wunet_backward_input. */
 int wunet_backward(wunet_ctx* ctx, const float* noisy, const float* const* params,
                    const float* enhanced, const float* grad_enhanced, void* workspace,
                    float* const* grads, void* stream);
@@ -109,6 +109,15 @@ int wunet_backward_range_async(wunet_ctx* ctx, const float* noisy, const float* 
                                const float* enhanced, const float* grad_enhanced, void* workspace,
                                float* const* grads, int layer_begin, int layer_end, void* stream);
 int wunet_backward_join(wunet_ctx* ctx, void* stream);
+/* autograd's gradient with respect to the waveform input of Model.forward (model/unet_basic.py:77-100): grad_noisy [B,1,T]
+ * receives dL/d(noisy) and is overwritten.  Must follow the backward call that covers layer 0 (wunet_backward, or the _range /
+ * _range_async call with layer_begin == 0) with the same ctx, workspace, params, frozen mask and stream, before the next forward on
+ * that workspace: it reads what that backward left in the workspace (the head gradient, encoder.0's gradient or the data gradients
+ * it is rebuilt from).  Capture-safe: no allocation, no synchronisation, no host read-back.  Changes nothing else - parameter
+ * gradients, running statistics and the workspace size are those of the backward alone.  No reference counterpart (the reference
+ * gets it from autograd). */
+int wunet_backward_input(wunet_ctx* ctx, const float* noisy, const float* const* params, void* workspace,
+                         float* grad_noisy, void* stream);
 
 /* Replaces loss_function(clean, enhanced) (trainer/trainer.py:36; model/loss.py:3-7), mean reduction.
  * scratch: >= wunet_loss_scratch_bytes() device bytes.  loss_out: device float. */

@@ -18,7 +18,7 @@ EXPORTS = [
     "wunet_adam_step", "wunet_set_h3", "wunet_op_conv1d_split", "wunet_op_conv1d_dgrad_split", "wunet_op_conv1d_wgrad_split",
     "wunet_backward_range_async", "wunet_backward_join", "wunet_debug_set_conv_trace", "wunet_crop_windows",
     "wunet_comm_unique_id", "wunet_comm_create", "wunet_comm_allreduce_sum", "wunet_comm_world", "wunet_comm_destroy",
-    "wunet_debug_stamps", "wunet_set_bn_frozen",
+    "wunet_debug_stamps", "wunet_set_bn_frozen", "wunet_backward_input",
 ]
 
 _vp = ctypes.c_void_p
@@ -40,6 +40,8 @@ def declare(lib):
     lib.wunet_backward_range.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]
     lib.wunet_backward_range_async.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]
     lib.wunet_backward_join.argtypes = [_vp, _vp]
+    if hasattr(lib, "wunet_backward_input"):     # (saved libraries of earlier versions do not have it)
+        lib.wunet_backward_input.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp]
     lib.wunet_loss_scratch_bytes.restype = _sz
     lib.wunet_loss_scratch_bytes.argtypes = []
     lib.wunet_loss_forward.argtypes = [_i, _vp, _vp, _sz, _vp, _vp, _vp]

@@ -3,6 +3,7 @@
 #include "wunet_elementwise.h"
 #include "wunet_tiny.h"
 #include "wunet_h3_elem.h"
+#include "wunet_input_grad.h"
 
 using namespace wunet_host;
 
@@ -35,6 +36,34 @@ bool dx_stays_split(const wunet_ctx* c, int i)
     if (i < 1 || i > c->n) return false;
     const LayerPlan& l = c->ly[i];
     return l.d.ksplit > 1 && l.L >= 4 && c->ly[i - 1].L >= 4;       // (neither end on the scalar kernels of the 1-2-sample levels)
+}
+
+// How the backward assembles layer i's gradient, and so where its g_z ends up.  One definition for backward_range_impl and for
+// wunet_backward_input, which reads the first layer's g_z in whatever form that backward left it (first_layer_gz_source).
+struct BwdLayerPath {
+    bool tiny;          // a level of < 4 samples: the scalar kernels (g_z written in place of g)
+    bool fuse;          // a whole channel in one pass of one block: finalize and g_z inside pass A (g_z written in place of g)
+    bool gz_in_wgrad;   // the first layer: g stored, its weight gradient forms g_z while it stages its chunks
+    bool e0;            // ... and its weight gradient's sums are taken by pass A instead: nothing written
+};
+BwdLayerPath bwd_layer_path(const wunet_ctx* c, int i)
+{
+    const LayerPlan& l = c->ly[i];
+    BwdLayerPath q;
+    q.tiny = l.L < 4;
+    const bool one_block = l.a_split == 1 && (size_t)c->B * l.L <= 4 * WUNET_THREADS;
+    q.gz_in_wgrad = i == 0 && !q.tiny && !l.h3d && !l.h3w && l.w.wsplit && !one_block;     // (not where pass A finishes g_z itself)
+    q.fuse = !q.tiny && i < c->NL - 1 && !(i > 0 && l.h3d) && one_block;
+    q.e0 = c->e0 && q.gz_in_wgrad && !q.fuse && l.cin == 1 && l.taps == 15 && l.L >= 16 && !dx_stays_split(c, 1) && c->n >= 1;
+    return q;
+}
+
+// input_grad_kernel's mode: the first layer's g_z rebuilt from its consumers' data gradients (E0 wrote nothing), formed from the stored g,
+// or read as stored (gz_materialize_kernel in place, pass A's fused finalize, the scalar kernels)
+int first_layer_gz_source(const wunet_ctx* c)
+{
+    const BwdLayerPath q = bwd_layer_path(c, 0);
+    return q.e0 ? IG_ENC : q.gz_in_wgrad ? IG_G : IG_GZ;
 }
 
 int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* params, const float* enhanced,
@@ -101,18 +130,18 @@ int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* pa
         // grid (pieces, channels): consecutive blocks walk consecutive pieces of ONE channel row (rounds 1 - 3 had (channels, pieces):
         // neighbours 4 L bytes apart; 5.156 -> 5.139 ms per step; WUNET_PA_SWAP=0: A/B switch)
         static const int pa_swap = getenv("WUNET_PA_SWAP") ? atoi(getenv("WUNET_PA_SWAP")) : 1;
-        const bool tiny = l.L < 4;
+        const BwdLayerPath path = bwd_layer_path(c, i);
+        const bool tiny = path.tiny;
         p.swap = (pa_swap && l.a_split > 1 && !tiny) ? 1 : 0;        // (pass_a_scalar_kernel reads its channel from blockIdx.x)
         const dim3 ga(p.swap ? l.a_split : l.cout, p.swap ? l.cout : l.a_split);
         // the first layer's g_z has one reader: its weight gradient forms it while it stages its chunks (WUNET_NO_GZ_FUSE: A/B switch)
-        const bool gz_in_wgrad = i == 0 && !tiny && !l.h3d && !l.h3w && l.w.wsplit &&
-                                 !(l.a_split == 1 && (size_t)c->B * l.L <= 4 * WUNET_THREADS);       // (not where pass A finishes g_z itself)
+        const bool gz_in_wgrad = path.gz_in_wgrad;
         // a whole channel in one pass of one block (the levels of <= 16 samples at batch 64): BatchNorm-backward finalize and
         // g_z inside pass A - two launches of ~5 us (latency, not bandwidth) less per such level
-        const bool fuse = !tiny && i < NL - 1 && !(i > 0 && l.h3d) && l.a_split == 1 && (size_t)c->B * l.L <= 4 * WUNET_THREADS;
+        const bool fuse = path.fuse;
         // the first layer (Cin = 1, 15 taps): its weight gradient's sums are taken by this pass and finished by the finalize - no g written, no
         // weight-gradient GEMM, no split reduce (the last 66 us of the backward, alone on the chip; WUNET_NO_E0=1 when the context is planned: A/B switch)
-        const bool e0 = c->e0 && gz_in_wgrad && !fuse && l.cin == 1 && l.taps == 15 && l.L >= 16 && !dx_stays_split(c, 1) && n >= 1;
+        const bool e0 = path.e0;
         if (fuse) {
             p.gamma = params[4 * i + 2]; p.dgamma = grads[4 * i + 2]; p.dbeta = grads[4 * i + 3]; p.dbias = grads[4 * i + 1];
             p.k1 = ws + l.k1; p.k2 = ws + l.k2; p.k3 = ws + l.k3; p.count = (double)c->B * l.Lt; p.frozen = fz;
@@ -456,6 +485,38 @@ int wunet_backward(wunet_ctx* c, const float* noisy, const float* const* params,
 {
     if (!c) return fail(WUNET_E_ARG, "null ctx");
     return backward_range_impl(c, noisy, params, enhanced, grad_enhanced, workspace, grads, 0, c->NL, stream, true);
+}
+
+int wunet_backward_input(wunet_ctx* c, const float* noisy, const float* const* params, void* workspace, float* grad_noisy, void* stream)
+{
+    // (noisy is not read: the input enters the network linearly - the head's input channel and encoder.0's conv)
+    if (!c || !noisy || !params || !workspace || !grad_noisy) return fail(WUNET_E_ARG, "null argument");
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const LayerPlan& l = c->ly[0];
+    const int src = first_layer_gz_source(c);
+    InputGradArgs A{};
+    A.z = ws + l.z; A.k1 = ws + l.k1; A.k2 = ws + l.k2; A.k3 = ws + l.k3;
+    A.w0 = params[0]; A.wh = params[4 * c->NL]; A.gh = ws + c->gh_off; A.dx = grad_noisy;
+    A.B = c->B; A.C = l.cout; A.L = l.L; A.Lt = l.Lt; A.Tt = c->Tt;
+    A.vec = (reinterpret_cast<size_t>(grad_noisy) & 15) == 0 && (c->Tt & 3) == 0;
+    if (src == IG_ENC) {
+        const LayerPlan& dc = c->ly[2 * c->n];
+        A.a = ws + l.a; A.s = ws + l.s; A.gd = ws + dc.dx; A.Cg0 = dc.cin; A.coff = dc.c0; A.ge = ws + c->ly[1].dx;
+    } else {
+        A.g = ws + l.g;
+    }
+    const dim3 grid((unsigned)((l.L + WUNET_IG_TP - 1) / WUNET_IG_TP), (unsigned)c->B);
+    // algorithmic bytes: z + the rebuilt gradient's sources (IG_ENC: skip rows, half-length encoder.1 rows), g or g_z; gh read, the result written
+    const double pe = (double)c->B * l.cout * l.L;
+    prof_begin(st, src == IG_ENC ? "input_grad_kernel<ENC>" : src == IG_G ? "input_grad_kernel<G>" : "input_grad_kernel<GZ>",
+               2.0 * 15.0 * pe, pe * (src == IG_ENC ? 10.0 : src == IG_G ? 8.0 : 4.0) + 4.0 * c->B * ((double)l.L + c->Tt));
+    if (src == IG_ENC) WUNET_LAUNCH(input_grad_kernel<IG_ENC>, grid, dim3(WUNET_THREADS), 0, st, A);
+    else if (src == IG_G) WUNET_LAUNCH(input_grad_kernel<IG_G>, grid, dim3(WUNET_THREADS), 0, st, A);
+    else WUNET_LAUNCH(input_grad_kernel<IG_GZ>, grid, dim3(WUNET_THREADS), 0, st, A);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
 }
 
 }  // extern "C"

@@ -300,6 +300,17 @@ class Engine:
             self._check(fn(h, noisy.data_ptr(), self._ptrs(params), enhanced.data_ptr(), grad_enhanced.data_ptr(), ws.data_ptr(),
                            gptrs, lb, le, self._stream(noisy.device)))
 
+    def backward_input(self, n_layers, ci, noisy, params, ws):
+        """dL/d(noisy) [B, 1, T] (include/wunet_hip.h: wunet_backward_input): enqueued on the current stream right behind the backward
+        call that covered layer 0 on `ws` (same context, frozen mask and stream)."""
+        self._require(noisy, "input")
+        B, _, T = noisy.shape
+        g = torch.empty_like(noisy)
+        with self._using(n_layers, ci, B, T, noisy.device) as h, self._device_guard(noisy.device):
+            self._check(self.lib.wunet_backward_input(h, noisy.data_ptr(), self._ptrs(params), ws.data_ptr(), g.data_ptr(),
+                                                      self._stream(noisy.device)))
+        return g
+
     def join_weight_gradients(self, n_layers, ci, noisy):
         """Torch's current stream waits for everything the weight-gradient side stream has been given so far."""
         B, _, T = noisy.shape

@@ -38,9 +38,9 @@ class _Level(nn.Module):
 class _WaveUNetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, owner, need_grad, noisy, *params):
-        if noisy.requires_grad:           # before anything runs: a training-mode forward updates the running statistics
-            raise NotImplementedError("gradient w.r.t. the waveform input is not part of the reference hot path "
-                                      "(encoder[0] needs no data gradient); detach the input")
+        if noisy.requires_grad and not getattr(owner, "input_grad", False):     # before anything runs: a training-mode forward updates the running statistics
+            raise NotImplementedError("gradient w.r.t. the waveform input is off by default (the training step needs none): build the "
+                                      "model with Model(..., input_grad=True) or set model.input_grad = True, or detach the input")
         engine = owner._engine()
         running, nbt = owner._wunet_buffers()
         # Every BatchNorm module obeys its own .training flag.  None frozen: the training forward.  All frozen in an eval-mode model:
@@ -97,17 +97,23 @@ class _WaveUNetFn(torch.autograd.Function):
             engine.backward(owner.n_layers, owner.channels_interval, noisy, params, out, grad_out.contiguous(), ws, fg, frozen=mask)
         else:
             sync.run(engine, owner, noisy, params, out, grad_out.contiguous(), ws, fg, flat, frozen=mask)
+        # the input gradient: behind the backward's last range on this stream, from what it left in the workspace (each rank's own
+        # input: not reduced, not scaled)
+        gx = engine.backward_input(owner.n_layers, owner.channels_interval, noisy, params, ws) if ctx.needs_input_grad[2] else None
         grads = [g.view(p.shape) for g, p in zip(flat.split(sizes), params)]
         owner.last_flat_grad = flat
         ctx.ws = None
-        return (None, None, None, *grads)
+        return (None, None, gx, *grads)
 
 
 class Model(nn.Module):
-    def __init__(self, n_layers=12, channels_interval=24):
+    def __init__(self, n_layers=12, channels_interval=24, input_grad=False):
         super().__init__()
         self.n_layers = n_layers
         self.channels_interval = channels_interval
+        # an input that requires grad gets dL/d(input) (cascades, a trainable front end, attacks / saliency on a trained model); off:
+        # such an input is refused, as the reference hot path never needs it
+        self.input_grad = input_grad
         shapes = conv_layer_shapes(n_layers, channels_interval)
         enc, mid, dec = shapes[:n_layers], shapes[n_layers], shapes[n_layers + 1:]
         # construction order == reference order, so default init consumes the RNG identically
@@ -162,5 +168,5 @@ class Model(nn.Module):
         if input.dtype != torch.float32:
             raise TypeError(f"Model expects float32 waveforms, got {input.dtype}")
         params = self._wunet_params()
-        need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        need_grad = torch.is_grad_enabled() and ((getattr(self, "input_grad", False) and input.requires_grad) or any(p.requires_grad for p in params))
         return _WaveUNetFn.apply(self, need_grad, input.contiguous(), *params)
