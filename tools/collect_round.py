@@ -43,9 +43,8 @@ def lib_name(k):
     base, args = k.split("<", 1)
     a = [t.strip() for t in args.rstrip(">").split(",")]
     if base == "conv_h3d_kernel":
-        mode = a[5] if len(a) > 5 else "0"           # (BSUM template argument: 1 / 2 = BatchNorm-backward sums in the epilogue, 3 = UPT)
         return "%s<%s, %s, %s%s>" % (base, a[0], a[1], a[2], ", bf16" if len(a) > 3 and a[3] == "true" else ", evop" if len(a) > 4 and a[4] == "true" else
-                                     ", upt" if mode == "3" else ", bsum" if mode in ("1", "2") else "")
+                                     ", upt" if len(a) > 5 and a[5] == "true" else "")
     if base == "conv_h3u_kernel":
         return "%s<%s>" % (base, a[0])
     if base == "wgrad_h3d_kernel":

@@ -38,23 +38,112 @@ bool dx_stays_split(const wunet_ctx* c, int i)
     return l.d.ksplit > 1 && l.L >= 4 && c->ly[i - 1].L >= 4;       // (neither end on the scalar kernels of the 1-2-sample levels)
 }
 
-// How the backward assembles layer i's gradient, and so where its g_z ends up.  One definition for backward_range_impl and for
-// wunet_backward_input, which reads the first layer's g_z in whatever form that backward left it (first_layer_gz_source).
-struct BwdLayerPath {
-    bool tiny;          // a level of < 4 samples: the scalar kernels (g_z written in place of g)
-    bool fuse;          // a whole channel in one pass of one block: finalize and g_z inside pass A (g_z written in place of g)
+// ---- A/B switches of the backward's elementwise passes, read once per process
+// WUNET_NO_ENC_GZ=1: the encoder layers' g written by pass A and read back instead of recomputed by gz_split_h3_kernel
+bool enc_gz_off()
+{
+    static const bool off = getenv("WUNET_NO_ENC_GZ") != nullptr;
+    return off;
+}
+// WUNET_PA_SWAP=0: pass A on the (channels, pieces) grid of rounds 1 - 3
+bool pa_swap_on()
+{
+    static const int on = getenv("WUNET_PA_SWAP") ? atoi(getenv("WUNET_PA_SWAP")) : 1;
+    return on != 0;
+}
+
+// a level of < 4 samples: the scalar kernels (g_z written in place of g)
+bool bwd_tiny(const wunet_ctx* c, int i) { return c->ly[i].L < 4; }
+// a whole channel in one pass of one block (the levels of <= 16 samples at batch 64)
+bool bwd_one_block(const wunet_ctx* c, int i) { return c->ly[i].a_split == 1 && (size_t)c->B * c->ly[i].L <= 4 * WUNET_THREADS; }
+// ... with the BatchNorm-backward finalize and g_z inside pass A - two launches of ~5 us (latency, not bandwidth) less per such level
+bool bwd_fuse(const wunet_ctx* c, int i) { return !bwd_tiny(c, i) && i < c->NL - 1 && !(i > 0 && c->ly[i].h3d) && bwd_one_block(c, i); }
+
+// The UPT hand-off (planned by layout_workspace, LayerPlan::upt) is ONE decision read by both of its ends: decoder layer q's data
+// gradient stores the rows of its upsampled half at the producer's resolution (conv_h3d_kernel<.., UPT>: dxh, usp) if and only if pass A
+// and gz_split_h3_kernel of layer q - 1 read them there (pass_a_kernel<A_UPH>, GZ_UPH) - the producer's gradient assembly is then
+// elementwise.  Were the two ends decided apart and ever disagreed, pass_a_kernel<A_UP> would read stale rows of dx.
+bool upt_handoff(const wunet_ctx* c, int q) { return q > c->n && q < c->NL && c->ly[q].upt; }
+// what both ends rely on at run time: the data gradient un-split on the split kernels, its upsampled half produced by layer q - 1, that
+// layer's g_z on the split kernels (neither the scalar kernels nor the finalize inside pass A)
+bool upt_handoff_sound(const wunet_ctx* c, int q)
+{
+    const LayerPlan& l = c->ly[q];
+    return l.src0 == q - 1 && l.h3d && l.d.ksplit == 1 && c->ly[q - 1].h3d && !bwd_tiny(c, q - 1) && !bwd_fuse(c, q - 1);
+}
+
+// How the backward runs layer i: which kernels, who reads what, and so where its g_z ends up.  The one place where these decisions are
+// made - a function of the context and the layer alone (the frozen mask is run-time state and not part of it) - for the stages of
+// backward_range_impl and for wunet_backward_input, which reads the first layer's g_z in whatever form that backward left it
+// (first_layer_gz_source).
+enum { DG_NONE = 0, DG_H3 = 1, DG_SCALAR = 2, DG_FP32 = 3 };
+struct BwdLayerPlan {
+    bool tiny;          // bwd_tiny
+    bool fuse;          // bwd_fuse: finalize and g_z inside pass A (g_z written in place of g)
+    bool gz_h3;         // g_z on the split kernels: pass A also takes the maxima, gz_split_h3_kernel scales and splits
     bool gz_in_wgrad;   // the first layer: g stored, its weight gradient forms g_z while it stages its chunks
     bool e0;            // ... and its weight gradient's sums are taken by pass A instead: nothing written
+    // pass A: its source of dL/d(activation) (A_HEAD / A_UPH / A_UP / A_ENC), the bytes per element it reads there, whether it stores g
+    // (no: gz_split_h3_kernel forms g again from the same source - its HEAD / ENC / UPH modes - or, E0, nobody reads it)
+    int pa_mode;
+    const char* pa_name;
+    double g_src_bytes;
+    bool stores_g;
+    bool swap;          // grid (pieces, channels) instead of (channels, pieces)
+    bool g1_split;      // A_ENC: the next encoder layer's data gradient arrives as split-K partials (dx_stays_split)
+    bool fin_in_gz;     // the finalize runs in the prologue of gz_split_h3_kernel's blocks
+    int gz_mode;        // gz_split_h3_kernel's source of g: GZ_G, or pass A's source again
+    // the data gradient: family, split-K partials summed by split_sum_kernel or left to the reader (dx_stays_split), UPT hand-off
+    int dgrad;
+    bool dx_split, dx_sum;
+    bool upt;           // upt_handoff(c, i): this layer's data gradient writes the half-resolution rows
+    // algorithmic bytes per element of the gradient assembly (HBM-bound): z + the source of g read, g written where it is stored
+    double pa_bytes() const { return 4.0 + g_src_bytes + (stores_g ? 4.0 : 0.0); }
+    // ... and of gz_split_h3_kernel, without its output: z + g, or g's source again
+    double gz_bytes() const { return 4.0 + (gz_mode == GZ_G ? 4.0 : g_src_bytes); }
 };
-BwdLayerPath bwd_layer_path(const wunet_ctx* c, int i)
+BwdLayerPlan bwd_layer_plan(const wunet_ctx* c, int i)
 {
     const LayerPlan& l = c->ly[i];
-    BwdLayerPath q;
-    q.tiny = l.L < 4;
-    const bool one_block = l.a_split == 1 && (size_t)c->B * l.L <= 4 * WUNET_THREADS;
-    q.gz_in_wgrad = i == 0 && !q.tiny && !l.h3d && !l.h3w && l.w.wsplit && !one_block;     // (not where pass A finishes g_z itself)
-    q.fuse = !q.tiny && i < c->NL - 1 && !(i > 0 && l.h3d) && one_block;
-    q.e0 = c->e0 && q.gz_in_wgrad && !q.fuse && l.cin == 1 && l.taps == 15 && l.L >= 16 && !dx_stays_split(c, 1) && c->n >= 1;
+    const int NL = c->NL, n = c->n;
+    BwdLayerPlan q{};
+    q.tiny = bwd_tiny(c, i);
+    q.fuse = bwd_fuse(c, i);
+    q.gz_h3 = i > 0 && l.h3d;
+    // the first layer's g_z has one reader: its weight gradient forms it while it stages its chunks (not where pass A finishes g_z itself)
+    q.gz_in_wgrad = i == 0 && !q.tiny && !l.h3d && !l.h3w && l.w.wsplit && !bwd_one_block(c, i);
+    // the first layer (Cin = 1, 15 taps): its weight gradient's sums are taken by pass A and finished by the finalize - no g written, no
+    // weight-gradient GEMM, no split reduce (the last 66 us of the backward, alone on the chip; WUNET_NO_E0=1 when the context is planned: A/B switch)
+    q.e0 = c->e0 && q.gz_in_wgrad && !q.fuse && l.cin == 1 && l.taps == 15 && l.L >= 16 && !dx_stays_split(c, 1) && n >= 1;
+    const bool recompute = q.gz_h3 && !q.fuse && !q.tiny;      // gz_split_h3_kernel can form g itself
+    q.stores_g = true;
+    if (i == NL - 1) {
+        // the last layer on the split kernels: its g is recomputed from the head gradient by gz_split_h3_kernel (HEAD mode), not stored
+        q.pa_mode = A_HEAD; q.pa_name = "pass_a_kernel<HEAD>"; q.g_src_bytes = 0.0; q.gz_mode = GZ_HEAD;
+        q.stores_g = !recompute;
+    } else if (i >= n && upt_handoff(c, i + 1)) {
+        // a layer behind an upsample whose consumer's data gradient arrives at this layer's resolution: g is not stored
+        q.pa_mode = A_UPH; q.pa_name = "pass_a_kernel<UPH>"; q.g_src_bytes = 4.0; q.gz_mode = GZ_UPH;
+        q.stores_g = false;
+    } else if (i >= n) {
+        q.pa_mode = A_UP; q.pa_name = "pass_a_kernel<UP>"; q.g_src_bytes = 8.0; q.gz_mode = GZ_G;
+    } else {
+        // an encoder layer on the split kernels whose two data gradients are whole tensors: g is recomputed by gz_split_h3_kernel (ENC
+        // mode) from them instead of written here and read back (WUNET_NO_ENC_GZ=1: A/B switch)
+        q.g1_split = dx_stays_split(c, i + 1);
+        q.pa_mode = A_ENC; q.pa_name = q.e0 ? "pass_a_kernel<ENC, e0>" : "pass_a_kernel<ENC>"; q.g_src_bytes = 6.0; q.gz_mode = GZ_ENC;
+        q.stores_g = !(!enc_gz_off() && recompute && !q.g1_split) && !q.e0;
+    }
+    if (q.stores_g) q.gz_mode = GZ_G;
+    // grid (pieces, channels): consecutive blocks walk consecutive pieces of ONE channel row (rounds 1 - 3 had (channels, pieces):
+    // neighbours 4 L bytes apart; 5.156 -> 5.139 ms per step; WUNET_PA_SWAP=0: A/B switch)
+    q.swap = pa_swap_on() && l.a_split > 1 && !q.tiny;        // (pass_a_scalar_kernel reads its channel from blockIdx.x)
+    // (short levels on the split kernels: the finalize runs in the prologue of gz_split_h3_kernel's blocks instead of a launch of its own)
+    q.fin_in_gz = !q.fuse && q.gz_h3 && l.a_split * l.cout <= WUNET_GZ_FIN_LOADS && l.cout <= WUNET_GZ_FIN_C;
+    q.dgrad = i == 0 ? DG_NONE : l.h3d ? DG_H3 : q.tiny ? DG_SCALAR : DG_FP32;      // (not needed for the first layer)
+    q.dx_split = q.dgrad != DG_NONE && q.dgrad != DG_SCALAR && l.d.ksplit > 1;
+    q.dx_sum = q.dx_split && !dx_stays_split(c, i);
+    q.upt = upt_handoff(c, i);
     return q;
 }
 
@@ -62,8 +151,277 @@ BwdLayerPath bwd_layer_path(const wunet_ctx* c, int i)
 // or read as stored (gz_materialize_kernel in place, pass A's fused finalize, the scalar kernels)
 int first_layer_gz_source(const wunet_ctx* c)
 {
-    const BwdLayerPath q = bwd_layer_path(c, 0);
+    const BwdLayerPlan q = bwd_layer_plan(c, 0);
     return q.e0 ? IG_ENC : q.gz_in_wgrad ? IG_G : IG_GZ;
+}
+
+// what every stage of one backward call shares
+struct BwdCall {
+    wunet_ctx* c; float* ws; const float* const* params; float* const* grads; const float* noisy;
+    hipStream_t st, sd;           // the caller's stream (the critical chain), the weight gradients' stream (== st: one stream)
+    wunet_ctx::Side* side;
+};
+
+// ---- the backward's weight packs and the head: gh = gout * tanh', d wh, d bh
+int head_backward(const BwdCall& k, void* workspace, const float* enhanced, const float* grad_enhanced)
+{
+    wunet_ctx* c = k.c; float* ws = k.ws; const hipStream_t st = k.st;
+    // flipped/transposed weights for every data gradient: already enqueued on the side stream by the training forward of this
+    // workspace (they only depend on the weights: off the critical path), else packed here
+    if (k.side->packed_ws == workspace && k.sd != st) {
+        k.side->packed_ws = nullptr;
+        if (hipStreamWaitEvent(st, k.side->ev_pack, 0) != hipSuccess) return fail(WUNET_E_RUNTIME, "waiting for the weight packs failed");
+    } else {
+        k.side->packed_ws = nullptr;
+        const int rc = launch_backward_packs(c, k.params, ws, st);
+        if (rc) return rc;
+    }
+    const LayerPlan& l = c->ly[c->NL - 1];
+    HeadBwdArgs h{};
+    h.z = ws + l.z; h.a = ws + l.a; h.s = ws + l.s; h.in = k.noisy; h.out = enhanced; h.gout = grad_enhanced;
+    h.gh = ws + c->gh_off; h.part = ws + c->hpart_off; h.B = c->B; h.C = c->ci; h.T = c->T; h.logT = ilog2(c->T);
+    WUNET_LAUNCH(head_bwd_kernel, dim3(c->head_blocks), dim3(WUNET_THREADS), 0, st, h);
+    WUNET_CHECK_LAUNCH();
+    // (d(weight of the input channel), d bias and the ci per-channel head-weight gradients - sums of head_bwd_kernel's and of the last layer's
+    //  pass A's partial rows - are parameter gradients nothing on the chain reads: they are taken on the weight-gradient stream, weight_gradient)
+    return WUNET_OK;
+}
+
+// ---- pass A: assemble dL/d(BN output), LeakyReLU', BN-backward partial sums
+// (fz: the layer is frozen by wunet_set_bn_frozen - running statistics in the forward: every finalize emits g_z = a g (k2 = k3 = 0) and the
+//  conv bias's gradient a sum g)
+int pass_a(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
+{
+    wunet_ctx* c = k.c; float* ws = k.ws; const hipStream_t st = k.st;
+    const int NL = c->NL, n = c->n;
+    const LayerPlan& l = c->ly[i];
+    PassAArgs p{};
+    p.z = ws + l.z; p.a = ws + l.a; p.s = ws + l.s; p.mean = ws + l.mean; p.rstd = ws + l.rstd;
+    p.gpre = q.stores_g ? ws + l.g : nullptr; p.part = ws + c->bpart_off; p.pmax = q.gz_h3 ? ws + c->bmax_off : nullptr;
+    p.B = c->B; p.C = l.cout; p.L = l.L; p.logL = l.logL; p.Lt = l.Lt;
+    p.swap = q.swap ? 1 : 0;
+    const dim3 ga(p.swap ? l.a_split : l.cout, p.swap ? l.cout : l.a_split);
+    if (q.fuse) {
+        p.gamma = k.params[4 * i + 2]; p.dgamma = k.grads[4 * i + 2]; p.dbeta = k.grads[4 * i + 3]; p.dbias = k.grads[4 * i + 1];
+        p.k1 = ws + l.k1; p.k2 = ws + l.k2; p.k3 = ws + l.k3; p.count = (double)c->B * l.Lt; p.frozen = fz;
+    }
+    prof_begin(st, q.pa_name, 0.0, (double)c->B * l.cout * l.L * q.pa_bytes() + (q.pa_mode == A_HEAD ? 4.0 * c->B * l.L : 0.0));
+    if (q.pa_mode == A_HEAD) {
+        p.g0 = ws + c->gh_off; p.g1 = k.params[4 * NL]; p.hpart = ws + c->hpart2_off;
+        WUNET_LAUNCH(pass_a_kernel<A_HEAD>, ga, dim3(WUNET_THREADS), 0, st, p);      // (the last layer has T >= 4 samples)
+    } else if (q.pa_mode == A_UPH) {
+        // the next decoder layer's data gradient arrived at THIS resolution (conv_h3d_kernel<.., UPT>): elementwise; g is not stored -
+        // gz_split_h3_kernel forms it again from the same two arrays (UPH mode)
+        const LayerPlan& nx = c->ly[i + 1];
+        p.g0 = ws + nx.dxh; p.sp = ws + nx.usp; p.ntiles = (int)(((size_t)c->B * nx.L + 255) / 256); p.tpr = l.L >> 7;
+        WUNET_LAUNCH(pass_a_kernel<A_UPH>, ga, dim3(WUNET_THREADS), 0, st, p);
+    } else if (q.pa_mode == A_UP) {
+        const LayerPlan& nx = c->ly[i + 1];
+        p.g0 = ws + nx.dx; p.Cg0 = nx.cin;
+        p.up_scale = (float)(l.Lt - 1) / (float)(2 * l.Lt - 1);
+        if (q.tiny) WUNET_LAUNCH(pass_a_scalar_kernel<A_UP>, ga, dim3(WUNET_THREADS), 0, st, p);
+        else if (q.fuse) WUNET_LAUNCH((pass_a_kernel<A_UP, true>), ga, dim3(WUNET_THREADS), 0, st, p);
+        else WUNET_LAUNCH(pass_a_kernel<A_UP>, ga, dim3(WUNET_THREADS), 0, st, p);
+    } else {
+        const LayerPlan& dc = c->ly[2 * n - i];
+        const LayerPlan& nx = c->ly[i + 1];
+        p.g0 = ws + dc.dx; p.Cg0 = dc.cin; p.coff = dc.c0; p.g1 = ws + nx.dx;
+        if (q.g1_split) {
+            p.g1 = ws + c->spart_off; p.g1_splits = nx.d.ksplit; p.g1_stride = (size_t)c->B * nx.cin * nx.L;
+        }
+        if (q.e0) { p.x0 = k.noisy; p.e0rows = ws + c->e0part_off; }
+        if (q.tiny) WUNET_LAUNCH(pass_a_scalar_kernel<A_ENC>, ga, dim3(WUNET_THREADS), 0, st, p);
+        else if (q.e0) WUNET_LAUNCH((pass_a_kernel<A_ENC, false, false, true>), ga, dim3(WUNET_THREADS), 0, st, p);
+        else if (q.fuse && p.g1_splits > 1) WUNET_LAUNCH((pass_a_kernel<A_ENC, true, true>), ga, dim3(WUNET_THREADS), 0, st, p);
+        else if (q.fuse) WUNET_LAUNCH((pass_a_kernel<A_ENC, true>), ga, dim3(WUNET_THREADS), 0, st, p);
+        else if (p.g1_splits > 1) WUNET_LAUNCH((pass_a_kernel<A_ENC, false, true>), ga, dim3(WUNET_THREADS), 0, st, p);
+        else WUNET_LAUNCH(pass_a_kernel<A_ENC>, ga, dim3(WUNET_THREADS), 0, st, p);
+    }
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---- BatchNorm-backward finalize, then g_z = k1*g + k2*z + k3, materialised once for both gradient GEMMs (fp32 in place, or scaled
+// hi/lo halves).  (Not for a fused layer: pass A did both.)
+int finalize_and_gz(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
+{
+    wunet_ctx* c = k.c; float* ws = k.ws; const hipStream_t st = k.st;
+    const LayerPlan& l = c->ly[i];
+    BnBwdArgs b{};
+    b.part = ws + c->bpart_off; b.rows = l.a_split; b.gamma = k.params[4 * i + 2]; b.mean = ws + l.mean; b.rstd = ws + l.rstd;
+    b.dgamma = k.grads[4 * i + 2]; b.dbeta = k.grads[4 * i + 3]; b.dbias = k.grads[4 * i + 1]; b.k1 = ws + l.k1; b.k2 = ws + l.k2; b.k3 = ws + l.k3;
+    b.C = l.cout; b.count = (double)c->B * l.Lt; b.frozen = fz;
+    b.pmax = q.gz_h3 ? ws + c->bmax_off : nullptr; b.bound = ws + c->bound_off;
+    if (q.e0) { b.e0rows = ws + c->e0part_off; b.dw0 = k.grads[0]; }
+    if (!q.fin_in_gz) {
+        WUNET_LAUNCH(bn_finalize_bwd_kernel, dim3(l.cout), dim3(WUNET_THREADS), 0, st, b);
+        WUNET_CHECK_LAUNCH();
+    }
+    const size_t n4 = (size_t)c->B * l.cout * l.L / 4;
+    if (q.gz_h3) {
+        const int c8 = (l.cout + 7) / 8;
+        const size_t nt = (size_t)c->B * c8 * (l.L / 4);
+        size_t hb = (nt + WUNET_THREADS - 1) / WUNET_THREADS;
+        if (hb > 8192) hb = 8192;
+        prof_begin(st, "gz_split_h3_kernel", 0.0, (double)c->B * l.cout * l.L * (q.gz_bytes() + (c->bf ? 2.0 : 4.0)));
+        GzHeadArgs hd{};
+        if (q.gz_mode != GZ_G) { hd.a = ws + l.a; hd.s = ws + l.s; }
+        if (q.gz_mode == GZ_HEAD) { hd.gh = ws + c->gh_off; hd.wh = k.params[4 * c->NL]; }
+        if (q.gz_mode == GZ_UPH) hd.gq = ws + c->ly[i + 1].dxh;
+        if (q.gz_mode == GZ_ENC) {
+            const LayerPlan& dc = c->ly[2 * c->n - i];
+            hd.gd = ws + dc.dx; hd.Cg0 = dc.cin; hd.coff = dc.c0; hd.ge = ws + c->ly[i + 1].dx;
+        }
+        // (the source of g is a compile-time mode of the kernel: every load of a thread is issued before its first use)
+#define WUNET_GZ_LAUNCH(FIN_, GM_, BF_)                                                                                                               \
+    WUNET_LAUNCH((gz_split_h3_kernel<FIN_, GM_, BF_>), dim3((unsigned)hb), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z), \
+                 (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), (const float*)(ws + c->bound_off),                 \
+                 ws + c->h3_slot + 8 + 4 * i, reinterpret_cast<wunet_half*>(ws + l.gzh), reinterpret_cast<wunet_half*>(ws + l.gzl),                  \
+                 c->B, l.cout, c8, l.L, l.logL, l.Lt, b, hd)
+#define WUNET_GZ_MODE(GM_)                                                                                                                            \
+    case GM_:                                                                                                                                         \
+        if (q.fin_in_gz) { if (c->bf) WUNET_GZ_LAUNCH(true, GM_, true); else WUNET_GZ_LAUNCH(true, GM_, false); }                                     \
+        else { if (c->bf) WUNET_GZ_LAUNCH(false, GM_, true); else WUNET_GZ_LAUNCH(false, GM_, false); }                                               \
+        break;
+        switch (q.gz_mode) { WUNET_GZ_MODE(GZ_G) WUNET_GZ_MODE(GZ_HEAD) WUNET_GZ_MODE(GZ_ENC) WUNET_GZ_MODE(GZ_UPH) }
+#undef WUNET_GZ_MODE
+#undef WUNET_GZ_LAUNCH
+        prof_end(st);
+    } else if (q.tiny) {
+        WUNET_LAUNCH(gz_scalar_kernel, dim3((unsigned)((n4 * 4 + WUNET_THREADS - 1) / WUNET_THREADS) + 1), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g),
+                     (const float*)(ws + l.z), (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), l.cout, l.logL,
+                     (size_t)c->B * l.cout * l.L, ws + l.g);
+    } else if (!q.gz_in_wgrad) {
+        size_t blocks = (n4 + WUNET_THREADS - 1) / WUNET_THREADS;
+        if (blocks > 8192) blocks = 8192;
+        WUNET_LAUNCH(gz_materialize_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z),
+                     (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), l.cout, l.logL, n4, ws + l.g, l.Lt);   // in place
+    }
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// the partials of a split-K data gradient summed into dx, in split order
+int sum_dx_splits(const BwdCall& k, const LayerPlan& l)
+{
+    const size_t nd = (size_t)k.c->B * l.cin * l.L;
+    size_t blocks = (nd + WUNET_THREADS - 1) / WUNET_THREADS;
+    if (blocks > 2048) blocks = 2048;
+    WUNET_LAUNCH(split_sum_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, k.st, (const float*)(k.ws + k.c->spart_off), l.d.ksplit, nd, k.ws + l.dx, (const float*)nullptr, 1, 0);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---- data gradient: the same conv kernel on the flipped/transposed pack
+int data_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
+{
+    wunet_ctx* c = k.c; float* ws = k.ws; const hipStream_t st = k.st;
+    const LayerPlan& l = c->ly[i];
+    float* const dx = q.dx_split ? ws + c->spart_off : ws + l.dx;
+    if (q.dgrad == DG_H3) {
+        // fp16-split data gradient: scale g_z by a power of two into fp16's range, split, 3 MFMA passes, un-scale
+        // (UPT: the rows of the upsampled half leave at the producer's resolution - upt_handoff)
+        ConvH3Upt up{};
+        if (q.upt) {
+            up.c0 = l.c0; up.up_scale = (float)(l.Lt / 2 - 1) / (float)(l.Lt - 1);
+            up.uh_out = ws + l.dxh; up.uh_spill = ws + l.usp;
+        }
+        const int rc = launch_conv_h3(l.taps, l.h3d_mrep, l.h3d_mtp, l.h3d_sps, reinterpret_cast<wunet_half*>(ws + l.gzh), reinterpret_cast<wunet_half*>(ws + l.gzl),
+                                      reinterpret_cast<const wunet_half*>(ws + c->h3_wb_hi) + l.h3d_wpk,
+                                      reinterpret_cast<const wunet_half*>(ws + c->h3_wb_lo) + l.h3d_wpk, nullptr, ws + c->h3_slot + 8 + 4 * i,
+                                      ws + c->fslot_off + (size_t)WUNET_SLOT_FLOATS * i + 2,
+                                      dx, nullptr, c->B, l.cin, l.cout, l.h3d_nch, l.L, st, ws + l.gzp, nullptr, nullptr,
+                                      nullptr, c->bf, l.h3d_ntt, nullptr, q.upt ? &up : nullptr);
+        if (rc) return rc;
+        WUNET_CHECK_LAUNCH();
+    } else if (q.dgrad == DG_SCALAR) {
+        const size_t nd = (size_t)c->B * l.cin * l.L;
+        WUNET_LAUNCH(tiny_conv_kernel, dim3((unsigned)((nd + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st,
+                     (const float*)(ws + l.g), k.params[4 * i], ws + l.dx, c->B, l.cout, l.cin, l.L, l.logL, l.taps, 1);
+        WUNET_CHECK_LAUNCH();
+    } else if (q.dgrad == DG_FP32) {
+        const ConvArgs a = make_conv_args(ws + l.g, l.cout, ws + c->wpkb_off + l.d_wpk, nullptr, dx, nullptr, c->B, l.cin, l.L, l.taps, l.d,
+                                          (size_t)c->B * l.cin * l.L);
+        const int rc = launch_conv(l.taps, a, l.d, st);
+        if (rc) return rc;
+        WUNET_CHECK_LAUNCH();
+    }
+    return q.dx_sum ? sum_dx_splits(k, l) : WUNET_OK;
+}
+
+// ---- weight gradient on the side stream: GEMM over positions on the materialised operands, split-K partials + deterministic reduce
+int weight_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
+{
+    wunet_ctx* c = k.c; float* ws = k.ws; const hipStream_t sd = k.sd;
+    const int NL = c->NL;
+    const LayerPlan& l = c->ly[i];
+    if (sd != k.st && hipStreamWaitEvent(sd, k.side->ev_fork, 0) != hipSuccess) return fail(WUNET_E_RUNTIME, "fork onto the weight-gradient stream failed");
+    WUNET_STAMP(sd, 2 * i + 1)
+    if (i == NL - 1) {
+        // the head's parameter gradients (rounds 1 - 6: two 4.7 us launches between the kernels of the main chain, which never reads them):
+        // d(weight of the input channel), d bias from head_bwd_kernel's rows; the ci per-channel weight gradients from pass A's
+        WUNET_LAUNCH(rows_sum_kernel, dim3(2), dim3(WUNET_THREADS), 0, sd,
+                     (const float*)(ws + c->hpart_off), c->head_blocks, 2, k.grads[4 * NL] + c->ci, 1, k.grads[4 * NL + 1]);
+        WUNET_CHECK_LAUNCH();
+        WUNET_LAUNCH(rows_sum_kernel, dim3(c->ci), dim3(WUNET_THREADS), 0, sd,
+                     (const float*)(ws + c->hpart2_off), l.a_split, c->ci, k.grads[4 * NL], c->ci, k.grads[4 * NL + 1]);
+        WUNET_CHECK_LAUNCH();
+    }
+    if (q.e0) return WUNET_OK;                          // (finished by bn_finalize_bwd_kernel from pass A's sums)
+    const float* xin = i == 0 ? k.noisy : ws + l.xin;
+    const size_t nw = (size_t)l.cout * l.cin * l.taps;
+    if (q.tiny) {
+        WUNET_LAUNCH(tiny_wgrad_kernel, dim3((unsigned)((nw + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, sd,
+                     (const float*)(ws + l.g), xin, k.grads[4 * i], c->B, l.cin, l.cout, l.L, l.taps);
+        WUNET_CHECK_LAUNCH();
+        return WUNET_OK;
+    }
+    int rc;
+    if (l.h3w)
+        rc = launch_wgrad_h3(l, reinterpret_cast<const wunet_half*>(ws + l.xh), reinterpret_cast<const wunet_half*>(ws + l.xl),
+                             reinterpret_cast<const wunet_half*>(ws + l.gzh), reinterpret_cast<const wunet_half*>(ws + l.gzl),
+                             ws + c->h3_slot + 8 + 4 * i, ws + c->fslot_off + (size_t)WUNET_SLOT_FLOATS * i,
+                             ws + c->wgpart_off, c->B, sd, c->bf);
+    else {
+        WgradArgs w = make_wgrad_args(xin, ws + l.g, ws + c->wgpart_off, c->B, l.cin, l.cout, l.L, l.taps, l.w.cps);
+        if (q.gz_in_wgrad) {
+            w.z = ws + l.z; w.k1 = ws + l.k1; w.k2 = ws + l.k2; w.k3 = ws + l.k3; w.Lt = l.Lt;
+        }
+        rc = launch_wgrad_any(l.taps, w, l.w, sd);
+    }
+    if (rc) return rc;
+    WUNET_CHECK_LAUNCH();
+    if (l.h3w) {
+        WgradH3ReduceArgs ra{};
+        ra.part = ws + c->wgpart_off; ra.part_stride = h3w_part_stride(l); ra.splits = l.h3w_ksplit; ra.dw = k.grads[4 * i];
+        ra.Cout = l.cout; ra.Cin = l.cin; ra.taps = l.taps; ra.mrep = l.h3w_mrep; ra.tw = l.taps == 15 ? 8 : 5;
+        ra.nblocks = l.h3w_nblocks; ra.mblocks = l.h3w_mblocks; ra.cib = l.taps == 15 ? 32 : 64;
+        // few splits over many outputs: the barrier-free serial form (64, 8192: 6.19 -> 6.13 ms per step in round 1).
+        // Emulator-build test hook WUNET_REDUCE_SERIAL = "<max splits>,<min float4 outputs>": tiny shapes reach that kernel
+        int serial_max = 64; long long serial_min_n4 = 8192;
+#ifdef WUNET_EMU
+        if (const char* e = getenv("WUNET_REDUCE_SERIAL")) sscanf(e, "%d,%lld", &serial_max, &serial_min_n4);
+#endif
+        const size_t n4 = ra.part_stride / 4;
+        if (ra.splits <= serial_max && (long long)n4 >= serial_min_n4) {
+            size_t blocks = (n4 + WUNET_THREADS - 1) / WUNET_THREADS;
+            if (blocks > 4096) blocks = 4096;
+            WUNET_LAUNCH(wgrad_h3_reduce_serial_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd, ra);
+        } else {
+            size_t blocks = (n4 + 15) / 16;
+            if (blocks > 4096) blocks = 4096;
+            WUNET_LAUNCH(wgrad_h3_reduce_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd, ra);
+        }
+    } else {
+        size_t blocks = (nw / 4 + 15) / 16;                   // 16 float4 groups of outputs per block
+        if (blocks > 4096) blocks = 4096;
+        if (blocks < 1) blocks = 1;
+        WUNET_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd,
+                     (const float*)(ws + c->wgpart_off), l.w.rows, nw, k.grads[4 * i]);
+    }
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
 }
 
 int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* params, const float* enhanced,
@@ -72,15 +430,17 @@ int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* pa
 {
     if (!c || !noisy || !params || !enhanced || !grad_enhanced || !workspace || !grads) return fail(WUNET_E_ARG, "null argument");
     if (layer_begin < 0 || layer_end > c->NL || layer_begin >= layer_end) return fail(WUNET_E_ARG, "bad layer range");
+    // (both ends of a UPT hand-off read LayerPlan::upt; a plan that sets it where they cannot run is refused before anything is launched)
+    for (int q = c->n + 1; q < c->NL; ++q)
+        if (upt_handoff(c, q) && !upt_handoff_sound(c, q)) return fail(WUNET_E_ARG, "layer %d: UPT planned where the data gradient or its producer cannot run it", q);
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
-    const int NL = c->NL, n = c->n;
+    const int NL = c->NL;
     // weight gradients run on a side stream: they only depend on g_z and x of their own layer, so the HBM-bound
     // gradient-assembly kernels of the next layers overlap with them instead of idling the matrix cores
     wunet_ctx::Side* side = side_for_current_device(c);
     if (!side) return WUNET_E_RUNTIME;
-    static const bool no_side = getenv("WUNET_NO_SIDE_STREAM") != nullptr;     // profiling switch: one stream, serial kernels
-    hipStream_t sd = (g_prof_on || no_side) ? st : side->stream;  // the per-kernel profiler serialises everything on one stream
+    hipStream_t sd = (g_prof_on || side_stream_off()) ? st : side->stream;  // the per-kernel profiler serialises everything on one stream
     if (c->padded) {
         // the forward's zero-padded copies of the input and of the result are still in the workspace; the incoming gradient is
         // padded with zeros here (the head's backward then gives the row padding a zero gradient)
@@ -91,341 +451,25 @@ int backward_range_impl(wunet_ctx* c, const float* noisy, const float* const* pa
             return fail(WUNET_E_RUNTIME, "padding the output gradient failed");
         noisy = ws + c->pad_in; enhanced = ws + c->pad_out; grad_enhanced = ws + c->pad_gout;
     }
-
-    if (layer_end == NL) {
-        // flipped/transposed weights for every data gradient: already enqueued on the side stream by the training forward of this
-        // workspace (they only depend on the weights: off the critical path), else packed here
-        if (side->packed_ws == workspace && sd != st) {
-            side->packed_ws = nullptr;
-            if (hipStreamWaitEvent(st, side->ev_pack, 0) != hipSuccess) return fail(WUNET_E_RUNTIME, "waiting for the weight packs failed");
-        } else {
-            side->packed_ws = nullptr;
-            const int rc = launch_backward_packs(c, params, ws, st);
-            if (rc) return rc;
-        }
-        // head backward: gh = gout * tanh', d wh, d bh
-        const LayerPlan& l = c->ly[NL - 1];
-        HeadBwdArgs h{};
-        h.z = ws + l.z; h.a = ws + l.a; h.s = ws + l.s; h.in = noisy; h.out = enhanced; h.gout = grad_enhanced;
-        h.gh = ws + c->gh_off; h.part = ws + c->hpart_off; h.B = c->B; h.C = c->ci; h.T = c->T; h.logT = ilog2(c->T);
-        WUNET_LAUNCH(head_bwd_kernel, dim3(c->head_blocks), dim3(WUNET_THREADS), 0, st, h);
-        WUNET_CHECK_LAUNCH();
-        // (d(weight of the input channel), d bias and the ci per-channel head-weight gradients - sums of head_bwd_kernel's and of the last layer's
-        //  pass A's partial rows - are parameter gradients nothing on the chain reads: they are taken on the weight-gradient stream, below)
-    }
+    const BwdCall k{c, ws, params, grads, noisy, st, sd, side};
+    if (layer_end == NL) { const int rc = head_backward(k, workspace, enhanced, grad_enhanced); if (rc) return rc; }
 
     for (int i = layer_end - 1; i >= layer_begin; --i) {
-        const LayerPlan& l = c->ly[i];
-        // a layer frozen by wunet_set_bn_frozen (running statistics in the forward): every finalize below emits g_z = a g (k2 = k3 = 0)
-        // and the conv bias's gradient a sum g
-        const int fz = (c->any_frozen && c->frozen[i]) ? 1 : 0;
-        // ---- a layer whose BatchNorm-backward sums came out of its consumers' data-gradient epilogues (conv_h3d_kernel<.., BSUM>, planned by
-        // layout_workspace): no pass A; finalize from the per-tile rows; g_z formed by gz_split_h3_kernel from the data gradients themselves
-        static const bool no_enc_gz_ = getenv("WUNET_NO_ENC_GZ") != nullptr;
-        const bool bsum = l.bsum && !(i < n && no_enc_gz_);
-        // ---- pass A: assemble dL/d(BN output), LeakyReLU', BN-backward partial sums
-        PassAArgs p{};
-        p.z = ws + l.z; p.a = ws + l.a; p.s = ws + l.s; p.mean = ws + l.mean; p.rstd = ws + l.rstd;
-        p.gpre = ws + l.g; p.part = ws + c->bpart_off; p.pmax = (i > 0 && l.h3d) ? ws + c->bmax_off : nullptr; p.B = c->B; p.C = l.cout; p.L = l.L; p.logL = l.logL; p.Lt = l.Lt;
-        // grid (pieces, channels): consecutive blocks walk consecutive pieces of ONE channel row (rounds 1 - 3 had (channels, pieces):
-        // neighbours 4 L bytes apart; 5.156 -> 5.139 ms per step; WUNET_PA_SWAP=0: A/B switch)
-        static const int pa_swap = getenv("WUNET_PA_SWAP") ? atoi(getenv("WUNET_PA_SWAP")) : 1;
-        const BwdLayerPath path = bwd_layer_path(c, i);
-        const bool tiny = path.tiny;
-        p.swap = (pa_swap && l.a_split > 1 && !tiny) ? 1 : 0;        // (pass_a_scalar_kernel reads its channel from blockIdx.x)
-        const dim3 ga(p.swap ? l.a_split : l.cout, p.swap ? l.cout : l.a_split);
-        // the first layer's g_z has one reader: its weight gradient forms it while it stages its chunks (WUNET_NO_GZ_FUSE: A/B switch)
-        const bool gz_in_wgrad = path.gz_in_wgrad;
-        // a whole channel in one pass of one block (the levels of <= 16 samples at batch 64): BatchNorm-backward finalize and
-        // g_z inside pass A - two launches of ~5 us (latency, not bandwidth) less per such level
-        const bool fuse = path.fuse;
-        // the first layer (Cin = 1, 15 taps): its weight gradient's sums are taken by this pass and finished by the finalize - no g written, no
-        // weight-gradient GEMM, no split reduce (the last 66 us of the backward, alone on the chip; WUNET_NO_E0=1 when the context is planned: A/B switch)
-        const bool e0 = path.e0;
-        if (fuse) {
-            p.gamma = params[4 * i + 2]; p.dgamma = grads[4 * i + 2]; p.dbeta = grads[4 * i + 3]; p.dbias = grads[4 * i + 1];
-            p.k1 = ws + l.k1; p.k2 = ws + l.k2; p.k3 = ws + l.k3; p.count = (double)c->B * l.Lt; p.frozen = fz;
-        }
-        // the last layer on the split kernels: its g is recomputed from the head gradient by gz_split_h3_kernel (HEAD mode), not stored
-        const bool head_in_gz = i == NL - 1 && i > 0 && l.h3d && !fuse && !tiny;
-        // an encoder layer on the split kernels whose two data gradients are whole tensors: g is recomputed by gz_split_h3_kernel (ENC
-        // mode) from them instead of written here and read back (WUNET_NO_ENC_GZ=1: A/B switch)
-        static const bool no_enc_gz = getenv("WUNET_NO_ENC_GZ") != nullptr;
-        const bool enc_in_gz = i > 0 && i < n && l.h3d && !fuse && !tiny && !dx_stays_split(c, i + 1) && !no_enc_gz;
-        // a layer behind an upsample whose consumer's data gradient arrives at this layer's resolution (UPT, planned by layout_workspace)
-        const bool uph = !bsum && i >= n && i + 1 < NL && c->ly[i + 1].upt && l.h3d && !fuse && !tiny;
-        if (!bsum) {   // algorithmic bytes of the gradient assembly (HBM-bound): z + the consumers' data gradients read, g written
-            const double pe = (double)c->B * l.cout * l.L;
-            const char* nm = i == NL - 1 ? "pass_a_kernel<HEAD>" : i >= n ? "pass_a_kernel<UP>" : e0 ? "pass_a_kernel<ENC, e0>" : "pass_a_kernel<ENC>";
-            prof_begin(st, uph ? "pass_a_kernel<UPH>" : nm, 0.0, pe * (i == NL - 1 ? (head_in_gz ? 4.0 : 8.0) : uph ? 8.0 : i >= n ? 16.0 : ((enc_in_gz || e0) ? 10.0 : 14.0)) + (i == NL - 1 ? 4.0 * c->B * l.L : 0.0));
-        }
-        if (bsum) {
-        } else if (i == NL - 1) {
-            if (head_in_gz) p.gpre = nullptr;
-            p.g0 = ws + c->gh_off; p.g1 = params[4 * NL]; p.hpart = ws + c->hpart2_off;
-            WUNET_LAUNCH(pass_a_kernel<A_HEAD>, ga, dim3(WUNET_THREADS), 0, st, p);      // (the last layer has T >= 4 samples)
-            prof_end(st);
-        } else if (i >= n && uph) {
-            // the next decoder layer's data gradient arrived at THIS resolution (conv_h3d_kernel<.., 3>): elementwise; g is not stored -
-            // gz_split_h3_kernel forms it again from the same two arrays (UPH mode)
-            const LayerPlan& nx = c->ly[i + 1];
-            p.g0 = ws + nx.dxh; p.sp = ws + nx.usp; p.ntiles = (int)(((size_t)c->B * nx.L + 255) / 256); p.tpr = l.L >> 7;
-            p.gpre = nullptr;
-            WUNET_LAUNCH(pass_a_kernel<A_UPH>, ga, dim3(WUNET_THREADS), 0, st, p);
-            prof_end(st);
-        } else if (i >= n) {
-            const LayerPlan& nx = c->ly[i + 1];
-            p.g0 = ws + nx.dx; p.Cg0 = nx.cin;
-            p.up_scale = (float)(l.Lt - 1) / (float)(2 * l.Lt - 1);
-            if (tiny) WUNET_LAUNCH(pass_a_scalar_kernel<A_UP>, ga, dim3(WUNET_THREADS), 0, st, p);
-            else if (fuse) WUNET_LAUNCH((pass_a_kernel<A_UP, true>), ga, dim3(WUNET_THREADS), 0, st, p);
-            else WUNET_LAUNCH(pass_a_kernel<A_UP>, ga, dim3(WUNET_THREADS), 0, st, p);
-            prof_end(st);
-        } else {
-            const LayerPlan& dc = c->ly[2 * n - i];
-            const LayerPlan& nx = c->ly[i + 1];
-            p.g0 = ws + dc.dx; p.Cg0 = dc.cin; p.coff = dc.c0; p.g1 = ws + nx.dx;
-            if (enc_in_gz) p.gpre = nullptr;
-            if (dx_stays_split(c, i + 1)) {
-                p.g1 = ws + c->spart_off; p.g1_splits = nx.d.ksplit; p.g1_stride = (size_t)c->B * nx.cin * nx.L;
-            }
-            if (e0) { p.gpre = nullptr; p.x0 = noisy; p.e0rows = ws + c->e0part_off; }
-            if (tiny) WUNET_LAUNCH(pass_a_scalar_kernel<A_ENC>, ga, dim3(WUNET_THREADS), 0, st, p);
-            else if (e0) WUNET_LAUNCH((pass_a_kernel<A_ENC, false, false, true>), ga, dim3(WUNET_THREADS), 0, st, p);
-            else if (fuse && p.g1_splits > 1) WUNET_LAUNCH((pass_a_kernel<A_ENC, true, true>), ga, dim3(WUNET_THREADS), 0, st, p);
-            else if (fuse) WUNET_LAUNCH((pass_a_kernel<A_ENC, true>), ga, dim3(WUNET_THREADS), 0, st, p);
-            else if (p.g1_splits > 1) WUNET_LAUNCH((pass_a_kernel<A_ENC, false, true>), ga, dim3(WUNET_THREADS), 0, st, p);
-            else WUNET_LAUNCH(pass_a_kernel<A_ENC>, ga, dim3(WUNET_THREADS), 0, st, p);
-            prof_end(st);
-        }
-        WUNET_CHECK_LAUNCH();
-        if (!fuse) {
-            BnBwdArgs b{};
-            b.part = ws + c->bpart_off; b.rows = l.a_split; b.gamma = params[4 * i + 2]; b.mean = ws + l.mean; b.rstd = ws + l.rstd;
-            b.dgamma = grads[4 * i + 2]; b.dbeta = grads[4 * i + 3]; b.dbias = grads[4 * i + 1]; b.k1 = ws + l.k1; b.k2 = ws + l.k2; b.k3 = ws + l.k3;
-            b.C = l.cout; b.count = (double)c->B * l.Lt; b.frozen = fz;
-            b.pmax = (i > 0 && l.h3d) ? ws + c->bmax_off : nullptr; b.bound = ws + c->bound_off;
-            if (e0) { b.e0rows = ws + c->e0part_off; b.dw0 = grads[0]; }
-            // (short levels on the split kernels: the finalize runs in the prologue of gz_split_h3_kernel's blocks instead -
-            //  WUNET_NO_BWDFIN_FUSE=1: A/B switch)
-            const bool fin_in_gz = !bsum && i > 0 && l.h3d && l.a_split * l.cout <= WUNET_GZ_FIN_LOADS && l.cout <= WUNET_GZ_FIN_C;
-            if (bsum) {
-                BnBwdTilesArgs t{};
-                if (i >= n) {            // one set: rows 0 .. c0 - 1 of the next decoder layer's data gradient
-                    const LayerPlan& q = c->ly[i + 1];
-                    t.part0 = ws + q.bsp; t.tiles0 = (int)(((size_t)c->B * q.L + 255) / 256);
-                } else {                 // the skip rows of decoder layer 2n - i, then the decimated rows of layer i + 1
-                    const LayerPlan& dq = c->ly[2 * n - i];
-                    const LayerPlan& eq = c->ly[i + 1];
-                    t.tiles0 = (int)(((size_t)c->B * dq.L + 255) / 256); t.part0 = ws + dq.bsp + (size_t)dq.c0 * t.tiles0 * 4;
-                    t.tiles1 = (int)(((size_t)c->B * eq.L + 255) / 256); t.part1 = ws + eq.bsp;
-                }
-                t.gamma = b.gamma; t.mean = b.mean; t.rstd = b.rstd; t.dgamma = b.dgamma; t.dbeta = b.dbeta; t.dbias = b.dbias;
-                t.k1 = b.k1; t.k2 = b.k2; t.k3 = b.k3; t.bound = b.bound; t.C = l.cout; t.count = b.count; t.frozen = fz;
-                WUNET_LAUNCH(bn_finalize_bwd_tiles_kernel, dim3(l.cout), dim3(WUNET_THREADS), 0, st, t);
-                WUNET_CHECK_LAUNCH();
-            } else if (!fin_in_gz) {
-                WUNET_LAUNCH(bn_finalize_bwd_kernel, dim3(l.cout), dim3(WUNET_THREADS), 0, st, b);
-                WUNET_CHECK_LAUNCH();
-            }
-
-            // ---- g_z = k1*g + k2*z + k3, materialised once for both gradient GEMMs (fp32 in place, or scaled hi/lo halves)
-            {
-                const size_t n4 = (size_t)c->B * l.cout * l.L / 4;
-                size_t blocks = (n4 + WUNET_THREADS - 1) / WUNET_THREADS;
-                if (blocks > 8192) blocks = 8192;
-                if (i > 0 && l.h3d) {
-                    const int c8 = (l.cout + 7) / 8;
-                    const size_t nt = (size_t)c->B * c8 * (l.L / 4);
-                    size_t hb = (nt + WUNET_THREADS - 1) / WUNET_THREADS;
-                    if (hb > 8192) hb = 8192;
-                    const bool up_in_gz = bsum && i >= n;
-                    prof_begin(st, "gz_split_h3_kernel", 0.0, (double)c->B * l.cout * l.L * ((head_in_gz ? 4.0 : enc_in_gz ? 10.0 : up_in_gz ? 12.0 : 8.0) + (c->bf ? 2.0 : 4.0)));
-                    GzHeadArgs hd{};
-                    if (head_in_gz) { hd.gh = ws + c->gh_off; hd.wh = params[4 * NL]; hd.a = ws + l.a; hd.s = ws + l.s; }
-                    if (uph) {
-                        const LayerPlan& q = c->ly[i + 1];
-                        hd.gq = ws + q.dxh; hd.a = ws + l.a; hd.s = ws + l.s;
-                    }
-                    if (up_in_gz) {
-                        const LayerPlan& q = c->ly[i + 1];
-                        hd.gu = ws + q.dx; hd.Cg0 = q.cin; hd.up_scale = (float)(l.Lt - 1) / (float)(2 * l.Lt - 1); hd.a = ws + l.a; hd.s = ws + l.s;
-                    }
-                    if (enc_in_gz) {
-                        const LayerPlan& dc = c->ly[2 * n - i];
-                        hd.gd = ws + dc.dx; hd.Cg0 = dc.cin; hd.coff = dc.c0; hd.ge = ws + c->ly[i + 1].dx; hd.a = ws + l.a; hd.s = ws + l.s;
-                    }
-                    // (the source of g is a compile-time mode of the kernel: every load of a thread is issued before its first use)
-                    const int gm = head_in_gz ? GZ_HEAD : enc_in_gz ? GZ_ENC : uph ? GZ_UPH : up_in_gz ? GZ_UP : GZ_G;
-#define WUNET_GZ_LAUNCH(FIN_, GM_, BF_)                                                                                                               \
-    WUNET_LAUNCH((gz_split_h3_kernel<FIN_, GM_, BF_>), dim3((unsigned)hb), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z), \
-                 (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), (const float*)(ws + c->bound_off),                 \
-                 ws + c->h3_slot + 8 + 4 * i, reinterpret_cast<wunet_half*>(ws + l.gzh), reinterpret_cast<wunet_half*>(ws + l.gzl),                  \
-                 c->B, l.cout, c8, l.L, l.logL, l.Lt, b, hd)
-#define WUNET_GZ_MODE(GM_)                                                                                                                            \
-    case GM_:                                                                                                                                         \
-        if (fin_in_gz) { if (c->bf) WUNET_GZ_LAUNCH(true, GM_, true); else WUNET_GZ_LAUNCH(true, GM_, false); }                                       \
-        else { if (c->bf) WUNET_GZ_LAUNCH(false, GM_, true); else WUNET_GZ_LAUNCH(false, GM_, false); }                                               \
-        break;
-                    switch (gm) { WUNET_GZ_MODE(GZ_G) WUNET_GZ_MODE(GZ_HEAD) WUNET_GZ_MODE(GZ_ENC) WUNET_GZ_MODE(GZ_UPH) WUNET_GZ_MODE(GZ_UP) }
-#undef WUNET_GZ_MODE
-#undef WUNET_GZ_LAUNCH
-                    prof_end(st);
-                } else if (tiny)
-                    WUNET_LAUNCH(gz_scalar_kernel, dim3((unsigned)((n4 * 4 + WUNET_THREADS - 1) / WUNET_THREADS) + 1), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g),
-                                 (const float*)(ws + l.z), (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), l.cout, l.logL,
-                                 (size_t)c->B * l.cout * l.L, ws + l.g);
-                else if (gz_in_wgrad) {
-                } else
-                    WUNET_LAUNCH(gz_materialize_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z),
-                                 (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), l.cout, l.logL, n4, ws + l.g, l.Lt);   // in place
-                WUNET_CHECK_LAUNCH();
-            }
-        }
-        // ---- weight gradient on the side stream: GEMM over positions on the materialised operands, split-K partials
-        //      + deterministic reduce
-        // The fork EVENT is recorded here, right behind g_z; the side stream's launches are issued after the data gradient's (below), so
+        const BwdLayerPlan q = bwd_layer_plan(c, i);
+        const int fz = (c->any_frozen && c->frozen[i]) ? 1 : 0;      // (run-time state: wunet_set_bn_frozen may change it between calls)
+        int rc = pass_a(k, i, q, fz);
+        if (rc) return rc;
+        if (!q.fuse && (rc = finalize_and_gz(k, i, q, fz)) != 0) return rc;
+        // The weight gradient's fork EVENT is recorded here, right behind g_z; the side stream's launches are issued after the data gradient's, so
         // that the kernel of the critical chain is enqueued - and, in a captured graph, created - FIRST: its persistent blocks take the
         // CUs and the weight gradient fills in behind it and beside the next layer's memory-bound passes.  Eager launches got that order
         // anyway (the event wait costs the side stream ~6 us); a captured graph released both kernels at once, the weight gradient
         // won the race (data gradient 204 us instead of 110) and the replay was 10 % slower than the eager step (5.93 -> 5.25 ms with
         // this order, eager 5.26: profiles/r4_graph_vs_eager.txt).
         if (sd != st && hipEventRecord(side->ev_fork, st) != hipSuccess) return fail(WUNET_E_RUNTIME, "fork onto the weight-gradient stream failed");
-        auto weight_gradient = [&]() -> int {
-            if (sd != st) {
-                if (hipStreamWaitEvent(sd, side->ev_fork, 0) != hipSuccess)
-                    return fail(WUNET_E_RUNTIME, "fork onto the weight-gradient stream failed");
-            }
-            WUNET_STAMP(sd, 2 * i + 1)
-            if (i == NL - 1) {
-                // the head's parameter gradients (rounds 1 - 6: two 4.7 us launches between the kernels of the main chain, which never reads them):
-                // d(weight of the input channel), d bias from head_bwd_kernel's rows; the ci per-channel weight gradients from pass A's
-                WUNET_LAUNCH(rows_sum_kernel, dim3(2), dim3(WUNET_THREADS), 0, sd,
-                             (const float*)(ws + c->hpart_off), c->head_blocks, 2, grads[4 * NL] + c->ci, 1, grads[4 * NL + 1]);
-                WUNET_CHECK_LAUNCH();
-                if (!bsum) {
-                    WUNET_LAUNCH(rows_sum_kernel, dim3(c->ci), dim3(WUNET_THREADS), 0, sd,
-                                 (const float*)(ws + c->hpart2_off), l.a_split, c->ci, grads[4 * NL], c->ci, grads[4 * NL + 1]);
-                    WUNET_CHECK_LAUNCH();
-                }
-            }
-            if (e0) return 0;                          // (finished by bn_finalize_bwd_kernel from pass A's sums)
-            const float* xin = i == 0 ? noisy : ws + l.xin;
-            const size_t nw = (size_t)l.cout * l.cin * l.taps;
-            if (tiny) {
-                WUNET_LAUNCH(tiny_wgrad_kernel, dim3((unsigned)((nw + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, sd,
-                             (const float*)(ws + l.g), xin, grads[4 * i], c->B, l.cin, l.cout, l.L, l.taps);
-                WUNET_CHECK_LAUNCH();
-            } else {
-                int rc;
-                if (l.h3w)
-                    rc = launch_wgrad_h3(l, reinterpret_cast<const wunet_half*>(ws + l.xh), reinterpret_cast<const wunet_half*>(ws + l.xl),
-                                         reinterpret_cast<const wunet_half*>(ws + l.gzh), reinterpret_cast<const wunet_half*>(ws + l.gzl),
-                                         ws + c->h3_slot + 8 + 4 * i, ws + c->fslot_off + (size_t)WUNET_SLOT_FLOATS * i,
-                                         ws + c->wgpart_off, c->B, sd, c->bf);
-                else {
-                    WgradArgs w = make_wgrad_args(xin, ws + l.g, ws + c->wgpart_off, c->B, l.cin, l.cout, l.L, l.taps, l.w.cps);
-                    if (gz_in_wgrad) {
-                        w.z = ws + l.z; w.k1 = ws + l.k1; w.k2 = ws + l.k2; w.k3 = ws + l.k3; w.Lt = l.Lt;
-                    }
-                    rc = launch_wgrad_any(l.taps, w, l.w, sd);
-                }
-                if (rc) return rc;
-                WUNET_CHECK_LAUNCH();
-                if (l.h3w) {
-                    WgradH3ReduceArgs ra{};
-                    ra.part = ws + c->wgpart_off; ra.part_stride = h3w_part_stride(l); ra.splits = l.h3w_ksplit; ra.dw = grads[4 * i];
-                    ra.Cout = l.cout; ra.Cin = l.cin; ra.taps = l.taps; ra.mrep = l.h3w_mrep; ra.tw = l.taps == 15 ? 8 : 5;
-                    ra.nblocks = l.h3w_nblocks; ra.mblocks = l.h3w_mblocks; ra.cib = l.taps == 15 ? 32 : 64;
-                    // few splits over many outputs: the barrier-free serial form (64, 8192: 6.19 -> 6.13 ms per step in round 1).
-                    // Emulator-build test hook WUNET_REDUCE_SERIAL = "<max splits>,<min float4 outputs>": tiny shapes reach that kernel
-                    int serial_max = 64; long long serial_min_n4 = 8192;
-#ifdef WUNET_EMU
-                    if (const char* e = getenv("WUNET_REDUCE_SERIAL")) sscanf(e, "%d,%lld", &serial_max, &serial_min_n4);
-#endif
-                    const size_t n4 = ra.part_stride / 4;
-                    if (ra.splits <= serial_max && (long long)n4 >= serial_min_n4) {
-                        size_t blocks = (n4 + WUNET_THREADS - 1) / WUNET_THREADS;
-                        if (blocks > 4096) blocks = 4096;
-                        WUNET_LAUNCH(wgrad_h3_reduce_serial_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd, ra);
-                    } else {
-                        size_t blocks = (n4 + 15) / 16;
-                        if (blocks > 4096) blocks = 4096;
-                        WUNET_LAUNCH(wgrad_h3_reduce_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd, ra);
-                    }
-                } else {
-                    size_t blocks = (nw / 4 + 15) / 16;                   // 16 float4 groups of outputs per block
-                    if (blocks > 4096) blocks = 4096;
-                    if (blocks < 1) blocks = 1;
-                    WUNET_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd,
-                                 (const float*)(ws + c->wgpart_off), l.w.rows, nw, grads[4 * i]);
-                }
-                WUNET_CHECK_LAUNCH();
-            }
-            return 0;
-        };
-        // ---- data gradient (not needed for the first layer): the same conv kernel on the flipped/transposed pack
         WUNET_STAMP(st, 2 * i)
-        if (i > 0 && l.h3d) {
-            // fp16-split data gradient: scale g_z by a power of two into fp16's range, split, 3 MFMA passes, un-scale
-            float* sc = ws + c->h3_slot + 8 + 4 * i;
-            wunet_half* gh = reinterpret_cast<wunet_half*>(ws + l.gzh);
-            wunet_half* gl = reinterpret_cast<wunet_half*>(ws + l.gzl);
-            const bool split = l.d.ksplit > 1;
-            // (BSUM: the epilogue also takes the BatchNorm-backward sums of the layers that produced this layer's input rows)
-            ConvH3Bsum bs{};
-            // (UPT: the rows of the upsampled half leave at the producer's resolution - the producer's gradient assembly is then elementwise)
-            const bool upt = l.upt && !split && c->ly[l.src0].h3d;
-            if (upt) {
-                bs.kind = 3; bs.c0 = l.c0; bs.up_scale = (float)(l.Lt / 2 - 1) / (float)(l.Lt - 1);
-                bs.uh_out = ws + l.dxh; bs.uh_spill = ws + l.usp;
-            }
-            if (l.bs_kind && !split) {
-                const LayerPlan& pa = c->ly[l.src0];
-                bs.kind = l.bs_kind; bs.c0 = l.c0; bs.up_scale = (float)(l.Lt / 2 - 1) / (float)(l.Lt - 1); bs.part = ws + l.bsp;
-                const bool on_a = pa.bsum && !(l.src0 < n && no_enc_gz_);
-                bs.z[0] = on_a ? ws + pa.z : nullptr; bs.cst[0] = ws + pa.cst; bs.C[0] = pa.cout;
-                if (l.bs_kind == 1) {
-                    const LayerPlan& pb = c->ly[l.src1];
-                    bs.z[1] = (pb.bsum && !no_enc_gz_) ? ws + pb.z : nullptr; bs.cst[1] = ws + pb.cst; bs.C[1] = pb.cout;
-                }
-            }
-            int rc = launch_conv_h3(l.taps, l.h3d_mrep, l.h3d_mtp, l.h3d_sps, gh, gl,
-                                    reinterpret_cast<const wunet_half*>(ws + c->h3_wb_hi) + l.h3d_wpk,
-                                    reinterpret_cast<const wunet_half*>(ws + c->h3_wb_lo) + l.h3d_wpk, nullptr, sc,
-                                    ws + c->fslot_off + (size_t)WUNET_SLOT_FLOATS * i + 2,
-                                    split ? ws + c->spart_off : ws + l.dx, nullptr, c->B, l.cin, l.cout, l.h3d_nch, l.L, st, ws + l.gzp, nullptr, nullptr,
-                                    nullptr, c->bf, l.h3d_ntt, nullptr, (upt || bs.z[0] || bs.z[1]) ? &bs : nullptr);
-            if (rc) return rc;
-            WUNET_CHECK_LAUNCH();
-            if (split && !dx_stays_split(c, i)) {
-                const size_t nd = (size_t)c->B * l.cin * l.L;
-                size_t blocks = (nd + WUNET_THREADS - 1) / WUNET_THREADS;
-                if (blocks > 2048) blocks = 2048;
-                WUNET_LAUNCH(split_sum_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, (const float*)(ws + c->spart_off), l.d.ksplit, nd, ws + l.dx, (const float*)nullptr, 1, 0);
-                WUNET_CHECK_LAUNCH();
-            }
-        } else if (i > 0 && tiny) {
-            const size_t nd = (size_t)c->B * l.cin * l.L;
-            WUNET_LAUNCH(tiny_conv_kernel, dim3((unsigned)((nd + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st,
-                         (const float*)(ws + l.g), params[4 * i], ws + l.dx, c->B, l.cout, l.cin, l.L, l.logL, l.taps, 1);
-            WUNET_CHECK_LAUNCH();
-        } else if (i > 0) {
-            const bool split = l.d.ksplit > 1;
-            const size_t nd = (size_t)c->B * l.cin * l.L;
-            const ConvArgs a = make_conv_args(ws + l.g, l.cout, ws + c->wpkb_off + l.d_wpk, nullptr,
-                                              split ? ws + c->spart_off : ws + l.dx, nullptr, c->B, l.cin, l.L, l.taps, l.d, nd);
-            int rc = launch_conv(l.taps, a, l.d, st);
-            if (rc) return rc;
-            WUNET_CHECK_LAUNCH();
-            if (split && !dx_stays_split(c, i)) {
-                size_t blocks = (nd + WUNET_THREADS - 1) / WUNET_THREADS;
-                if (blocks > 2048) blocks = 2048;
-                WUNET_LAUNCH(split_sum_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, (const float*)(ws + c->spart_off), l.d.ksplit, nd, ws + l.dx, (const float*)nullptr, 1, 0);
-                WUNET_CHECK_LAUNCH();
-            }
-        }
-        { const int rc = weight_gradient(); if (rc) return rc; }
+        if ((rc = data_gradient(k, i, q)) != 0) return rc;
+        if ((rc = weight_gradient(k, i, q)) != 0) return rc;
     }
     // join: the caller's stream sees every weight gradient.  An un-joined range (wunet_backward_range_async) leaves them to
     // wunet_backward_join - except the range that ends the backward, which always joins: the next forward overwrites the
@@ -472,8 +516,7 @@ int wunet_backward_join(wunet_ctx* c, void* stream)
     if (!c) return fail(WUNET_E_ARG, "null ctx");
     wunet_ctx::Side* side = side_for_current_device(c);
     if (!side) return WUNET_E_RUNTIME;
-    static const bool no_side = getenv("WUNET_NO_SIDE_STREAM") != nullptr;
-    if (g_prof_on || no_side) return WUNET_OK;                   // the weight gradients ran on the caller's stream
+    if (g_prof_on || side_stream_off()) return WUNET_OK;                   // the weight gradients ran on the caller's stream
     if (hipEventRecord(side->ev_join, side->stream) != hipSuccess ||
         hipStreamWaitEvent((hipStream_t)stream, side->ev_join, 0) != hipSuccess)
         return fail(WUNET_E_RUNTIME, "join of the weight-gradient stream failed");

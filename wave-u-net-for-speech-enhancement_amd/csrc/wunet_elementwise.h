@@ -102,7 +102,6 @@ struct BnFwdArgs {
     float* s;             // out: shift  beta - mean*a
     float* mean;          // out (training): batch mean of z
     float* rstd;          // out (training)
-    float* cst;           // out (training) or nullptr: the same four as ONE 16-byte row per channel {a, s, mean, rstd} (conv_h3d_kernel<.., BSUM> loads a row's constants with one instruction)
     int C;
     double count;         // B*L
     int training;
@@ -133,7 +132,6 @@ __device__ __forceinline__ void bn_finalize_core(const BnFwdArgs& A, int c, doub
     A.s[c] = sh;
     A.mean[c] = (float)mean;
     A.rstd[c] = rstd;
-    if (A.cst) { A.cst[4 * c] = a; A.cst[4 * c + 1] = sh; A.cst[4 * c + 2] = (float)mean; A.cst[4 * c + 3] = rstd; }
     const double unbiased = A.count > 1.0 ? var * A.count / (A.count - 1.0) : var;
     A.running_mean[c] = (float)(0.9 * (double)P.rmean + 0.1 * mean);
     A.running_var[c] = (float)(0.9 * (double)P.rvar + 0.1 * unbiased);
@@ -150,10 +148,10 @@ __device__ __forceinline__ void bn_eval_core(const BnFwdArgs& A, int c)
 
 // Eval mode: the BatchNorm scale / shift of EVERY layer in one launch - they only depend on the running statistics, so nothing
 // of it belongs on the layer-to-layer chain (25 launches of ~4 us less per eval forward).  grid = (ceil(maxC / 256), layers).
-// Training mode, the layers frozen by wunet_set_bn_frozen (nn.BatchNorm1d in eval mode): the same scale / shift, and mean / rstd (+ cst)
+// Training mode, the layers frozen by wunet_set_bn_frozen (nn.BatchNorm1d in eval mode): the same scale / shift, and mean / rstd
 // = running_mean / 1/sqrt(running_var + eps), from which the backward rebuilds xhat; nullptr in eval mode.
 struct BnEvalDesc { const float* gamma; const float* beta; const float* running_mean; const float* running_var; float* a; float* s; int C;
-                    float* mean; float* rstd; float* cst; };
+                    float* mean; float* rstd; };
 struct BnEvalTable { BnEvalDesc d[WUNET_MAX_CONV_LAYERS]; };
 static __global__ __launch_bounds__(WUNET_THREADS) void bn_eval_all_kernel(BnEvalTable T)
 {
@@ -169,7 +167,6 @@ static __global__ __launch_bounds__(WUNET_THREADS) void bn_eval_all_kernel(BnEva
         const float mu = d.running_mean[c], sh = d.beta[c] - mu * a;
         d.mean[c] = mu;
         d.rstd[c] = rstd;
-        if (d.cst) { d.cst[4 * c] = a; d.cst[4 * c + 1] = sh; d.cst[4 * c + 2] = mu; d.cst[4 * c + 3] = rstd; }
     }
 }
 
@@ -960,66 +957,6 @@ static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_kernel(B
             const float k1 = (float)a, k2 = (float)(-a * m2 * (double)rs), k3 = (float)(a * m2 * (double)rs * (double)mu - a * m1);
             A.dw0[c * 15 + tid] = (float)((double)k1 * e0s[tid] + (double)k2 * e0s[15 + tid] + (double)k3 * e0s[30 + tid]);      // (e0s[30 ..]: channel 0's rows)
         }
-    }
-}
-
-// The same finalize for a layer whose sums were taken by its consumers' data-gradient epilogues (conv_h3d_kernel<.., BSUM>): up to two sets
-// of per-tile rows [channel][tiles][4] = {sum g, sum g xhat, bound of max |g|, max |z - mean|} - the skip consumer's and the decimating
-// consumer's for an encoder layer, one set for a layer that feeds an upsample.  Sums: tiles in order, set 0 then set 1, in double;
-// max |g| <= the sum of the two sets' bounds (g is the sum of the two consumers' gradients).
-struct BnBwdTilesArgs {
-    const float* part0; int tiles0;      // rows of THIS layer's channel c start at part0 + c * tiles0 * 4 (the caller applied the row offset)
-    const float* part1; int tiles1;      // nullptr: one set
-    const float* gamma; const float* mean; const float* rstd;
-    float* dgamma; float* dbeta; float* dbias; float* k1; float* k2; float* k3; float* bound;
-    int C; double count;
-    int frozen;                          // BnBwdArgs::frozen
-};
-static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_tiles_kernel(BnBwdTilesArgs A)
-{
-    __shared__ double red[2 * WUNET_THREADS];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    double s1 = 0.0, s2 = 0.0;
-    float mg0 = 0.0f, mg1 = 0.0f, mz = 0.0f;
-    {
-        const float* p = A.part0 + (size_t)c * A.tiles0 * 4;
-        int r = tid;
-        for (; r + 3 * WUNET_THREADS < A.tiles0; r += 4 * WUNET_THREADS) {      // (four loads in flight, same order of additions)
-            const wunet_f4 v0 = wunet_ld4(p + 4 * (size_t)r), v1 = wunet_ld4(p + 4 * (size_t)(r + WUNET_THREADS));
-            const wunet_f4 v2 = wunet_ld4(p + 4 * (size_t)(r + 2 * WUNET_THREADS)), v3 = wunet_ld4(p + 4 * (size_t)(r + 3 * WUNET_THREADS));
-            s1 += (double)v0[0]; s2 += (double)v0[1]; s1 += (double)v1[0]; s2 += (double)v1[1];
-            s1 += (double)v2[0]; s2 += (double)v2[1]; s1 += (double)v3[0]; s2 += (double)v3[1];
-            mg0 = fmaxf(fmaxf(mg0, v0[2]), fmaxf(fmaxf(v1[2], v2[2]), v3[2]));
-            mz = fmaxf(fmaxf(mz, v0[3]), fmaxf(fmaxf(v1[3], v2[3]), v3[3]));
-        }
-        for (; r < A.tiles0; r += WUNET_THREADS) {
-            const wunet_f4 v = wunet_ld4(p + 4 * (size_t)r);
-            s1 += (double)v[0]; s2 += (double)v[1]; mg0 = fmaxf(mg0, v[2]); mz = fmaxf(mz, v[3]);
-        }
-    }
-    if (A.part1) {
-        const float* p = A.part1 + (size_t)c * A.tiles1 * 4;
-        for (int r = tid; r < A.tiles1; r += WUNET_THREADS) {
-            const wunet_f4 v = wunet_ld4(p + 4 * (size_t)r);
-            s1 += (double)v[0]; s2 += (double)v[1]; mg1 = fmaxf(mg1, v[2]); mz = fmaxf(mz, v[3]);
-        }
-    }
-    block_sum2(s1, s2, red);
-    __syncthreads();
-    block_max2(mg0, mg1, red);
-    __syncthreads();
-    float dummy = 0.0f;
-    block_max2(mz, dummy, red);
-    if (tid == 0) {
-        const double m1 = A.frozen ? 0.0 : s1 / A.count, m2 = A.frozen ? 0.0 : s2 / A.count;
-        const double a = (double)A.gamma[c] * (double)A.rstd[c];
-        A.dgamma[c] = (float)s2;
-        A.dbeta[c] = (float)s1;
-        A.dbias[c] = A.frozen ? (float)(a * s1) : 0.0f;
-        A.k1[c] = (float)a;
-        A.k2[c] = (float)(-a * m2 * (double)A.rstd[c]);
-        A.k3[c] = (float)(a * m2 * (double)A.rstd[c] * (double)A.mean[c] - a * m1);
-        A.bound[c] = (float)(fabs(a) * ((double)mg0 + (double)mg1) + fabs(a * m2 * (double)A.rstd[c]) * (double)mz + fabs(a * m1));
     }
 }
 

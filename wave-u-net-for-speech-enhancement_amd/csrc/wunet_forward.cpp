@@ -40,13 +40,12 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
     }
     // 1. pack all forward weights into MFMA-fragment order (one launch each for the fp32 and the split packs).  A training forward
     // whose first layer runs conv_first_kernel (it reads the raw weights) enqueues them - and the operand scales - on the side stream:
-    // conv_first and its BatchNorm finalize run beside them instead of behind three launches that only read the weights
-    // (WUNET_NO_EARLY_FPACK=1: A/B switch).  Order on the side stream: scales, split pack (first needed by layer 1), fp32 pack (the
+    // conv_first and its BatchNorm finalize run beside them instead of behind three launches that only read the weights.
+    // Order on the side stream: scales, split pack (first needed by layer 1), fp32 pack (the
     // levels of <= 8 samples), then the backward's packs.
     wunet_ctx::Side* fside = nullptr;
     if (training && c->NL > 1 && c->ly[0].first && !g_prof_on && !frozen(0)) {      // (a frozen first layer measures its bound before layer 1)
-        static const bool no_side = getenv("WUNET_NO_SIDE_STREAM") != nullptr;       // (profiling switch: everything on the caller's stream)
-        if (!no_side) fside = side_for_current_device(c);
+        if (!side_stream_off()) fside = side_for_current_device(c);
         if (fside && (hipEventRecord(fside->ev_fork, st) != hipSuccess || hipStreamWaitEvent(fside->stream, fside->ev_fork, 0) != hipSuccess))
             return fail(WUNET_E_RUNTIME, "fork onto the side stream failed");
     }
@@ -140,11 +139,10 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
     bool fpack_joined = fside == nullptr, fpack2_joined = fside == nullptr;
     // The backward's flipped / transposed weight packs only depend on the weights (and on the maxima h3_scales_kernel has just
     // taken): a training forward that will be followed by a backward enqueues them on the side stream now, beside the first convs,
-    // instead of leaving two launches at the head of the backward's critical path (WUNET_NO_EARLY_BPACK=1: A/B switch).
+    // instead of leaving two launches at the head of the backward's critical path.
     wunet_ctx::Side* bside = nullptr;          // the side stream holds this forward's backward packs
     if (training && save_for_backward && c->NL > 1) {
-        static const bool no_side = getenv("WUNET_NO_SIDE_STREAM") != nullptr;
-        wunet_ctx::Side* side = (no_side || g_prof_on) ? nullptr : side_for_current_device(c);
+        wunet_ctx::Side* side = (side_stream_off() || g_prof_on) ? nullptr : side_for_current_device(c);
         if (side) {
             // (behind the forward's packs on the side stream when they are there: no second fork)
             if (side != fside && (hipEventRecord(side->ev_fork, st) != hipSuccess || hipStreamWaitEvent(side->stream, side->ev_fork, 0) != hipSuccess))
@@ -170,7 +168,7 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
         WUNET_LAUNCH(bn_eval_all_kernel, dim3((unsigned)((maxc + WUNET_THREADS - 1) / WUNET_THREADS), (unsigned)c->NL), dim3(WUNET_THREADS), 0, st, T);
         WUNET_CHECK_LAUNCH();
     } else if (c->any_frozen) {
-        // the frozen layers: scale / shift and the backward's mean / rstd (+ the BSUM constants) from the running statistics, one launch
+        // the frozen layers: scale / shift and the backward's mean / rstd from the running statistics, one launch
         BnEvalTable T{};
         int nf = 0, maxc = 1;
         for (int i = 0; i < c->NL; ++i) {
@@ -179,7 +177,7 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
             BnEvalDesc& d = T.d[nf++];
             d.gamma = params[4 * i + 2]; d.beta = params[4 * i + 3]; d.running_mean = running[2 * i]; d.running_var = running[2 * i + 1];
             d.a = ws + l.a; d.s = ws + l.s; d.C = l.cout;
-            d.mean = ws + l.mean; d.rstd = ws + l.rstd; d.cst = l.bsum ? ws + l.cst : nullptr;
+            d.mean = ws + l.mean; d.rstd = ws + l.rstd;
             if (l.cout > maxc) maxc = l.cout;
         }
         if (nf > 0) {
@@ -290,7 +288,6 @@ int wunet_forward(wunet_ctx* c, const float* noisy, const float* const* params, 
         b.gamma = params[4 * i + 2]; b.beta = params[4 * i + 3];
         b.running_mean = running[2 * i]; b.running_var = running[2 * i + 1]; b.nbt = nbt[i];
         b.a = ws + l.a; b.s = ws + l.s; b.mean = ws + l.mean; b.rstd = ws + l.rstd;
-        b.cst = (bstats && l.bsum) ? ws + l.cst : nullptr;      // (read by the consumers' data-gradient epilogues, conv_h3d_kernel<.., BSUM>)
         b.C = l.cout; b.count = (double)c->B * l.Lt; b.training = bstats ? 1 : 0;
         // eval mode, a layer whose activation feeds split operands: its consumers' operand scale comes from the measured maximum
         // of |a z + s| (no batch statistics bound it).  The large producers (conv_first_kernel, un-split conv_h3_kernel) take it

@@ -288,13 +288,9 @@ static __global__ __launch_bounds__(WUNET_THREADS) void wgrad_h3_reduce_kernel(W
 // ENC (an encoder layer whose data gradients are whole tensors): its g = (dXdec[b, coff+c, l] + (l even ? dXenc[b, c, l/2] : 0)) * LeakyReLU'
 // (pass_a_kernel<A_ENC>'s arithmetic, bit for bit) is recomputed here from the two data gradients (6 bytes per value read instead of
 // the 4 of g) so that pass A does not WRITE g (4 bytes per value; a written byte costs 1.4 x a read one on this part).
-// UP (a layer that feeds an upsample and whose BatchNorm-backward sums came out of the consumer's data-gradient epilogue, conv_h3d_kernel<.., BSUM>:
-// no pass A ran, no g exists): g = upsample^T(dX of the next decoder layer) * LeakyReLU' is formed here from dX [B][Cg0][2L] (8 bytes per value
-// read instead of the 4 of a stored g; wunet_upT_row - pass_a_kernel<A_UP>'s arithmetic).
 struct GzHeadArgs {
-    const float* gh; const float* wh; const float* a; const float* s;      // HEAD (gh != nullptr); a, s also ENC and UP
+    const float* gh; const float* wh; const float* a; const float* s;      // HEAD (gh != nullptr); a, s also ENC and UPH
     const float* gd; const float* ge; int Cg0, coff;                        // ENC (gd != nullptr): dXdec [B][Cg0][L], dXenc [B][C][L/2]
-    const float* gu; float up_scale;                                        // UP (gu != nullptr): dX [B][Cg0][2L]; (float)(Lt-1)/(2Lt-1)
     const float* gq;                                                        // UPH (gq != nullptr): dXh [B][C][L], completed by pass_a_kernel<A_UPH>
 };
 #define WUNET_GZ_FIN_LOADS 1536   // (sweep 1152 / 2048 / 3100 / all: 5.41 / 5.42 / 5.46 / 5.50 ms per step - beyond the 512-sample level the prologue costs more than the launch)
@@ -304,7 +300,7 @@ struct GzHeadArgs {
 // vmcnt(0)` per channel, eight serialised memory round trips per thread at 197 VGPRs (two waves per SIMD) - and the pass ran at HALF the rate of
 // a kernel that moves the same bytes (tools/microbench/elem_passes.hip: 92.6 us against 46 us on decoder.10's geometry).  With the mode a
 // template parameter every load of the iteration is issued before the first value is used, as in prep_h3_kernel.
-enum { GZ_G = 0, GZ_HEAD = 1, GZ_ENC = 2, GZ_UPH = 3, GZ_UP = 4 };
+enum { GZ_G = 0, GZ_HEAD = 1, GZ_ENC = 2, GZ_UPH = 3 };
 template <bool FIN, int GM, bool BFM>
 __global__ __launch_bounds__(WUNET_THREADS) void gz_split_h3_kernel(const float* g, const float* z, const float* k1, const float* k2,
                                                                      const float* k3, const float* bound, float* sc, wunet_half* hi,
@@ -394,8 +390,6 @@ __global__ __launch_bounds__(WUNET_THREADS) void gz_split_h3_kernel(const float*
             float whv[GM == GZ_HEAD ? 8 : 1];
             wunet_f4 gh4 = wunet_f4{0.f, 0.f, 0.f, 0.f};
             if (GM == GZ_HEAD) gh4 = wunet_ld4(H.gh + (size_t)b * L + 4 * l4);
-            WunetUpT U;
-            if (GM == GZ_UP) wunet_upT_coords(4 * l4, Lt, H.up_scale, U);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int cc = c0_ + e < C ? c0_ + e : C - 1;
@@ -452,12 +446,6 @@ __global__ __launch_bounds__(WUNET_THREADS) void gz_split_h3_kernel(const float*
 #pragma unroll
                     for (int j = 0; j < 4; ++j)
                         if (!(ha * zv[e][j] + hs > 0.0f)) gg[j] *= WUNET_SLOPE;
-                } else if (GM == GZ_UP) {
-                    float gu[4];
-                    const int cc = ok ? c0_ + e : C - 1;
-                    wunet_upT_row(H.gu + ((size_t)b * H.Cg0 + cc) * (size_t)(2 * L), 4 * l4, 2 * L, 2 * Lt, Lt, H.up_scale, U, gu);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) gg[j] = (ha * zv[e][j] + hs > 0.0f) ? gu[j] : gu[j] * WUNET_SLOPE;
                 }
                 const float a = kA[e], bb = kB[e], d = kD[e];
 #pragma unroll
