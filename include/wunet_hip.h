@@ -138,6 +138,26 @@ int wunet_loss_backward(int kind, const float* clean, const float* enhanced, con
 int wunet_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                     float* const* exp_avg_sq, const size_t* numels, double lr, double beta1, double beta2, double eps,
                     long long step, double grad_scale, long long* step_dev, float* hyper_dev, void* stream);
+/* wunet_adam_step with three optional parts, each a per-step scalar in device memory so that a captured step replays unchanged:
+ * replaces torch.nn.utils.clip_grad_norm_(params, max_grad_norm) + torch.optim.AdamW(params, lr, betas, eps, weight_decay).step()
+ * (no reference counterpart: train.py:31-35 builds a plain Adam and trainer/trainer.py:34-38 does not clip).
+ *   max_grad_norm > 0: the 2-norm over ALL n_tensors gradients (after grad_scale) is summed in double by one extra read of the
+ *     gradients, clip = min(1, max_grad_norm / (norm + 1e-6)) multiplies every gradient inside the update.  The gradient tensors
+ *     are NOT modified (clip_grad_norm_ scales them in place).  A non-finite norm propagates as in torch with
+ *     error_if_nonfinite=False.  scratch: >= wunet_adam_scratch_bytes(n_tensors) device bytes, no memset needed.
+ *   weight_decay > 0: decoupled, p <- p * (1 - lr * weight_decay) before the update (torch.optim.AdamW's order).
+ *   lr_dev != NULL: the learning rate is read from this device double (`lr` is ignored): a scheduler changes the value, the
+ *     launches and their arguments stay the same.
+ * step_dev may be NULL (then `step` counts, as in wunet_adam_step).  hyper_dev is required, WUNET_ADAM_HYPER_FLOATS floats that
+ * the call overwrites: [0] lr / (1 - beta1^t), [1] sqrt(1 - beta2^t), [2] clip (1 when off), [3] the norm before clipping
+ * (0 when off), [4] 1 - lr * weight_decay, the rest reserved.  Capture-safe: no allocation, no synchronisation, no host read-back.
+ * With all three parts off the result has the bits of wunet_adam_step. */
+#define WUNET_ADAM_HYPER_FLOATS 8
+size_t wunet_adam_scratch_bytes(int n_tensors);
+int wunet_adam_step_ex(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                       float* const* exp_avg_sq, const size_t* numels, double lr, double beta1, double beta2, double eps,
+                       long long step, double grad_scale, double weight_decay, double max_grad_norm, long long* step_dev,
+                       float* hyper_dev, const double* lr_dev, void* scratch, void* stream);
 
 /* Introspection for tests / profiling: float offset of layer i's raw conv output inside the
  * workspace, its channel count and length. */

@@ -1,0 +1,82 @@
+"""GPU box: what the options of the fused Adam step cost.  The captured training step at batch 64 x 16384 with
+FusedAdamW(max_grad_norm, device_lr, weight_decay) against the default FusedAdam, alternating three times, and the optimiser step
+alone (a graph of 10 steps, so launch gaps do not count): the difference is one read of the gradients by grad_sqnorm_partial_kernel
+plus the one-block adam_hyper_ex_kernel.   python tools/adam_options_bench.py"""
+import importlib, sys, os, statistics
+import torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+PKG = "wave-u-net-for-speech-enhancement_amd"
+pkg = importlib.import_module(PKG)
+optim = importlib.import_module(PKG + ".optim")
+dev = torch.device("cuda:0")
+n, ci, B, T = 12, 24, 64, 16384
+g = torch.Generator().manual_seed(1)
+clean = torch.rand(B, 1, T, generator=g) * 2 - 1
+noisy = (clean + 0.1 * torch.randn(B, 1, T, generator=g)).to(dev)
+clean = clean.to(dev)
+
+def build(on):
+    torch.manual_seed(0)
+    m = pkg.Model(n_layers=n, channels_interval=ci).to(dev).train()
+    crit = pkg.smooth_l1_loss()
+    if on:
+        opt = optim.FusedAdamW(m.parameters(), lr=1e-3, weight_decay=0.01, device_step=True, device_lr=True, max_grad_norm=1.0)
+    else:
+        opt = optim.FusedAdam(m.parameters(), lr=1e-3, device_step=True)
+    def step():
+        opt.zero_grad(set_to_none=True)
+        loss = crit(clean, m(noisy)); loss.backward(); opt.step(); return loss
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    opt.zero_grad(set_to_none=True)
+    with torch.cuda.graph(graph):
+        step()
+    opt.advance_host_step(-1)
+    torch.cuda.synchronize()
+    return m, opt, graph
+
+def time_replays(graph, opt, k=60):
+    for _ in range(10):
+        graph.replay()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(k):
+        graph.replay()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / k
+
+def time_opt_step(opt, k=200):
+    for _ in range(10):
+        opt.step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    g2 = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g2):
+        for _ in range(10):
+            opt.step()
+    opt.advance_host_step(-10)
+    g2.replay(); torch.cuda.synchronize()
+    e0.record()
+    for _ in range(k // 10):
+        g2.replay()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / (k // 10 * 10)
+
+res = {}
+for on in (False, True):
+    res[on] = build(on)
+nel = sum(p.numel() for p in res[True][0].parameters())
+print(f"parameters {nel} = {nel * 4 / 1e6:.1f} MB of gradients")
+for rep in range(3):
+    for on in (False, True):
+        m, opt, graph = res[on]
+        print(f"rep {rep} options {'on ' if on else 'off'}: captured step {time_replays(graph, opt):.4f} ms")
+for rep in range(3):
+    for on in (False, True):
+        m, opt, graph = res[on]
+        print(f"rep {rep} options {'on ' if on else 'off'}: optimiser step alone (graph of 10 steps) {time_opt_step(opt) * 1e3:.1f} us")
+opt = res[True][1]
+print("last_grad_norm", float(opt.last_grad_norm), "clip", float(opt._dev[0][1][2]), "decay", float(opt._dev[0][1][4]))

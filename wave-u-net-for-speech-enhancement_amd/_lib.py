@@ -18,7 +18,7 @@ EXPORTS = [
     "wunet_adam_step", "wunet_set_h3", "wunet_op_conv1d_split", "wunet_op_conv1d_dgrad_split", "wunet_op_conv1d_wgrad_split",
     "wunet_backward_range_async", "wunet_backward_join", "wunet_debug_set_conv_trace", "wunet_crop_windows",
     "wunet_comm_unique_id", "wunet_comm_create", "wunet_comm_allreduce_sum", "wunet_comm_world", "wunet_comm_destroy",
-    "wunet_debug_stamps", "wunet_set_bn_frozen", "wunet_backward_input",
+    "wunet_debug_stamps", "wunet_set_bn_frozen", "wunet_backward_input", "wunet_adam_scratch_bytes", "wunet_adam_step_ex",
 ]
 
 _vp = ctypes.c_void_p
@@ -54,6 +54,12 @@ def declare(lib):
         getattr(lib, name).argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
     lib.wunet_adam_step.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                     ctypes.c_double, ctypes.c_longlong, ctypes.c_double, _vp, _vp, _vp]
+    if hasattr(lib, "wunet_adam_step_ex"):       # (saved libraries of earlier versions do not have it)
+        lib.wunet_adam_scratch_bytes.argtypes = [_i]
+        lib.wunet_adam_scratch_bytes.restype = _sz
+        lib.wunet_adam_step_ex.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_longlong, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                           _vp, _vp, _vp, _vp, _vp]
     lib.wunet_set_h3.argtypes = [_vp, _i]
     if hasattr(lib, "wunet_set_bn_frozen"):      # (saved libraries of earlier versions - tools/lib_ab.sh - do not have it)
         lib.wunet_set_bn_frozen.argtypes = [_vp, _vp, _i]

@@ -1339,3 +1339,128 @@ static __global__ void adam_hyper_kernel(long long* step, double lr, double beta
     hyper[0] = (float)(lr / bc1);
     hyper[1] = (float)sqrt(bc2);
 }
+
+// ---------------------------------------------------------------------------- fused Adam, the optional parts (wunet_adam_step_ex)
+// Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_), decoupled weight decay (torch.optim.AdamW) and an lr read from
+// device memory: per-step scalars that live in the hyper buffer next to {step_size, bc2_sqrt}, so a captured step replays unchanged
+// under an lr schedule.  Slots of the hyper buffer (WUNET_ADAM_HYPER_FLOATS of include/wunet_hip.h):
+#define WUNET_HYPER_STEP_SIZE 0
+#define WUNET_HYPER_BC2_SQRT 1
+#define WUNET_HYPER_CLIP 2        // min(1, max_norm / (norm + 1e-6)); 1 when clipping is off
+#define WUNET_HYPER_NORM 3        // the norm of the scaled gradient before clipping; 0 when clipping is off
+#define WUNET_HYPER_DECAY 4       // 1 - lr * weight_decay
+
+// Sum of (gscale * g)^2 per block, in double.  Grid as for adam_kernel (blockIdx.y = tensor, blockIdx.x strides inside it); block
+// (x, y) writes part[y * gridDim.x + x] - also when it had no element (0): the slots need no memset and adam_hyper_ex_kernel adds
+// every one of them.  Four trips' loads are in flight ahead of the first use (loss_partial_kernel); the terms are added in the
+// one-trip loop's order.
+static __global__ __launch_bounds__(WUNET_THREADS) void grad_sqnorm_partial_kernel(AdamTable T, float gscale, double* part)
+{
+    __shared__ double red[2 * WUNET_THREADS];
+    const int t = blockIdx.y;
+    const float* g = T.g[t];
+    const unsigned n = T.n[t];
+    const double gs = (double)gscale;
+    double s = 0.0, dummy = 0.0;
+    const size_t stride = (size_t)gridDim.x * WUNET_THREADS;
+    size_t i = (size_t)blockIdx.x * WUNET_THREADS + threadIdx.x;
+    for (; i + 3 * stride < n; i += 4 * stride) {
+        float e[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) e[u] = g[i + u * stride];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { const double x = gs * (double)e[u]; s += x * x; }
+    }
+    for (; i < n; i += stride) { const double x = gs * (double)g[i]; s += x * x; }
+    block_sum2(s, dummy, red);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// adam_hyper_kernel with the optional parts, one block.  n_part > 0: the n_part partial sums of grad_sqnorm_partial_kernel are
+// added in a fixed order in double (thread k takes k, k + 256, ...; then block_sum2's tree), norm = sqrt(sum) and
+// clip = min(1, max_norm / (norm + 1e-6)) - clip_grad_norm_'s formula, in double, rounded to float once; a non-finite norm
+// propagates as in torch (error_if_nonfinite=False): inf gives clip 0, NaN gives NaN.  lr_dev != nullptr: the learning rate is
+// read from device memory (a double: lr / bc1 then has the bits of the host path).  step_dev != nullptr: the device counter is
+// incremented and used, otherwise `step` is the host's count.
+static __global__ __launch_bounds__(WUNET_THREADS) void adam_hyper_ex_kernel(long long* step_dev, long long step, double lr, const double* lr_dev,
+                                                                       double beta1, double beta2, double weight_decay, double max_norm,
+                                                                       const double* part, int n_part, float* hyper)
+{
+    __shared__ double red[2 * WUNET_THREADS];
+    double s = 0.0, dummy = 0.0;
+    int r = threadIdx.x;
+    for (; r + 3 * WUNET_THREADS < n_part; r += 4 * WUNET_THREADS) {
+        double e[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) e[u] = part[r + u * WUNET_THREADS];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) s += e[u];
+    }
+    for (; r < n_part; r += WUNET_THREADS) s += part[r];
+    block_sum2(s, dummy, red);
+    if (threadIdx.x != 0) return;
+    long long t = step;
+    if (step_dev) {
+        t = *step_dev + 1;
+        *step_dev = t;
+    }
+    if (lr_dev) lr = *lr_dev;
+    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+    double norm = 0.0, clip = 1.0;
+    if (n_part > 0) {
+        norm = sqrt(s);
+        const double c = max_norm / (norm + 1e-6);
+        clip = c > 1.0 ? 1.0 : c;                   // (a NaN stays: torch.clamp(max=1) keeps it too)
+    }
+    hyper[WUNET_HYPER_STEP_SIZE] = (float)(lr / bc1);
+    hyper[WUNET_HYPER_BC2_SQRT] = (float)sqrt(bc2);
+    hyper[WUNET_HYPER_CLIP] = (float)clip;
+    hyper[WUNET_HYPER_NORM] = (float)norm;
+    hyper[WUNET_HYPER_DECAY] = (float)(1.0 - lr * weight_decay);
+}
+
+// The roundings of adam_kernel AS hipcc COMPILES IT for gfx950, written out so that adam_ex_kernel with neutral options (clip 1, decay 1)
+// gives adam_kernel's bits whatever the optimiser decides here: under the default -ffp-contract=fast adam_kernel's two moment lines come
+// out as separate multiplies and adds (v_pk_mul_f32 / v_pk_add_f32: every product rounded) and only its last line, p - step_size * q,
+// as ONE v_fma_f32.  adam_ex_kernel therefore pins contraction off and asks for that one fma by name; the emulator build
+// (-ffp-contract=off) rounds that product in adam_kernel too.  tests/test_gpu_adam_options.py compares the two kernels bit for bit.
+__device__ __forceinline__ float adam_update(float p, float step_size, float q)
+{
+#ifdef WUNET_EMU
+    return p - step_size * q;
+#else
+    return __builtin_fmaf(-step_size, q, p);
+#endif
+}
+
+// adam_kernel with the optional parts; everything per-step comes from the hyper buffer.  gi = g * (gscale * clip), no multiply when
+// the factor is exactly 1; p <- p * decay first when decay != 1 (torch.optim.AdamW's order: the decayed parameter is rounded to
+// float before the update is subtracted, never fused into it); then adam_kernel's moment and update lines.  The gradient itself is NOT modified
+// (clip_grad_norm_ scales it in place; the fused step does not pay that write).
+static __global__ __launch_bounds__(WUNET_THREADS) void adam_ex_kernel(AdamTable T, float one_minus_b1, float b2, float one_minus_b2,
+                                                                 float eps, float gscale, const float* hyper)
+{
+    const float step_size = hyper[WUNET_HYPER_STEP_SIZE], bc2_sqrt = hyper[WUNET_HYPER_BC2_SQRT];
+    const float factor = gscale * hyper[WUNET_HYPER_CLIP], decay = hyper[WUNET_HYPER_DECAY];
+    const int t = blockIdx.y;
+    float* p = T.p[t];
+    const float* g = T.g[t];
+    float* m = T.m[t];
+    float* v = T.v[t];
+    const unsigned n = T.n[t];
+    for (unsigned i = blockIdx.x * WUNET_THREADS + threadIdx.x; i < n; i += gridDim.x * WUNET_THREADS) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+        const float gi = factor == 1.0f ? g[i] : g[i] * factor;
+        float mi = m[i], vi = v[i];
+        mi = mi + one_minus_b1 * (gi - mi);
+        vi = vi * b2 + one_minus_b2 * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        float pi = p[i];
+        if (decay != 1.0f) pi = pi * decay;
+        p[i] = adam_update(pi, step_size, mi / denom);
+    }
+}

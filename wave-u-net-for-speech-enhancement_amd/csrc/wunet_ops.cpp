@@ -71,6 +71,69 @@ int wunet_adam_step(int n_tensors, float* const* params, const float* const* gra
     return WUNET_OK;
 }
 
+// One launch of an Adam step: up to WUNET_ADAM_MAX tensors, grid (bx, cnt) as wunet_adam_step builds it.
+struct AdamLaunch {
+    AdamTable T;
+    unsigned bx;
+    int cnt;
+};
+
+static void adam_launch_at(int n_tensors, int base, float* const* params, const float* const* grads, float* const* exp_avg,
+                           float* const* exp_avg_sq, const size_t* numels, AdamLaunch& L)
+{
+    L.T = AdamTable{};
+    L.cnt = n_tensors - base < WUNET_ADAM_MAX ? n_tensors - base : WUNET_ADAM_MAX;
+    size_t nmax = 0;
+    for (int k = 0; k < L.cnt; ++k) {
+        L.T.p[k] = params[base + k]; L.T.g[k] = grads[base + k]; L.T.m[k] = exp_avg[base + k]; L.T.v[k] = exp_avg_sq[base + k];
+        L.T.n[k] = (unsigned)numels[base + k];
+        if (numels[base + k] > nmax) nmax = numels[base + k];
+    }
+    size_t bx = (nmax + WUNET_THREADS * 4 - 1) / (WUNET_THREADS * 4);
+    if (bx < 1) bx = 1;
+    if (bx > 256) bx = 256;
+    L.bx = (unsigned)bx;
+}
+
+// one double per block of the norm's launches: at most 256 blocks per tensor
+size_t wunet_adam_scratch_bytes(int n_tensors) { return n_tensors > 0 ? (size_t)n_tensors * 256 * sizeof(double) : 0; }
+
+int wunet_adam_step_ex(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                       float* const* exp_avg_sq, const size_t* numels, double lr, double beta1, double beta2, double eps,
+                       long long step, double grad_scale, double weight_decay, double max_grad_norm, long long* step_dev,
+                       float* hyper_dev, const double* lr_dev, void* scratch, void* stream)
+{
+    if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numels))) return fail(WUNET_E_ARG, "null argument");
+    if (!hyper_dev) return fail(WUNET_E_ARG, "wunet_adam_step_ex needs the hyper buffer (WUNET_ADAM_HYPER_FLOATS floats)");
+    if (!step_dev && step < 1) return fail(WUNET_E_ARG, "step must be >= 1");
+    if (!(weight_decay >= 0.0)) return fail(WUNET_E_ARG, "weight_decay must be >= 0 (got %g)", weight_decay);
+    if (max_grad_norm != max_grad_norm) return fail(WUNET_E_ARG, "max_grad_norm is NaN");
+    const bool clip = max_grad_norm > 0.0 && n_tensors > 0;
+    if (clip && !scratch) return fail(WUNET_E_ARG, "max_grad_norm > 0 needs wunet_adam_scratch_bytes(n_tensors) bytes of scratch");
+    for (int k = 0; k < n_tensors; ++k)          // (before anything is enqueued: a refused call leaves the device counter alone)
+        if (numels[k] >= (1ull << 32)) return fail(WUNET_E_ARG, "tensor too large");
+    hipStream_t st = (hipStream_t)stream;
+    AdamLaunch L;
+    // the norm first: the launches of the step write their partial sums one behind the other
+    int n_part = 0;
+    for (int base = 0; clip && base < n_tensors; base += WUNET_ADAM_MAX) {
+        adam_launch_at(n_tensors, base, params, grads, exp_avg, exp_avg_sq, numels, L);
+        WUNET_LAUNCH(grad_sqnorm_partial_kernel, dim3(L.bx, L.cnt), dim3(WUNET_THREADS), 0, st, L.T, (float)grad_scale, (double*)scratch + n_part);
+        WUNET_CHECK_LAUNCH();
+        n_part += (int)L.bx * L.cnt;
+    }
+    WUNET_LAUNCH(adam_hyper_ex_kernel, dim3(1), dim3(WUNET_THREADS), 0, st, step_dev, step, lr, lr_dev, beta1, beta2, weight_decay, max_grad_norm,
+                 (const double*)scratch, n_part, hyper_dev);
+    WUNET_CHECK_LAUNCH();
+    for (int base = 0; base < n_tensors; base += WUNET_ADAM_MAX) {
+        adam_launch_at(n_tensors, base, params, grads, exp_avg, exp_avg_sq, numels, L);
+        WUNET_LAUNCH(adam_ex_kernel, dim3(L.bx, L.cnt), dim3(WUNET_THREADS), 0, st, L.T, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                     (float)eps, (float)grad_scale, (const float*)hyper_dev);
+        WUNET_CHECK_LAUNCH();
+    }
+    return WUNET_OK;
+}
+
 // ---------------------------------------------------------------------------- profiler
 int wunet_profile_enable(int on)
 {

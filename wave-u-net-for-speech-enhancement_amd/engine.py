@@ -348,13 +348,36 @@ class Engine:
         return g
 
 
-def _adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, hyper_dev=None):
+def _adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, hyper_dev=None, *,
+               weight_decay=0.0, max_grad_norm=None, lr_dev=None, scratch=None):
     """One fused Adam step over a list of tensors.  step_dev (int64 device scalar) + hyper_dev (2 floats):
-    the step count lives on the device and the call increments it (capturable in a hipGraph); otherwise `step` is the host's."""
+    the step count lives on the device and the call increments it (capturable in a hipGraph); otherwise `step` is the host's.
+    Keyword arguments (include/wunet_hip.h: wunet_adam_step_ex; with all of them off the call is wunet_adam_step as before):
+    weight_decay - decoupled (AdamW); max_grad_norm - clipping by the global norm inside the step, `scratch` then holds
+    adam_scratch_bytes(len(params)) bytes (p.grad is NOT modified); lr_dev - a float64 device scalar the learning rate is read from.
+    Any of them needs hyper_dev with ADAM_HYPER_FLOATS floats: [2] clip, [3] the norm before clipping, [4] 1 - lr * weight_decay."""
+    ex = bool(weight_decay) or max_grad_norm is not None or lr_dev is not None
+    if ex:
+        clip = float(max_grad_norm) if max_grad_norm is not None else 0.0
+        if max_grad_norm is not None and not clip > 0.0:
+            raise WunetError(f"adam_step: max_grad_norm must be > 0 (got {max_grad_norm}); None turns clipping off")
+        if hyper_dev is None or hyper_dev.dtype != torch.float32 or hyper_dev.numel() < ADAM_HYPER_FLOATS or not hyper_dev.is_contiguous():
+            raise WunetError(f"adam_step: weight_decay / max_grad_norm / lr_dev need hyper_dev with {ADAM_HYPER_FLOATS} float32")
+        if lr_dev is not None and (lr_dev.dtype != torch.float64 or lr_dev.numel() != 1):
+            raise WunetError("adam_step: lr_dev must be ONE float64")
+        if clip > 0.0 and (scratch is None or scratch.numel() * scratch.element_size() < self.adam_scratch_bytes(len(params))):
+            raise WunetError("adam_step: max_grad_norm needs `scratch` of adam_scratch_bytes(len(params)) bytes")
+        extra = [t for t in (step_dev, hyper_dev, lr_dev, scratch) if t is not None]
+        if any(t.device != params[0].device for t in extra):
+            raise WunetError("adam_step: step_dev / hyper_dev / lr_dev / scratch must live on the parameters' device")
     if self._fast is not None:
         try:
-            self._fast.adam_step(params, grads, exp_avg, exp_avg_sq, float(lr), float(beta1), float(beta2), float(eps), int(step),
-                                 float(grad_scale), step_dev, hyper_dev)
+            if ex:
+                self._fast.adam_step_ex(params, grads, exp_avg, exp_avg_sq, float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                        float(grad_scale), float(weight_decay), clip, step_dev, hyper_dev, lr_dev, scratch)
+            else:
+                self._fast.adam_step(params, grads, exp_avg, exp_avg_sq, float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                     float(grad_scale), step_dev, hyper_dev)
         except RuntimeError as e:
             raise WunetError(str(e).split("\n")[0]) from None
         return
@@ -363,14 +386,26 @@ def _adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, 
     n = len(params)
     numels = (ctypes.c_size_t * n)(*[p.numel() for p in params])
     dev = params[0].device
+    ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
     with self._device_guard(dev):
-        self._check(self.lib.wunet_adam_step(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg),
-                                             self._ptrs(exp_avg_sq), numels, float(lr), float(beta1), float(beta2),
-                                             float(eps), int(step), float(grad_scale),
-                                             step_dev.data_ptr() if step_dev is not None else None,
-                                             hyper_dev.data_ptr() if hyper_dev is not None else None, self._stream(dev)))
+        if ex:
+            self._check(self.lib.wunet_adam_step_ex(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg), self._ptrs(exp_avg_sq),
+                                                    numels, float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                                    float(grad_scale), float(weight_decay), clip, ptr(step_dev), ptr(hyper_dev),
+                                                    ptr(lr_dev), ptr(scratch), self._stream(dev)))
+        else:
+            self._check(self.lib.wunet_adam_step(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg),
+                                                 self._ptrs(exp_avg_sq), numels, float(lr), float(beta1), float(beta2),
+                                                 float(eps), int(step), float(grad_scale), ptr(step_dev), ptr(hyper_dev), self._stream(dev)))
 
 
+def _adam_scratch_bytes(self, n_tensors):
+    """Device bytes of the partial sums of the gradient norm (adam_step(max_grad_norm=...)) over n_tensors tensors."""
+    return int(self.lib.wunet_adam_scratch_bytes(int(n_tensors)))
+
+
+ADAM_HYPER_FLOATS = 8                # WUNET_ADAM_HYPER_FLOATS of include/wunet_hip.h
+Engine.adam_scratch_bytes = _adam_scratch_bytes
 Engine.adam_step = _adam_step
 
 

@@ -1,4 +1,4 @@
-// Host-side marshalling of the three per-step calls (forward, backward range, Adam step) as a PyTorch C++ extension over the C ABI
+// Host-side marshalling of the three per-step calls (forward, backward range, Adam step / its _ex form) as a PyTorch C++ extension over the C ABI
 // (include/wunet_hip.h): validates the ~100 - 400 tensors of a call, collects their addresses, allocates output / workspace from
 // torch's caching allocator, takes torch's current HIP stream and calls libwunet_hip.so - what engine.py does through ctypes in
 // ~0.2 ms of Python per step, here in ~20 us.  Optional: engine.py falls back to its ctypes path when this module is not built;
@@ -123,6 +123,44 @@ void adam_step(const std::vector<at::Tensor>& params, const std::vector<at::Tens
     if (rc) fail_rc(rc);
 }
 
+// wunet_adam_step_ex: the step with clipping by the global norm, decoupled weight decay and / or a device-side lr (engine.Engine.adam_step's
+// keyword arguments).  hyper_dev: WUNET_ADAM_HYPER_FLOATS floats, required; scratch: wunet_adam_scratch_bytes(n) bytes when max_grad_norm > 0.
+void adam_step_ex(const std::vector<at::Tensor>& params, const std::vector<at::Tensor>& grads, const std::vector<at::Tensor>& exp_avg,
+                  const std::vector<at::Tensor>& exp_avg_sq, double lr, double beta1, double beta2, double eps, int64_t step, double grad_scale,
+                  double weight_decay, double max_grad_norm, const c10::optional<at::Tensor>& step_dev, const at::Tensor& hyper_dev,
+                  const c10::optional<at::Tensor>& lr_dev, const c10::optional<at::Tensor>& scratch)
+{
+    TORCH_CHECK(!params.empty() && grads.size() == params.size() && exp_avg.size() == params.size() && exp_avg_sq.size() == params.size(),
+                "adam_step_ex: four lists of one length");
+    const c10::Device dev = params[0].device();
+    require_all(params, "adam param", dev);
+    require_all(grads, "adam grad", dev);
+    require_all(exp_avg, "adam exp_avg", dev);
+    require_all(exp_avg_sq, "adam exp_avg_sq", dev);
+    require_all({hyper_dev}, "adam hyper_dev", dev);
+    TORCH_CHECK(hyper_dev.numel() >= WUNET_ADAM_HYPER_FLOATS, "adam_step_ex: hyper_dev holds fewer than WUNET_ADAM_HYPER_FLOATS floats");
+    if (step_dev) require_all({*step_dev}, "adam step_dev", dev, at::kLong);
+    if (lr_dev)
+        TORCH_CHECK(lr_dev->scalar_type() == at::kDouble && lr_dev->numel() == 1 && lr_dev->device() == dev, "adam_step_ex: lr_dev must be ONE float64 on the parameters' device");
+    if (max_grad_norm > 0.0)
+        TORCH_CHECK(scratch && scratch->device() == dev && scratch->is_contiguous()
+                        && (size_t)scratch->numel() * scratch->element_size() >= wunet_adam_scratch_bytes((int)params.size()),
+                    "adam_step_ex: max_grad_norm needs wunet_adam_scratch_bytes(n) bytes of scratch on the parameters' device");
+    c10::DeviceGuard guard(dev);
+    std::vector<size_t> numels(params.size());
+    for (size_t k = 0; k < params.size(); ++k) numels[k] = (size_t)params[k].numel();
+    auto pp = pointers<float>(params);
+    auto gp = pointers<const float>(grads);
+    auto mp = pointers<float>(exp_avg);
+    auto vp = pointers<float>(exp_avg_sq);
+    const int rc = wunet_adam_step_ex((int)params.size(), pp.data(), gp.data(), mp.data(), vp.data(), numels.data(), lr, beta1, beta2, eps,
+                                      (long long)step, grad_scale, weight_decay, max_grad_norm,
+                                      step_dev ? (long long*)step_dev->data_ptr() : nullptr, hyper_dev.data_ptr<float>(),
+                                      lr_dev ? (const double*)lr_dev->data_ptr() : nullptr, scratch ? scratch->data_ptr() : nullptr,
+                                      current_stream(dev));
+    if (rc) fail_rc(rc);
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
@@ -133,4 +171,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
           py::arg("with_backward"), py::arg("ws_reuse") = py::none(), py::arg("packs_valid") = false, py::call_guard<py::gil_scoped_release>());
     m.def("backward_range", &backward_range, py::call_guard<py::gil_scoped_release>());
     m.def("adam_step", &adam_step, py::call_guard<py::gil_scoped_release>());
+    m.def("adam_step_ex", &adam_step_ex, py::call_guard<py::gil_scoped_release>());
 }

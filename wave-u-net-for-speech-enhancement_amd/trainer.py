@@ -16,7 +16,10 @@ Differences from the reference loop, all on the f2 list:
   * after a few eager steps the whole step - forward, loss, backward, Adam (optim.FusedAdam with its device-side step counter) - is
     captured once in a hipGraph (torch.cuda.CUDAGraph) on static input buffers and replayed: ~230 kernel launches become one graph
     launch per step (default on one GPU with FusedAdam; `"graph": false` in the trainer config or WUNET_GRAPH=0 keeps eager launches;
-    hyper-parameters that change every step - a per-step LR schedule - make it fall back to eager by itself);
+    hyper-parameters that change every step - a per-step LR schedule - make it fall back to eager by itself, unless the optimiser
+    reads its lr from device memory: `"device_lr": true` in the trainer config / FusedAdam(device_lr=True) keeps the one graph);
+  * `"max_grad_norm": <float>` in the trainer config: gradient clipping by the global norm inside the fused step (optim.FusedAdam);
+    `trainer.lr_scheduler` (None by default): its .step() is called after every optimiser step;
   * checkpoints keep the reference's names and keys (base_trainer.py:83-124) so either side can resume; only rank 0 writes.
 """
 import os
@@ -60,6 +63,16 @@ class Trainer:
         self.optimizer = optimizer
         fused = isinstance(optimizer, FusedAdam)
         tcfg = config["trainer"]
+        # "max_grad_norm" / "device_lr": options of the fused step (optim.FusedAdam); another optimiser cannot honour them
+        for key in ("max_grad_norm", "device_lr"):
+            if tcfg.get(key) is None:
+                continue
+            if not fused:
+                raise ValueError(f'trainer config "{key}" needs optim.FusedAdam / FusedAdamW (got {type(optimizer).__name__}): '
+                                 "it is applied inside the fused step")
+            if key == "max_grad_norm" and not float(tcfg[key]) > 0.0:
+                raise ValueError(f'trainer config "max_grad_norm" must be > 0 (got {tcfg[key]}); leave it out to train without clipping')
+            setattr(optimizer, key, bool(tcfg[key]) if key == "device_lr" else float(tcfg[key]))
         # "native_rccl": the bucket all-reduces through the library's own RCCL entry (wunet_comm_*, capturable in the step graph)
         # instead of torch.distributed's process group; default: torch.distributed (measured on hardware only at world size 1 so far)
         native = bool(tcfg.get("native_rccl", os.environ.get("WUNET_NATIVE_RCCL", "0") not in ("", "0"))) and self.device.type == "cuda"
@@ -90,6 +103,8 @@ class Trainer:
         self._recaptures = 0          # consecutive graphs, dropped for a changed lr / betas / eps, that did not earn their capture back
         self._replays = 0
         self._capture_s = 0.0         # wall time of the live graph's capture
+        self.captures = 0             # step graphs captured so far
+        self.lr_scheduler = None      # set by the caller: .step() after every optimiser step (eager or replay)
         self.start_epoch = 1
         self.best_score = float("-inf")
         root = Path(os.path.expanduser(config.get("root_dir", "."))).absolute() / config.get("experiment_name", "exp")
@@ -165,6 +180,7 @@ class Trainer:
             self.optimizer.step()               # (host side of step(): state["step"] += 1 happened once, here)
             self._static_loss = loss.detach()
         self._graph = graph
+        self.captures += 1
         self._graph_sig = self.optimizer.hyper_signature()
         self._graph_bn = self._bn_signature()
         # capture does not execute: undo the host-side count of the captured call; every replay counts itself
@@ -178,6 +194,12 @@ class Trainer:
         return (m.training, frozen() if frozen is not None else None)
 
     def _step(self, mixture, clean):
+        loss = self._optimizer_step(mixture, clean)
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.step()
+        return loss
+
+    def _optimizer_step(self, mixture, clean):
         if not self.use_graph:
             return self._eager_step(mixture, clean)
         if self._graph is not None and self._bn_signature() != self._graph_bn:
@@ -196,7 +218,8 @@ class Trainer:
             if self._recaptures >= MAX_RECAPTURES:
                 import warnings
                 warnings.warn("Trainer: the optimiser's hyper-parameters change every few steps (a per-step LR schedule?); the captured "
-                              "step graph would be rebuilt each time - falling back to eager launches", RuntimeWarning)
+                              "step graph would be rebuilt each time - falling back to eager launches (FusedAdam(device_lr=True) or "
+                              '"device_lr": true in the trainer config keeps the graph under an lr schedule)', RuntimeWarning)
                 self.use_graph = False
                 self._fall_back_to_host_step()
                 return self._eager_step(mixture, clean)
@@ -213,6 +236,7 @@ class Trainer:
             return loss
         self._static[0].copy_(mixture, non_blocking=True)
         self._static[1].copy_(clean, non_blocking=True)
+        self.optimizer.sync_device_hyper()                  # (device_lr: a changed lr reaches the device before the replay reads it)
         self._graph.replay()
         self._replays += 1
         self.optimizer.advance_host_step(1)
