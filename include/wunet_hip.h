@@ -35,6 +35,8 @@ typedef struct wunet_ctx wunet_ctx;
 #define WUNET_LOSS_MSE 0        /* model/loss.py:3-4  torch.nn.MSELoss()      */
 #define WUNET_LOSS_L1 1         /* model/loss.py:6-7  torch.nn.L1Loss()       */
 #define WUNET_LOSS_SMOOTH_L1 2  /* torch.nn.SmoothL1Loss(beta=1), SURVEY.md §0 */
+#define WUNET_LOSS_SI_SDR 3     /* scale-invariant SDR per row; wunet_loss_rows_* only (no reference counterpart) */
+#define WUNET_LOSS_SNR 4        /* SNR per row; wunet_loss_rows_* only (no reference counterpart) */
 
 const char* wunet_last_error(void);
 
@@ -127,6 +129,31 @@ int wunet_loss_forward(int kind, const float* clean, const float* enhanced, size
 /* grad_enhanced[i] = grad_loss[0] * d loss / d enhanced[i]  (grad_loss: device float, usually 1). */
 int wunet_loss_backward(int kind, const float* clean, const float* enhanced, const float* grad_loss,
                         size_t n, float* grad_enhanced, void* stream);
+
+/* Row losses: scale-invariant SDR (Le Roux et al., "SDR - half-baked or well done?") and plain SNR per utterance, the criterion and
+ * the validation score of speech enhancement.  No reference counterpart (model/loss.py has the two element-wise means only).
+ * clean = s and enhanced = e are [rows][row_len]; zero_mean != 0 removes each row's own mean from s and from e first.  Per row, with
+ * p = <e,s>, q = <s,s>, r = <e,e>:
+ *   WUNET_LOSS_SI_SDR: alpha = p / (q + eps), Et = alpha^2 q, En = r - 2 alpha p + alpha^2 q (= |e - alpha s|^2, not below 0)
+ *   WUNET_LOSS_SNR:    Et = q, En = sum (e - s)^2 accumulated from the differences
+ *   v = 10 log10((Et + eps) / (En + eps)) [dB];  loss_out = -(1 / rows) sum v.
+ * One pass over the pair; every sum and everything derived from it is double, only the outputs are rounded to float; fixed
+ * summation order, no atomics: bit-identical run to run.  per_row_db (NULL or [rows]) receives v.  coefs (NULL when no backward
+ * follows, else [rows * WUNET_LOSS_ROW_COEFS] doubles) receives A, C, D, v, mx, ms per row with dv/d e[i] = A e[i] + C s[i] + D;
+ * mx / ms are the row means that were removed (of e, or of e - s for SNR, and of s; 0 without zero_mean), D = -A mx - C ms.
+ * scratch: >= wunet_loss_rows_scratch_bytes(rows, row_len) device bytes, no memset needed.  The backward (same kind as the forward)
+ * writes grad_enhanced[i] = grad_loss[0] * (-1 / rows) * (A e[i] + C s[i] + D), applied in double in its centred form
+ * A (e[i] - mx) + C (s[i] - ms) and rounded once: a sample at its row's mean gets an exact 0.
+ * Caller-owned memory, no allocation, no synchronisation, no host read-back: both calls can be captured.  Pointers need 4-byte
+ * alignment only (16-byte loads where clean, enhanced and the gradient agree modulo 16).
+ * wunet_loss_forward / wunet_loss_backward keep refusing these two kinds. */
+#define WUNET_LOSS_ROW_COEFS 6   /* A, C, D, v, mx, ms per row, double */
+size_t wunet_loss_rows_scratch_bytes(size_t rows, size_t row_len);
+int wunet_loss_rows_forward(int kind, int zero_mean, double eps, const float* clean, const float* enhanced,
+                            size_t rows, size_t row_len, float* loss_out, float* per_row_db, double* coefs,
+                            void* scratch, void* stream);
+int wunet_loss_rows_backward(int kind, const float* clean, const float* enhanced, const double* coefs, const float* grad_loss,
+                             size_t rows, size_t row_len, float* grad_enhanced, void* stream);
 
 /* replaces optimizer.step() of torch.optim.Adam(params, lr, betas) as the reference builds it
  * (train.py:31-35; eps, weight_decay=0, amsgrad=False fixed by the reference's call) for n_tensors tensors in one

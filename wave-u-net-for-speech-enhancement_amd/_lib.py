@@ -19,6 +19,7 @@ EXPORTS = [
     "wunet_backward_range_async", "wunet_backward_join", "wunet_debug_set_conv_trace", "wunet_crop_windows",
     "wunet_comm_unique_id", "wunet_comm_create", "wunet_comm_allreduce_sum", "wunet_comm_world", "wunet_comm_destroy",
     "wunet_debug_stamps", "wunet_set_bn_frozen", "wunet_backward_input", "wunet_adam_scratch_bytes", "wunet_adam_step_ex",
+    "wunet_loss_rows_scratch_bytes", "wunet_loss_rows_forward", "wunet_loss_rows_backward",
 ]
 
 _vp = ctypes.c_void_p
@@ -46,6 +47,11 @@ def declare(lib):
     lib.wunet_loss_scratch_bytes.argtypes = []
     lib.wunet_loss_forward.argtypes = [_i, _vp, _vp, _sz, _vp, _vp, _vp]
     lib.wunet_loss_backward.argtypes = [_i, _vp, _vp, _vp, _sz, _vp, _vp]
+    if hasattr(lib, "wunet_loss_rows_forward"):  # (saved libraries of earlier versions do not have it)
+        lib.wunet_loss_rows_scratch_bytes.argtypes = [_sz, _sz]
+        lib.wunet_loss_rows_scratch_bytes.restype = _sz
+        lib.wunet_loss_rows_forward.argtypes = [_i, _i, ctypes.c_double, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]
+        lib.wunet_loss_rows_backward.argtypes = [_i, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]
     lib.wunet_layer_info.argtypes = [_vp, _i, ctypes.POINTER(_sz), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     lib.wunet_num_conv_layers.argtypes = [_vp]
     for name in ("wunet_op_conv1d", "wunet_op_conv1d_split"):

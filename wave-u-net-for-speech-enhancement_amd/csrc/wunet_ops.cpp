@@ -3,6 +3,7 @@
 #include "wunet_host.h"
 #include "wunet_elementwise.h"
 #include "wunet_h3_elem.h"
+#include "wunet_loss_rows.h"
 
 using namespace wunet_host;
 
@@ -30,6 +31,75 @@ int wunet_loss_backward(int kind, const float* clean, const float* enhanced, con
     size_t blocks = (n + WUNET_THREADS * 4 - 1) / (WUNET_THREADS * 4);
     if (blocks > 2048) blocks = 2048;
     WUNET_LAUNCH(loss_bwd_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, grad_loss, n, grad_enhanced);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- row losses (SI-SDR / SNR per utterance)
+// Pieces per row and samples per piece for (rows, T): about WUNET_ROWS_BLOCKS blocks in all, so one long row still fills the device,
+// but never less than WUNET_ROWS_MIN_PIECE samples per block (4 trips of 16-byte loads per thread) - many rows get one piece each.
+// plen is a multiple of 4 (every piece of an aligned row starts aligned) and ppr is recomputed from it: no piece is empty.
+#define WUNET_ROWS_BLOCKS 512
+#define WUNET_ROWS_MIN_PIECE 4096
+static void loss_rows_plan(size_t rows, size_t T, size_t& ppr, size_t& plen)
+{
+    size_t want = (WUNET_ROWS_BLOCKS + rows - 1) / rows;
+    const size_t most = (T + WUNET_ROWS_MIN_PIECE - 1) / WUNET_ROWS_MIN_PIECE;
+    if (want > most) want = most;
+    if (want < 1) want = 1;
+    plen = (((T + want - 1) / want) + 3) & ~(size_t)3;
+    ppr = (T + plen - 1) / plen;
+}
+
+static int loss_rows_shape_check(size_t rows, size_t row_len)
+{
+    if (rows == 0 || row_len == 0) return fail(WUNET_E_ARG, "row loss: rows and row_len must be > 0 (got %zu x %zu)", rows, row_len);
+    if (rows >= (1ull << 30) || row_len >= (1ull << 40)) return fail(WUNET_E_ARG, "row loss: shape too large (%zu x %zu)", rows, row_len);
+    return 0;
+}
+
+size_t wunet_loss_rows_scratch_bytes(size_t rows, size_t row_len)
+{
+    if (rows == 0 || row_len == 0) return 0;
+    size_t ppr, plen;
+    loss_rows_plan(rows, row_len, ppr, plen);
+    return rows * ppr * WUNET_ROWS_SUMS * sizeof(double);
+}
+
+int wunet_loss_rows_forward(int kind, int zero_mean, double eps, const float* clean, const float* enhanced, size_t rows, size_t row_len,
+                            float* loss_out, float* per_row_db, double* coefs, void* scratch, void* stream)
+{
+    if (kind != WUNET_LOSS_SI_SDR && kind != WUNET_LOSS_SNR) return fail(WUNET_E_ARG, "row loss: unknown kind %d (WUNET_LOSS_SI_SDR or WUNET_LOSS_SNR)", kind);
+    if (loss_rows_shape_check(rows, row_len)) return WUNET_E_ARG;
+    if (!clean || !enhanced || !loss_out || !scratch) return fail(WUNET_E_ARG, "row loss: null argument");
+    if (!(eps >= 0.0) || eps > 1.7976931348623157e308) return fail(WUNET_E_ARG, "row loss: eps must be finite and >= 0 (got %g)", eps);
+    hipStream_t st = (hipStream_t)stream;
+    size_t ppr, plen;
+    loss_rows_plan(rows, row_len, ppr, plen);
+    WUNET_LAUNCH(loss_rows_partial_kernel, dim3((unsigned)(rows * ppr)), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, row_len, (unsigned)ppr,
+                 plen, (double*)scratch);
+    WUNET_CHECK_LAUNCH();
+    LossRowsFinalArgs A{};
+    A.part = (const double*)scratch; A.rows = rows; A.T = row_len; A.ppr = (unsigned)ppr;
+    A.group = 1;
+    while (A.group < 64 && (size_t)A.group < ppr) A.group <<= 1;
+    A.kind = kind; A.zero_mean = zero_mean != 0; A.eps = eps; A.loss = loss_out; A.per_row = per_row_db; A.coefs = coefs;
+    WUNET_LAUNCH(loss_rows_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, st, A);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_loss_rows_backward(int kind, const float* clean, const float* enhanced, const double* coefs, const float* grad_loss, size_t rows,
+                             size_t row_len, float* grad_enhanced, void* stream)
+{
+    if (kind != WUNET_LOSS_SI_SDR && kind != WUNET_LOSS_SNR) return fail(WUNET_E_ARG, "row loss: unknown kind %d (WUNET_LOSS_SI_SDR or WUNET_LOSS_SNR)", kind);
+    if (loss_rows_shape_check(rows, row_len)) return WUNET_E_ARG;
+    if (!clean || !enhanced || !coefs || !grad_loss || !grad_enhanced) return fail(WUNET_E_ARG, "row loss: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    size_t ppr, plen;
+    loss_rows_plan(rows, row_len, ppr, plen);
+    WUNET_LAUNCH(loss_rows_bwd_kernel, dim3((unsigned)(rows * ppr)), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, coefs, grad_loss, rows, row_len,
+                 (unsigned)ppr, plen, grad_enhanced);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
 }

@@ -12,6 +12,8 @@ import torch
 from . import _lib
 
 LOSS_KINDS = {"mse": 0, "l1": 1, "smooth_l1": 2}
+ROW_LOSS_KINDS = {"si_sdr": 3, "snr": 4}      # WUNET_LOSS_SI_SDR / WUNET_LOSS_SNR: per-row criteria, wunet_loss_rows_* only
+LOSS_ROW_COEFS = 6                             # WUNET_LOSS_ROW_COEFS of include/wunet_hip.h
 
 
 class WunetError(RuntimeError):
@@ -345,6 +347,58 @@ class Engine:
             self._check(self.lib.wunet_loss_backward(LOSS_KINDS[kind], clean.data_ptr(), enhanced.data_ptr(),
                                                      gl.data_ptr(), enhanced.numel(), g.data_ptr(),
                                                      self._stream(enhanced.device)))
+        return g
+
+    # ------------------------------------------------------------------ row losses (SI-SDR / SNR per utterance)
+    def loss_rows_forward(self, kind, clean, enhanced, zero_mean=True, eps=1e-8, per_row=False, with_backward=True):
+        """include/wunet_hip.h: wunet_loss_rows_forward.  The last dimension is the row, all leading ones are flattened.  Returns
+        (loss, coefs, per_row_db): loss - device scalar, -mean of the rows' dB values; coefs - float64 [rows, LOSS_ROW_COEFS] for
+        `loss_rows_backward` (None with with_backward=False); per_row_db - float32 [rows] with per_row=True, else None."""
+        if kind not in ROW_LOSS_KINDS:
+            raise WunetError(f"row loss: unknown kind {kind!r} (one of {sorted(ROW_LOSS_KINDS)})")
+        self._require(clean, "clean")
+        self._require(enhanced, "enhanced")
+        if clean.dtype != torch.float32 or enhanced.dtype != torch.float32:
+            raise WunetError("row loss: expected float32 waveforms")
+        if clean.shape != enhanced.shape or clean.device != enhanced.device:
+            raise WunetError(f"row loss: shape / device mismatch {tuple(clean.shape)} vs {tuple(enhanced.shape)}")
+        if enhanced.dim() < 1 or enhanced.numel() == 0:
+            raise WunetError(f"row loss: needs at least one row of at least one sample, got {tuple(enhanced.shape)}")
+        T = enhanced.shape[-1]
+        R = enhanced.numel() // T
+        dev = enhanced.device
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        rows = torch.empty(R, dtype=torch.float32, device=dev) if per_row else None
+        coefs = torch.empty(R, LOSS_ROW_COEFS, dtype=torch.float64, device=dev) if with_backward else None
+        scratch = torch.empty(max(1, self.lib.wunet_loss_rows_scratch_bytes(R, T) // 8), dtype=torch.float64, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_loss_rows_forward(ROW_LOSS_KINDS[kind], 1 if zero_mean else 0, float(eps), clean.data_ptr(),
+                                                         enhanced.data_ptr(), R, T, out.data_ptr(), ptr(rows), ptr(coefs),
+                                                         scratch.data_ptr(), self._stream(dev)))
+        return out, coefs, rows
+
+    def loss_rows_backward(self, kind, clean, enhanced, coefs, grad_loss):
+        """d loss / d enhanced of the `loss_rows_forward` of the same kind that produced `coefs`, times grad_loss (a scalar tensor)."""
+        if kind not in ROW_LOSS_KINDS:
+            raise WunetError(f"row loss: unknown kind {kind!r} (one of {sorted(ROW_LOSS_KINDS)})")
+        self._require(clean, "clean")
+        self._require(enhanced, "enhanced")
+        if clean.dtype != torch.float32 or enhanced.dtype != torch.float32:
+            raise WunetError("row loss: expected float32 waveforms")
+        if clean.shape != enhanced.shape or clean.device != enhanced.device:
+            raise WunetError(f"row loss: shape / device mismatch {tuple(clean.shape)} vs {tuple(enhanced.shape)}")
+        if enhanced.dim() < 1 or enhanced.numel() == 0:
+            raise WunetError(f"row loss: needs at least one row of at least one sample, got {tuple(enhanced.shape)}")
+        T = enhanced.shape[-1]
+        R = enhanced.numel() // T
+        if coefs.dtype != torch.float64 or coefs.numel() != R * LOSS_ROW_COEFS or not coefs.is_contiguous() or coefs.device != enhanced.device:
+            raise WunetError(f"row loss: coefs must be the float64 [{R}, {LOSS_ROW_COEFS}] tensor of loss_rows_forward")
+        g = torch.empty_like(enhanced)
+        gl = grad_loss.to(device=enhanced.device, dtype=torch.float32).contiguous()
+        with self._device_guard(enhanced.device):
+            self._check(self.lib.wunet_loss_rows_backward(ROW_LOSS_KINDS[kind], clean.data_ptr(), enhanced.data_ptr(), coefs.data_ptr(), gl.data_ptr(), R, T,
+                                                          g.data_ptr(), self._stream(enhanced.device)))
         return g
 
 

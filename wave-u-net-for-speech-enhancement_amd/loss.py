@@ -6,6 +6,11 @@ zero-argument factories returning a module called as `loss(clean, enhanced)`
 
 `smooth_l1_loss` (torch.nn.SmoothL1Loss semantics, beta = 1) is the loss BASELINE.json's config 3
 names; the reference only mentions it in its README.
+
+`si_sdr_loss` / `snr_loss` (no reference counterpart): the negative mean over the utterances of the batch of the scale-invariant
+SDR / the SNR in dB, each row of the last dimension on its own (include/wunet_hip.h: wunet_loss_rows_*):
+
+    "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "si_sdr_loss", "args": {}}
 """
 import torch
 import torch.nn as nn
@@ -50,3 +55,45 @@ def l1_loss():
 
 def smooth_l1_loss():
     return HipLoss("smooth_l1")
+
+
+class _RowLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, kind, zero_mean, eps, engine, clean, enhanced):
+        if clean.requires_grad:                 # (before anything runs)
+            raise NotImplementedError(f"{kind}_loss: no gradient with respect to `clean` (the target also sets the signal energy, so it is "
+                                      "not minus the gradient of `enhanced` as for the element-wise losses): detach it")
+        clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
+        loss, coefs, _ = engine.loss_rows_forward(kind, clean_c, enh_c, zero_mean, eps)
+        ctx.kind, ctx.engine = kind, engine
+        ctx.save_for_backward(clean_c, enh_c, coefs)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        clean, enh, coefs = ctx.saved_tensors
+        g = ctx.engine.loss_rows_backward(ctx.kind, clean, enh, coefs, grad_loss) if ctx.needs_input_grad[5] else None
+        return None, None, None, None, None, g
+
+
+class HipRowLoss(nn.Module):
+    """loss(clean, enhanced) -> -mean over rows of si_sdr / snr [dB]; the last dimension is the utterance."""
+
+    def __init__(self, kind, zero_mean=True, eps=1e-8):
+        super().__init__()
+        if not (eps >= 0.0 and eps < float("inf")):
+            raise ValueError(f"{kind}_loss: eps must be finite and >= 0 (got {eps})")
+        self.kind, self.zero_mean, self.eps = kind, bool(zero_mean), float(eps)
+        self._engine_override = None
+
+    def forward(self, clean, enhanced):
+        engine = self._engine_override if self._engine_override is not None else default_engine()
+        return _RowLossFn.apply(self.kind, self.zero_mean, self.eps, engine, clean, enhanced)
+
+
+def si_sdr_loss(zero_mean=True, eps=1e-8):
+    return HipRowLoss("si_sdr", zero_mean, eps)
+
+
+def snr_loss(zero_mean=True, eps=1e-8):
+    return HipRowLoss("snr", zero_mean, eps)

@@ -3,8 +3,9 @@
     "trainer": {"module": "wave-u-net-for-speech-enhancement_amd.trainer", "main": "Trainer", "epochs": ..., ...}
 
 Same constructor as the reference's Trainer (/root/reference/trainer/trainer.py:13-25, called from train.py:41-49)
-and the same `.train()` entry (train.py:51), covering the hot loop only (trainer/trainer.py:27-43,
-base_trainer.py:187-197): validation, TensorBoard and metrics are out of scope.
+and the same `.train()` entry (train.py:51), covering the hot loop (trainer/trainer.py:27-43, base_trainer.py:187-197) and, opt-in,
+a validation epoch scored on the device (below); TensorBoard and the host metrics STOI / PESQ are out of scope (SURVEY.md §2 rows 6,
+10, 11).
 Differences from the reference loop, all on the f2 list:
   * one process per GPU: launched under torchrun (RANK / WORLD_SIZE / LOCAL_RANK in the environment) the constructor joins the
     process group itself (backend "nccl" = RCCL on a GPU box, "gloo" without one), pins the process to its GPU, re-wraps the
@@ -20,6 +21,13 @@ Differences from the reference loop, all on the f2 list:
     reads its lr from device memory: `"device_lr": true` in the trainer config / FusedAdam(device_lr=True) keeps the one graph);
   * `"max_grad_norm": <float>` in the trainer config: gradient clipping by the global norm inside the fused step (optim.FusedAdam);
     `trainer.lr_scheduler` (None by default): its .step() is called after every optimiser step;
+  * validation, strictly opt-in: with `"validation": {"metric": "si_sdr", "interval": N, "find_max": true, "custom": {"sample_length":
+    16384}}` in the trainer config and a validation loader (batch 1 items `(mixture, clean, name)`, trainer/trainer.py:58-78), every N
+    epochs rank 0 enhances each recording with inference.enhance in eval mode and scores the mean SI-SDR improvement in dB over the noisy
+    input (metrics.si_sdr_improvement) - accumulated on the device, one device->host read per validation epoch.  The score is appended
+    to `validation_scores`, compared with `best_score` as base_trainer.py:149-157 does, and a best one writes best_model.tar
+    (base_trainer.py:118-120).  Every module's training flag (a frozen BatchNorm layer included) is restored afterwards, so a captured
+    step graph stays valid.  Without the "metric" key the loader stays unused, as in earlier versions of this trainer;
   * checkpoints keep the reference's names and keys (base_trainer.py:83-124) so either side can resume; only rank 0 writes.
 """
 import os
@@ -82,7 +90,16 @@ class Trainer:
             if fused:
                 optimizer.grad_scale = 1.0 / self.world
         self.train_data_loader = self._shard_loader(train_dataloader)
-        self.validation_data_loader = validation_dataloader      # accepted for signature compatibility, unused
+        self.validation_data_loader = validation_dataloader      # used only with "validation": {"metric": "si_sdr", ...} (below)
+        vcfg = tcfg.get("validation") or {}
+        self.validation_metric = vcfg.get("metric")
+        if self.validation_metric not in (None, "si_sdr"):
+            raise ValueError(f'trainer config "validation.metric" must be "si_sdr" (got {self.validation_metric!r}); STOI / PESQ are host '
+                             "metrics and out of scope")
+        self.validation_interval = int(vcfg.get("interval", 0)) if self.validation_metric and validation_dataloader is not None else 0
+        self.validation_find_max = bool(vcfg.get("find_max", True))
+        self.validation_sample_length = int((vcfg.get("custom") or {}).get("sample_length", 16384))
+        self.validation_scores = []   # one mean SI-SDR improvement [dB] per validation epoch
         self.epochs = tcfg["epochs"]
         self.save_checkpoint_interval = tcfg.get("save_checkpoint_interval", 0)
         # default ON where it can be used (one GPU, or the native RCCL entry; fused Adam): the replay is as fast as the eager
@@ -106,7 +123,7 @@ class Trainer:
         self.captures = 0             # step graphs captured so far
         self.lr_scheduler = None      # set by the caller: .step() after every optimiser step (eager or replay)
         self.start_epoch = 1
-        self.best_score = float("-inf")
+        self.best_score = float("-inf") if self.validation_find_max or not self.validation_interval else float("inf")
         root = Path(os.path.expanduser(config.get("root_dir", "."))).absolute() / config.get("experiment_name", "exp")
         self.checkpoints_dir = root / "checkpoints"
         self.epoch_losses = []
@@ -149,7 +166,7 @@ class Trainer:
         self.optimizer.load_state_dict(ckpt["optimizer"])
         self.model.load_state_dict(ckpt["model"])
 
-    def _save_checkpoint(self, epoch):
+    def _save_checkpoint(self, epoch, is_best=False):
         if self.rank != 0:
             return
         self.checkpoints_dir.mkdir(parents=True, exist_ok=True)
@@ -157,6 +174,42 @@ class Trainer:
                  "model": {k: v.cpu() for k, v in self.model.state_dict().items()}}
         torch.save(state, (self.checkpoints_dir / "latest_model.tar").as_posix())
         torch.save(state["model"], (self.checkpoints_dir / f"model_{str(epoch).zfill(4)}.pth").as_posix())
+        if is_best:                                      # base_trainer.py:118-120
+            torch.save(state, (self.checkpoints_dir / "best_model.tar").as_posix())
+
+    # ---- validation (trainer/trainer.py:58-78 without the host metrics): mean SI-SDR improvement over the recordings, on the device
+    def _is_best(self, score):
+        """base_trainer.py:149-157."""
+        if (score >= self.best_score) if self.validation_find_max else (score <= self.best_score):
+            self.best_score = score
+            return True
+        return False
+
+    @torch.no_grad()
+    def _validation_epoch(self, epoch):
+        from . import metrics
+        from .inference import enhance
+        model = getattr(self.model, "module", self.model)
+        engine = getattr(model, "_engine_override", None)
+        modes = [(m, m.training) for m in self.model.modules()]
+        self.model.eval()
+        gains = []
+        try:
+            for mixture, clean, _name in self.validation_data_loader:
+                if mixture.dim() != 3 or mixture.shape[0] != 1:
+                    raise ValueError("Only support batch size is 1 in enhancement stage.")       # reference wording, trainer/trainer.py:64
+                mixture = mixture.to(self.device, non_blocking=True)
+                clean = clean.to(self.device, non_blocking=True)
+                enhanced = enhance(model, mixture, self.validation_sample_length)
+                gains.append(metrics.si_sdr_improvement(clean, mixture, enhanced, engine=engine))
+        finally:
+            for m, was in modes:                         # exactly the flags of before: a frozen BatchNorm layer stays frozen
+                m.training = was
+        if not gains:
+            raise ValueError("validation: the validation loader yielded no recording")
+        score = torch.cat(gains).double().mean().item()  # the only device->host read of the validation epoch
+        self.validation_scores.append(score)
+        return score
 
     # ---- one step of the hot loop (trainer/trainer.py:34-38)
     def _eager_step(self, mixture, clean):
@@ -269,6 +322,9 @@ class Trainer:
             self._train_epoch(epoch)
             if self.save_checkpoint_interval != 0 and epoch % self.save_checkpoint_interval == 0:
                 self._save_checkpoint(epoch)
+            if self.validation_interval != 0 and epoch % self.validation_interval == 0 and self.rank == 0:       # base_trainer.py:199-205
+                if self._is_best(self._validation_epoch(epoch)):
+                    self._save_checkpoint(epoch, is_best=True)
         if self._own_pg and dist.is_initialized():
             dist.barrier()
             dist.destroy_process_group()
