@@ -155,6 +155,48 @@ int wunet_loss_rows_forward(int kind, int zero_mean, double eps, const float* cl
 int wunet_loss_rows_backward(int kind, const float* clean, const float* enhanced, const double* coefs, const float* grad_loss,
                              size_t rows, size_t row_len, float* grad_enhanced, void* stream);
 
+/* Multi-resolution STFT loss (Yamamoto et al., "Parallel WaveGAN"): spectral convergence plus log-magnitude L1.  No reference
+ * counterpart (the reference only looks at STFT magnitudes in its validation epoch, trainer/trainer.py:108-110, on the host).
+ * One resolution (n_fft = N, hop = H, win_length = W <= N) of clean = c and enhanced = e, both [rows][row_len = T]:
+ *   window   periodic Hann of length W, w[j] = 0.5 - 0.5 cos(2 pi j / W), zero-padded to N with (N - W) / 2 zeros on the left;
+ *   framing  center=True, pad_mode="reflect": x_pad[j] = x[reflect(j - N/2)], frames f = 0 .. T / H (F = 1 + T / H); needs N/2 <= T - 1;
+ *   spectrum X[f][b] = sum_k w[k] x_pad[f H + k] exp(-2 pi i k b / N), b = 0 .. N/2;  P = re^2 + im^2,  S = sqrt(max(P, clamp));
+ *   sc  = sqrt(sum (S_c - S_e)^2) / sqrt(sum S_c^2),  mag = mean |ln S_c - ln S_e|, both over all rows, frames and bins;
+ *   loss = (1 / n_res) sum_i (sc_weight sc_i + mag_weight mag_i).
+ * Gradient with respect to `enhanced` only.  It follows torch.clamp: a bin with P_e < clamp passes no gradient.  ONE departure from
+ * autograd: where sum (S_c - S_e)^2 == 0 the sc term contributes 0 instead of NaN.
+ * Supported: 16 <= N <= 4096 with N % 16 == 0, 1 <= H <= N, 1 <= W <= N, clamp > 0; anything else is WUNET_E_ARG with a message.
+ * Arithmetic: fp32 operands and fp32 MFMA accumulation against a basis computed in double and rounded once; every reduction and
+ * coefficient in double; no atomics, every sum has one fixed order: bit-identical run to run.
+ * The calls of one loss:
+ *   once per (N, W): wunet_stft_basis into wunet_stft_basis_bytes(N) bytes (16-byte aligned);
+ *   per resolution:  wunet_stft_forward(clean, enhanced, ..) writes its partial sums to `scratch` (>= wunet_stft_scratch_bytes(..)),
+ *                    and, when `saved` is given (>= wunet_stft_saved_bytes(..)), re_e, im_e and S_c for the backward; mag_out (NULL or
+ *                    [rows * F][N/2 + 1]) receives S_e.  clean == NULL: the magnitudes of `enhanced` alone into mag_out (scratch and
+ *                    saved unused, clamp >= 0) - the metric path;
+ *   once:            wunet_stft_finalize over the TABLE of the resolutions' scratch buffers (host arrays of n_res <=
+ *                    WUNET_STFT_MAX_RESOLUTIONS entries, read during the call): the loss, accumulated over the resolutions in double
+ *                    and rounded once, and coefs[n_res][WUNET_STFT_COEFS] = a, b, sc, mag with
+ *                    a = sc_weight / (n_res |S_c - S_e| |S_c|), b = mag_weight / (n_res rows F bins);
+ *   per resolution:  wunet_stft_backward(saved, coefs + i * WUNET_STFT_COEFS, grad_loss, ..): the adjoint GEMM into `scratch`
+ *                    (>= wunet_stft_scratch_bytes(.., with_backward = 1); the forward's buffer may be reused after the finalize), then
+ *                    the overlap-add as a gather; grad_enhanced = (accumulate ? grad_enhanced : 0) + grad_loss[0] * d loss_i / d e,
+ *                    so several resolutions sum in the order of the calls.
+ * Caller-owned memory, no allocation, no synchronisation, no host read-back: every call can be captured. */
+#define WUNET_STFT_MAX_RESOLUTIONS 8
+#define WUNET_STFT_COEFS 4       /* a, b, sc, mag per resolution, double */
+size_t wunet_stft_basis_bytes(int n_fft);
+int wunet_stft_basis(int n_fft, int win_length, float* basis, void* stream);
+size_t wunet_stft_scratch_bytes(size_t rows, size_t row_len, int n_fft, int hop, int with_backward);
+size_t wunet_stft_saved_bytes(size_t rows, size_t row_len, int n_fft, int hop);
+int wunet_stft_forward(const float* clean, const float* enhanced, size_t rows, size_t row_len, int n_fft, int hop, int win_length,
+                       double clamp, const float* basis, void* scratch, float* saved, float* mag_out, void* stream);
+int wunet_stft_finalize(int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop,
+                        double sc_weight, double mag_weight, float* loss_out, double* coefs, void* stream);
+int wunet_stft_backward(const float* saved, const double* coefs, const float* grad_loss, size_t rows, size_t row_len, int n_fft, int hop,
+                        int win_length, double clamp, const float* basis, void* scratch, float* grad_enhanced, int accumulate,
+                        void* stream);
+
 /* replaces optimizer.step() of torch.optim.Adam(params, lr, betas) as the reference builds it
  * (train.py:31-35; eps, weight_decay=0, amsgrad=False fixed by the reference's call) for n_tensors tensors in one
  * or two launches.  step is the 1-based step count AFTER the increment (torch's state["step"]).  numels: host array.

@@ -20,6 +20,8 @@ EXPORTS = [
     "wunet_comm_unique_id", "wunet_comm_create", "wunet_comm_allreduce_sum", "wunet_comm_world", "wunet_comm_destroy",
     "wunet_debug_stamps", "wunet_set_bn_frozen", "wunet_backward_input", "wunet_adam_scratch_bytes", "wunet_adam_step_ex",
     "wunet_loss_rows_scratch_bytes", "wunet_loss_rows_forward", "wunet_loss_rows_backward",
+    "wunet_stft_basis_bytes", "wunet_stft_basis", "wunet_stft_scratch_bytes", "wunet_stft_saved_bytes", "wunet_stft_forward",
+    "wunet_stft_finalize", "wunet_stft_backward",
 ]
 
 _vp = ctypes.c_void_p
@@ -52,6 +54,17 @@ def declare(lib):
         lib.wunet_loss_rows_scratch_bytes.restype = _sz
         lib.wunet_loss_rows_forward.argtypes = [_i, _i, ctypes.c_double, _vp, _vp, _sz, _sz, _vp, _vp, _vp, _vp, _vp]
         lib.wunet_loss_rows_backward.argtypes = [_i, _vp, _vp, _vp, _vp, _sz, _sz, _vp, _vp]
+    if hasattr(lib, "wunet_stft_forward"):       # (saved libraries of earlier versions do not have it)
+        lib.wunet_stft_basis_bytes.argtypes = [_i]
+        lib.wunet_stft_basis_bytes.restype = _sz
+        lib.wunet_stft_basis.argtypes = [_i, _i, _vp, _vp]
+        lib.wunet_stft_scratch_bytes.argtypes = [_sz, _sz, _i, _i, _i]
+        lib.wunet_stft_scratch_bytes.restype = _sz
+        lib.wunet_stft_saved_bytes.argtypes = [_sz, _sz, _i, _i]
+        lib.wunet_stft_saved_bytes.restype = _sz
+        lib.wunet_stft_forward.argtypes = [_vp, _vp, _sz, _sz, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]
+        lib.wunet_stft_finalize.argtypes = [_i, _vp, _sz, _sz, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]
+        lib.wunet_stft_backward.argtypes = [_vp, _vp, _vp, _sz, _sz, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _i, _vp]
     lib.wunet_layer_info.argtypes = [_vp, _i, ctypes.POINTER(_sz), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     lib.wunet_num_conv_layers.argtypes = [_vp]
     for name in ("wunet_op_conv1d", "wunet_op_conv1d_split"):

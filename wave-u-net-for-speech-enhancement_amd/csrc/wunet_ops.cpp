@@ -4,6 +4,7 @@
 #include "wunet_elementwise.h"
 #include "wunet_h3_elem.h"
 #include "wunet_loss_rows.h"
+#include "wunet_stft.h"
 
 using namespace wunet_host;
 
@@ -100,6 +101,149 @@ int wunet_loss_rows_backward(int kind, const float* clean, const float* enhanced
     loss_rows_plan(rows, row_len, ppr, plen);
     WUNET_LAUNCH(loss_rows_bwd_kernel, dim3((unsigned)(rows * ppr)), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, coefs, grad_loss, rows, row_len,
                  (unsigned)ppr, plen, grad_enhanced);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- multi-resolution STFT loss (wunet_stft.h)
+namespace {
+struct StftShape { unsigned M, F; int BP, bins, k0, k1; unsigned mtiles; };
+
+// every constraint of one resolution on (rows, T); fills the derived sizes.  T == 0: the checks that need the waveform are skipped
+// (the basis calls).
+int stft_shape(size_t rows, size_t T, int N, int H, int W, StftShape& s)
+{
+    if (N < 16 || N > 4096 || N % 16) return fail(WUNET_E_ARG, "stft: n_fft must be a multiple of 16 in 16 .. 4096 (got %d)", N);
+    if (W < 1 || W > N) return fail(WUNET_E_ARG, "stft: win_length must be in 1 .. n_fft (got %d, n_fft %d)", W, N);
+    s.bins = N / 2 + 1;
+    s.BP = (s.bins + WUNET_STFT_BN - 1) / WUNET_STFT_BN * WUNET_STFT_BN;
+    const int left = (N - W) / 2;
+    s.k0 = left / WUNET_STFT_KT * WUNET_STFT_KT;
+    s.k1 = (left + W + WUNET_STFT_KT - 1) / WUNET_STFT_KT * WUNET_STFT_KT;
+    if (T == 0) return 0;
+    if (H < 1 || H > N) return fail(WUNET_E_ARG, "stft: hop must be in 1 .. n_fft (got %d, n_fft %d)", H, N);
+    if (rows == 0) return fail(WUNET_E_ARG, "stft: rows must be > 0");
+    if ((size_t)(N / 2) + 1 > T) return fail(WUNET_E_ARG, "stft: reflect padding needs n_fft / 2 <= T - 1 (n_fft %d, T %zu)", N, T);
+    if (T >= (1ull << 30) || rows >= (1ull << 30) || rows * T >= (1ull << 38)) return fail(WUNET_E_ARG, "stft: shape too large (%zu x %zu)", rows, T);
+    const size_t F = 1 + T / (size_t)H, M = rows * F;
+    if (M >= (1ull << 31) - WUNET_STFT_FM) return fail(WUNET_E_ARG, "stft: too many frames (%zu rows x %zu)", rows, F);
+    s.F = (unsigned)F; s.M = (unsigned)M;
+    s.mtiles = (unsigned)((M + WUNET_STFT_FM - 1) / WUNET_STFT_FM);
+    return 0;
+}
+inline size_t stft_nparts(const StftShape& s) { return (size_t)s.mtiles * (size_t)(s.BP / WUNET_STFT_BN); }
+}  // namespace
+
+size_t wunet_stft_basis_bytes(int n_fft)
+{
+    StftShape s{};
+    if (stft_shape(0, 0, n_fft, 1, 1, s)) return 0;
+    return (size_t)n_fft * 2 * s.BP * sizeof(float);
+}
+
+int wunet_stft_basis(int n_fft, int win_length, float* basis, void* stream)
+{
+    StftShape s{};
+    if (stft_shape(0, 0, n_fft, 1, win_length, s)) return WUNET_E_ARG;
+    if (!basis || ((size_t)basis & 15)) return fail(WUNET_E_ARG, "stft: the basis needs a 16-byte aligned buffer");
+    WUNET_LAUNCH(stft_basis_kernel, dim3((unsigned)((2 * s.BP + WUNET_THREADS - 1) / WUNET_THREADS), (unsigned)n_fft), dim3(WUNET_THREADS), 0,
+                 (hipStream_t)stream, n_fft, win_length, s.BP, basis);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+size_t wunet_stft_scratch_bytes(size_t rows, size_t row_len, int n_fft, int hop, int with_backward)
+{
+    StftShape s{};
+    if (row_len == 0 || stft_shape(rows, row_len, n_fft, hop, 1, s)) return 0;
+    const size_t fwd = stft_nparts(s) * 3 * sizeof(double), bwd = (size_t)s.M * n_fft * sizeof(float);
+    return with_backward && bwd > fwd ? bwd : fwd;
+}
+
+size_t wunet_stft_saved_bytes(size_t rows, size_t row_len, int n_fft, int hop)
+{
+    StftShape s{};
+    if (row_len == 0 || stft_shape(rows, row_len, n_fft, hop, 1, s)) return 0;
+    return (size_t)3 * s.M * s.BP * sizeof(float);
+}
+
+int wunet_stft_forward(const float* clean, const float* enhanced, size_t rows, size_t row_len, int n_fft, int hop, int win_length,
+                       double clamp, const float* basis, void* scratch, float* saved, float* mag_out, void* stream)
+{
+    StftShape s{};
+    if (row_len == 0) return fail(WUNET_E_ARG, "stft: row_len must be > 0");
+    if (stft_shape(rows, row_len, n_fft, hop, win_length, s)) return WUNET_E_ARG;
+    if (!enhanced || !basis || ((size_t)basis & 15)) return fail(WUNET_E_ARG, "stft: null argument (or a basis that is not 16-byte aligned)");
+    if (clean) {
+        if (!(clamp > 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "stft: clamp must be finite and > 0 (got %g)", clamp);
+        if (!scratch) return fail(WUNET_E_ARG, "stft: the loss forward needs wunet_stft_scratch_bytes of scratch");
+    } else {
+        if (!(clamp >= 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "stft: clamp must be finite and >= 0 (got %g)", clamp);
+        if (!mag_out || saved) return fail(WUNET_E_ARG, "stft: without `clean` the call writes mag_out only");
+    }
+    StftFwdArgs A{};
+    A.c = clean; A.e = enhanced; A.basis = basis; A.T = row_len; A.M = s.M; A.F = s.F; A.N = n_fft; A.H = hop; A.BP = s.BP; A.bins = s.bins;
+    A.k0 = s.k0; A.k1 = s.k1; A.clamp = (float)clamp; A.part = (double*)scratch; A.saved = saved; A.mag_out = mag_out;
+    const dim3 grid(s.mtiles, (unsigned)(s.BP / WUNET_STFT_BN));
+    // (profiler: 2 flops x frames x window support x 2 BP columns per signal; the waveforms and the basis once, the saved spectra)
+    prof_begin((hipStream_t)stream, clean ? "stft_fwd_kernel<pair>" : "stft_fwd_kernel<one>", (clean ? 2.0 : 1.0) * 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP,
+               4.0 * ((clean ? 2.0 : 1.0) * rows * row_len + (double)(s.k1 - s.k0) * 2.0 * s.BP + (saved ? 3.0 * s.M * s.BP : 0.0)));
+    if (clean) {
+        WUNET_LAUNCH(stft_fwd_kernel<true>, grid, dim3(WUNET_THREADS), 0, (hipStream_t)stream, A);
+    } else {
+        WUNET_LAUNCH(stft_fwd_kernel<false>, grid, dim3(WUNET_THREADS), 0, (hipStream_t)stream, A);
+    }
+    prof_end((hipStream_t)stream);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_stft_finalize(int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop,
+                        double sc_weight, double mag_weight, float* loss_out, double* coefs, void* stream)
+{
+    if (n_res < 1 || n_res > WUNET_STFT_MAX_RES) return fail(WUNET_E_ARG, "stft: 1 .. %d resolutions per call (got %d)", WUNET_STFT_MAX_RES, n_res);
+    if (!scratch || !n_fft || !hop || !loss_out) return fail(WUNET_E_ARG, "stft: null argument");
+    if (!(sc_weight == sc_weight) || !(mag_weight == mag_weight)) return fail(WUNET_E_ARG, "stft: a weight is NaN");
+    StftFinalArgs A{};
+    for (int i = 0; i < n_res; ++i) {
+        StftShape s{};
+        if (row_len == 0) return fail(WUNET_E_ARG, "stft: row_len must be > 0");
+        if (stft_shape(rows, row_len, n_fft[i], hop[i], 1, s)) return WUNET_E_ARG;
+        if (!scratch[i]) return fail(WUNET_E_ARG, "stft: null scratch of resolution %d", i);
+        A.part[i] = (const double*)scratch[i];
+        A.nparts[i] = (unsigned)stft_nparts(s);
+        A.count[i] = (double)s.M * (double)s.bins;
+    }
+    A.n_res = n_res; A.w_sc = sc_weight; A.w_mag = mag_weight; A.loss = loss_out; A.coefs = coefs;
+    WUNET_LAUNCH(stft_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, (hipStream_t)stream, A);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_stft_backward(const float* saved, const double* coefs, const float* grad_loss, size_t rows, size_t row_len, int n_fft, int hop,
+                        int win_length, double clamp, const float* basis, void* scratch, float* grad_enhanced, int accumulate, void* stream)
+{
+    StftShape s{};
+    if (row_len == 0) return fail(WUNET_E_ARG, "stft: row_len must be > 0");
+    if (stft_shape(rows, row_len, n_fft, hop, win_length, s)) return WUNET_E_ARG;
+    if (!saved || !coefs || !grad_loss || !basis || !scratch || !grad_enhanced || ((size_t)basis & 15))
+        return fail(WUNET_E_ARG, "stft: null argument (or a basis that is not 16-byte aligned)");
+    if (!(clamp > 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "stft: clamp must be finite and > 0 (got %g)", clamp);
+    hipStream_t st = (hipStream_t)stream;
+    StftBwdArgs B{};
+    B.saved = saved; B.coefs = coefs; B.basis = basis; B.M = s.M; B.N = n_fft; B.BP = s.BP; B.bins = s.bins; B.k0 = s.k0; B.k1 = s.k1;
+    B.clamp = (float)clamp; B.scratch = (float*)scratch;
+    B.ktiles = (unsigned)((s.k1 - s.k0 + WUNET_STFT_BWN - 1) / WUNET_STFT_BWN);           // (at most 32; mtiles < 2^25)
+    prof_begin(st, "stft_bwd_kernel", 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP, 4.0 * (3.0 * s.M * s.BP + (double)(s.k1 - s.k0) * (2.0 * s.BP + s.M)));
+    WUNET_LAUNCH(stft_bwd_kernel, dim3(B.ktiles * s.mtiles), dim3(WUNET_THREADS), 0, st, B);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    StftOlaArgs O{};
+    O.scratch = (const float*)scratch; O.gl = grad_loss; O.g = grad_enhanced; O.T = row_len; O.total = rows * row_len; O.F = s.F;
+    O.N = n_fft; O.H = hop; O.k0 = s.k0; O.k1 = s.k1; O.accumulate = accumulate != 0;
+    prof_begin(st, "stft_ola_kernel", 0.0, 4.0 * ((double)s.M * (s.k1 - s.k0) + (accumulate ? 2.0 : 1.0) * rows * row_len));
+    WUNET_LAUNCH(stft_ola_kernel, dim3((unsigned)((O.total + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st, O);
+    prof_end(st);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
 }

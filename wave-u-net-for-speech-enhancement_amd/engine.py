@@ -103,6 +103,7 @@ class Engine:
         # Bumped by everything that rewrites weights WITHOUT moving a Python version counter: the replay of a captured step graph
         # (FusedAdam.advance_host_step) - part of the eval cache's signature, so an eval forward after N replays re-packs.
         self.weights_generation = 0
+        self._stft_bases = {}                         # (n_fft, win_length, device) -> windowed DFT basis (stft_basis)
         # per-step calls marshalled in C++ when the extension is built and this engine drives the HIP library it is linked to
         self._fast = _load_torch_ext() if (lib is None and not host_memory) else None
 
@@ -400,6 +401,135 @@ class Engine:
             self._check(self.lib.wunet_loss_rows_backward(ROW_LOSS_KINDS[kind], clean.data_ptr(), enhanced.data_ptr(), coefs.data_ptr(), gl.data_ptr(), R, T,
                                                           g.data_ptr(), self._stream(enhanced.device)))
         return g
+
+
+# ---------------------------------------------------------------------- multi-resolution STFT loss (include/wunet_hip.h: wunet_stft_*)
+STFT_COEFS = 4                       # WUNET_STFT_COEFS of include/wunet_hip.h: a, b, sc, mag per resolution
+STFT_MAX_RESOLUTIONS = 8             # WUNET_STFT_MAX_RESOLUTIONS
+
+
+def check_stft_resolution(n_fft, hop, win_length):
+    """The constraints of one resolution that do not depend on the waveform (what wunet_stft_* refuses with WUNET_E_ARG)."""
+    n_fft, hop, win_length = int(n_fft), int(hop), int(win_length)
+    if n_fft < 16 or n_fft > 4096 or n_fft % 16:
+        raise ValueError(f"stft: n_fft must be a multiple of 16 in 16 .. 4096 (got {n_fft})")
+    if hop < 1 or hop > n_fft:
+        raise ValueError(f"stft: hop must be in 1 .. n_fft (got {hop}, n_fft {n_fft})")
+    if win_length < 1 or win_length > n_fft:
+        raise ValueError(f"stft: win_length must be in 1 .. n_fft (got {win_length}, n_fft {n_fft})")
+    return n_fft, hop, win_length
+
+
+def _stft_basis(self, n_fft, win_length, device):
+    """The windowed DFT basis of (n_fft, win_length) on `device`, built once: on the first (eager) call, so that a later graph capture
+    sees neither its allocation nor its launch."""
+    key = (n_fft, win_length, str(device))
+    basis = self._stft_bases.get(key)
+    if basis is None:
+        nbytes = self.lib.wunet_stft_basis_bytes(n_fft)
+        if nbytes == 0:
+            raise WunetError(f"wunet error -1: {self.lib.wunet_last_error().decode()}")
+        basis = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+        with self._device_guard(device):
+            self._check(self.lib.wunet_stft_basis(n_fft, win_length, basis.data_ptr(), self._stream(device)))
+        self._stft_bases[key] = basis
+    return basis
+
+
+def _stft_pair(self, clean, enhanced):
+    self._require(clean, "clean")
+    self._require(enhanced, "enhanced")
+    if clean.dtype != torch.float32 or enhanced.dtype != torch.float32:
+        raise WunetError("stft loss: expected float32 waveforms")
+    if clean.shape != enhanced.shape or clean.device != enhanced.device:
+        raise WunetError(f"stft loss: shape / device mismatch {tuple(clean.shape)} vs {tuple(enhanced.shape)}")
+    if enhanced.dim() < 1 or enhanced.numel() == 0:
+        raise WunetError(f"stft loss: needs at least one row of at least one sample, got {tuple(enhanced.shape)}")
+    T = enhanced.shape[-1]
+    return enhanced.numel() // T, T
+
+
+def _stft_loss_forward(self, clean, enhanced, resolutions, sc_weight=1.0, mag_weight=1.0, clamp=1e-7, with_backward=True):
+    """resolutions: a sequence of (n_fft, hop, win_length).  The last dimension is the utterance, all leading ones are flattened.
+    Returns (loss, coefs, saved): loss - device scalar; coefs - float64 [n_res, STFT_COEFS] (a, b, sc, mag per resolution);
+    saved - one float32 buffer per resolution for `stft_loss_backward` (None with with_backward=False)."""
+    R, T = self._stft_pair(clean, enhanced)
+    n = len(resolutions)
+    if n < 1 or n > STFT_MAX_RESOLUTIONS:
+        raise WunetError(f"stft loss: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {n})")
+    dev = enhanced.device
+    lib = self.lib
+    out = torch.empty((), dtype=torch.float32, device=dev)
+    coefs = torch.empty(n, STFT_COEFS, dtype=torch.float64, device=dev)
+    scratch, saved = [], []
+    with self._device_guard(dev):
+        st = self._stream(dev)
+        for N, H, W in resolutions:
+            basis = self.stft_basis(N, W, dev)
+            nbytes = lib.wunet_stft_scratch_bytes(R, T, N, H, 0)
+            if nbytes == 0:
+                raise WunetError(f"wunet error -1: {lib.wunet_last_error().decode()}")
+            scr = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+            sv = torch.empty(lib.wunet_stft_saved_bytes(R, T, N, H) // 4, dtype=torch.float32, device=dev) if with_backward else None
+            self._check(lib.wunet_stft_forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(clamp), basis.data_ptr(),
+                                               scr.data_ptr(), sv.data_ptr() if sv is not None else None, None, st))
+            scratch.append(scr)
+            saved.append(sv)
+        self._check(lib.wunet_stft_finalize(n, self._ptrs(scratch), R, T, (ctypes.c_int * n)(*[r[0] for r in resolutions]),
+                                            (ctypes.c_int * n)(*[r[1] for r in resolutions]), float(sc_weight), float(mag_weight),
+                                            out.data_ptr(), coefs.data_ptr(), st))
+    return out, coefs, (saved if with_backward else None)
+
+
+def _stft_loss_backward(self, shape, resolutions, coefs, saved, grad_loss, clamp=1e-7):
+    """d loss / d enhanced (a tensor of `shape`) of the `stft_loss_forward` that produced `coefs` and `saved`, times grad_loss (a scalar
+    tensor).  The resolutions are added in their order: one fixed order of sums."""
+    n = len(resolutions)
+    if coefs.dtype != torch.float64 or coefs.numel() != n * STFT_COEFS or not coefs.is_contiguous() or saved is None or len(saved) != n:
+        raise WunetError(f"stft loss: coefs / saved must be those of stft_loss_forward over the same {n} resolutions")
+    dev = coefs.device
+    T = shape[-1]
+    g = torch.empty(shape, dtype=torch.float32, device=dev)
+    R = g.numel() // T
+    gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+    lib = self.lib
+    with self._device_guard(dev):
+        st = self._stream(dev)
+        for i, (N, H, W) in enumerate(resolutions):
+            if saved[i].numel() * 4 != lib.wunet_stft_saved_bytes(R, T, N, H) or saved[i].device != dev:
+                raise WunetError(f"stft loss: saved[{i}] is not the buffer of resolution {(N, H, W)} on {tuple(shape)}")
+            scr = torch.empty(lib.wunet_stft_scratch_bytes(R, T, N, H, 1) // 4, dtype=torch.float32, device=dev)
+            self._check(lib.wunet_stft_backward(saved[i].data_ptr(), coefs.data_ptr() + 8 * STFT_COEFS * i, gl.data_ptr(), R, T, N, H, W,
+                                                float(clamp), self.stft_basis(N, W, dev).data_ptr(), scr.data_ptr(), g.data_ptr(),
+                                                1 if i else 0, st))
+    return g
+
+
+def _stft_magnitude(self, x, n_fft=320, hop=160, win_length=320):
+    """|STFT| of every row of x (periodic Hann, center=True, reflect padding - torch.stft's conventions): float32 [rows, F, n_fft/2 + 1]."""
+    self._require(x, "x")
+    if x.dtype != torch.float32 or x.dim() < 1 or x.numel() == 0:
+        raise WunetError(f"stft: expected a float32 waveform tensor, got {x.dtype} {tuple(x.shape)}")
+    n_fft, hop, win_length = check_stft_resolution(n_fft, hop, win_length)
+    T = x.shape[-1]
+    R = x.numel() // T
+    dev = x.device
+    if n_fft // 2 > T - 1:
+        raise WunetError(f"stft: reflect padding needs n_fft / 2 <= T - 1 (n_fft {n_fft}, T {T})")
+    F, bins = 1 + T // hop, n_fft // 2 + 1
+    mag = torch.empty(R, F, bins, dtype=torch.float32, device=dev)
+    with self._device_guard(dev):
+        basis = self.stft_basis(n_fft, win_length, dev)
+        self._check(self.lib.wunet_stft_forward(None, x.data_ptr(), R, T, n_fft, hop, win_length, 0.0, basis.data_ptr(), None, None,
+                                                mag.data_ptr(), self._stream(dev)))
+    return mag
+
+
+Engine.stft_basis = _stft_basis
+Engine._stft_pair = _stft_pair
+Engine.stft_loss_forward = _stft_loss_forward
+Engine.stft_loss_backward = _stft_loss_backward
+Engine.stft_magnitude = _stft_magnitude
 
 
 def _adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, hyper_dev=None, *,

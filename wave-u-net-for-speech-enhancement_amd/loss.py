@@ -11,11 +11,18 @@ names; the reference only mentions it in its README.
 SDR / the SNR in dB, each row of the last dimension on its own (include/wunet_hip.h: wunet_loss_rows_*):
 
     "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "si_sdr_loss", "args": {}}
+
+`stft_loss` (no reference counterpart): the multi-resolution STFT loss - spectral convergence plus log-magnitude L1 at several
+window sizes (include/wunet_hip.h: wunet_stft_*); `weighted_loss` sums several of the factories above, which is what a config needs
+to train on a waveform term plus the spectral one:
+
+    "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "weighted_loss",
+                      "args": {"terms": [["l1_loss", 1.0], ["stft_loss", 0.5, {"fft_sizes": [1024, 2048, 512]}]]}}
 """
 import torch
 import torch.nn as nn
 
-from .engine import default_engine
+from .engine import STFT_MAX_RESOLUTIONS, check_stft_resolution, default_engine
 
 
 class _LossFn(torch.autograd.Function):
@@ -97,3 +104,88 @@ def si_sdr_loss(zero_mean=True, eps=1e-8):
 
 def snr_loss(zero_mean=True, eps=1e-8):
     return HipRowLoss("snr", zero_mean, eps)
+
+
+class _StftLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mod, engine, clean, enhanced):
+        if clean.requires_grad:                 # (before anything runs)
+            raise NotImplementedError("stft_loss: no gradient with respect to `clean` (the target also sets the spectral-convergence "
+                                      "norm, so it is not minus the gradient of `enhanced`): detach it")
+        clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
+        loss, coefs, saved = engine.stft_loss_forward(clean_c, enh_c, mod.resolutions, mod.sc_weight, mod.mag_weight, mod.clamp)
+        ctx.mod, ctx.engine, ctx.shape = mod, engine, tuple(enh_c.shape)
+        ctx.save_for_backward(coefs, *saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        coefs, *saved = ctx.saved_tensors
+        g = None
+        if ctx.needs_input_grad[3]:
+            g = ctx.engine.stft_loss_backward(ctx.shape, ctx.mod.resolutions, coefs, saved, grad_loss, ctx.mod.clamp)
+        return None, None, None, g
+
+
+class HipStftLoss(nn.Module):
+    """loss(clean, enhanced) -> mean over the resolutions of sc_weight * spectral convergence + mag_weight * log-magnitude L1; the last
+    dimension is the utterance.  Gradient with respect to `enhanced` only."""
+
+    def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), sc_weight=1.0, mag_weight=1.0,
+                 clamp=1e-7):
+        super().__init__()
+        fft_sizes, hop_sizes, win_lengths = list(fft_sizes), list(hop_sizes), list(win_lengths)
+        if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
+            raise ValueError(f"stft_loss: fft_sizes, hop_sizes and win_lengths must have equal lengths (got {len(fft_sizes)}, "
+                             f"{len(hop_sizes)}, {len(win_lengths)})")
+        if not 1 <= len(fft_sizes) <= STFT_MAX_RESOLUTIONS:
+            raise ValueError(f"stft_loss: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {len(fft_sizes)})")
+        if not (clamp > 0.0 and clamp < float("inf")):
+            raise ValueError(f"stft_loss: clamp must be finite and > 0 (got {clamp})")
+        self.resolutions = tuple(check_stft_resolution(n, h, w) for n, h, w in zip(fft_sizes, hop_sizes, win_lengths))
+        self.sc_weight, self.mag_weight, self.clamp = float(sc_weight), float(mag_weight), float(clamp)
+        self._engine_override = None
+
+    def forward(self, clean, enhanced):
+        engine = self._engine_override if self._engine_override is not None else default_engine()
+        return _StftLossFn.apply(self, engine, clean, enhanced)
+
+
+def stft_loss(fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), sc_weight=1.0, mag_weight=1.0, clamp=1e-7):
+    return HipStftLoss(fft_sizes, hop_sizes, win_lengths, sc_weight, mag_weight, clamp)
+
+
+class WeightedLoss(nn.Module):
+    """The weighted sum of several of this module's losses: terms = [[factory_name, weight, args?], ...]; plain autograd over the
+    terms' own functions."""
+
+    def __init__(self, terms):
+        super().__init__()
+        if not terms:
+            raise ValueError("weighted_loss: at least one term")
+        mods, weights = [], []
+        for term in terms:
+            if len(term) not in (2, 3):
+                raise ValueError(f"weighted_loss: a term is [factory_name, weight] or [factory_name, weight, args] (got {term!r})")
+            name, weight = term[0], float(term[1])
+            factory = globals().get(name)
+            if name not in _FACTORIES or factory is None:
+                raise ValueError(f"weighted_loss: unknown loss {name!r} (one of {sorted(_FACTORIES)})")
+            mods.append(factory(**(dict(term[2]) if len(term) == 3 else {})))
+            weights.append(weight)
+        self.terms = nn.ModuleList(mods)
+        self.weights = weights
+
+    def forward(self, clean, enhanced):
+        total = None
+        for w, m in zip(self.weights, self.terms):
+            v = w * m(clean, enhanced)
+            total = v if total is None else total + v
+        return total
+
+
+_FACTORIES = ("mse_loss", "l1_loss", "smooth_l1_loss", "si_sdr_loss", "snr_loss", "stft_loss")
+
+
+def weighted_loss(terms):
+    return WeightedLoss(terms)

@@ -29,3 +29,13 @@ def snr(clean, estimate, zero_mean=True, eps=1e-8, engine=None):
 def si_sdr_improvement(clean, noisy, enhanced, zero_mean=True, eps=1e-8, engine=None):
     """SI-SDR of the enhanced signal minus SI-SDR of the noisy one, per row: what the enhancement gained."""
     return si_sdr(clean, enhanced, zero_mean, eps, engine) - si_sdr(clean, noisy, zero_mean, eps, engine)
+
+
+@torch.no_grad()
+def stft_magnitude(x, n_fft=320, hop=160, win_length=320, engine=None):
+    """|STFT| of every row of x on the device - the spectrum the reference's validation epoch looks at on the host
+    (trainer/trainer.py:108-110: n_fft 320, hop 160), torch.stft's conventions (periodic Hann, center=True, reflect padding).  The
+    forward GEMM of the STFT loss with its magnitude output only (include/wunet_hip.h: wunet_stft_forward), no clamp.
+    Returns float32 [rows, 1 + T // hop, n_fft // 2 + 1]."""
+    engine = engine if engine is not None else default_engine()
+    return engine.stft_magnitude(x.detach().contiguous(), n_fft, hop, win_length)
