@@ -197,6 +197,29 @@ int wunet_stft_backward(const float* saved, const double* coefs, const float* gr
                         int win_length, double clamp, const float* basis, void* scratch, float* grad_enhanced, int accumulate,
                         void* stream);
 
+/* STOI per row (no reference counterpart on the device: the reference's validation epoch calls pystoi on the host per recording,
+ * trainer/trainer.py:128-143, util/utils.py:116-117): Taal et al. 2011 with pystoi's choices for stoi(clean, estimate, fs,
+ * extended=False) - resample_poly to 10 kHz with pystoi's Kaiser filter, removal of the frames (256 / hop 128, hanning(258)[1:-1])
+ * more than 40 dB below the clean row's loudest, 512-point spectra of the overlap-added rest, 15 third-octave bands from 150 Hz,
+ * clipped and normalised correlations over all segments of 30 frames, their mean.  Fewer than 30 spectral frames (a row_len too short
+ * for one frame included): the score 1e-5, pystoi's value.
+ *   wunet_stoi_tables_bytes(fs): bytes of the per-rate tables (0: fs refused - fs <= 0, or a rate whose filter needs more than 4096
+ *     taps, i.e. max(p, q) > 56 for 10000 / fs = p / q in lowest terms; 8, 12, 16, 20, 24, 32 and 48 kHz all fit).
+ *   wunet_stoi_tables_build: the windowed 512-point DFT basis, the window and the resampler's taps into `tables` (16-byte aligned).
+ *     taps: DEVICE pointer to the n_taps = 2 L + 1 float32 filter taps (L = ceil(52 / (28.714 fc / 10)), fc = 1 / (2 max(p, q)),
+ *     h[t] = kaiser(2 L + 1, 0.1102 (60 - 8.7))[t + L] 2 p fc sinc(2 fc t), normalised to sum 1; computed by the caller in double);
+ *     n_taps = 0 and taps = NULL at fs = 10000.
+ *   wunet_stoi_forward: out[row] (float32) and, when frames_out != NULL, the spectral frame count of every row (int32).  scratch:
+ *     >= wunet_stoi_scratch_bytes(rows, row_len, fs) device bytes, 16-byte aligned, no memset needed; the waveforms need 4-byte
+ *     alignment only.  rows <= 65535.
+ * Every sum in double and in one fixed order, no atomics: bit-identical run to run.  Caller-owned memory, no allocation, no
+ * synchronisation, no host read-back (the per-row frame counts stay in device memory): every call can be captured. */
+size_t wunet_stoi_tables_bytes(int fs);
+int wunet_stoi_tables_build(int fs, const float* taps, size_t n_taps, float* tables, void* stream);
+size_t wunet_stoi_scratch_bytes(size_t rows, size_t row_len, int fs);
+int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                       float* out, int* frames_out, void* stream);
+
 /* replaces optimizer.step() of torch.optim.Adam(params, lr, betas) as the reference builds it
  * (train.py:31-35; eps, weight_decay=0, amsgrad=False fixed by the reference's call) for n_tensors tensors in one
  * or two launches.  step is the 1-based step count AFTER the increment (torch's state["step"]).  numels: host array.

@@ -22,6 +22,7 @@ EXPORTS = [
     "wunet_loss_rows_scratch_bytes", "wunet_loss_rows_forward", "wunet_loss_rows_backward",
     "wunet_stft_basis_bytes", "wunet_stft_basis", "wunet_stft_scratch_bytes", "wunet_stft_saved_bytes", "wunet_stft_forward",
     "wunet_stft_finalize", "wunet_stft_backward",
+    "wunet_stoi_tables_bytes", "wunet_stoi_tables_build", "wunet_stoi_scratch_bytes", "wunet_stoi_forward",
 ]
 
 _vp = ctypes.c_void_p
@@ -65,6 +66,13 @@ def declare(lib):
         lib.wunet_stft_forward.argtypes = [_vp, _vp, _sz, _sz, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]
         lib.wunet_stft_finalize.argtypes = [_i, _vp, _sz, _sz, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]
         lib.wunet_stft_backward.argtypes = [_vp, _vp, _vp, _sz, _sz, _i, _i, _i, ctypes.c_double, _vp, _vp, _vp, _i, _vp]
+    if hasattr(lib, "wunet_stoi_forward"):       # (saved libraries of earlier versions do not have it)
+        lib.wunet_stoi_tables_bytes.argtypes = [_i]
+        lib.wunet_stoi_tables_bytes.restype = _sz
+        lib.wunet_stoi_tables_build.argtypes = [_i, _vp, _sz, _vp, _vp]
+        lib.wunet_stoi_scratch_bytes.argtypes = [_sz, _sz, _i]
+        lib.wunet_stoi_scratch_bytes.restype = _sz
+        lib.wunet_stoi_forward.argtypes = [_vp, _vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp]
     lib.wunet_layer_info.argtypes = [_vp, _i, ctypes.POINTER(_sz), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     lib.wunet_num_conv_layers.argtypes = [_vp]
     for name in ("wunet_op_conv1d", "wunet_op_conv1d_split"):

@@ -5,6 +5,7 @@
 #include "wunet_h3_elem.h"
 #include "wunet_loss_rows.h"
 #include "wunet_stft.h"
+#include "wunet_stoi.h"
 
 using namespace wunet_host;
 
@@ -244,6 +245,139 @@ int wunet_stft_backward(const float* saved, const double* coefs, const float* gr
     prof_begin(st, "stft_ola_kernel", 0.0, 4.0 * ((double)s.M * (s.k1 - s.k0) + (accumulate ? 2.0 : 1.0) * rows * row_len));
     WUNET_LAUNCH(stft_ola_kernel, dim3((unsigned)((O.total + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st, O);
     prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- STOI per row (wunet_stoi.h)
+namespace {
+struct StoiShape {
+    int p, q, L;            // 10 kHz = fs p / q; L = 0 without resampling
+    size_t Tr;              // samples of a row at 10 kHz
+    unsigned F0, Fmax, M, nblk;
+    size_t o_nk, o_kept, o_energy, o_res, o_pw, o_part, bytes;   // byte offsets inside the scratch
+};
+
+// the resampler of one sample rate: p, q and the filter half length L = ceil(52 / (28.714 fc / 10)), fc = 1 / (2 max(p, q))
+int stoi_rate(int fs, StoiShape& s)
+{
+    if (fs <= 0) return fail(WUNET_E_ARG, "stoi: the sample rate must be > 0 (got %d)", fs);
+    int a = WUNET_STOI_FS, b = fs;
+    while (b) { const int t = a % b; a = b; b = t; }
+    s.p = WUNET_STOI_FS / a; s.q = fs / a; s.L = 0;
+    if (fs == WUNET_STOI_FS) return 0;
+    const double fc = 1.0 / (2.0 * (double)(s.p > s.q ? s.p : s.q));
+    const double L = std::ceil(52.0 / (28.714 * fc / 10.0));
+    if (2.0 * L + 1.0 > (double)WUNET_STOI_MAX_TAPS)
+        return fail(WUNET_E_ARG, "stoi: %d Hz is %d / %d of 10 kHz and needs %.0f filter taps; at most %d are supported (max(p, q) <= 56)", fs, s.q,
+                    s.p, 2.0 * L + 1.0, WUNET_STOI_MAX_TAPS);
+    s.L = (int)L;
+    return 0;
+}
+
+int stoi_shape(size_t rows, size_t T, int fs, StoiShape& s)
+{
+    if (stoi_rate(fs, s)) return WUNET_E_ARG;
+    if (rows == 0) return fail(WUNET_E_ARG, "stoi: rows must be > 0");
+    if (rows > 65535) return fail(WUNET_E_ARG, "stoi: at most 65535 rows per call (got %zu)", rows);       // (a grid's y)
+    if (T >= (1ull << 30) || rows * T >= (1ull << 36)) return fail(WUNET_E_ARG, "stoi: shape too large (%zu x %zu)", rows, T);
+    s.Tr = (T * (size_t)s.p + (size_t)s.q - 1) / (size_t)s.q;
+    if (s.Tr >= (1ull << 30) || rows * s.Tr >= (1ull << 36)) return fail(WUNET_E_ARG, "stoi: shape too large at 10 kHz (%zu x %zu)", rows, s.Tr);
+    s.F0 = s.Tr > WUNET_STOI_N ? (unsigned)((s.Tr - WUNET_STOI_N + WUNET_STOI_HOP - 1) / WUNET_STOI_HOP) : 0u;
+    s.Fmax = s.F0 > 0 ? s.F0 - 1 : 0u;
+    if ((size_t)rows * s.Fmax >= (1ull << 31) - WUNET_STFT_FM) return fail(WUNET_E_ARG, "stoi: too many frames (%zu rows x %u)", rows, s.Fmax);
+    s.M = (unsigned)(rows * s.Fmax);
+    s.nblk = s.Fmax >= WUNET_STOI_SEG ? (s.Fmax - WUNET_STOI_SEG + 1 + WUNET_STOI_SB - 1) / WUNET_STOI_SB : 0u;
+    size_t o = 0;
+    auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+    s.o_nk = take(rows * sizeof(int));
+    s.o_kept = take(rows * s.F0 * sizeof(int));
+    s.o_energy = take(rows * s.F0 * sizeof(double));
+    s.o_res = take(s.L ? 2 * rows * s.Tr * sizeof(float) : 0);
+    s.o_pw = take(s.nblk ? (size_t)2 * s.M * WUNET_STOI_BP * sizeof(float) : 0);
+    s.o_part = take(rows * s.nblk * sizeof(double));
+    s.bytes = o;
+    return 0;
+}
+}  // namespace
+
+size_t wunet_stoi_tables_bytes(int fs)
+{
+    StoiShape s{};
+    if (stoi_rate(fs, s)) return 0;
+    return ((size_t)WUNET_STOI_TAB_TAPS + (s.L ? 2 * (size_t)s.L + 1 : 0) + 3) / 4 * 4 * sizeof(float);
+}
+
+int wunet_stoi_tables_build(int fs, const float* taps, size_t n_taps, float* tables, void* stream)
+{
+    StoiShape s{};
+    if (stoi_rate(fs, s)) return WUNET_E_ARG;
+    const size_t want = s.L ? 2 * (size_t)s.L + 1 : 0;
+    if (n_taps != want) return fail(WUNET_E_ARG, "stoi: %d Hz needs %zu resampler taps (got %zu)", fs, want, n_taps);
+    if (!tables || ((size_t)tables & 15) || (want && !taps)) return fail(WUNET_E_ARG, "stoi: null argument (or tables that are not 16-byte aligned)");
+    const unsigned grid = WUNET_STOI_N + 1 + (unsigned)((want + WUNET_THREADS - 1) / WUNET_THREADS);
+    WUNET_LAUNCH(stoi_tables_kernel, dim3(grid), dim3(WUNET_THREADS), 0, (hipStream_t)stream, taps, (unsigned)want, tables);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+size_t wunet_stoi_scratch_bytes(size_t rows, size_t row_len, int fs)
+{
+    StoiShape s{};
+    if (stoi_shape(rows, row_len, fs, s)) return 0;
+    return s.bytes;
+}
+
+int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                       float* out, int* frames_out, void* stream)
+{
+    StoiShape s{};
+    if (stoi_shape(rows, row_len, fs, s)) return WUNET_E_ARG;
+    if (!clean || !estimate || !tables || !scratch || !out || ((size_t)tables & 15) || ((size_t)scratch & 15))
+        return fail(WUNET_E_ARG, "stoi: null argument (or tables / scratch that are not 16-byte aligned)");
+    hipStream_t st = (hipStream_t)stream;
+    char* sc = (char*)scratch;
+    int* nk = (int*)(sc + s.o_nk);
+    int* kept = (int*)(sc + s.o_kept);
+    double* part = (double*)(sc + s.o_part);
+    const float* w = tables + WUNET_STOI_TAB_W;
+    const float* x[2] = {clean, estimate};
+    if (s.L && s.Tr > 0) {
+        StoiResampleArgs R{};
+        R.in[0] = clean; R.in[1] = estimate; R.taps = tables + WUNET_STOI_TAB_TAPS; R.out = (float*)(sc + s.o_res);
+        R.T = row_len; R.Tr = s.Tr; R.rows = rows; R.p = s.p; R.q = s.q; R.L = s.L;
+        const unsigned per = WUNET_THREADS * WUNET_STOI_RPT;
+        prof_begin(st, "stoi_resample_kernel", 2.0 * 2.0 * rows * s.Tr * ((2.0 * s.L + 1.0) / s.p), 4.0 * 2.0 * rows * (row_len + s.Tr));
+        WUNET_LAUNCH(stoi_resample_kernel, dim3((unsigned)((s.Tr + per - 1) / per), (unsigned)rows, 2), dim3(WUNET_THREADS), 0, st, R);
+        prof_end(st);
+        WUNET_CHECK_LAUNCH();
+        x[0] = R.out; x[1] = R.out + rows * s.Tr;
+    }
+    if (s.F0 > 0) {
+        StoiMaskArgs K{};
+        K.x = x[0]; K.w = w; K.Tr = s.Tr; K.F0 = s.F0; K.energy = (double*)(sc + s.o_energy); K.kept = kept; K.nk = nk;
+        WUNET_LAUNCH(stoi_mask_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), 0, st, K);
+        WUNET_CHECK_LAUNCH();
+    }
+    if (s.nblk > 0) {       // (fewer than 30 frames at the most: no row has a segment, the final kernel alone writes 1e-5)
+        StoiSpecArgs P{};
+        P.x[0] = x[0]; P.x[1] = x[1]; P.basis = tables; P.w = w; P.kept = kept; P.nk = nk; P.Tr = s.Tr; P.M = s.M; P.Fmax = s.Fmax; P.F0 = s.F0;
+        P.pw = (float*)(sc + s.o_pw);
+        const unsigned mtiles = (s.M + WUNET_STFT_FM - 1) / WUNET_STFT_FM;
+        // (profiler: 2 flops x frames x 256 x 2 BP columns per signal, at the largest frame count; the signals once, the powers written)
+        prof_begin(st, "stoi_spec_kernel", 2.0 * 2.0 * s.M * WUNET_STOI_N * 2.0 * WUNET_STOI_BP, 4.0 * (2.0 * rows * s.Tr + 2.0 * s.M * WUNET_STOI_BP));
+        WUNET_LAUNCH(stoi_spec_kernel, dim3(mtiles, WUNET_STOI_BP / WUNET_STFT_BN), dim3(WUNET_THREADS), 0, st, P);
+        prof_end(st);
+        WUNET_CHECK_LAUNCH();
+        StoiSegArgs G{};
+        G.pw = P.pw; G.nk = nk; G.M = s.M; G.Fmax = s.Fmax; G.nblk = s.nblk; G.clip = 1.0 + std::pow(10.0, 15.0 / 20.0); G.part = part;
+        prof_begin(st, "stoi_segment_kernel", 0.0, 4.0 * 2.0 * s.M * WUNET_STOI_BP);
+        WUNET_LAUNCH(stoi_segment_kernel, dim3(s.nblk, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
+        prof_end(st);
+        WUNET_CHECK_LAUNCH();
+    }
+    WUNET_LAUNCH(stoi_final_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), 0, st, (const double*)part, (const int*)(s.F0 > 0 ? nk : nullptr), s.nblk,
+                 out, frames_out);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
 }

@@ -1,0 +1,366 @@
+// STOI per row (include/wunet_hip.h: wunet_stoi_*): Taal et al. 2011 with pystoi's choices for stoi(x, y, fs, extended=False), clean x
+// and estimate y, every row of the batch in one launch sequence and no host read - the per-row frame counts live in device memory, the
+// grids are sized for the largest possible count and blocks beyond a row's count leave early.
+//   stoi_tables_kernel    tables = basis[256][2 BP] (row k = w[k] cos(2 pi k b / 512) for b < BP, then -w[k] sin(..); BP = 224 covers the
+//                         bins 7 .. 218 of the third-octave bands) | w[256] = hanning(258)[1:-1] | the resampler's taps, copied
+//   stoi_resample_kernel  polyphase FIR to 10 kHz (resample_poly(x, p, q, window = taps)): an output sample reads only the taps of its
+//                         phase, staged in LDS; both signals in one launch; double accumulation, one rounding to float
+//   stoi_mask_kernel      ONE block per row: energies of the clean row's windowed frames [dB], their maximum, the frames above
+//                         maximum - 40 dB as a table kept[row][j] of original frame indices (an exclusive scan) + n_kept[row]
+//   stoi_spec_kernel      implicit GEMM [frames][256] x basis on v_mfma_f32_16x16x4_f32, stft_fwd_kernel's tiling.  The loader builds
+//                         each frame of the silence-free signal from the resampled one and the kept table - w[k] (in the basis) times the
+//                         sum of the at most two kept windowed frames over position k - so the overlap-added signal is never written;
+//                         the epilogue writes re^2 + im^2 of both signals
+//   stoi_segment_kernel   a block owns 64 segments of one row: band magnitudes (the powers of a band added in double, in bin order) of
+//                         its 93 frames into LDS, then per (segment, band) the clipped, centred, normalised correlation in double; one
+//                         partial per block
+//   stoi_final_kernel     one block per row: the partials in block order -> the mean over (segment, band), or 1e-5 below 30 frames
+// fp32 operands and MFMA accumulation, every reduction in double and in one fixed order, no atomics: bit-identical run to run.
+#pragma once
+#include "wunet_stft.h"
+
+#define WUNET_STOI_FS 10000          // the rate STOI is defined at
+#define WUNET_STOI_N 256             // frame length
+#define WUNET_STOI_HOP 128
+#define WUNET_STOI_NFFT 512
+#define WUNET_STOI_BP 224            // bins 0 .. 223 of the 257: seven tiles of WUNET_STFT_BN
+#define WUNET_STOI_BANDS 15
+#define WUNET_STOI_SEG 30            // frames per segment
+#define WUNET_STOI_SB 64             // segments per block of stoi_segment_kernel
+#define WUNET_STOI_MAX_TAPS 4096     // LDS budget of stoi_resample_kernel (16 KiB): 2 L + 1 taps, max(p, q) <= 56
+#define WUNET_STOI_RPT 4             // output samples per thread of stoi_resample_kernel
+#define WUNET_STOI_EPS 2.220446049250313e-16
+#define WUNET_STOI_TAB_W (WUNET_STOI_N * 2 * WUNET_STOI_BP)              // float offsets inside the tables
+#define WUNET_STOI_TAB_TAPS (WUNET_STOI_TAB_W + WUNET_STOI_N)
+
+// first bins of the 15 third-octave bands from 150 Hz at 10 kHz / 512 points, and the end of the last one
+__device__ __forceinline__ int stoi_band_edge(int i)
+{
+    const int e[WUNET_STOI_BANDS + 1] = {7, 9, 11, 14, 17, 22, 27, 34, 43, 55, 69, 87, 109, 138, 174, 219};
+    return e[i];
+}
+
+// grid (N + 1 + ceil(n_taps / 256)): block k < N writes basis row k, block N the window, the rest copy the taps
+static __global__ __launch_bounds__(WUNET_THREADS) void stoi_tables_kernel(const float* taps, unsigned n_taps, float* tables)
+{
+    const int k = blockIdx.x, tid = threadIdx.x;
+    double s, c;
+    if (k > WUNET_STOI_N) {
+        const unsigned i = (unsigned)(k - WUNET_STOI_N - 1) * WUNET_THREADS + tid;
+        if (i < n_taps) tables[WUNET_STOI_TAB_TAPS + i] = taps[i];
+        return;
+    }
+    if (k == WUNET_STOI_N) {
+        wunet_sincospi_d(2.0 * (double)(tid + 1) / (double)(WUNET_STOI_N + 1), &s, &c);
+        tables[WUNET_STOI_TAB_W + tid] = (float)(0.5 - 0.5 * c);
+        return;
+    }
+    wunet_sincospi_d(2.0 * (double)(k + 1) / (double)(WUNET_STOI_N + 1), &s, &c);
+    const double w = 0.5 - 0.5 * c;                                      // np.hanning(258)[k + 1]
+    for (int col = tid; col < 2 * WUNET_STOI_BP; col += WUNET_THREADS) {
+        const int b = col < WUNET_STOI_BP ? col : col - WUNET_STOI_BP;
+        const int ph = (k * b) % WUNET_STOI_NFFT;                        // the phase from (k b) mod N in integers
+        wunet_sincospi_d(2.0 * (double)ph / (double)WUNET_STOI_NFFT, &s, &c);
+        tables[(size_t)k * 2 * WUNET_STOI_BP + col] = (float)(col < WUNET_STOI_BP ? w * c : -(w * s));
+    }
+}
+
+struct StoiResampleArgs {
+    const float* in[2];     // clean, estimate [rows][T]
+    const float* taps;      // [2 L + 1], float32
+    float* out;             // [2][rows][Tr]
+    size_t T, Tr, rows;
+    int p, q, L;
+};
+
+// grid (Tr / (256 * RPT) rounded up, rows, 2).  y[n] = p sum_t h[t] x[(n q - t) / p] over -L <= t <= L with p | n q - t: with
+// c = n q + L, i_hi = c / p and phase = c mod p the terms are h[phase + p j - L] x[i_hi - j], j = 0 .. (2 L - phase) / p, zeros outside x.
+static __global__ __launch_bounds__(WUNET_THREADS) void stoi_resample_kernel(StoiResampleArgs A)
+{
+    __shared__ float hs[WUNET_STOI_MAX_TAPS];
+    const int tid = threadIdx.x, ntap = 2 * A.L + 1;
+    for (int i = tid; i < ntap; i += WUNET_THREADS) hs[i] = A.taps[i];
+    __syncthreads();
+    const size_t row = blockIdx.y;
+    const float* x = A.in[blockIdx.z] + row * A.T;
+    float* y = A.out + ((size_t)blockIdx.z * A.rows + row) * A.Tr;
+    const long long Tl = (long long)A.T;
+#pragma unroll
+    for (int u = 0; u < WUNET_STOI_RPT; ++u) {
+        const size_t n = ((size_t)blockIdx.x * WUNET_STOI_RPT + u) * WUNET_THREADS + tid;
+        if (n >= A.Tr) continue;
+        const long long c = (long long)n * A.q + A.L, ihi = c / A.p;
+        const int ph = (int)(c - ihi * A.p);
+        long long j0 = ihi - (Tl - 1), j1 = (2 * A.L - ph) / A.p;
+        if (j0 < 0) j0 = 0;
+        if (j1 > ihi) j1 = ihi;
+        double acc = 0.0;
+        for (long long j = j0; j <= j1; ++j) acc += (double)hs[ph + A.p * (int)j] * (double)x[ihi - j];
+        y[n] = (float)((double)A.p * acc);
+    }
+}
+
+struct StoiMaskArgs {
+    const float* x;         // the clean rows at 10 kHz [rows][Tr]
+    const float* w;         // [256]
+    size_t Tr;
+    unsigned F0;            // frames of a row: starts 0, 128, .. < Tr - 256
+    double* energy;         // [rows][F0] scratch
+    int* kept;              // [rows][F0]
+    int* nk;                // [rows]
+};
+
+// grid (rows).  Pass 1: a wave per frame, E_f = 20 log10(|w x_f| + EPS) with the sum in double (lane l takes samples l, l + 64, ..,
+// then a butterfly), and the row's maximum.  Pass 2: thread t owns the frames [t g, (t + 1) g), g = F0 / 256 rounded up; its count of
+// kept ones, an exclusive scan of the 256 counts, the indices written in frame order.
+static __global__ __launch_bounds__(WUNET_THREADS) void stoi_mask_kernel(StoiMaskArgs A)
+{
+    __shared__ double wmax[WUNET_WAVES];
+    __shared__ unsigned cnt[WUNET_THREADS];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t row = blockIdx.x;
+    const float* x = A.x + row * A.Tr;
+    double* en = A.energy + row * A.F0;
+    float wv[WUNET_STOI_N / 64];
+#pragma unroll
+    for (int u = 0; u < WUNET_STOI_N / 64; ++u) wv[u] = A.w[lane + 64 * u];
+    double emax = -1.0e300;
+    for (unsigned f = wave; f < A.F0; f += WUNET_WAVES) {
+        const float* xf = x + (size_t)f * WUNET_STOI_HOP;
+        double s = 0.0;
+#pragma unroll
+        for (int u = 0; u < WUNET_STOI_N / 64; ++u) {
+            const double v = (double)wv[u] * (double)xf[lane + 64 * u];
+            s += v * v;
+        }
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) s += wunet_shfl_xor_d(s, m);
+        const double e = 20.0 * log10(sqrt(s) + WUNET_STOI_EPS);
+        if (lane == 0) en[f] = e;
+        emax = e > emax ? e : emax;
+    }
+    if (lane == 0) wmax[wave] = emax;
+    __syncthreads();                                                     // (the energies too: written and read inside this block)
+    emax = -1.0e300;
+#pragma unroll
+    for (int k = 0; k < WUNET_WAVES; ++k) emax = wmax[k] > emax ? wmax[k] : emax;
+    const double thr = emax - 40.0;
+    const unsigned g = (A.F0 + WUNET_THREADS - 1) / WUNET_THREADS;
+    const unsigned f0 = (unsigned)tid * g < A.F0 ? (unsigned)tid * g : A.F0, f1 = f0 + g < A.F0 ? f0 + g : A.F0;
+    unsigned n = 0;
+    for (unsigned f = f0; f < f1; ++f) n += en[f] > thr ? 1u : 0u;
+    cnt[tid] = n;
+    __syncthreads();
+    unsigned at = 0;
+    for (int k = 0; k < tid; ++k) at += cnt[k];
+    int* kp = A.kept + row * A.F0;
+    for (unsigned f = f0; f < f1; ++f)
+        if (en[f] > thr) kp[at++] = (int)f;
+    if (tid == WUNET_THREADS - 1) A.nk[row] = (int)at;
+}
+
+struct StoiSpecArgs {
+    const float* x[2];      // clean, estimate at 10 kHz [rows][Tr]
+    const float* basis;     // [256][2 BP]
+    const float* w;         // [256]
+    const int* kept;        // [rows][F0]
+    const int* nk;          // [rows]
+    size_t Tr;
+    unsigned M, Fmax, F0;   // Fmax = F0 - 1: the most spectral frames a row can have; M = rows * Fmax
+    float* pw;              // [2][M][BP]: re^2 + im^2
+};
+
+// grid (M / 64 rounded up, BP / 32).  Frame m = row * Fmax + f is live for f < n_kept[row] - 1.  Frame f of the silence-free signal:
+// position k < 128 lies in the kept frames f (at k) and f - 1 (at k + 128), k >= 128 in f (at k) and f + 1 (at k - 128); each is
+// windowed once there, and once more by the basis.  A tile As[sig][64 frames][16 k], B tile Bs[16 k][32 cos | 32 -sin], the next
+// tile's global loads issued before the MFMAs of the current one (stft_fwd_kernel's pipeline).
+static __global__ __launch_bounds__(WUNET_THREADS) void stoi_spec_kernel(StoiSpecArgs A)
+{
+    __shared__ __attribute__((aligned(16))) float As[2 * WUNET_STFT_FM * WUNET_STFT_AS];
+    __shared__ __attribute__((aligned(16))) float Bs[WUNET_STFT_KT * WUNET_STFT_BS];
+    __shared__ float ws[WUNET_STOI_N];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lq = lane >> 4;
+    const unsigned m0 = blockIdx.x * WUNET_STFT_FM;
+    const int b0 = blockIdx.y * WUNET_STFT_BN;
+    {   // leave when none of the block's frames is live (the same answer in every thread)
+        const unsigned mlast = m0 + WUNET_STFT_FM - 1 < A.M - 1 ? m0 + WUNET_STFT_FM - 1 : A.M - 1;
+        bool any = false;
+        for (unsigned r = m0 / A.Fmax; r <= mlast / A.Fmax; ++r) {
+            const int live = A.nk[r] - 1;
+            const unsigned lo = r * A.Fmax > m0 ? r * A.Fmax : m0;
+            any = any || (live > 0 && lo < r * A.Fmax + (unsigned)live);
+        }
+        if (!any) return;
+    }
+    ws[tid] = A.w[tid];
+    // ---- loader roles.  A: k = tid & 15, frames (tid >> 4) + 16 j.  B: row tid >> 4, four columns from (tid & 15) * 4.
+    const int ak = tid & 15;
+    size_t abase[4];
+    int kc[4], kp[4], kn[4];            // the kept frame itself, the one before and the one after it (-1: none)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned m = m0 + (unsigned)(tid >> 4) + 16u * j;
+        const unsigned row = m < A.M ? m / A.Fmax : 0u, f = m - row * A.Fmax;
+        const bool ok = m < A.M && (int)f < A.nk[row] - 1;
+        const int* kr = A.kept + (size_t)row * A.F0;
+        abase[j] = (size_t)row * A.Tr;
+        kc[j] = ok ? kr[f] : -1;
+        kp[j] = ok && f > 0 ? kr[f - 1] : -1;
+        kn[j] = ok ? kr[f + 1] : -1;
+    }
+    const int bk = tid >> 4, bc = (tid & 15) * 4;
+    const float* bsrc = A.basis + (size_t)bk * 2 * WUNET_STOI_BP + (bc < WUNET_STFT_BN ? b0 + bc : WUNET_STOI_BP + b0 + bc - WUNET_STFT_BN);
+    float ra[2][4];
+    wunet_f4 rb;
+    __syncthreads();                                                     // ws
+#define WUNET_STOI_LOAD(KT_)                                                                                      \
+    do {                                                                                                          \
+        const int k_ = (KT_) + ak, ko_ = k_ < WUNET_STOI_HOP ? k_ + WUNET_STOI_HOP : k_ - WUNET_STOI_HOP;          \
+        const float w_ = ws[k_], wo_ = ws[ko_];                                                                   \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
+            const int other_ = k_ < WUNET_STOI_HOP ? kp[j] : kn[j];                                               \
+            const size_t o1_ = abase[j] + (size_t)(kc[j] < 0 ? 0 : kc[j]) * WUNET_STOI_HOP + k_;                  \
+            const size_t o2_ = abase[j] + (size_t)(other_ < 0 ? 0 : other_) * WUNET_STOI_HOP + ko_;               \
+            _Pragma("unroll") for (int s = 0; s < 2; ++s) {                                                       \
+                const float v1_ = kc[j] < 0 ? 0.0f : w_ * A.x[s][o1_];                                            \
+                const float v2_ = other_ < 0 ? 0.0f : wo_ * A.x[s][o2_];                                          \
+                ra[s][j] = v1_ + v2_;                                                                             \
+            }                                                                                                     \
+        }                                                                                                         \
+        rb = wunet_ld4(bsrc + (size_t)(KT_) * 2 * WUNET_STOI_BP);                                                 \
+    } while (0)
+    wunet_f4 acc[2][2][2];               // [signal][re, im][column tile]
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) acc[s][p][nt] = wunet_f4{0.f, 0.f, 0.f, 0.f};
+    WUNET_STOI_LOAD(0);
+    for (int kt = 0; kt < WUNET_STOI_N; kt += WUNET_STFT_KT) {
+        __syncthreads();                                               // the previous tile's reads are done
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int ml = (tid >> 4) + 16 * j;
+            As[ml * WUNET_STFT_AS + ak] = ra[0][j];
+            As[(WUNET_STFT_FM + ml) * WUNET_STFT_AS + ak] = ra[1][j];
+        }
+        wunet_st4(&Bs[bk * WUNET_STFT_BS + bc], rb);
+        __syncthreads();
+        if (kt + WUNET_STFT_KT < WUNET_STOI_N) WUNET_STOI_LOAD(kt + WUNET_STFT_KT);
+#pragma unroll
+        for (int s4 = 0; s4 < WUNET_STFT_KT / 4; ++s4) {
+            const int kk = s4 * 4 + lq;
+            const float a0 = As[(wave * 16 + li) * WUNET_STFT_AS + kk];
+            const float a1 = As[(WUNET_STFT_FM + wave * 16 + li) * WUNET_STFT_AS + kk];
+#pragma unroll
+            for (int p = 0; p < 2; ++p)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    const float b = Bs[kk * WUNET_STFT_BS + p * WUNET_STFT_BN + nt * 16 + li];
+                    acc[0][p][nt] = wunet_mfma16(a0, b, acc[0][p][nt]);
+                    acc[1][p][nt] = wunet_mfma16(a1, b, acc[1][p][nt]);
+                }
+        }
+    }
+#undef WUNET_STOI_LOAD
+    // ---- epilogue: D[row = 4 lq + r][col = li] of the wave's 16 frames (a dead frame of a live block: zeros, never read)
+    const size_t plane = (size_t)A.M * WUNET_STOI_BP;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt) {
+        const int b = b0 + nt * 16 + li;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const unsigned m = m0 + (unsigned)(wave * 16 + lq * 4 + r);
+            if (m >= A.M) continue;
+            const size_t o = (size_t)m * WUNET_STOI_BP + b;
+            A.pw[o] = stft_power(acc[0][0][nt][r], acc[0][1][nt][r]);
+            A.pw[plane + o] = stft_power(acc[1][0][nt][r], acc[1][1][nt][r]);
+        }
+    }
+}
+
+struct StoiSegArgs {
+    const float* pw;        // [2][M][BP]
+    const int* nk;          // [rows]
+    unsigned M, Fmax, nblk; // nblk = (Fmax - 29) / 64 rounded up: the grid's x
+    double clip;            // 1 + 10^(15 / 20)
+    double* part;           // [rows][nblk]
+};
+
+// frames of a row -> segments: 0 below 30 frames
+__device__ __forceinline__ int stoi_segments(int n_kept)
+{
+    const int fs = n_kept - 1;
+    return fs >= WUNET_STOI_SEG ? fs - WUNET_STOI_SEG + 1 : 0;
+}
+
+// grid (nblk, rows).  With X, Y the 30 band magnitudes of a segment: alpha = |X| / (|Y| + EPS), Y' = min(alpha Y, clip X), both
+// centred, each divided by (its norm + EPS), d = sum X Y' - all of it in double; a thread adds the d of its (segment, band) items
+// in index order, block_sum2 the threads.
+static __global__ __launch_bounds__(WUNET_THREADS) void stoi_segment_kernel(StoiSegArgs A)
+{
+    __shared__ double tb[2 * (WUNET_STOI_SB + WUNET_STOI_SEG - 1) * WUNET_STOI_BANDS];
+    __shared__ double red[2 * WUNET_WAVES];
+    const int tid = threadIdx.x;
+    const size_t row = blockIdx.y;
+    const int nseg = stoi_segments(A.nk[row]), s0 = (int)blockIdx.x * WUNET_STOI_SB;
+    if (s0 >= nseg) return;
+    const int ns = nseg - s0 < WUNET_STOI_SB ? nseg - s0 : WUNET_STOI_SB, nf = ns + WUNET_STOI_SEG - 1;
+    const size_t plane = (size_t)A.M * WUNET_STOI_BP;
+    constexpr int TBS = (WUNET_STOI_SB + WUNET_STOI_SEG - 1) * WUNET_STOI_BANDS;
+    for (int i = tid; i < 2 * nf * WUNET_STOI_BANDS; i += WUNET_THREADS) {
+        const int sig = i / (nf * WUNET_STOI_BANDS), fb = i - sig * nf * WUNET_STOI_BANDS, fr = fb / WUNET_STOI_BANDS, band = fb - fr * WUNET_STOI_BANDS;
+        const float* p = A.pw + sig * plane + (row * A.Fmax + (size_t)(s0 + fr)) * WUNET_STOI_BP;
+        double s = 0.0;
+        for (int b = stoi_band_edge(band); b < stoi_band_edge(band + 1); ++b) s += (double)p[b];
+        tb[sig * TBS + fb] = sqrt(s);
+    }
+    __syncthreads();
+    double dsum = 0.0, dummy = 0.0;
+    for (int i = tid; i < ns * WUNET_STOI_BANDS; i += WUNET_THREADS) {
+        const double* xs = tb + i;                                       // (segment i / 15, band i % 15): frame n at + 15 n
+        const double* ys = tb + TBS + i;
+        double sx2 = 0.0, sy2 = 0.0, sx = 0.0;
+#pragma unroll
+        for (int n = 0; n < WUNET_STOI_SEG; ++n) {
+            const double x = xs[n * WUNET_STOI_BANDS], y = ys[n * WUNET_STOI_BANDS];
+            sx2 += x * x; sy2 += y * y; sx += x;
+        }
+        const double alpha = sqrt(sx2) / (sqrt(sy2) + WUNET_STOI_EPS);
+        double sy = 0.0;
+#pragma unroll
+        for (int n = 0; n < WUNET_STOI_SEG; ++n) {
+            const double x = xs[n * WUNET_STOI_BANDS], y = alpha * ys[n * WUNET_STOI_BANDS], c = x * A.clip;
+            sy += y < c ? y : c;
+        }
+        const double mx = sx / WUNET_STOI_SEG, my = sy / WUNET_STOI_SEG;
+        double cxx = 0.0, cyy = 0.0, cxy = 0.0;
+#pragma unroll
+        for (int n = 0; n < WUNET_STOI_SEG; ++n) {
+            const double x = xs[n * WUNET_STOI_BANDS], y = alpha * ys[n * WUNET_STOI_BANDS], c = x * A.clip;
+            const double xc = x - mx, yc = (y < c ? y : c) - my;
+            cxx += xc * xc; cyy += yc * yc; cxy += xc * yc;
+        }
+        dsum += cxy / ((sqrt(cxx) + WUNET_STOI_EPS) * (sqrt(cyy) + WUNET_STOI_EPS));
+    }
+    block_sum2(dsum, dummy, red);
+    if (tid == 0) A.part[row * A.nblk + blockIdx.x] = dsum;
+}
+
+// grid (rows).  nk == nullptr: rows too short for one frame.  Thread t adds partials t, t + 256, .. in that order.
+static __global__ __launch_bounds__(WUNET_THREADS) void stoi_final_kernel(const double* part, const int* nk, unsigned nblk, float* out, int* frames)
+{
+    __shared__ double red[2 * WUNET_WAVES];
+    const int tid = threadIdx.x;
+    const size_t row = blockIdx.x;
+    const int n_kept = nk ? nk[row] : 0, nseg = stoi_segments(n_kept);
+    const int nb = (nseg + WUNET_STOI_SB - 1) / WUNET_STOI_SB;
+    double s = 0.0, dummy = 0.0;
+    for (int b = tid; b < nb; b += WUNET_THREADS) s += part[row * nblk + b];
+    block_sum2(s, dummy, red);
+    if (tid == 0) {
+        out[row] = nseg > 0 ? (float)(s / ((double)nseg * WUNET_STOI_BANDS)) : 1.0e-5f;
+        if (frames) frames[row] = n_kept > 0 ? n_kept - 1 : 0;
+    }
+}

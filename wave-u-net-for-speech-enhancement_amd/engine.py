@@ -104,6 +104,7 @@ class Engine:
         # (FusedAdam.advance_host_step) - part of the eval cache's signature, so an eval forward after N replays re-packs.
         self.weights_generation = 0
         self._stft_bases = {}                         # (n_fft, win_length, device) -> windowed DFT basis (stft_basis)
+        self._stoi_tables_cache = {}                  # (sample rate, device) -> basis | window | resampler taps (stoi_tables)
         # per-step calls marshalled in C++ when the extension is built and this engine drives the HIP library it is linked to
         self._fast = _load_torch_ext() if (lib is None and not host_memory) else None
 
@@ -530,6 +531,87 @@ Engine._stft_pair = _stft_pair
 Engine.stft_loss_forward = _stft_loss_forward
 Engine.stft_loss_backward = _stft_loss_backward
 Engine.stft_magnitude = _stft_magnitude
+
+
+# ---------------------------------------------------------------------- STOI per row (include/wunet_hip.h: wunet_stoi_*)
+STOI_FS = 10000
+_STOI_TAPS = {}                      # sample rate -> (p, q, float32 taps of pystoi's resampler) or None at 10 kHz
+
+
+def stoi_resampler_taps(sample_rate):
+    """pystoi's resampling filter for `sample_rate` -> 10 kHz: (p, q, h) with 10000 / sample_rate = p / q in lowest terms and
+    h[t + L] = kaiser(2 L + 1, 0.1102 (60 - 8.7))[t + L] 2 p fc sinc(2 fc t), fc = 1 / (2 max(p, q)), L = ceil(52 / (28.714 fc / 10)),
+    normalised to sum 1 - computed in float64 with numpy, rounded once to float32, cached per rate.  None at 10 kHz."""
+    fs = int(sample_rate)
+    if fs not in _STOI_TAPS:
+        import math
+        import numpy as np
+        if fs <= 0:
+            raise ValueError(f"stoi: the sample rate must be > 0 (got {sample_rate})")
+        if fs == STOI_FS:
+            _STOI_TAPS[fs] = None
+        else:
+            g = math.gcd(STOI_FS, fs)
+            p, q = STOI_FS // g, fs // g
+            fc = 1.0 / (2.0 * max(p, q))
+            L = int(math.ceil(52.0 / (28.714 * fc / 10.0)))
+            t = np.arange(-L, L + 1, dtype=np.float64)
+            h = np.kaiser(2 * L + 1, 0.1102 * (60.0 - 8.7)) * (2.0 * p * fc * np.sinc(2.0 * fc * t))
+            _STOI_TAPS[fs] = (p, q, (h / h.sum()).astype(np.float32))
+    return _STOI_TAPS[fs]
+
+
+def _stoi_tables(self, sample_rate, device):
+    """The tables of one (sample rate, device) - DFT basis, window, resampler taps - built once: on the first (eager) call, so that a
+    later graph capture sees neither their allocation nor their launch."""
+    key = (int(sample_rate), str(device))
+    tables = self._stoi_tables_cache.get(key)
+    if tables is None:
+        taps = stoi_resampler_taps(sample_rate)
+        nbytes = self.lib.wunet_stoi_tables_bytes(key[0])
+        if nbytes == 0:
+            raise WunetError(f"wunet error -1: {self.lib.wunet_last_error().decode()}")
+        tables = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+        h = torch.from_numpy(taps[2]).to(device) if taps is not None else None
+        with self._device_guard(device):
+            self._check(self.lib.wunet_stoi_tables_build(key[0], h.data_ptr() if h is not None else None, h.numel() if h is not None else 0,
+                                                         tables.data_ptr(), self._stream(device)))
+            if h is not None and not self.host_memory:
+                h.record_stream(torch.cuda.current_stream(device))       # (the copy kernel may still be reading it when h is freed)
+        self._stoi_tables_cache[key] = tables
+    return tables
+
+
+def _stoi(self, clean, estimate, sample_rate=16000, return_frames=False):
+    """include/wunet_hip.h: wunet_stoi_forward.  The last dimension is the utterance, all leading ones are flattened.  Returns float32
+    [rows] (and int32 [rows], the spectral frame count of every row, with return_frames).  Nothing is read back to the host."""
+    self._require(clean, "clean")
+    self._require(estimate, "estimate")
+    if clean.dtype != torch.float32 or estimate.dtype != torch.float32:
+        raise WunetError("stoi: expected float32 waveforms")
+    if clean.shape != estimate.shape or clean.device != estimate.device:
+        raise WunetError(f"stoi: shape / device mismatch {tuple(clean.shape)} vs {tuple(estimate.shape)}")
+    if estimate.dim() < 1 or estimate.numel() == 0:
+        raise WunetError(f"stoi: needs at least one row of at least one sample, got {tuple(estimate.shape)}")
+    fs = int(sample_rate)
+    T = estimate.shape[-1]
+    R = estimate.numel() // T
+    dev = estimate.device
+    tables = self.stoi_tables(fs, dev)
+    nbytes = self.lib.wunet_stoi_scratch_bytes(R, T, fs)
+    if nbytes == 0:
+        raise WunetError(f"wunet error -1: {self.lib.wunet_last_error().decode()}")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(R, dtype=torch.float32, device=dev)
+    frames = torch.empty(R, dtype=torch.int32, device=dev) if return_frames else None
+    with self._device_guard(dev):
+        self._check(self.lib.wunet_stoi_forward(clean.data_ptr(), estimate.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
+                                                out.data_ptr(), frames.data_ptr() if frames is not None else None, self._stream(dev)))
+    return (out, frames) if return_frames else out
+
+
+Engine.stoi_tables = _stoi_tables
+Engine.stoi = _stoi
 
 
 def _adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, hyper_dev=None, *,

@@ -1,7 +1,8 @@
-"""Scores computed on the device (no reference counterpart: the reference's validation epoch scores STOI / PESQ on the host,
-trainer/trainer.py:58-108, which stay out of scope - SURVEY.md §2).  Each call is the forward of the row losses
-(include/wunet_hip.h: wunet_loss_rows_forward) with its per-row output: one pass over the pair, sums in double, no backward.
-The last dimension is the utterance; all leading dimensions are flattened to rows.  Returns float32 [rows] in dB on the inputs' device.
+"""Scores computed on the device.  The reference's validation epoch scores STOI and PESQ on the host, per recording
+(trainer/trainer.py:58-143): `stoi` below is that STOI (pystoi, extended=False) as HIP kernels; PESQ (ITU-T P.862, a long procedural
+model) stays a host metric and out of scope - SURVEY.md §2.  `si_sdr` / `snr` are the forward of the row losses (include/wunet_hip.h:
+wunet_loss_rows_forward) with its per-row output: one pass over the pair, sums in double, no backward; float32 [rows] in dB.
+The last dimension is the utterance; all leading dimensions are flattened to rows.  Results live on the inputs' device.
 """
 import torch
 
@@ -39,3 +40,15 @@ def stft_magnitude(x, n_fft=320, hop=160, win_length=320, engine=None):
     Returns float32 [rows, 1 + T // hop, n_fft // 2 + 1]."""
     engine = engine if engine is not None else default_engine()
     return engine.stft_magnitude(x.detach().contiguous(), n_fft, hop, win_length)
+
+
+@torch.no_grad()
+def stoi(clean, estimate, sample_rate=16000, return_frames=False, engine=None):
+    """Short-time objective intelligibility of `estimate` against `clean`, per row: Taal et al. 2011 as pystoi computes it for
+    stoi(clean, estimate, sample_rate, extended=False) - what the reference's validation epoch calls on the host at 16 kHz
+    (util/utils.py:116-117) - on the device (include/wunet_hip.h: wunet_stoi_forward), without a host read: a row with fewer than 30
+    spectral frames after the removal of its silent frames scores 1e-5 (pystoi's value; its warning is not reproduced).
+    Returns float32 [rows]; with return_frames also int32 [rows], the spectral frame count of every row.  The tables of a
+    (device, sample_rate) are built on the first call; later calls allocate from torch's caching allocator only and can be captured."""
+    engine = engine if engine is not None else default_engine()
+    return engine.stoi(clean.detach().contiguous(), estimate.detach().contiguous(), sample_rate, return_frames)

@@ -4,8 +4,8 @@
 
 Same constructor as the reference's Trainer (/root/reference/trainer/trainer.py:13-25, called from train.py:41-49)
 and the same `.train()` entry (train.py:51), covering the hot loop (trainer/trainer.py:27-43, base_trainer.py:187-197) and, opt-in,
-a validation epoch scored on the device (below); TensorBoard and the host metrics STOI / PESQ are out of scope (SURVEY.md §2 rows 6,
-10, 11).
+a validation epoch scored on the device (below: SI-SDR improvement and, opt-in, STOI); TensorBoard and the host metric PESQ are out of
+scope.
 Differences from the reference loop, all on the f2 list:
   * one process per GPU: launched under torchrun (RANK / WORLD_SIZE / LOCAL_RANK in the environment) the constructor joins the
     process group itself (backend "nccl" = RCCL on a GPU box, "gloo" without one), pins the process to its GPU, re-wraps the
@@ -28,6 +28,11 @@ Differences from the reference loop, all on the f2 list:
     to `validation_scores`, compared with `best_score` as base_trainer.py:149-157 does, and a best one writes best_model.tar
     (base_trainer.py:118-120).  Every module's training flag (a frozen BatchNorm layer included) is restored afterwards, so a captured
     step graph stays valid.  Without the "metric" key the loader stays unused, as in earlier versions of this trainer;
+  * STOI, the first half of the reference's score (STOI + PESQ') / 2 (trainer/trainer.py:128-143), on the device: beside "metric":
+    "si_sdr" the optional key `"stoi": "report"` also appends (mean STOI of the noisy recordings, mean STOI of the enhanced ones) to
+    `validation_stoi` every validation epoch and leaves the score alone; `"stoi": "score"` makes the mean STOI of the enhanced
+    recordings the epoch's score (`validation_scores` holds it, "find_max" applies as in the reference).  metrics.stoi at
+    `"custom": {"sample_rate": 16000}` (the reference hard-codes 16 kHz); still one device->host read per validation epoch;
   * checkpoints keep the reference's names and keys (base_trainer.py:83-124) so either side can resume; only rank 0 writes.
 """
 import os
@@ -94,12 +99,19 @@ class Trainer:
         vcfg = tcfg.get("validation") or {}
         self.validation_metric = vcfg.get("metric")
         if self.validation_metric not in (None, "si_sdr"):
-            raise ValueError(f'trainer config "validation.metric" must be "si_sdr" (got {self.validation_metric!r}); STOI / PESQ are host '
-                             "metrics and out of scope")
+            raise ValueError(f'trainer config "validation.metric" must be "si_sdr" (got {self.validation_metric!r}); STOI is the key '
+                             '"validation.stoi" beside it, PESQ is a host metric and out of scope')
         self.validation_interval = int(vcfg.get("interval", 0)) if self.validation_metric and validation_dataloader is not None else 0
         self.validation_find_max = bool(vcfg.get("find_max", True))
         self.validation_sample_length = int((vcfg.get("custom") or {}).get("sample_length", 16384))
-        self.validation_scores = []   # one mean SI-SDR improvement [dB] per validation epoch
+        self.validation_scores = []   # one mean SI-SDR improvement [dB] per validation epoch (the mean enhanced STOI with "stoi": "score")
+        self.validation_stoi_mode = vcfg.get("stoi")
+        if self.validation_stoi_mode not in (None, "report", "score"):
+            raise ValueError(f'trainer config "validation.stoi" must be "report" or "score" (got {self.validation_stoi_mode!r})')
+        if self.validation_stoi_mode is not None and self.validation_metric != "si_sdr":
+            raise ValueError('trainer config "validation.stoi" needs "validation.metric": "si_sdr" beside it')
+        self.validation_sample_rate = int((vcfg.get("custom") or {}).get("sample_rate", 16000))
+        self.validation_stoi = []     # with "validation.stoi": (mean STOI noisy, mean STOI enhanced) per validation epoch
         self.epochs = tcfg["epochs"]
         self.save_checkpoint_interval = tcfg.get("save_checkpoint_interval", 0)
         # default ON where it can be used (one GPU, or the native RCCL entry; fused Adam): the replay is as fast as the eager
@@ -193,7 +205,8 @@ class Trainer:
         engine = getattr(model, "_engine_override", None)
         modes = [(m, m.training) for m in self.model.modules()]
         self.model.eval()
-        gains = []
+        gains, stois = [], []
+        fs = self.validation_sample_rate
         try:
             for mixture, clean, _name in self.validation_data_loader:
                 if mixture.dim() != 3 or mixture.shape[0] != 1:
@@ -202,12 +215,23 @@ class Trainer:
                 clean = clean.to(self.device, non_blocking=True)
                 enhanced = enhance(model, mixture, self.validation_sample_length)
                 gains.append(metrics.si_sdr_improvement(clean, mixture, enhanced, engine=engine))
+                if self.validation_stoi_mode is not None:
+                    stois.append(torch.cat([metrics.stoi(clean, mixture, sample_rate=fs, engine=engine).reshape(-1),
+                                            metrics.stoi(clean, enhanced, sample_rate=fs, engine=engine).reshape(-1)]))
         finally:
             for m, was in modes:                         # exactly the flags of before: a frozen BatchNorm layer stays frozen
                 m.training = was
         if not gains:
             raise ValueError("validation: the validation loader yielded no recording")
-        score = torch.cat(gains).double().mean().item()  # the only device->host read of the validation epoch
+        means = [torch.cat(gains).double().mean()]
+        if stois:                                        # [recordings, 2]: noisy, enhanced
+            means.extend(torch.stack(stois).double().mean(dim=0))
+        means = torch.stack(means).tolist()              # the only device->host read of the validation epoch
+        score = means[0]
+        if stois:
+            self.validation_stoi.append((means[1], means[2]))
+            if self.validation_stoi_mode == "score":
+                score = means[2]
         self.validation_scores.append(score)
         return score
 
