@@ -293,6 +293,31 @@ void wunet_comm_destroy(wunet_comm* comm);
 int wunet_crop_windows(const float* mixture_flat, const float* clean_flat, const long long* starts, long long total,
                        int batch, int length, float* mixture, float* clean, void* stream);
 
+/* Mixtures made on the device (no reference counterpart: the reference trains on pairs mixed when the corpus was written).  Row b of
+ * the batch is a clean window and a noise window gathered from two flat float32 arrays resident in HBM and mixed at a drawn SNR:
+ *   c[j] = clean_flat[cs + j], j < length; cs clamped into [0, clean_total - length] as in wunet_crop_windows.
+ *   n[j] = noise_flat[ns + (ph + j) mod nl]: the noise item [ns, ns + nl) read circularly from phase ph, so an item shorter than the
+ *     window wraps as often as needed.  The item range is cut to its part inside [0, noise_total) and ph is reduced modulo the
+ *     length that is left; fewer than 1 sample left (nl = 0 is how a caller asks for a clean row): no noise, g = 0.
+ *   Pc = sum c^2, Pn = sum n^2 over the window (raw sums, no mean removal), in double and in one fixed order.
+ *   g = sqrt(Pc / (Pn 10^(snr_db / 10))) in double; g = 0 when Pc or Pn is below length * 1e-12 (RMS 1e-6): a silent clean or noise
+ *     window passes the clean window through, never Inf or NaN.
+ *   a = level; with peak_limit > 0: bound = a (max|c| + g max|n|) and a <- a peak_limit / bound when bound > peak_limit (the bound is
+ *     conservative - max|c + g n| <= max|c| + g max|n| - and costs no pass over the mixed row).
+ *   mixture[b][j] = a (c[j] + g n[j]), clean_out[b][j] = a c[j], gains[b] = (g, a) (gains may be NULL), with g and a rounded to
+ *     float32 once before use; a row with g = 0 gets mixture == clean_out bit for bit.
+ * rows: device int64 [batch][4] = clean start, noise item start, noise item length, noise phase.  params: device float32 [batch][2] =
+ * snr_db, level (linear).  scratch: >= wunet_mix_scratch_bytes(batch, length) device bytes, 8-byte aligned, no memset needed.
+ * mixture / clean_out receive [batch][1][length] float32 (16-byte aligned when length % 4 == 0).  batch <= 65535, length <= 2^30.
+ * Two launches; everything a launch depends on is read from device memory, so a captured call follows the tables it was captured on.
+ * No atomics: bit-identical run to run.  Caller-owned memory, no allocation, no synchronisation. */
+size_t wunet_mix_scratch_bytes(int batch, int length);
+int wunet_mix_windows(const float* clean_flat, long long clean_total, const float* noise_flat, long long noise_total,
+                      const long long* rows,   /* [batch][4]: clean start, noise item start, noise item length, noise phase */
+                      const float* params,     /* [batch][2]: snr_db, level (linear) */
+                      float peak_limit, int batch, int length, void* scratch,
+                      float* mixture, float* clean_out, float* gains /* [batch][2] or NULL */, void* stream);
+
 /* Measurement aid (tools/conv_trace.py; no reference counterpart): a device buffer of gridDim.x * 64 uint64 that the DMA-staged
  * conv / data-gradient kernel (conv_h3d_kernel) fills with shader-clock stamps of each block's phases (entry; per K stage: tile
  * landed, W buffer released, MFMAs issued; epilogue done), or NULL (default) to turn the stamps off.  Process-wide. */

@@ -6,6 +6,7 @@
 #include "wunet_loss_rows.h"
 #include "wunet_stft.h"
 #include "wunet_stoi.h"
+#include "wunet_mix.h"
 
 using namespace wunet_host;
 
@@ -509,6 +510,67 @@ int wunet_crop_windows(const float* mixture_flat, const float* clean_flat, const
     const unsigned bx = (unsigned)((length + 4 * WUNET_THREADS - 1) / (4 * WUNET_THREADS));
     WUNET_LAUNCH(crop_windows_kernel, dim3(bx, (unsigned)batch), dim3(WUNET_THREADS), 0, st, mixture_flat, clean_flat, starts, total, length,
                  mixture, clean);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- data input: mixtures made on the device (wunet_mix.h)
+// Pieces per row for (batch, length): about WUNET_MIX_BLOCKS blocks in all and never less than WUNET_MIX_MIN_PIECE samples per block
+// (one trip of 4 samples per thread); plen is a multiple of 4 and ppr is recomputed from it, so no piece is empty.
+#define WUNET_MIX_BLOCKS 1024
+#define WUNET_MIX_MIN_PIECE 1024
+static void mix_plan(int batch, int length, unsigned& ppr, int& plen)
+{
+    long long want = (WUNET_MIX_BLOCKS + (long long)batch - 1) / batch;
+    const long long most = ((long long)length + WUNET_MIX_MIN_PIECE - 1) / WUNET_MIX_MIN_PIECE;
+    if (want > most) want = most;
+    if (want < 1) want = 1;
+    plen = (int)(((((long long)length + want - 1) / want) + 3) & ~3LL);
+    ppr = (unsigned)(((long long)length + plen - 1) / plen);
+}
+
+static int mix_shape_check(int batch, int length)
+{
+    if (batch < 1 || length < 1) return fail(WUNET_E_ARG, "mix: batch and length must be >= 1 (got %d x %d)", batch, length);
+    if (batch > 65535 || length > (1 << 30)) return fail(WUNET_E_ARG, "mix: at most 65535 rows of 2^30 samples per call (got %d x %d)", batch, length);
+    return 0;
+}
+
+size_t wunet_mix_scratch_bytes(int batch, int length)
+{
+    if (batch < 1 || length < 1 || batch > 65535 || length > (1 << 30)) return 0;
+    unsigned ppr;
+    int plen;
+    mix_plan(batch, length, ppr, plen);
+    return (size_t)batch * ppr * WUNET_MIX_PART * sizeof(double);
+}
+
+int wunet_mix_windows(const float* clean_flat, long long clean_total, const float* noise_flat, long long noise_total, const long long* rows,
+                      const float* params, float peak_limit, int batch, int length, void* scratch, float* mixture, float* clean_out,
+                      float* gains, void* stream)
+{
+    if (mix_shape_check(batch, length)) return WUNET_E_ARG;
+    if (clean_total < length) return fail(WUNET_E_ARG, "mix: the clean array is shorter than one window (clean_total=%lld length=%d)", clean_total, length);
+    if (noise_total < 1) return fail(WUNET_E_ARG, "mix: the noise array is empty (noise_total=%lld)", noise_total);
+    if (clean_total >= (1LL << 60) || noise_total >= (1LL << 60)) return fail(WUNET_E_ARG, "mix: array too large");
+    if (!clean_flat || !noise_flat || !rows || !params || !scratch || !mixture || !clean_out) return fail(WUNET_E_ARG, "mix: null argument");
+    if (!(peak_limit == peak_limit)) return fail(WUNET_E_ARG, "mix: peak_limit is NaN");
+    if (((size_t)scratch & 7) || ((length & 3) == 0 && (((size_t)mixture | (size_t)clean_out) & 15)))
+        return fail(WUNET_E_ARG, "mix: scratch needs 8-byte alignment, the outputs 16-byte alignment when length %% 4 == 0");
+    hipStream_t st = (hipStream_t)stream;
+    MixArgs A{};
+    A.clean_flat = clean_flat; A.noise_flat = noise_flat; A.clean_total = clean_total; A.noise_total = noise_total; A.rows = rows;
+    A.params = params; A.peak_limit = peak_limit; A.length = length; A.part = (double*)scratch; A.mixture = mixture; A.clean_out = clean_out;
+    A.gains = gains;
+    mix_plan(batch, length, A.ppr, A.plen);
+    const double n = (double)batch * length;
+    prof_begin(st, "mix_partial_kernel", 4.0 * n, 4.0 * 2.0 * n);
+    WUNET_LAUNCH(mix_partial_kernel, dim3((unsigned)batch * A.ppr), dim3(WUNET_THREADS), 0, st, A);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    prof_begin(st, "mix_apply_kernel", 3.0 * n, 4.0 * 4.0 * n);
+    WUNET_LAUNCH(mix_apply_kernel, dim3(A.ppr, (unsigned)batch), dim3(WUNET_THREADS), 0, st, A);
+    prof_end(st);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
 }

@@ -692,6 +692,40 @@ def _crop_windows(self, mixture_flat, clean_flat, starts, mixture, clean):
 Engine.crop_windows = _crop_windows
 
 
+def _mix_windows(self, clean_flat, noise_flat, rows, params, mixture, clean_out, gains=None, peak_limit=0.99):
+    """include/wunet_hip.h: wunet_mix_windows.  mixture[b, 0, :] = a (c + g n), clean_out[b, 0, :] = a c for the clean window and the
+    circular noise window that rows[b] = (clean start, noise item start, noise item length, noise phase) names, at params[b] =
+    (snr_db, linear level); gains (optional float32 [B, 2]) receives (g, a).  Two launches, nothing read back; the scratch comes from
+    torch's allocator."""
+    f32 = torch.float32
+    if rows.dtype != torch.int64 or any(t.dtype != f32 for t in (clean_flat, noise_flat, params, mixture, clean_out)) or \
+            (gains is not None and gains.dtype != f32):
+        raise WunetError("mix_windows: float32 arrays, params, outputs and gains and int64 rows expected")
+    for t in (clean_flat, noise_flat, rows, params, mixture, clean_out) + ((gains,) if gains is not None else ()):
+        self._require(t, "mix tensor")
+    if clean_flat.dim() != 1 or noise_flat.dim() != 1 or mixture.dim() < 2:
+        raise WunetError("mix_windows: the two arrays must be flat and the outputs [B, ..., L]")
+    B, L = mixture.shape[0], mixture.shape[-1]
+    if mixture.shape != clean_out.shape or mixture.numel() != B * L or tuple(rows.shape) != (B, 4) or tuple(params.shape) != (B, 2) or \
+            (gains is not None and tuple(gains.shape) != (B, 2)):
+        raise WunetError("mix_windows: shape mismatch (rows [B, 4], params [B, 2], gains [B, 2], outputs [B, 1, L])")
+    dev = mixture.device
+    if any(t.device != dev for t in (clean_flat, noise_flat, rows, params, clean_out)) or (gains is not None and gains.device != dev):
+        raise WunetError("mix_windows: every tensor must live on the outputs' device")
+    nbytes = self.lib.wunet_mix_scratch_bytes(B, L)
+    if nbytes == 0:
+        raise WunetError(f"mix_windows: bad shape (batch={B} length={L})")
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    with self._device_guard(dev):
+        self._check(self.lib.wunet_mix_windows(clean_flat.data_ptr(), clean_flat.numel(), noise_flat.data_ptr(), noise_flat.numel(),
+                                               rows.data_ptr(), params.data_ptr(), float(peak_limit), B, L, scratch.data_ptr(),
+                                               mixture.data_ptr(), clean_out.data_ptr(), gains.data_ptr() if gains is not None else None,
+                                               self._stream(dev)))
+
+
+Engine.mix_windows = _mix_windows
+
+
 class _CtxHold:
     """`with engine._using(shape...) as handle`: the context cannot be evicted while the block runs."""
 

@@ -18,6 +18,10 @@ Two pieces, both float32 mono like the reference's items:
   once (a 100-hour 16 kHz corpus is 46 GB of the 288 GB) and every batch is one gather on the GPU: random item, random
   aligned start, `[B,1,sample_length]` mixture and clean, no host work and no H2D copy per step.  Iterating it yields
   the DataLoader batch contract `(mixture, clean, names)` the reference trainer loop consumes (trainer/trainer.py:30).
+
+* `pack_mono_shard` + `MixLoader` - mixtures made on the device: a clean corpus and a noise corpus, each one flat float32 shard in
+  HBM, combined per row at a freshly drawn SNR and level every step (include/wunet_hip.h: wunet_mix_windows - two launches per
+  batch).  The host draws integers and a few floats per batch; the same batch contract comes out.
 """
 import json
 import os
@@ -226,4 +230,126 @@ class ShardLoader:
         for _ in range(self.steps):
             pick, first = self.draw()
             mixture, clean = self.crop(first)
+            yield mixture, clean, [self.names[i] for i in pick.tolist()]
+
+
+# ---------------------------------------------------------------------------------------------- mixtures made on the device
+def pack_mono_shard(list_file, prefix, limit=None, offset=0):
+    """Decode every file of the list (one path per line; `offset` lines skipped, then at most `limit` kept) once into `<prefix>.f32`
+    (flat float32) and `<prefix>.index.json` (pack_shard's keys: {"names", "starts", "lengths", "sample_rate"}; an item's name is its
+    file's stem).  The clean corpus and the noise corpus of a MixLoader are each one such shard.  Returns the number of items."""
+    with open(os.path.abspath(os.path.expanduser(list_file)), "r") as f:
+        paths = [ln.strip() for ln in f][offset:]
+    paths = [p for p in (paths[:limit] if limit else paths) if p]
+    names, starts, lengths, rate, pos = [], [], [], None, 0
+    with open(prefix + ".f32", "wb") as out:
+        for path in paths:
+            x, r = read_wav(path)
+            assert rate is None or rate == r, f"mixed sample rates: {path}"
+            rate = r
+            out.write(x.tobytes())
+            names.append(os.path.splitext(os.path.basename(path))[0])
+            starts.append(pos)
+            lengths.append(len(x))
+            pos += len(x)
+    with open(prefix + ".index.json", "w") as f:
+        json.dump({"names": names, "starts": starts, "lengths": lengths, "sample_rate": rate}, f)
+    return len(names)
+
+
+class MixLoader:
+    """Batches of noisy mixtures made on the device from a clean shard and a noise shard that live in device memory.
+
+    for mixture, clean, names in MixLoader(clean_prefix, noise_prefix, batch_size=64, device="cuda:0"): ...   # [B,1,L] float32 each
+    Per row: a random window of a random clean item (ShardLoader's draw), a random noise item read circularly from a random phase (so
+    noise items of any length >= 1 are usable), an SNR uniform in dB over `snr_db` and a level uniform in dB over `level_db` (0 dB
+    when None).  The SNR is defined over the window on raw sums (no mean removal): 10 log10(sum c^2 / sum (g n)^2).  A window whose
+    clean or noise RMS is below 1e-6 comes out unmixed (g = 0); with probability `p_clean` a row is passed clean on purpose.  With
+    peak_limit > 0 a row whose bound a (max|c| + g max|n|) exceeds it is scaled down as a whole - mixture and clean alike, the SNR
+    stays.  `clean_prefix` is a mono shard (pack_mono_shard) or a pair shard (pack_shard: its `.clean.f32` is used).  `last_draw`
+    keeps the host tables and the device gains of the last batch: {"rows": int64 [B,4], "params": float32 [B,2], "gains": [B,2]}.
+    There is no host implementation of the mix: device="cpu" needs an engine (the tests inject the emulator's).  Every rank of a
+    data-parallel job passes its own `seed` (e.g. seed + rank)."""
+
+    def __init__(self, clean_prefix, noise_prefix, batch_size, sample_length=16384, snr_db=(0.0, 20.0), level_db=None, peak_limit=0.99,
+                 p_clean=0.0, device="cpu", seed=0, steps_per_epoch=None, engine=None):
+        self.device = torch.device(device)
+        if self.device.type != "cuda" and engine is None:
+            raise ValueError("MixLoader mixes on the device: device='cpu' needs an engine (there is no host implementation of the mix)")
+        cidx = json.load(open(clean_prefix + ".index.json"))
+        nidx = json.load(open(noise_prefix + ".index.json"))
+        if cidx["sample_rate"] != nidx["sample_rate"]:
+            raise ValueError(f"clean and noise sample rates differ: {cidx['sample_rate']} vs {nidx['sample_rate']}")
+        self.sample_rate = cidx["sample_rate"]
+        self.names = cidx["names"]
+        starts, lengths = np.asarray(cidx["starts"], np.int64), np.asarray(cidx["lengths"], np.int64)
+        usable = np.nonzero(lengths >= sample_length)[0]
+        if len(usable) == 0:
+            raise ValueError("no clean item is at least sample_length long")
+        nstarts, nlengths = np.asarray(nidx["starts"], np.int64), np.asarray(nidx["lengths"], np.int64)
+        nusable = np.nonzero(nlengths >= 1)[0]
+        if len(nusable) == 0:
+            raise ValueError("the noise shard has no item of at least one sample")
+        clean_file = clean_prefix + ".f32" if os.path.exists(clean_prefix + ".f32") else clean_prefix + ".clean.f32"
+        self.clean = self._resident(clean_file, int(starts[-1] + lengths[-1]))          # one upload each; they stay resident
+        self.noise = self._resident(noise_prefix + ".f32", int(nstarts[-1] + nlengths[-1]))
+        self.usable, self.starts = torch.from_numpy(usable), torch.from_numpy(starts)
+        self.spare = torch.from_numpy(lengths - sample_length + 1)                      # number of valid window starts per item
+        self.noise_usable, self.noise_starts, self.noise_lengths = torch.from_numpy(nusable), torch.from_numpy(nstarts), torch.from_numpy(nlengths)
+        self.batch_size, self.sample_length = batch_size, sample_length
+        self.snr_db = (float(snr_db[0]), float(snr_db[1]))
+        self.level_db = None if level_db is None else (float(level_db[0]), float(level_db[1]))
+        self.peak_limit, self.p_clean = float(peak_limit), float(p_clean)
+        self.steps = steps_per_epoch if steps_per_epoch is not None else max(1, len(usable) // batch_size)
+        self.gen = torch.Generator().manual_seed(seed)
+        self.engine = engine
+        self.last_draw = None
+
+    UPLOAD_CHUNK = ShardLoader.UPLOAD_CHUNK
+    _resident = ShardLoader._resident
+
+    def __len__(self):
+        return self.steps
+
+    def _uniform_int(self, count):
+        """One integer per row, uniform over [0, count[b]) (count int64 [B], >= 1) - ShardLoader.draw's rule."""
+        v = (torch.rand(self.batch_size, generator=self.gen, dtype=torch.float64) * count.double()).long()
+        return torch.minimum(v, count - 1)
+
+    def draw(self):
+        """(clean item ids, rows int64 [B,4], params float32 [B,2]) of one batch - the host's whole share of it.  rows[b] = clean
+        window start, noise item start, noise item length (0: the row is passed clean), noise phase; params[b] = snr_db, linear level."""
+        B, gen = self.batch_size, self.gen
+        pick = self.usable[torch.randint(len(self.usable), (B,), generator=gen)]
+        first = self.starts[pick] + self._uniform_int(self.spare[pick])
+        npick = self.noise_usable[torch.randint(len(self.noise_usable), (B,), generator=gen)]
+        nlen = self.noise_lengths[npick]
+        phase = self._uniform_int(nlen)
+        u = torch.rand(3, B, generator=gen, dtype=torch.float64)
+        snr = self.snr_db[0] + (self.snr_db[1] - self.snr_db[0]) * u[0]
+        level_db = torch.zeros(B, dtype=torch.float64) if self.level_db is None else self.level_db[0] + (self.level_db[1] - self.level_db[0]) * u[1]
+        nlen = torch.where(u[2] < self.p_clean, torch.zeros_like(nlen), nlen)
+        rows = torch.stack([first, self.noise_starts[npick], nlen, phase], dim=1).contiguous()
+        params = torch.stack([snr, 10.0 ** (level_db / 20.0)], dim=1).float().contiguous()
+        return pick, rows, params
+
+    def mix(self, rows, params):
+        """The batch that the two host tables describe: mixture, clean [B, 1, L] and gains [B, 2] on the device.  One non-blocking copy
+        per table, then the two launches of wunet_mix_windows (csrc/wunet_mix.h)."""
+        if self.engine is None:
+            from .engine import default_engine
+            self.engine = default_engine()
+        B, L, dev = rows.shape[0], self.sample_length, self.device
+        mixture = torch.empty(B, 1, L, dtype=torch.float32, device=dev)
+        clean = torch.empty(B, 1, L, dtype=torch.float32, device=dev)
+        gains = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        self.engine.mix_windows(self.clean, self.noise, rows.to(dev, non_blocking=True), params.to(dev, non_blocking=True), mixture, clean,
+                                gains, peak_limit=self.peak_limit)
+        return mixture, clean, gains
+
+    def __iter__(self):
+        for _ in range(self.steps):
+            pick, rows, params = self.draw()
+            mixture, clean, gains = self.mix(rows, params)
+            self.last_draw = {"rows": rows, "params": params, "gains": gains}
             yield mixture, clean, [self.names[i] for i in pick.tolist()]
