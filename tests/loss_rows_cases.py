@@ -8,7 +8,7 @@ import si_sdr_ref as R
 from conftest import PKG_NAME
 
 KINDS = ("si_sdr", "snr")
-# (rows, T) -> pieces per row / lanes per row in the finalize (csrc/wunet_ops.cpp: loss_rows_plan) / rows per trip of its row loop:
+# (rows, T) -> pieces per row / lanes per row in the finalize (csrc/wunet_ops.cpp: row_pieces) / rows per trip of its row loop:
 #   (1,1) one sample; (3,7) odd and tiny; (2,1000) one piece with a tail; (70,257) many rows of odd length - all 1 piece, 1 lane, 1 trip
 #   (5,4099)   2 pieces, 2 lanes per row: rows whose 16-byte phase differs (odd T), a 3-sample second piece
 #   (1,200003) one row over 49 pieces (64 lanes), odd tail

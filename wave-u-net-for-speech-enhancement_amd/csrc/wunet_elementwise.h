@@ -43,25 +43,44 @@ static __global__ __launch_bounds__(WUNET_THREADS) void pack_weights_kernel(Pack
 }
 
 // ---------------------------------------------------------------------------- block reduce helper
-// sums two doubles over the 256-thread block; result valid in thread 0. red = 2*WUNET_THREADS doubles of LDS (8 used).
+// sums N doubles over the 256-thread block; result valid in every thread.  red = N * WUNET_WAVES doubles of LDS.
 // Butterfly inside each wave (no barrier), the four wave sums through LDS: two barriers instead of the nine of a 256-wide LDS tree -
 // these reductions end kernels that are a few microseconds of pure latency (BatchNorm finalizes, split-K sums).  Fixed order.
-__device__ __forceinline__ void block_sum2(double& a, double& b, double* red)
+template <int N>
+__device__ __forceinline__ void block_sum(double (&a)[N], double* red)
 {
     const int tid = threadIdx.x;
 #pragma unroll
     for (int m = 32; m > 0; m >>= 1) {
-        a += wunet_shfl_xor_d(a, m);
-        b += wunet_shfl_xor_d(b, m);
+#pragma unroll
+        for (int k = 0; k < N; ++k) a[k] += wunet_shfl_xor_d(a[k], m);
     }
     __syncthreads();                           // (the previous user of red is done with it)
     if ((tid & 63) == 0) {
-        red[tid >> 6] = a;
-        red[WUNET_WAVES + (tid >> 6)] = b;
+#pragma unroll
+        for (int k = 0; k < N; ++k) red[k * WUNET_WAVES + (tid >> 6)] = a[k];
     }
     __syncthreads();
-    a = (red[0] + red[1]) + (red[2] + red[3]);
-    b = (red[WUNET_WAVES] + red[WUNET_WAVES + 1]) + (red[WUNET_WAVES + 2] + red[WUNET_WAVES + 3]);
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+        a[k] = (red[k * WUNET_WAVES] + red[k * WUNET_WAVES + 1]) + (red[k * WUNET_WAVES + 2] + red[k * WUNET_WAVES + 3]);
+}
+
+// the two sums of the network's own kernels (BatchNorm finalizes, split-K sums, the head's backward)
+__device__ __forceinline__ void block_sum2(double& a, double& b, double* red)
+{
+    double v[2] = {a, b};
+    block_sum<2>(v, red);
+    a = v[0]; b = v[1];
+}
+
+// Piece `piece` of row `row`, a row being `len` samples cut into pieces of `plen` (row_pieces in wunet_ops.cpp): samples [beg, end) of
+// the row, never empty.
+struct RowPiece { size_t row, piece, beg, end; };
+__device__ __forceinline__ RowPiece row_piece(size_t row, size_t piece, size_t plen, size_t len)
+{
+    const size_t beg = piece * plen;
+    return RowPiece{row, piece, beg, beg + plen < len ? beg + plen : len};
 }
 
 // max of two non-negative floats over the block (same LDS buffer, after a block_sum2); result valid in thread 0
@@ -1246,8 +1265,8 @@ __device__ __forceinline__ float loss_dterm(int kind, float d)   // derivative w
 
 static __global__ __launch_bounds__(WUNET_THREADS) void loss_partial_kernel(int kind, const float* clean, const float* enh, size_t n, double* part)
 {
-    __shared__ double red[2 * WUNET_THREADS];
-    double s = 0.0, dummy = 0.0;
+    __shared__ double red[WUNET_WAVES];
+    double s[1] = {0.0};
     // four trips' loads in flight (a thread's 16 trips at batch 64 x 16384 were 16 dependent memory round trips: 10.4 us for 8 MB); the terms are
     // added in the one-trip loop's order - the same bits
     const size_t stride = (size_t)gridDim.x * WUNET_THREADS;
@@ -1257,20 +1276,20 @@ static __global__ __launch_bounds__(WUNET_THREADS) void loss_partial_kernel(int 
 #pragma unroll
         for (int u = 0; u < 4; ++u) { e[u] = enh[i + u * stride]; c[u] = clean[i + u * stride]; }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) s += (double)loss_term(kind, e[u] - c[u]);
+        for (int u = 0; u < 4; ++u) s[0] += (double)loss_term(kind, e[u] - c[u]);
     }
-    for (; i < n; i += stride) s += (double)loss_term(kind, enh[i] - clean[i]);
-    block_sum2(s, dummy, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = s;
+    for (; i < n; i += stride) s[0] += (double)loss_term(kind, enh[i] - clean[i]);
+    block_sum<1>(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = s[0];
 }
 
 static __global__ __launch_bounds__(WUNET_THREADS) void loss_final_kernel(const double* part, int rows, size_t n, float* loss)
 {
-    __shared__ double red[2 * WUNET_THREADS];
-    double s = 0.0, dummy = 0.0;
-    for (int r = threadIdx.x; r < rows; r += WUNET_THREADS) s += part[r];
-    block_sum2(s, dummy, red);
-    if (threadIdx.x == 0) *loss = (float)(s / (double)n);
+    __shared__ double red[WUNET_WAVES];
+    double s[1] = {0.0};
+    for (int r = threadIdx.x; r < rows; r += WUNET_THREADS) s[0] += part[r];
+    block_sum<1>(s, red);
+    if (threadIdx.x == 0) *loss = (float)(s[0] / (double)n);
 }
 
 // grad_enh[i] = gscale[0] * dterm(enh - clean) / n
@@ -1356,12 +1375,12 @@ static __global__ void adam_hyper_kernel(long long* step, double lr, double beta
 // one-trip loop's order.
 static __global__ __launch_bounds__(WUNET_THREADS) void grad_sqnorm_partial_kernel(AdamTable T, float gscale, double* part)
 {
-    __shared__ double red[2 * WUNET_THREADS];
+    __shared__ double red[WUNET_WAVES];
     const int t = blockIdx.y;
     const float* g = T.g[t];
     const unsigned n = T.n[t];
     const double gs = (double)gscale;
-    double s = 0.0, dummy = 0.0;
+    double s[1] = {0.0};
     const size_t stride = (size_t)gridDim.x * WUNET_THREADS;
     size_t i = (size_t)blockIdx.x * WUNET_THREADS + threadIdx.x;
     for (; i + 3 * stride < n; i += 4 * stride) {
@@ -1369,15 +1388,15 @@ static __global__ __launch_bounds__(WUNET_THREADS) void grad_sqnorm_partial_kern
 #pragma unroll
         for (int u = 0; u < 4; ++u) e[u] = g[i + u * stride];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) { const double x = gs * (double)e[u]; s += x * x; }
+        for (int u = 0; u < 4; ++u) { const double x = gs * (double)e[u]; s[0] += x * x; }
     }
-    for (; i < n; i += stride) { const double x = gs * (double)g[i]; s += x * x; }
-    block_sum2(s, dummy, red);
-    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+    for (; i < n; i += stride) { const double x = gs * (double)g[i]; s[0] += x * x; }
+    block_sum<1>(s, red);
+    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
 }
 
 // adam_hyper_kernel with the optional parts, one block.  n_part > 0: the n_part partial sums of grad_sqnorm_partial_kernel are
-// added in a fixed order in double (thread k takes k, k + 256, ...; then block_sum2's tree), norm = sqrt(sum) and
+// added in a fixed order in double (thread k takes k, k + 256, ...; then block_sum's tree), norm = sqrt(sum) and
 // clip = min(1, max_norm / (norm + 1e-6)) - clip_grad_norm_'s formula, in double, rounded to float once; a non-finite norm
 // propagates as in torch (error_if_nonfinite=False): inf gives clip 0, NaN gives NaN.  lr_dev != nullptr: the learning rate is
 // read from device memory (a double: lr / bc1 then has the bits of the host path).  step_dev != nullptr: the device counter is
@@ -1386,18 +1405,18 @@ static __global__ __launch_bounds__(WUNET_THREADS) void adam_hyper_ex_kernel(lon
                                                                        double beta1, double beta2, double weight_decay, double max_norm,
                                                                        const double* part, int n_part, float* hyper)
 {
-    __shared__ double red[2 * WUNET_THREADS];
-    double s = 0.0, dummy = 0.0;
+    __shared__ double red[WUNET_WAVES];
+    double s[1] = {0.0};
     int r = threadIdx.x;
     for (; r + 3 * WUNET_THREADS < n_part; r += 4 * WUNET_THREADS) {
         double e[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) e[u] = part[r + u * WUNET_THREADS];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) s += e[u];
+        for (int u = 0; u < 4; ++u) s[0] += e[u];
     }
-    for (; r < n_part; r += WUNET_THREADS) s += part[r];
-    block_sum2(s, dummy, red);
+    for (; r < n_part; r += WUNET_THREADS) s[0] += part[r];
+    block_sum<1>(s, red);
     if (threadIdx.x != 0) return;
     long long t = step;
     if (step_dev) {
@@ -1408,7 +1427,7 @@ static __global__ __launch_bounds__(WUNET_THREADS) void adam_hyper_ex_kernel(lon
     const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
     double norm = 0.0, clip = 1.0;
     if (n_part > 0) {
-        norm = sqrt(s);
+        norm = sqrt(s[0]);
         const double c = max_norm / (norm + 1e-6);
         clip = c > 1.0 ? 1.0 : c;                   // (a NaN stays: torch.clamp(max=1) keeps it too)
     }

@@ -13,27 +13,6 @@
 #define WUNET_ROWS_KIND_SNR 4        // == WUNET_LOSS_SNR
 #define WUNET_ROWS_COEFS 6           // == WUNET_LOSS_ROW_COEFS: A, C, D, v, mean of x, mean of s (0 without zero_mean)
 
-// five doubles over the 256-thread block, block_sum2's idiom (butterfly inside each wave, the four wave sums through LDS in wave
-// order, one barrier pair); result valid in every thread.  red: WUNET_ROWS_SUMS * WUNET_WAVES doubles.
-__device__ __forceinline__ void block_sum5(double (&a)[WUNET_ROWS_SUMS], double* red)
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-#pragma unroll
-        for (int k = 0; k < WUNET_ROWS_SUMS; ++k) a[k] += wunet_shfl_xor_d(a[k], m);
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < WUNET_ROWS_SUMS; ++k) red[k * WUNET_WAVES + (tid >> 6)] = a[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < WUNET_ROWS_SUMS; ++k)
-        a[k] = (red[k * WUNET_WAVES] + red[k * WUNET_WAVES + 1]) + (red[k * WUNET_WAVES + 2] + red[k * WUNET_WAVES + 3]);
-}
-
 // one sample pair into the five sums.  (double)s * (double)s is exact (24 x 24 bits), so contracting it into an fma changes nothing.
 __device__ __forceinline__ void loss_rows_acc(bool snr, float sf, float ef, double (&a)[WUNET_ROWS_SUMS])
 {
@@ -55,63 +34,73 @@ __device__ __forceinline__ int loss_rows_head(const void* p0, const void* p1, co
     return (int)((16 - m0) >> 2) & 3;
 }
 
-// grid = rows * ppr blocks (block = row * ppr + piece); piece p of a row is samples [p * plen, min(T, (p + 1) * plen)), plen a multiple
-// of 4 chosen by the host from (rows, T): no block is empty.  part[block][WUNET_ROWS_SUMS].
-static __global__ __launch_bounds__(WUNET_THREADS) void loss_rows_partial_kernel(int kind, const float* clean, const float* enh, size_t T,
-                                                                           unsigned ppr, size_t plen, double* part)
+// One piece of one row: n samples at s and e (and g, the output of the backward, or nullptr).  Pointers that agree modulo 16 take the
+// 16-byte way: op.four(i, s[i .. i + 3], e[i .. i + 3]) on every aligned group of four, the eight loads of four trips issued before the
+// first is used (loss_partial_kernel's comment: one trip at a time is one dependent memory round trip per trip), op.one(i, s[i], e[i])
+// on the at most three samples before and after them.  Otherwise - a base that is only 4-byte aligned, or rows of odd length whose
+// pointers fall apart - op.one on every sample, four trips in flight.  A thread meets its samples in one fixed order: the head
+// element, the tail element, then its trips in trip order.
+template <class Op>
+__device__ __forceinline__ void loss_rows_walk(const float* s, const float* e, const void* g, size_t n, Op& op)
 {
-    __shared__ double red[WUNET_ROWS_SUMS * WUNET_WAVES];
-    const bool snr = kind == WUNET_ROWS_KIND_SNR;
-    const size_t row = blockIdx.x / ppr, piece = blockIdx.x % ppr;
-    const size_t beg = piece * plen, end = beg + plen < T ? beg + plen : T;
-    const float* s = clean + row * T + beg;
-    const float* e = enh + row * T + beg;
-    const size_t n = end - beg;
     const int tid = threadIdx.x;
-    double a[WUNET_ROWS_SUMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
-    const int head = loss_rows_head(s, e, nullptr);
+    const int head = loss_rows_head(s, e, g);
     if (head < 0) {
-        // a base that is only 4-byte aligned (or rows of odd length whose two pointers fall apart): scalar loads, four trips in flight
         size_t i = tid;
         for (; i + 3 * WUNET_THREADS < n; i += 4 * WUNET_THREADS) {
             float sv[4], ev[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) { sv[u] = s[i + u * WUNET_THREADS]; ev[u] = e[i + u * WUNET_THREADS]; }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) loss_rows_acc(snr, sv[u], ev[u], a);
+            for (int u = 0; u < 4; ++u) op.one(i + u * WUNET_THREADS, sv[u], ev[u]);
         }
-        for (; i < n; i += WUNET_THREADS) loss_rows_acc(snr, s[i], e[i], a);
-    } else {
-        const size_t h = (size_t)head < n ? (size_t)head : n;
-        const size_t nvec = (n - h) >> 2, tail = h + (nvec << 2);
-        if ((size_t)tid < h) loss_rows_acc(snr, s[tid], e[tid], a);
-        if (tail + tid < n) loss_rows_acc(snr, s[tail + tid], e[tail + tid], a);
-        const float* sb = s + h;
-        const float* eb = e + h;
-        // 16-byte loads, the eight of four trips issued before the first is used (loss_partial_kernel's comment: one trip at a time is
-        // one dependent memory round trip per trip)
-        size_t v = tid;
-        for (; v + 3 * WUNET_THREADS < nvec; v += 4 * WUNET_THREADS) {
-            wunet_f4 sv[4], ev[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { sv[u] = wunet_ld4(sb + ((v + u * WUNET_THREADS) << 2)); ev[u] = wunet_ld4(eb + ((v + u * WUNET_THREADS) << 2)); }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) loss_rows_acc(snr, sv[u][j], ev[u][j], a);
-            }
-        }
-        for (; v < nvec; v += WUNET_THREADS) {
-            const wunet_f4 sv = wunet_ld4(sb + (v << 2)), ev = wunet_ld4(eb + (v << 2));
-#pragma unroll
-            for (int j = 0; j < 4; ++j) loss_rows_acc(snr, sv[j], ev[j], a);
-        }
+        for (; i < n; i += WUNET_THREADS) op.one(i, s[i], e[i]);
+        return;
     }
-    block_sum5(a, red);
-    if (tid == 0) {
+    const size_t h = (size_t)head < n ? (size_t)head : n;
+    const size_t nvec = (n - h) >> 2, tail = h + (nvec << 2);
+    if ((size_t)tid < h) op.one(tid, s[tid], e[tid]);
+    if (tail + tid < n) op.one(tail + tid, s[tail + tid], e[tail + tid]);
+    size_t v = tid;
+    for (; v + 3 * WUNET_THREADS < nvec; v += 4 * WUNET_THREADS) {
+        wunet_f4 sv[4], ev[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) { sv[u] = wunet_ld4(s + h + ((v + u * WUNET_THREADS) << 2)); ev[u] = wunet_ld4(e + h + ((v + u * WUNET_THREADS) << 2)); }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) op.four(h + ((v + u * WUNET_THREADS) << 2), sv[u], ev[u]);
+    }
+    for (; v < nvec; v += WUNET_THREADS) {
+        const wunet_f4 sv = wunet_ld4(s + h + (v << 2)), ev = wunet_ld4(e + h + (v << 2));
+        op.four(h + (v << 2), sv, ev);
+    }
+}
+
+// the forward's op: every sample pair into the five raw sums
+struct LossRowsSumOp {
+    bool snr;
+    double a[WUNET_ROWS_SUMS];
+    __device__ __forceinline__ void one(size_t, float sf, float ef) { loss_rows_acc(snr, sf, ef, a); }
+    __device__ __forceinline__ void four(size_t, const wunet_f4& sv, const wunet_f4& ev)
+    {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) loss_rows_acc(snr, sv[j], ev[j], a);
+    }
+};
+
+// grid = rows * ppr blocks (block = row * ppr + piece); piece p of a row is samples [p * plen, min(T, (p + 1) * plen)), plen a multiple
+// of 4 chosen by the host from (rows, T): no block is empty.  part[block][WUNET_ROWS_SUMS].
+static __global__ __launch_bounds__(WUNET_THREADS) void loss_rows_partial_kernel(int kind, const float* clean, const float* enh, size_t T,
+                                                                           unsigned ppr, size_t plen, double* part)
+{
+    __shared__ double red[WUNET_ROWS_SUMS * WUNET_WAVES];
+    const RowPiece P = row_piece(blockIdx.x / ppr, blockIdx.x % ppr, plen, T);
+    LossRowsSumOp op{kind == WUNET_ROWS_KIND_SNR, {0.0, 0.0, 0.0, 0.0, 0.0}};
+    loss_rows_walk(clean + P.row * T + P.beg, enh + P.row * T + P.beg, nullptr, P.end - P.beg, op);
+    block_sum<WUNET_ROWS_SUMS>(op.a, red);
+    if (threadIdx.x == 0) {
         double* o = part + (size_t)blockIdx.x * WUNET_ROWS_SUMS;
 #pragma unroll
-        for (int k = 0; k < WUNET_ROWS_SUMS; ++k) o[k] = a[k];
+        for (int k = 0; k < WUNET_ROWS_SUMS; ++k) o[k] = op.a[k];
     }
 }
 
@@ -129,16 +118,16 @@ struct LossRowsFinalArgs {
 
 // ONE block.  A row is owned by `group` neighbouring lanes of a wave: lane j adds pieces j, j + group, ... in that order, a butterfly
 // over the group adds the lanes' sums (fixed order), the group's first lane forms the centred moments, v and the coefficients.  The
-// block walks the rows 256 / group at a time - any row count - and every thread keeps the sum of the v it wrote; block_sum2 ends it.
+// block walks the rows 256 / group at a time - any row count - and every thread keeps the sum of the v it wrote; block_sum ends it.
 static __global__ __launch_bounds__(WUNET_THREADS) void loss_rows_final_kernel(LossRowsFinalArgs A)
 {
-    __shared__ double red[2 * WUNET_WAVES];
+    __shared__ double red[WUNET_WAVES];
     const int tid = threadIdx.x, G = A.group;
     const int lane_in = tid & (G - 1);
     const size_t per_pass = (size_t)(WUNET_THREADS / G);
     const bool snr = A.kind == WUNET_ROWS_KIND_SNR;
     const double Td = (double)A.T;
-    double vsum = 0.0, dummy = 0.0;
+    double vsum[1] = {0.0};
     for (size_t base = 0; base < A.rows; base += per_pass) {          // (uniform trip count: the shuffles below need every lane)
         const size_t row = base + (size_t)(tid / G);
         const bool live = row < A.rows;
@@ -180,15 +169,15 @@ static __global__ __launch_bounds__(WUNET_THREADS) void loss_rows_final_kernel(L
             cd = -ca * mx - cc * ms;
         }
         const double v = 10.0 * log10((Et + A.eps) / (En + A.eps));
-        vsum += v;
+        vsum[0] += v;
         if (A.per_row) A.per_row[row] = (float)v;
         if (A.coefs) {
             double* o = A.coefs + row * WUNET_ROWS_COEFS;
             o[0] = ca; o[1] = cc; o[2] = cd; o[3] = v; o[4] = mx; o[5] = ms;
         }
     }
-    block_sum2(vsum, dummy, red);
-    if (tid == 0) *A.loss = (float)(-vsum / (double)A.rows);
+    block_sum<1>(vsum, red);
+    if (tid == 0) *A.loss = (float)(-vsum[0] / (double)A.rows);
 }
 
 // grad_enh[row][i] = gscale[0] * (-1 / rows) * (A e + C s + D): the coefficients applied in double, one rounding to float (A e and C s
@@ -196,64 +185,35 @@ static __global__ __launch_bounds__(WUNET_THREADS) void loss_rows_final_kernel(L
 // as such - si_sdr: A (e - mx) + C (s - ms), snr: A ((e - s) - mx) - not as a third term: next to A e (2 k / eps = 9e8 times e on a row
 // without noise energy) the rounding of a separately formed D is 1e-16 of THAT, 1e-8 where the gradient is exactly 0 (a row of one
 // sample; every sample equal to the row's mean).  The differences are exact or rounded relative to themselves.
-// Same (row, piece) grid as the partial kernel.
+// The backward's op, then its kernel: the same (row, piece) grid as the partial kernel.
+struct LossRowsGradOp {
+    bool snr;
+    double ca, cc, mx, ms;
+    float* g;
+    // snr: x = e - s as the forward formed it, C = -A folded into x;  si_sdr: x = e
+    // (one fma asked for by name: the scalar and the 16-byte paths then round alike whatever the compiler contracts elsewhere)
+    __device__ __forceinline__ float grad(float sf, float ef) const
+    {
+        return (float)fma(ca, ((double)ef - (snr ? (double)sf : 0.0)) - mx, cc * ((double)sf - ms));
+    }
+    __device__ __forceinline__ void one(size_t i, float sf, float ef) { g[i] = grad(sf, ef); }
+    __device__ __forceinline__ void four(size_t i, const wunet_f4& sv, const wunet_f4& ev)
+    {
+        wunet_f4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = grad(sv[j], ev[j]);
+        wunet_st4(g + i, o);
+    }
+};
+
 static __global__ __launch_bounds__(WUNET_THREADS) void loss_rows_bwd_kernel(int kind, const float* clean, const float* enh, const double* coefs,
                                                                        const float* gscale, size_t rows, size_t T, unsigned ppr,
                                                                        size_t plen, float* genh)
 {
     const bool snr = kind == WUNET_ROWS_KIND_SNR;
-    const size_t row = blockIdx.x / ppr, piece = blockIdx.x % ppr;
-    const size_t beg = piece * plen, end = beg + plen < T ? beg + plen : T;
-    const float* s = clean + row * T + beg;
-    const float* e = enh + row * T + beg;
-    float* g = genh + row * T + beg;
-    const size_t n = end - beg;
-    const int tid = threadIdx.x;
+    const RowPiece P = row_piece(blockIdx.x / ppr, blockIdx.x % ppr, plen, T);
     const double sc = -(double)gscale[0] / (double)rows;
-    const double* co = coefs + row * WUNET_ROWS_COEFS;
-    const double ca = sc * co[0], cc = snr ? 0.0 : sc * co[1], mx = co[4], ms = co[5];
-    // snr: x = e - s as the forward formed it, C = -A folded into x;  si_sdr: x = e
-    // (one fma asked for by name: the scalar and the 16-byte paths then round alike whatever the compiler contracts elsewhere)
-#define WUNET_ROWS_G(E_, S_) ((float)fma(ca, ((double)(E_) - (snr ? (double)(S_) : 0.0)) - mx, cc * ((double)(S_) - ms)))
-    const int head = loss_rows_head(s, e, g);
-    if (head < 0) {
-        size_t i = tid;
-        for (; i + 3 * WUNET_THREADS < n; i += 4 * WUNET_THREADS) {
-            float sv[4], ev[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { sv[u] = s[i + u * WUNET_THREADS]; ev[u] = e[i + u * WUNET_THREADS]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) g[i + u * WUNET_THREADS] = WUNET_ROWS_G(ev[u], sv[u]);
-        }
-        for (; i < n; i += WUNET_THREADS) g[i] = WUNET_ROWS_G(e[i], s[i]);
-        return;
-    }
-    const size_t h = (size_t)head < n ? (size_t)head : n;
-    const size_t nvec = (n - h) >> 2, tail = h + (nvec << 2);
-    if ((size_t)tid < h) g[tid] = WUNET_ROWS_G(e[tid], s[tid]);
-    if (tail + tid < n) g[tail + tid] = WUNET_ROWS_G(e[tail + tid], s[tail + tid]);
-    const float* sb = s + h;
-    const float* eb = e + h;
-    float* gb = g + h;
-    size_t v = tid;
-    for (; v + 3 * WUNET_THREADS < nvec; v += 4 * WUNET_THREADS) {       // (four trips' loads ahead of the first store)
-        wunet_f4 sv[4], ev[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { sv[u] = wunet_ld4(sb + ((v + u * WUNET_THREADS) << 2)); ev[u] = wunet_ld4(eb + ((v + u * WUNET_THREADS) << 2)); }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            wunet_f4 o;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = WUNET_ROWS_G(ev[u][j], sv[u][j]);
-            wunet_st4(gb + ((v + u * WUNET_THREADS) << 2), o);
-        }
-    }
-    for (; v < nvec; v += WUNET_THREADS) {
-        const wunet_f4 sv = wunet_ld4(sb + (v << 2)), ev = wunet_ld4(eb + (v << 2));
-        wunet_f4 o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = WUNET_ROWS_G(ev[j], sv[j]);
-        wunet_st4(gb + (v << 2), o);
-    }
-#undef WUNET_ROWS_G
+    const double* co = coefs + P.row * WUNET_ROWS_COEFS;
+    LossRowsGradOp op{snr, sc * co[0], snr ? 0.0 : sc * co[1], co[4], co[5], genh + P.row * T + P.beg};
+    loss_rows_walk(clean + P.row * T + P.beg, enh + P.row * T + P.beg, op.g, P.end - P.beg, op);
 }

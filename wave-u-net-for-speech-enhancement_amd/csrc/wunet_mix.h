@@ -4,7 +4,7 @@
 //   mix_apply_kernel     every block folds its row's partials in piece order -> g, a (double, rounded once to float32), then
 //                        mixture = a (c + g n), clean_out = a c over its piece
 // The row description is read from device memory (rows[b] = clean start, noise item start, noise item length, noise phase; params[b] =
-// snr_db, level), so a captured pair of launches follows the tables it was captured on.  The sums use block_sum2's fixed order and the
+// snr_db, level), so a captured pair of launches follows the tables it was captured on.  The sums use block_sum's fixed order and the
 // partials are folded in piece order by every block on its own: no atomics, bit-identical run to run.  Window starts are any sample,
 // so the loads are dwords (crop_windows_kernel's reasoning); a thread owns 4 consecutive samples and stores one float4 per output when
 // the row length allows it.
@@ -70,9 +70,9 @@ __device__ __forceinline__ MixRow mix_row(const MixArgs& A, int b)
 static __global__ __launch_bounds__(WUNET_THREADS) void mix_partial_kernel(MixArgs A)
 {
     __shared__ double red[2 * WUNET_WAVES];
-    const int b = (int)(blockIdx.x / A.ppr), piece = (int)(blockIdx.x % A.ppr), tid = threadIdx.x;
+    const RowPiece P = row_piece(blockIdx.x / A.ppr, blockIdx.x % A.ppr, (size_t)A.plen, (size_t)A.length);
+    const int b = (int)P.row, beg = (int)P.beg, end = (int)P.end, tid = threadIdx.x;
     const MixRow R = mix_row(A, b);
-    const int beg = piece * A.plen, end = beg + A.plen < A.length ? beg + A.plen : A.length;
     const bool noisy = R.nl > 0;
     long long k = noisy ? (R.ph + beg + 4 * tid) % R.nl : 0;
     const long long step = noisy ? (long long)(4 * WUNET_THREADS) % R.nl : 0;
@@ -110,7 +110,8 @@ static __global__ __launch_bounds__(WUNET_THREADS) void mix_partial_kernel(MixAr
 // no pass over the mixed row.  g and a are rounded to float32 once; a row without noise (g == 0) writes a c to both outputs.
 static __global__ __launch_bounds__(WUNET_THREADS) void mix_apply_kernel(MixArgs A)
 {
-    const int b = blockIdx.y, piece = blockIdx.x, tid = threadIdx.x;
+    const RowPiece P = row_piece(blockIdx.y, blockIdx.x, (size_t)A.plen, (size_t)A.length);
+    const int b = (int)P.row, piece = (int)P.piece, beg = (int)P.beg, end = (int)P.end, tid = threadIdx.x;
     const MixRow R = mix_row(A, b);
     double Pc = 0.0, Pn = 0.0, Mc = 0.0, Mn = 0.0;
     const double* p = A.part + (size_t)b * A.ppr * WUNET_MIX_PART;
@@ -134,7 +135,6 @@ static __global__ __launch_bounds__(WUNET_THREADS) void mix_apply_kernel(MixArgs
         A.gains[2 * b] = gf;
         A.gains[2 * b + 1] = af;
     }
-    const int beg = piece * A.plen, end = beg + A.plen < A.length ? beg + A.plen : A.length;
     const bool noisy = gf != 0.0f;
     const bool vec = (A.length & 3) == 0;
     long long k = noisy ? (R.ph + beg + 4 * tid) % R.nl : 0;

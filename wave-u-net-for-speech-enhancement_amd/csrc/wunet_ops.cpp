@@ -38,21 +38,23 @@ int wunet_loss_backward(int kind, const float* clean, const float* enhanced, con
     return WUNET_OK;
 }
 
-// ---------------------------------------------------------------------------- row losses (SI-SDR / SNR per utterance)
-// Pieces per row and samples per piece for (rows, T): about WUNET_ROWS_BLOCKS blocks in all, so one long row still fills the device,
-// but never less than WUNET_ROWS_MIN_PIECE samples per block (4 trips of 16-byte loads per thread) - many rows get one piece each.
-// plen is a multiple of 4 (every piece of an aligned row starts aligned) and ppr is recomputed from it: no piece is empty.
-#define WUNET_ROWS_BLOCKS 512
-#define WUNET_ROWS_MIN_PIECE 4096
-static void loss_rows_plan(size_t rows, size_t T, size_t& ppr, size_t& plen)
+// ---------------------------------------------------------------------------- the (row, piece) grids of the row losses and the mixer
+// Pieces per row and samples per piece for `rows` rows of `len` samples: about want_blocks blocks in all, so one long row still fills
+// the device, but never less than min_piece samples per block - many rows get one piece each.  plen is a multiple of 4 (every piece of
+// an aligned row starts aligned) and ppr is recomputed from it: no piece is empty (row_piece in wunet_elementwise.h).
+static void row_pieces(size_t rows, size_t len, size_t want_blocks, size_t min_piece, size_t& ppr, size_t& plen)
 {
-    size_t want = (WUNET_ROWS_BLOCKS + rows - 1) / rows;
-    const size_t most = (T + WUNET_ROWS_MIN_PIECE - 1) / WUNET_ROWS_MIN_PIECE;
+    size_t want = (want_blocks + rows - 1) / rows;
+    const size_t most = (len + min_piece - 1) / min_piece;
     if (want > most) want = most;
     if (want < 1) want = 1;
-    plen = (((T + want - 1) / want) + 3) & ~(size_t)3;
-    ppr = (T + plen - 1) / plen;
+    plen = (((len + want - 1) / want) + 3) & ~(size_t)3;
+    ppr = (len + plen - 1) / plen;
 }
+
+// ---------------------------------------------------------------------------- row losses (SI-SDR / SNR per utterance)
+#define WUNET_ROWS_BLOCKS 512
+#define WUNET_ROWS_MIN_PIECE 4096        // 4 trips of 16-byte loads per thread
 
 static int loss_rows_shape_check(size_t rows, size_t row_len)
 {
@@ -65,7 +67,7 @@ size_t wunet_loss_rows_scratch_bytes(size_t rows, size_t row_len)
 {
     if (rows == 0 || row_len == 0) return 0;
     size_t ppr, plen;
-    loss_rows_plan(rows, row_len, ppr, plen);
+    row_pieces(rows, row_len, WUNET_ROWS_BLOCKS, WUNET_ROWS_MIN_PIECE, ppr, plen);
     return rows * ppr * WUNET_ROWS_SUMS * sizeof(double);
 }
 
@@ -78,7 +80,7 @@ int wunet_loss_rows_forward(int kind, int zero_mean, double eps, const float* cl
     if (!(eps >= 0.0) || eps > 1.7976931348623157e308) return fail(WUNET_E_ARG, "row loss: eps must be finite and >= 0 (got %g)", eps);
     hipStream_t st = (hipStream_t)stream;
     size_t ppr, plen;
-    loss_rows_plan(rows, row_len, ppr, plen);
+    row_pieces(rows, row_len, WUNET_ROWS_BLOCKS, WUNET_ROWS_MIN_PIECE, ppr, plen);
     WUNET_LAUNCH(loss_rows_partial_kernel, dim3((unsigned)(rows * ppr)), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, row_len, (unsigned)ppr,
                  plen, (double*)scratch);
     WUNET_CHECK_LAUNCH();
@@ -100,7 +102,7 @@ int wunet_loss_rows_backward(int kind, const float* clean, const float* enhanced
     if (!clean || !enhanced || !coefs || !grad_loss || !grad_enhanced) return fail(WUNET_E_ARG, "row loss: null argument");
     hipStream_t st = (hipStream_t)stream;
     size_t ppr, plen;
-    loss_rows_plan(rows, row_len, ppr, plen);
+    row_pieces(rows, row_len, WUNET_ROWS_BLOCKS, WUNET_ROWS_MIN_PIECE, ppr, plen);
     WUNET_LAUNCH(loss_rows_bwd_kernel, dim3((unsigned)(rows * ppr)), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, coefs, grad_loss, rows, row_len,
                  (unsigned)ppr, plen, grad_enhanced);
     WUNET_CHECK_LAUNCH();
@@ -384,43 +386,7 @@ int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, s
 }
 
 // ---------------------------------------------------------------------------- fused Adam
-int wunet_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
-                    float* const* exp_avg_sq, const size_t* numels, double lr, double beta1, double beta2, double eps,
-                    long long step, double grad_scale, long long* step_dev, float* hyper_dev, void* stream)
-{
-    if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numels))) return fail(WUNET_E_ARG, "null argument");
-    if (!step_dev && step < 1) return fail(WUNET_E_ARG, "step must be >= 1");
-    if (step_dev && !hyper_dev) return fail(WUNET_E_ARG, "a device step counter needs the 2-float hyper buffer");
-    hipStream_t st = (hipStream_t)stream;
-    float step_size = 0.0f, bc2_sqrt = 1.0f;
-    if (step_dev) {
-        WUNET_LAUNCH(adam_hyper_kernel, dim3(1), dim3(1), 0, st, step_dev, lr, beta1, beta2, hyper_dev);
-        WUNET_CHECK_LAUNCH();
-    } else {
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        step_size = (float)(lr / bc1); bc2_sqrt = (float)sqrt(bc2);
-    }
-    for (int base = 0; base < n_tensors; base += WUNET_ADAM_MAX) {
-        AdamTable T{};
-        const int cnt = n_tensors - base < WUNET_ADAM_MAX ? n_tensors - base : WUNET_ADAM_MAX;
-        size_t nmax = 0;
-        for (int k = 0; k < cnt; ++k) {
-            if (numels[base + k] >= (1ull << 32)) return fail(WUNET_E_ARG, "tensor too large");
-            T.p[k] = params[base + k]; T.g[k] = grads[base + k]; T.m[k] = exp_avg[base + k]; T.v[k] = exp_avg_sq[base + k];
-            T.n[k] = (unsigned)numels[base + k];
-            if (numels[base + k] > nmax) nmax = numels[base + k];
-        }
-        size_t bx = (nmax + WUNET_THREADS * 4 - 1) / (WUNET_THREADS * 4);
-        if (bx < 1) bx = 1;
-        if (bx > 256) bx = 256;
-        WUNET_LAUNCH(adam_kernel, dim3((unsigned)bx, cnt), dim3(WUNET_THREADS), 0, st, T, (float)(1.0 - beta1), (float)beta2,
-                     (float)(1.0 - beta2), bc2_sqrt, (float)eps, step_size, (float)grad_scale, (const float*)(step_dev ? hyper_dev : nullptr));
-        WUNET_CHECK_LAUNCH();
-    }
-    return WUNET_OK;
-}
-
-// One launch of an Adam step: up to WUNET_ADAM_MAX tensors, grid (bx, cnt) as wunet_adam_step builds it.
+// One launch of an Adam step: up to WUNET_ADAM_MAX tensors, grid (bx, cnt): blockIdx.y = tensor, blockIdx.x strides inside it.
 struct AdamLaunch {
     AdamTable T;
     unsigned bx;
@@ -442,6 +408,34 @@ static void adam_launch_at(int n_tensors, int base, float* const* params, const 
     if (bx < 1) bx = 1;
     if (bx > 256) bx = 256;
     L.bx = (unsigned)bx;
+}
+
+int wunet_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                    float* const* exp_avg_sq, const size_t* numels, double lr, double beta1, double beta2, double eps,
+                    long long step, double grad_scale, long long* step_dev, float* hyper_dev, void* stream)
+{
+    if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numels))) return fail(WUNET_E_ARG, "null argument");
+    if (!step_dev && step < 1) return fail(WUNET_E_ARG, "step must be >= 1");
+    if (step_dev && !hyper_dev) return fail(WUNET_E_ARG, "a device step counter needs the 2-float hyper buffer");
+    for (int k = 0; k < n_tensors; ++k)          // (before anything is enqueued: a refused call leaves the device counter alone)
+        if (numels[k] >= (1ull << 32)) return fail(WUNET_E_ARG, "tensor too large");
+    hipStream_t st = (hipStream_t)stream;
+    float step_size = 0.0f, bc2_sqrt = 1.0f;
+    if (step_dev) {
+        WUNET_LAUNCH(adam_hyper_kernel, dim3(1), dim3(1), 0, st, step_dev, lr, beta1, beta2, hyper_dev);
+        WUNET_CHECK_LAUNCH();
+    } else {
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        step_size = (float)(lr / bc1); bc2_sqrt = (float)sqrt(bc2);
+    }
+    AdamLaunch L;
+    for (int base = 0; base < n_tensors; base += WUNET_ADAM_MAX) {
+        adam_launch_at(n_tensors, base, params, grads, exp_avg, exp_avg_sq, numels, L);
+        WUNET_LAUNCH(adam_kernel, dim3(L.bx, L.cnt), dim3(WUNET_THREADS), 0, st, L.T, (float)(1.0 - beta1), (float)beta2,
+                     (float)(1.0 - beta2), bc2_sqrt, (float)eps, step_size, (float)grad_scale, (const float*)(step_dev ? hyper_dev : nullptr));
+        WUNET_CHECK_LAUNCH();
+    }
+    return WUNET_OK;
 }
 
 // one double per block of the norm's launches: at most 256 blocks per tensor
@@ -515,19 +509,8 @@ int wunet_crop_windows(const float* mixture_flat, const float* clean_flat, const
 }
 
 // ---------------------------------------------------------------------------- data input: mixtures made on the device (wunet_mix.h)
-// Pieces per row for (batch, length): about WUNET_MIX_BLOCKS blocks in all and never less than WUNET_MIX_MIN_PIECE samples per block
-// (one trip of 4 samples per thread); plen is a multiple of 4 and ppr is recomputed from it, so no piece is empty.
 #define WUNET_MIX_BLOCKS 1024
-#define WUNET_MIX_MIN_PIECE 1024
-static void mix_plan(int batch, int length, unsigned& ppr, int& plen)
-{
-    long long want = (WUNET_MIX_BLOCKS + (long long)batch - 1) / batch;
-    const long long most = ((long long)length + WUNET_MIX_MIN_PIECE - 1) / WUNET_MIX_MIN_PIECE;
-    if (want > most) want = most;
-    if (want < 1) want = 1;
-    plen = (int)(((((long long)length + want - 1) / want) + 3) & ~3LL);
-    ppr = (unsigned)(((long long)length + plen - 1) / plen);
-}
+#define WUNET_MIX_MIN_PIECE 1024         // one trip of 4 samples per thread
 
 static int mix_shape_check(int batch, int length)
 {
@@ -539,9 +522,8 @@ static int mix_shape_check(int batch, int length)
 size_t wunet_mix_scratch_bytes(int batch, int length)
 {
     if (batch < 1 || length < 1 || batch > 65535 || length > (1 << 30)) return 0;
-    unsigned ppr;
-    int plen;
-    mix_plan(batch, length, ppr, plen);
+    size_t ppr, plen;
+    row_pieces((size_t)batch, (size_t)length, WUNET_MIX_BLOCKS, WUNET_MIX_MIN_PIECE, ppr, plen);
     return (size_t)batch * ppr * WUNET_MIX_PART * sizeof(double);
 }
 
@@ -562,7 +544,9 @@ int wunet_mix_windows(const float* clean_flat, long long clean_total, const floa
     A.clean_flat = clean_flat; A.noise_flat = noise_flat; A.clean_total = clean_total; A.noise_total = noise_total; A.rows = rows;
     A.params = params; A.peak_limit = peak_limit; A.length = length; A.part = (double*)scratch; A.mixture = mixture; A.clean_out = clean_out;
     A.gains = gains;
-    mix_plan(batch, length, A.ppr, A.plen);
+    size_t ppr, plen;
+    row_pieces((size_t)batch, (size_t)length, WUNET_MIX_BLOCKS, WUNET_MIX_MIN_PIECE, ppr, plen);
+    A.ppr = (unsigned)ppr; A.plen = (int)plen;
     const double n = (double)batch * length;
     prof_begin(st, "mix_partial_kernel", 4.0 * n, 4.0 * 2.0 * n);
     WUNET_LAUNCH(mix_partial_kernel, dim3((unsigned)batch * A.ppr), dim3(WUNET_THREADS), 0, st, A);

@@ -68,83 +68,109 @@ struct StftFwdArgs {
     float* mag_out;         // nullptr or [M][bins]: S_e
 };
 
-// grid (M / 64 rounded up, BP / 32).  PAIR: both signals and the sums; else `e` alone and mag_out only (the metric).
-// A tile As[sig][64 frames][16 k], B tile Bs[16 k][32 cos | 32 -sin]; the next tile's global loads are issued before the MFMAs of the
-// current one and stored to LDS behind them.
-template <bool PAIR>
-static __global__ __launch_bounds__(WUNET_THREADS) void stft_fwd_kernel(StftFwdArgs A)
+// The main loop of one block's DFT GEMM: acc[signal][re, im][column tile] = sum over k_begin <= k < k_end (multiples of WUNET_STFT_KT) of
+// A[signal][64 frames][k] x basis[k][bins b0 .. b0 + 31, cos | -sin]; basis rows are 2 BP floats.  A tile As[signal][64 frames][16 k],
+// B tile Bs[16 k][32 cos | 32 -sin]; the next tile's global loads are issued before the MFMAs of the current one and stored to LDS
+// behind them.  Loader roles.  A: k = tid & 15, frames (tid >> 4) + 16 j - loader.load(kt, ra) fetches ra[signal][j] at k = kt + (tid & 15).
+// B: row tid >> 4, four columns from (tid & 15) * 4.  Every thread of the block takes part (two barriers per K tile).
+template <int NSIG, class Loader>
+__device__ __forceinline__ void dft_tile_gemm(const Loader& loader, const float* basis, int BP, int b0, int k_begin, int k_end, float* As, float* Bs,
+                                              wunet_f4 (&acc)[NSIG][2][2])
 {
-    __shared__ __attribute__((aligned(16))) float As[(PAIR ? 2 : 1) * WUNET_STFT_FM * WUNET_STFT_AS];
-    __shared__ __attribute__((aligned(16))) float Bs[WUNET_STFT_KT * WUNET_STFT_BS];
-    __shared__ double red[2 * WUNET_WAVES];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lq = lane >> 4;
-    const unsigned m0 = blockIdx.x * WUNET_STFT_FM;
-    const int b0 = blockIdx.y * WUNET_STFT_BN;
-    // ---- loader roles.  A: k = tid & 15, frames (tid >> 4) + 16 j.  B: row tid >> 4, four columns from (tid & 15) * 4.
-    const int ak = tid & 15;
-    size_t abase[4];
-    long long apos[4];
-    bool aok[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const unsigned m = m0 + (unsigned)(tid >> 4) + 16u * j;
-        aok[j] = m < A.M;
-        const unsigned row = aok[j] ? m / A.F : 0u, f = aok[j] ? m - row * A.F : 0u;
-        abase[j] = (size_t)row * A.T;
-        apos[j] = (long long)f * A.H - A.N / 2 + ak;
-    }
-    const int bk = tid >> 4, bc = (tid & 15) * 4;
-    const float* bsrc = A.basis + (size_t)bk * 2 * A.BP + (bc < WUNET_STFT_BN ? b0 + bc : A.BP + b0 + bc - WUNET_STFT_BN);
-    const long long Tl = (long long)A.T;
-    float ra_e[4], ra_c[4];
+    const int ak = tid & 15, bk = tid >> 4, bc = (tid & 15) * 4;
+    const float* bsrc = basis + (size_t)bk * 2 * BP + (bc < WUNET_STFT_BN ? b0 + bc : BP + b0 + bc - WUNET_STFT_BN);
+    float ra[NSIG][4];
     wunet_f4 rb;
-#define WUNET_STFT_LOAD(KT_)                                                                                      \
-    do {                                                                                                          \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
-            long long p = apos[j] + (KT_);                                                                        \
-            p = p < 0 ? -p : (p >= Tl ? 2 * (Tl - 1) - p : p);               /* reflect, once: N / 2 <= T - 1 */   \
-            ra_e[j] = aok[j] ? A.e[abase[j] + (size_t)p] : 0.0f;                                                  \
-            if (PAIR) ra_c[j] = aok[j] ? A.c[abase[j] + (size_t)p] : 0.0f;                                        \
-        }                                                                                                         \
-        rb = wunet_ld4(bsrc + (size_t)(KT_) * 2 * A.BP);                                                          \
-    } while (0)
-    wunet_f4 acc[PAIR ? 2 : 1][2][2];            // [signal: e, c][re, im][column tile]
 #pragma unroll
-    for (int s = 0; s < (PAIR ? 2 : 1); ++s)
+    for (int s = 0; s < NSIG; ++s)
 #pragma unroll
         for (int p = 0; p < 2; ++p)
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) acc[s][p][nt] = wunet_f4{0.f, 0.f, 0.f, 0.f};
-    WUNET_STFT_LOAD(A.k0);
-    for (int kt = A.k0; kt < A.k1; kt += WUNET_STFT_KT) {
+    loader.load(k_begin, ra);
+    rb = wunet_ld4(bsrc + (size_t)k_begin * 2 * BP);
+    for (int kt = k_begin; kt < k_end; kt += WUNET_STFT_KT) {
         __syncthreads();                                               // the previous tile's reads are done
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int ml = (tid >> 4) + 16 * j;
-            As[ml * WUNET_STFT_AS + ak] = ra_e[j];
-            if (PAIR) As[(WUNET_STFT_FM + ml) * WUNET_STFT_AS + ak] = ra_c[j];
+#pragma unroll
+            for (int s = 0; s < NSIG; ++s) As[(s * WUNET_STFT_FM + ml) * WUNET_STFT_AS + ak] = ra[s][j];
         }
         wunet_st4(&Bs[bk * WUNET_STFT_BS + bc], rb);
         __syncthreads();
-        if (kt + WUNET_STFT_KT < A.k1) WUNET_STFT_LOAD(kt + WUNET_STFT_KT);
+        if (kt + WUNET_STFT_KT < k_end) {
+            loader.load(kt + WUNET_STFT_KT, ra);
+            rb = wunet_ld4(bsrc + (size_t)(kt + WUNET_STFT_KT) * 2 * BP);
+        }
 #pragma unroll
         for (int s4 = 0; s4 < WUNET_STFT_KT / 4; ++s4) {
             const int kk = s4 * 4 + lq;
-            const float ae = As[(wave * 16 + li) * WUNET_STFT_AS + kk];
-            const float ac = PAIR ? As[(WUNET_STFT_FM + wave * 16 + li) * WUNET_STFT_AS + kk] : 0.0f;
+            float a[NSIG];
+#pragma unroll
+            for (int s = 0; s < NSIG; ++s) a[s] = As[(s * WUNET_STFT_FM + wave * 16 + li) * WUNET_STFT_AS + kk];
 #pragma unroll
             for (int p = 0; p < 2; ++p)
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
                     const float b = Bs[kk * WUNET_STFT_BS + p * WUNET_STFT_BN + nt * 16 + li];
-                    acc[0][p][nt] = wunet_mfma16(ae, b, acc[0][p][nt]);
-                    if (PAIR) acc[PAIR ? 1 : 0][p][nt] = wunet_mfma16(ac, b, acc[PAIR ? 1 : 0][p][nt]);
+#pragma unroll
+                    for (int s = 0; s < NSIG; ++s) acc[s][p][nt] = wunet_mfma16(a[s], b, acc[s][p][nt]);
                 }
         }
     }
-#undef WUNET_STFT_LOAD
+}
+
+// A of the STFT: frame f of a row starts at f H - N / 2 of the waveform, reflect-padded.  Signal 0 = enhanced, 1 = clean.
+template <int NSIG>
+struct StftFrameLoader {
+    const float* x[2];
+    size_t abase[4];
+    long long apos[4], Tl;
+    bool aok[4];
+    __device__ __forceinline__ StftFrameLoader(const StftFwdArgs& A, unsigned m0)
+    {
+        const int tid = threadIdx.x;
+        x[0] = A.e; x[1] = A.c;
+        Tl = (long long)A.T;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned m = m0 + (unsigned)(tid >> 4) + 16u * j;
+            aok[j] = m < A.M;
+            const unsigned row = aok[j] ? m / A.F : 0u, f = aok[j] ? m - row * A.F : 0u;
+            abase[j] = (size_t)row * A.T;
+            apos[j] = (long long)f * A.H - A.N / 2 + (tid & 15);
+        }
+    }
+    __device__ __forceinline__ void load(int kt, float (&ra)[NSIG][4]) const
+    {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            long long p = apos[j] + kt;
+            p = p < 0 ? -p : (p >= Tl ? 2 * (Tl - 1) - p : p);               // reflect, once: N / 2 <= T - 1
+#pragma unroll
+            for (int s = 0; s < NSIG; ++s) ra[s][j] = aok[j] ? x[s][abase[j] + (size_t)p] : 0.0f;
+        }
+    }
+};
+
+// grid (M / 64 rounded up, BP / 32).  PAIR: both signals and the sums; else `e` alone and mag_out only (the metric).  One block owns
+// 64 frames x 32 bins: dft_tile_gemm, then the magnitudes and the block's partial.
+template <bool PAIR>
+static __global__ __launch_bounds__(WUNET_THREADS) void stft_fwd_kernel(StftFwdArgs A)
+{
+    constexpr int NSIG = PAIR ? 2 : 1;
+    __shared__ __attribute__((aligned(16))) float As[NSIG * WUNET_STFT_FM * WUNET_STFT_AS];
+    __shared__ __attribute__((aligned(16))) float Bs[WUNET_STFT_KT * WUNET_STFT_BS];
+    __shared__ double red[3 * WUNET_WAVES];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lq = lane >> 4;
+    const unsigned m0 = blockIdx.x * WUNET_STFT_FM;
+    const int b0 = blockIdx.y * WUNET_STFT_BN;
+    wunet_f4 acc[NSIG][2][2];                    // [signal: e, c][re, im][column tile]
+    dft_tile_gemm<NSIG>(StftFrameLoader<NSIG>(A, m0), A.basis, A.BP, b0, A.k0, A.k1, As, Bs, acc);
     // ---- epilogue: D[row = 4 lq + r][col = li] of the wave's 16 frames
-    double s_d = 0.0, s_c = 0.0, s_l = 0.0, dummy = 0.0;
+    double sum[3] = {0.0, 0.0, 0.0};             // (S_c - S_e)^2, S_c^2, |ln S_c - ln S_e|
     const size_t plane = (size_t)A.M * A.BP;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
@@ -160,9 +186,9 @@ static __global__ __launch_bounds__(WUNET_THREADS) void stft_fwd_kernel(StftFwdA
                 const float pc = fmaxf(stft_power(acc[PAIR ? 1 : 0][0][nt][r], acc[PAIR ? 1 : 0][1][nt][r]), A.clamp), sc = sqrtf(pc);
                 if (b < A.bins) {
                     const double d = (double)sc - (double)se;
-                    s_d += d * d;
-                    s_c += (double)sc * (double)sc;
-                    s_l += fabs(0.5 * log((double)pc / (double)pe));     // ln S_c - ln S_e from the powers: one log, no rounding of the roots in it
+                    sum[0] += d * d;
+                    sum[1] += (double)sc * (double)sc;
+                    sum[2] += fabs(0.5 * log((double)pc / (double)pe));     // ln S_c - ln S_e from the powers: one log, no rounding of the roots in it
                 }
                 if (A.saved) {                                           // (the padding columns too: re = im = 0 there, below the clamp)
                     const size_t o = (size_t)m * A.BP + b;
@@ -174,11 +200,10 @@ static __global__ __launch_bounds__(WUNET_THREADS) void stft_fwd_kernel(StftFwdA
         }
     }
     if (PAIR) {
-        block_sum2(s_d, s_c, red);
-        block_sum2(s_l, dummy, red);
+        block_sum<3>(sum, red);
         if (tid == 0) {
             double* o = A.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
-            o[0] = s_d; o[1] = s_c; o[2] = s_l;
+            o[0] = sum[0]; o[1] = sum[1]; o[2] = sum[2];
         }
     }
 }
@@ -193,24 +218,24 @@ struct StftFinalArgs {
     double* coefs;                         // [n_res][WUNET_STFT_NCOEF]
 };
 
-// ONE block over the table of resolutions: thread t adds partials t, t + 256, ... in that order, block_sum2 adds the threads (fixed
+// ONE block over the table of resolutions: thread t adds partials t, t + 256, ... in that order, block_sum adds the threads (fixed
 // order).  a = w_sc / (n_res |S_c - S_e| |S_c|), 0 where S_c == S_e everywhere (the one departure from autograd, which gives NaN);
 // b = w_mag / (n_res count).  The loss is accumulated over the resolutions in double and rounded once.
 static __global__ __launch_bounds__(WUNET_THREADS) void stft_final_kernel(StftFinalArgs A)
 {
-    __shared__ double red[2 * WUNET_WAVES];
+    __shared__ double red[3 * WUNET_WAVES];
     const int tid = threadIdx.x;
     double total = 0.0;
     for (int i = 0; i < A.n_res; ++i) {
-        double s_d = 0.0, s_c = 0.0, s_l = 0.0, dummy = 0.0;
+        double sum[3] = {0.0, 0.0, 0.0};
         for (unsigned p = tid; p < A.nparts[i]; p += WUNET_THREADS) {
             const double* q = A.part[i] + (size_t)p * 3;
-            s_d += q[0]; s_c += q[1]; s_l += q[2];
+            sum[0] += q[0]; sum[1] += q[1]; sum[2] += q[2];
         }
-        block_sum2(s_d, s_c, red);
-        block_sum2(s_l, dummy, red);
-        const double nd = sqrt(s_d), nc = sqrt(s_c);
-        const double sc = nd / nc, mag = s_l / A.count[i];
+        block_sum<3>(sum, red);
+        const double s_d = sum[0];
+        const double nd = sqrt(s_d), nc = sqrt(sum[1]);
+        const double sc = nd / nc, mag = sum[2] / A.count[i];
         total += A.w_sc * sc + A.w_mag * mag;
         if (tid == 0 && A.coefs) {
             double* o = A.coefs + (size_t)i * WUNET_STFT_NCOEF;

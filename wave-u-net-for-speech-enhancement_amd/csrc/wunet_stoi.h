@@ -7,7 +7,7 @@
 //                         phase, staged in LDS; both signals in one launch; double accumulation, one rounding to float
 //   stoi_mask_kernel      ONE block per row: energies of the clean row's windowed frames [dB], their maximum, the frames above
 //                         maximum - 40 dB as a table kept[row][j] of original frame indices (an exclusive scan) + n_kept[row]
-//   stoi_spec_kernel      implicit GEMM [frames][256] x basis on v_mfma_f32_16x16x4_f32, stft_fwd_kernel's tiling.  The loader builds
+//   stoi_spec_kernel      implicit GEMM [frames][256] x basis on v_mfma_f32_16x16x4_f32 (dft_tile_gemm of wunet_stft.h).  The loader builds
 //                         each frame of the silence-free signal from the resampled one and the kept table - w[k] (in the basis) times the
 //                         sum of the at most two kept windowed frames over position k - so the overlap-added signal is never written;
 //                         the epilogue writes re^2 + im^2 of both signals
@@ -170,10 +170,51 @@ struct StoiSpecArgs {
     float* pw;              // [2][M][BP]: re^2 + im^2
 };
 
-// grid (M / 64 rounded up, BP / 32).  Frame m = row * Fmax + f is live for f < n_kept[row] - 1.  Frame f of the silence-free signal:
-// position k < 128 lies in the kept frames f (at k) and f - 1 (at k + 128), k >= 128 in f (at k) and f + 1 (at k - 128); each is
-// windowed once there, and once more by the basis.  A tile As[sig][64 frames][16 k], B tile Bs[16 k][32 cos | 32 -sin], the next
-// tile's global loads issued before the MFMAs of the current one (stft_fwd_kernel's pipeline).
+// A of stoi_spec_kernel: frame f of the silence-free signal, built from the resampled one and the kept table.  Position k < 128 lies
+// in the kept frames f (at k) and f - 1 (at k + 128), k >= 128 in f (at k) and f + 1 (at k - 128); each is windowed once there (ws, the
+// window in LDS), and once more by the basis.  Signal 0 = clean, 1 = estimate.
+struct StoiFrameLoader {
+    const float* x[2];
+    const float* ws;
+    size_t abase[4];
+    int kc[4], kp[4], kn[4];            // the kept frame itself, the one before and the one after it (-1: none)
+    __device__ __forceinline__ StoiFrameLoader(const StoiSpecArgs& A, unsigned m0, const float* ws_) : ws(ws_)
+    {
+        const int tid = threadIdx.x;
+        x[0] = A.x[0]; x[1] = A.x[1];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const unsigned m = m0 + (unsigned)(tid >> 4) + 16u * j;
+            const unsigned row = m < A.M ? m / A.Fmax : 0u, f = m - row * A.Fmax;
+            const bool ok = m < A.M && (int)f < A.nk[row] - 1;
+            const int* kr = A.kept + (size_t)row * A.F0;
+            abase[j] = (size_t)row * A.Tr;
+            kc[j] = ok ? kr[f] : -1;
+            kp[j] = ok && f > 0 ? kr[f - 1] : -1;
+            kn[j] = ok ? kr[f + 1] : -1;
+        }
+    }
+    __device__ __forceinline__ void load(int kt, float (&ra)[2][4]) const
+    {
+        const int k = kt + ((int)threadIdx.x & 15), ko = k < WUNET_STOI_HOP ? k + WUNET_STOI_HOP : k - WUNET_STOI_HOP;
+        const float w = ws[k], wo = ws[ko];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int other = k < WUNET_STOI_HOP ? kp[j] : kn[j];
+            const size_t o1 = abase[j] + (size_t)(kc[j] < 0 ? 0 : kc[j]) * WUNET_STOI_HOP + k;
+            const size_t o2 = abase[j] + (size_t)(other < 0 ? 0 : other) * WUNET_STOI_HOP + ko;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float v1 = kc[j] < 0 ? 0.0f : w * x[s][o1];
+                const float v2 = other < 0 ? 0.0f : wo * x[s][o2];
+                ra[s][j] = v1 + v2;
+            }
+        }
+    }
+};
+
+// grid (M / 64 rounded up, BP / 32).  Frame m = row * Fmax + f is live for f < n_kept[row] - 1.  One block owns 64 frames x 32 bins of
+// both signals: dft_tile_gemm (wunet_stft.h) over the 256 window positions, then the powers.
 static __global__ __launch_bounds__(WUNET_THREADS) void stoi_spec_kernel(StoiSpecArgs A)
 {
     __shared__ __attribute__((aligned(16))) float As[2 * WUNET_STFT_FM * WUNET_STFT_AS];
@@ -193,77 +234,10 @@ static __global__ __launch_bounds__(WUNET_THREADS) void stoi_spec_kernel(StoiSpe
         if (!any) return;
     }
     ws[tid] = A.w[tid];
-    // ---- loader roles.  A: k = tid & 15, frames (tid >> 4) + 16 j.  B: row tid >> 4, four columns from (tid & 15) * 4.
-    const int ak = tid & 15;
-    size_t abase[4];
-    int kc[4], kp[4], kn[4];            // the kept frame itself, the one before and the one after it (-1: none)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const unsigned m = m0 + (unsigned)(tid >> 4) + 16u * j;
-        const unsigned row = m < A.M ? m / A.Fmax : 0u, f = m - row * A.Fmax;
-        const bool ok = m < A.M && (int)f < A.nk[row] - 1;
-        const int* kr = A.kept + (size_t)row * A.F0;
-        abase[j] = (size_t)row * A.Tr;
-        kc[j] = ok ? kr[f] : -1;
-        kp[j] = ok && f > 0 ? kr[f - 1] : -1;
-        kn[j] = ok ? kr[f + 1] : -1;
-    }
-    const int bk = tid >> 4, bc = (tid & 15) * 4;
-    const float* bsrc = A.basis + (size_t)bk * 2 * WUNET_STOI_BP + (bc < WUNET_STFT_BN ? b0 + bc : WUNET_STOI_BP + b0 + bc - WUNET_STFT_BN);
-    float ra[2][4];
-    wunet_f4 rb;
+    const StoiFrameLoader loader(A, m0, ws);
     __syncthreads();                                                     // ws
-#define WUNET_STOI_LOAD(KT_)                                                                                      \
-    do {                                                                                                          \
-        const int k_ = (KT_) + ak, ko_ = k_ < WUNET_STOI_HOP ? k_ + WUNET_STOI_HOP : k_ - WUNET_STOI_HOP;          \
-        const float w_ = ws[k_], wo_ = ws[ko_];                                                                   \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                           \
-            const int other_ = k_ < WUNET_STOI_HOP ? kp[j] : kn[j];                                               \
-            const size_t o1_ = abase[j] + (size_t)(kc[j] < 0 ? 0 : kc[j]) * WUNET_STOI_HOP + k_;                  \
-            const size_t o2_ = abase[j] + (size_t)(other_ < 0 ? 0 : other_) * WUNET_STOI_HOP + ko_;               \
-            _Pragma("unroll") for (int s = 0; s < 2; ++s) {                                                       \
-                const float v1_ = kc[j] < 0 ? 0.0f : w_ * A.x[s][o1_];                                            \
-                const float v2_ = other_ < 0 ? 0.0f : wo_ * A.x[s][o2_];                                          \
-                ra[s][j] = v1_ + v2_;                                                                             \
-            }                                                                                                     \
-        }                                                                                                         \
-        rb = wunet_ld4(bsrc + (size_t)(KT_) * 2 * WUNET_STOI_BP);                                                 \
-    } while (0)
     wunet_f4 acc[2][2][2];               // [signal][re, im][column tile]
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) acc[s][p][nt] = wunet_f4{0.f, 0.f, 0.f, 0.f};
-    WUNET_STOI_LOAD(0);
-    for (int kt = 0; kt < WUNET_STOI_N; kt += WUNET_STFT_KT) {
-        __syncthreads();                                               // the previous tile's reads are done
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ml = (tid >> 4) + 16 * j;
-            As[ml * WUNET_STFT_AS + ak] = ra[0][j];
-            As[(WUNET_STFT_FM + ml) * WUNET_STFT_AS + ak] = ra[1][j];
-        }
-        wunet_st4(&Bs[bk * WUNET_STFT_BS + bc], rb);
-        __syncthreads();
-        if (kt + WUNET_STFT_KT < WUNET_STOI_N) WUNET_STOI_LOAD(kt + WUNET_STFT_KT);
-#pragma unroll
-        for (int s4 = 0; s4 < WUNET_STFT_KT / 4; ++s4) {
-            const int kk = s4 * 4 + lq;
-            const float a0 = As[(wave * 16 + li) * WUNET_STFT_AS + kk];
-            const float a1 = As[(WUNET_STFT_FM + wave * 16 + li) * WUNET_STFT_AS + kk];
-#pragma unroll
-            for (int p = 0; p < 2; ++p)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    const float b = Bs[kk * WUNET_STFT_BS + p * WUNET_STFT_BN + nt * 16 + li];
-                    acc[0][p][nt] = wunet_mfma16(a0, b, acc[0][p][nt]);
-                    acc[1][p][nt] = wunet_mfma16(a1, b, acc[1][p][nt]);
-                }
-        }
-    }
-#undef WUNET_STOI_LOAD
+    dft_tile_gemm<2>(loader, A.basis, WUNET_STOI_BP, b0, 0, WUNET_STOI_N, As, Bs, acc);
     // ---- epilogue: D[row = 4 lq + r][col = li] of the wave's 16 frames (a dead frame of a live block: zeros, never read)
     const size_t plane = (size_t)A.M * WUNET_STOI_BP;
 #pragma unroll
@@ -297,11 +271,11 @@ __device__ __forceinline__ int stoi_segments(int n_kept)
 
 // grid (nblk, rows).  With X, Y the 30 band magnitudes of a segment: alpha = |X| / (|Y| + EPS), Y' = min(alpha Y, clip X), both
 // centred, each divided by (its norm + EPS), d = sum X Y' - all of it in double; a thread adds the d of its (segment, band) items
-// in index order, block_sum2 the threads.
+// in index order, block_sum the threads.
 static __global__ __launch_bounds__(WUNET_THREADS) void stoi_segment_kernel(StoiSegArgs A)
 {
     __shared__ double tb[2 * (WUNET_STOI_SB + WUNET_STOI_SEG - 1) * WUNET_STOI_BANDS];
-    __shared__ double red[2 * WUNET_WAVES];
+    __shared__ double red[WUNET_WAVES];
     const int tid = threadIdx.x;
     const size_t row = blockIdx.y;
     const int nseg = stoi_segments(A.nk[row]), s0 = (int)blockIdx.x * WUNET_STOI_SB;
@@ -317,7 +291,7 @@ static __global__ __launch_bounds__(WUNET_THREADS) void stoi_segment_kernel(Stoi
         tb[sig * TBS + fb] = sqrt(s);
     }
     __syncthreads();
-    double dsum = 0.0, dummy = 0.0;
+    double dsum[1] = {0.0};
     for (int i = tid; i < ns * WUNET_STOI_BANDS; i += WUNET_THREADS) {
         const double* xs = tb + i;                                       // (segment i / 15, band i % 15): frame n at + 15 n
         const double* ys = tb + TBS + i;
@@ -342,25 +316,25 @@ static __global__ __launch_bounds__(WUNET_THREADS) void stoi_segment_kernel(Stoi
             const double xc = x - mx, yc = (y < c ? y : c) - my;
             cxx += xc * xc; cyy += yc * yc; cxy += xc * yc;
         }
-        dsum += cxy / ((sqrt(cxx) + WUNET_STOI_EPS) * (sqrt(cyy) + WUNET_STOI_EPS));
+        dsum[0] += cxy / ((sqrt(cxx) + WUNET_STOI_EPS) * (sqrt(cyy) + WUNET_STOI_EPS));
     }
-    block_sum2(dsum, dummy, red);
-    if (tid == 0) A.part[row * A.nblk + blockIdx.x] = dsum;
+    block_sum<1>(dsum, red);
+    if (tid == 0) A.part[row * A.nblk + blockIdx.x] = dsum[0];
 }
 
 // grid (rows).  nk == nullptr: rows too short for one frame.  Thread t adds partials t, t + 256, .. in that order.
 static __global__ __launch_bounds__(WUNET_THREADS) void stoi_final_kernel(const double* part, const int* nk, unsigned nblk, float* out, int* frames)
 {
-    __shared__ double red[2 * WUNET_WAVES];
+    __shared__ double red[WUNET_WAVES];
     const int tid = threadIdx.x;
     const size_t row = blockIdx.x;
     const int n_kept = nk ? nk[row] : 0, nseg = stoi_segments(n_kept);
     const int nb = (nseg + WUNET_STOI_SB - 1) / WUNET_STOI_SB;
-    double s = 0.0, dummy = 0.0;
-    for (int b = tid; b < nb; b += WUNET_THREADS) s += part[row * nblk + b];
-    block_sum2(s, dummy, red);
+    double s[1] = {0.0};
+    for (int b = tid; b < nb; b += WUNET_THREADS) s[0] += part[row * nblk + b];
+    block_sum<1>(s, red);
     if (tid == 0) {
-        out[row] = nseg > 0 ? (float)(s / ((double)nseg * WUNET_STOI_BANDS)) : 1.0e-5f;
+        out[row] = nseg > 0 ? (float)(s[0] / ((double)nseg * WUNET_STOI_BANDS)) : 1.0e-5f;
         if (frames) frames[row] = n_kept > 0 ? n_kept - 1 : 0;
     }
 }

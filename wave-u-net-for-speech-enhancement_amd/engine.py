@@ -82,6 +82,54 @@ def _load_torch_ext():
         return None
 
 
+# ---------------------------------------------------------------------- multi-resolution STFT loss (include/wunet_hip.h: wunet_stft_*)
+STFT_COEFS = 4                       # WUNET_STFT_COEFS of include/wunet_hip.h: a, b, sc, mag per resolution
+STFT_MAX_RESOLUTIONS = 8             # WUNET_STFT_MAX_RESOLUTIONS
+
+
+def check_stft_resolution(n_fft, hop, win_length):
+    """The constraints of one resolution that do not depend on the waveform (what wunet_stft_* refuses with WUNET_E_ARG)."""
+    n_fft, hop, win_length = int(n_fft), int(hop), int(win_length)
+    if n_fft < 16 or n_fft > 4096 or n_fft % 16:
+        raise ValueError(f"stft: n_fft must be a multiple of 16 in 16 .. 4096 (got {n_fft})")
+    if hop < 1 or hop > n_fft:
+        raise ValueError(f"stft: hop must be in 1 .. n_fft (got {hop}, n_fft {n_fft})")
+    if win_length < 1 or win_length > n_fft:
+        raise ValueError(f"stft: win_length must be in 1 .. n_fft (got {win_length}, n_fft {n_fft})")
+    return n_fft, hop, win_length
+
+
+# ---------------------------------------------------------------------- STOI per row (include/wunet_hip.h: wunet_stoi_*)
+STOI_FS = 10000
+_STOI_TAPS = {}                      # sample rate -> (p, q, float32 taps of pystoi's resampler) or None at 10 kHz
+
+
+def stoi_resampler_taps(sample_rate):
+    """pystoi's resampling filter for `sample_rate` -> 10 kHz: (p, q, h) with 10000 / sample_rate = p / q in lowest terms and
+    h[t + L] = kaiser(2 L + 1, 0.1102 (60 - 8.7))[t + L] 2 p fc sinc(2 fc t), fc = 1 / (2 max(p, q)), L = ceil(52 / (28.714 fc / 10)),
+    normalised to sum 1 - computed in float64 with numpy, rounded once to float32, cached per rate.  None at 10 kHz."""
+    fs = int(sample_rate)
+    if fs not in _STOI_TAPS:
+        import math
+        import numpy as np
+        if fs <= 0:
+            raise ValueError(f"stoi: the sample rate must be > 0 (got {sample_rate})")
+        if fs == STOI_FS:
+            _STOI_TAPS[fs] = None
+        else:
+            g = math.gcd(STOI_FS, fs)
+            p, q = STOI_FS // g, fs // g
+            fc = 1.0 / (2.0 * max(p, q))
+            L = int(math.ceil(52.0 / (28.714 * fc / 10.0)))
+            t = np.arange(-L, L + 1, dtype=np.float64)
+            h = np.kaiser(2 * L + 1, 0.1102 * (60.0 - 8.7)) * (2.0 * p * fc * np.sinc(2.0 * fc * t))
+            _STOI_TAPS[fs] = (p, q, (h / h.sum()).astype(np.float32))
+    return _STOI_TAPS[fs]
+
+
+ADAM_HYPER_FLOATS = 8                # WUNET_ADAM_HYPER_FLOATS of include/wunet_hip.h
+
+
 class Engine:
     """One per process is enough (see `default_engine`).  `lib`/`host_memory` exist so the CPU test
     suite can drive the same host logic against the emulator build with CPU tensors; product code
@@ -197,6 +245,26 @@ class Engine:
 
     def _device_guard(self, device):
         return torch.cuda.device(device) if not self.host_memory else _NullCtx()
+
+    def _wave_pair(self, what, clean, other, other_name="enhanced"):
+        """The checks every (clean, other) waveform pair gets; `what` starts the messages.  The last dimension is the row, all leading
+        ones are flattened: returns (rows, T, device)."""
+        self._require(clean, "clean")
+        self._require(other, other_name)
+        if clean.dtype != torch.float32 or other.dtype != torch.float32:
+            raise WunetError(f"{what}: expected float32 waveforms")
+        if clean.shape != other.shape or clean.device != other.device:
+            raise WunetError(f"{what}: shape / device mismatch {tuple(clean.shape)} vs {tuple(other.shape)}")
+        if other.dim() < 1 or other.numel() == 0:
+            raise WunetError(f"{what}: needs at least one row of at least one sample, got {tuple(other.shape)}")
+        T = other.shape[-1]
+        return other.numel() // T, T, other.device
+
+    def _sized(self, nbytes):
+        """The answer of a size query of the C ABI: 0 is a refused shape, and wunet_last_error says why."""
+        if nbytes == 0:
+            raise WunetError(f"wunet error -1: {self.lib.wunet_last_error().decode()}")
+        return nbytes
 
     # ------------------------------------------------------------------ network
     def forward(self, n_layers, ci, noisy, params, running, nbt, training, with_backward, frozen=None):
@@ -358,17 +426,7 @@ class Engine:
         `loss_rows_backward` (None with with_backward=False); per_row_db - float32 [rows] with per_row=True, else None."""
         if kind not in ROW_LOSS_KINDS:
             raise WunetError(f"row loss: unknown kind {kind!r} (one of {sorted(ROW_LOSS_KINDS)})")
-        self._require(clean, "clean")
-        self._require(enhanced, "enhanced")
-        if clean.dtype != torch.float32 or enhanced.dtype != torch.float32:
-            raise WunetError("row loss: expected float32 waveforms")
-        if clean.shape != enhanced.shape or clean.device != enhanced.device:
-            raise WunetError(f"row loss: shape / device mismatch {tuple(clean.shape)} vs {tuple(enhanced.shape)}")
-        if enhanced.dim() < 1 or enhanced.numel() == 0:
-            raise WunetError(f"row loss: needs at least one row of at least one sample, got {tuple(enhanced.shape)}")
-        T = enhanced.shape[-1]
-        R = enhanced.numel() // T
-        dev = enhanced.device
+        R, T, dev = self._wave_pair("row loss", clean, enhanced)
         out = torch.empty((), dtype=torch.float32, device=dev)
         rows = torch.empty(R, dtype=torch.float32, device=dev) if per_row else None
         coefs = torch.empty(R, LOSS_ROW_COEFS, dtype=torch.float64, device=dev) if with_backward else None
@@ -384,346 +442,227 @@ class Engine:
         """d loss / d enhanced of the `loss_rows_forward` of the same kind that produced `coefs`, times grad_loss (a scalar tensor)."""
         if kind not in ROW_LOSS_KINDS:
             raise WunetError(f"row loss: unknown kind {kind!r} (one of {sorted(ROW_LOSS_KINDS)})")
-        self._require(clean, "clean")
-        self._require(enhanced, "enhanced")
-        if clean.dtype != torch.float32 or enhanced.dtype != torch.float32:
-            raise WunetError("row loss: expected float32 waveforms")
-        if clean.shape != enhanced.shape or clean.device != enhanced.device:
-            raise WunetError(f"row loss: shape / device mismatch {tuple(clean.shape)} vs {tuple(enhanced.shape)}")
-        if enhanced.dim() < 1 or enhanced.numel() == 0:
-            raise WunetError(f"row loss: needs at least one row of at least one sample, got {tuple(enhanced.shape)}")
-        T = enhanced.shape[-1]
-        R = enhanced.numel() // T
-        if coefs.dtype != torch.float64 or coefs.numel() != R * LOSS_ROW_COEFS or not coefs.is_contiguous() or coefs.device != enhanced.device:
+        R, T, dev = self._wave_pair("row loss", clean, enhanced)
+        if coefs.dtype != torch.float64 or coefs.numel() != R * LOSS_ROW_COEFS or not coefs.is_contiguous() or coefs.device != dev:
             raise WunetError(f"row loss: coefs must be the float64 [{R}, {LOSS_ROW_COEFS}] tensor of loss_rows_forward")
         g = torch.empty_like(enhanced)
-        gl = grad_loss.to(device=enhanced.device, dtype=torch.float32).contiguous()
-        with self._device_guard(enhanced.device):
+        gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+        with self._device_guard(dev):
             self._check(self.lib.wunet_loss_rows_backward(ROW_LOSS_KINDS[kind], clean.data_ptr(), enhanced.data_ptr(), coefs.data_ptr(), gl.data_ptr(), R, T,
-                                                          g.data_ptr(), self._stream(enhanced.device)))
+                                                          g.data_ptr(), self._stream(dev)))
         return g
 
+    # ------------------------------------------------------------------ multi-resolution STFT loss (wunet_stft_*)
+    def stft_basis(self, n_fft, win_length, device):
+        """The windowed DFT basis of (n_fft, win_length) on `device`, built once: on the first (eager) call, so that a later graph capture
+        sees neither its allocation nor its launch."""
+        key = (n_fft, win_length, str(device))
+        basis = self._stft_bases.get(key)
+        if basis is None:
+            basis = torch.empty(self._sized(self.lib.wunet_stft_basis_bytes(n_fft)) // 4, dtype=torch.float32, device=device)
+            with self._device_guard(device):
+                self._check(self.lib.wunet_stft_basis(n_fft, win_length, basis.data_ptr(), self._stream(device)))
+            self._stft_bases[key] = basis
+        return basis
 
-# ---------------------------------------------------------------------- multi-resolution STFT loss (include/wunet_hip.h: wunet_stft_*)
-STFT_COEFS = 4                       # WUNET_STFT_COEFS of include/wunet_hip.h: a, b, sc, mag per resolution
-STFT_MAX_RESOLUTIONS = 8             # WUNET_STFT_MAX_RESOLUTIONS
+    def stft_loss_forward(self, clean, enhanced, resolutions, sc_weight=1.0, mag_weight=1.0, clamp=1e-7, with_backward=True):
+        """resolutions: a sequence of (n_fft, hop, win_length).  The last dimension is the utterance, all leading ones are flattened.
+        Returns (loss, coefs, saved): loss - device scalar; coefs - float64 [n_res, STFT_COEFS] (a, b, sc, mag per resolution);
+        saved - one float32 buffer per resolution for `stft_loss_backward` (None with with_backward=False)."""
+        R, T, dev = self._wave_pair("stft loss", clean, enhanced)
+        n = len(resolutions)
+        if n < 1 or n > STFT_MAX_RESOLUTIONS:
+            raise WunetError(f"stft loss: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {n})")
+        lib = self.lib
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        coefs = torch.empty(n, STFT_COEFS, dtype=torch.float64, device=dev)
+        scratch, saved = [], []
+        with self._device_guard(dev):
+            st = self._stream(dev)
+            for N, H, W in resolutions:
+                basis = self.stft_basis(N, W, dev)
+                scr = torch.empty(self._sized(lib.wunet_stft_scratch_bytes(R, T, N, H, 0)) // 8, dtype=torch.float64, device=dev)
+                sv = torch.empty(lib.wunet_stft_saved_bytes(R, T, N, H) // 4, dtype=torch.float32, device=dev) if with_backward else None
+                self._check(lib.wunet_stft_forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(clamp), basis.data_ptr(),
+                                                   scr.data_ptr(), sv.data_ptr() if sv is not None else None, None, st))
+                scratch.append(scr)
+                saved.append(sv)
+            self._check(lib.wunet_stft_finalize(n, self._ptrs(scratch), R, T, (ctypes.c_int * n)(*[r[0] for r in resolutions]),
+                                                (ctypes.c_int * n)(*[r[1] for r in resolutions]), float(sc_weight), float(mag_weight),
+                                                out.data_ptr(), coefs.data_ptr(), st))
+        return out, coefs, (saved if with_backward else None)
 
+    def stft_loss_backward(self, shape, resolutions, coefs, saved, grad_loss, clamp=1e-7):
+        """d loss / d enhanced (a tensor of `shape`) of the `stft_loss_forward` that produced `coefs` and `saved`, times grad_loss (a scalar
+        tensor).  The resolutions are added in their order: one fixed order of sums."""
+        n = len(resolutions)
+        if coefs.dtype != torch.float64 or coefs.numel() != n * STFT_COEFS or not coefs.is_contiguous() or saved is None or len(saved) != n:
+            raise WunetError(f"stft loss: coefs / saved must be those of stft_loss_forward over the same {n} resolutions")
+        dev = coefs.device
+        T = shape[-1]
+        g = torch.empty(shape, dtype=torch.float32, device=dev)
+        R = g.numel() // T
+        gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+        lib = self.lib
+        with self._device_guard(dev):
+            st = self._stream(dev)
+            for i, (N, H, W) in enumerate(resolutions):
+                if saved[i].numel() * 4 != lib.wunet_stft_saved_bytes(R, T, N, H) or saved[i].device != dev:
+                    raise WunetError(f"stft loss: saved[{i}] is not the buffer of resolution {(N, H, W)} on {tuple(shape)}")
+                scr = torch.empty(lib.wunet_stft_scratch_bytes(R, T, N, H, 1) // 4, dtype=torch.float32, device=dev)
+                self._check(lib.wunet_stft_backward(saved[i].data_ptr(), coefs.data_ptr() + 8 * STFT_COEFS * i, gl.data_ptr(), R, T, N, H, W,
+                                                    float(clamp), self.stft_basis(N, W, dev).data_ptr(), scr.data_ptr(), g.data_ptr(),
+                                                    1 if i else 0, st))
+        return g
 
-def check_stft_resolution(n_fft, hop, win_length):
-    """The constraints of one resolution that do not depend on the waveform (what wunet_stft_* refuses with WUNET_E_ARG)."""
-    n_fft, hop, win_length = int(n_fft), int(hop), int(win_length)
-    if n_fft < 16 or n_fft > 4096 or n_fft % 16:
-        raise ValueError(f"stft: n_fft must be a multiple of 16 in 16 .. 4096 (got {n_fft})")
-    if hop < 1 or hop > n_fft:
-        raise ValueError(f"stft: hop must be in 1 .. n_fft (got {hop}, n_fft {n_fft})")
-    if win_length < 1 or win_length > n_fft:
-        raise ValueError(f"stft: win_length must be in 1 .. n_fft (got {win_length}, n_fft {n_fft})")
-    return n_fft, hop, win_length
+    def stft_magnitude(self, x, n_fft=320, hop=160, win_length=320):
+        """|STFT| of every row of x (periodic Hann, center=True, reflect padding - torch.stft's conventions): float32 [rows, F, n_fft/2 + 1]."""
+        self._require(x, "x")
+        if x.dtype != torch.float32 or x.dim() < 1 or x.numel() == 0:
+            raise WunetError(f"stft: expected a float32 waveform tensor, got {x.dtype} {tuple(x.shape)}")
+        n_fft, hop, win_length = check_stft_resolution(n_fft, hop, win_length)
+        T = x.shape[-1]
+        R = x.numel() // T
+        dev = x.device
+        if n_fft // 2 > T - 1:
+            raise WunetError(f"stft: reflect padding needs n_fft / 2 <= T - 1 (n_fft {n_fft}, T {T})")
+        F, bins = 1 + T // hop, n_fft // 2 + 1
+        mag = torch.empty(R, F, bins, dtype=torch.float32, device=dev)
+        with self._device_guard(dev):
+            basis = self.stft_basis(n_fft, win_length, dev)
+            self._check(self.lib.wunet_stft_forward(None, x.data_ptr(), R, T, n_fft, hop, win_length, 0.0, basis.data_ptr(), None, None,
+                                                    mag.data_ptr(), self._stream(dev)))
+        return mag
 
+    # ------------------------------------------------------------------ STOI per row (wunet_stoi_*)
+    def stoi_tables(self, sample_rate, device):
+        """The tables of one (sample rate, device) - DFT basis, window, resampler taps - built once: on the first (eager) call, so that a
+        later graph capture sees neither their allocation nor their launch."""
+        key = (int(sample_rate), str(device))
+        tables = self._stoi_tables_cache.get(key)
+        if tables is None:
+            taps = stoi_resampler_taps(sample_rate)
+            tables = torch.empty(self._sized(self.lib.wunet_stoi_tables_bytes(key[0])) // 4, dtype=torch.float32, device=device)
+            h = torch.from_numpy(taps[2]).to(device) if taps is not None else None
+            with self._device_guard(device):
+                self._check(self.lib.wunet_stoi_tables_build(key[0], h.data_ptr() if h is not None else None, h.numel() if h is not None else 0,
+                                                             tables.data_ptr(), self._stream(device)))
+                if h is not None and not self.host_memory:
+                    h.record_stream(torch.cuda.current_stream(device))       # (the copy kernel may still be reading it when h is freed)
+            self._stoi_tables_cache[key] = tables
+        return tables
 
-def _stft_basis(self, n_fft, win_length, device):
-    """The windowed DFT basis of (n_fft, win_length) on `device`, built once: on the first (eager) call, so that a later graph capture
-    sees neither its allocation nor its launch."""
-    key = (n_fft, win_length, str(device))
-    basis = self._stft_bases.get(key)
-    if basis is None:
-        nbytes = self.lib.wunet_stft_basis_bytes(n_fft)
-        if nbytes == 0:
-            raise WunetError(f"wunet error -1: {self.lib.wunet_last_error().decode()}")
-        basis = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-        with self._device_guard(device):
-            self._check(self.lib.wunet_stft_basis(n_fft, win_length, basis.data_ptr(), self._stream(device)))
-        self._stft_bases[key] = basis
-    return basis
+    def stoi(self, clean, estimate, sample_rate=16000, return_frames=False):
+        """include/wunet_hip.h: wunet_stoi_forward.  The last dimension is the utterance, all leading ones are flattened.  Returns float32
+        [rows] (and int32 [rows], the spectral frame count of every row, with return_frames).  Nothing is read back to the host."""
+        R, T, dev = self._wave_pair("stoi", clean, estimate, "estimate")
+        fs = int(sample_rate)
+        tables = self.stoi_tables(fs, dev)
+        scratch = torch.empty(self._sized(self.lib.wunet_stoi_scratch_bytes(R, T, fs)) // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(R, dtype=torch.float32, device=dev)
+        frames = torch.empty(R, dtype=torch.int32, device=dev) if return_frames else None
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_stoi_forward(clean.data_ptr(), estimate.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
+                                                    out.data_ptr(), frames.data_ptr() if frames is not None else None, self._stream(dev)))
+        return (out, frames) if return_frames else out
 
-
-def _stft_pair(self, clean, enhanced):
-    self._require(clean, "clean")
-    self._require(enhanced, "enhanced")
-    if clean.dtype != torch.float32 or enhanced.dtype != torch.float32:
-        raise WunetError("stft loss: expected float32 waveforms")
-    if clean.shape != enhanced.shape or clean.device != enhanced.device:
-        raise WunetError(f"stft loss: shape / device mismatch {tuple(clean.shape)} vs {tuple(enhanced.shape)}")
-    if enhanced.dim() < 1 or enhanced.numel() == 0:
-        raise WunetError(f"stft loss: needs at least one row of at least one sample, got {tuple(enhanced.shape)}")
-    T = enhanced.shape[-1]
-    return enhanced.numel() // T, T
-
-
-def _stft_loss_forward(self, clean, enhanced, resolutions, sc_weight=1.0, mag_weight=1.0, clamp=1e-7, with_backward=True):
-    """resolutions: a sequence of (n_fft, hop, win_length).  The last dimension is the utterance, all leading ones are flattened.
-    Returns (loss, coefs, saved): loss - device scalar; coefs - float64 [n_res, STFT_COEFS] (a, b, sc, mag per resolution);
-    saved - one float32 buffer per resolution for `stft_loss_backward` (None with with_backward=False)."""
-    R, T = self._stft_pair(clean, enhanced)
-    n = len(resolutions)
-    if n < 1 or n > STFT_MAX_RESOLUTIONS:
-        raise WunetError(f"stft loss: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {n})")
-    dev = enhanced.device
-    lib = self.lib
-    out = torch.empty((), dtype=torch.float32, device=dev)
-    coefs = torch.empty(n, STFT_COEFS, dtype=torch.float64, device=dev)
-    scratch, saved = [], []
-    with self._device_guard(dev):
-        st = self._stream(dev)
-        for N, H, W in resolutions:
-            basis = self.stft_basis(N, W, dev)
-            nbytes = lib.wunet_stft_scratch_bytes(R, T, N, H, 0)
-            if nbytes == 0:
-                raise WunetError(f"wunet error -1: {lib.wunet_last_error().decode()}")
-            scr = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-            sv = torch.empty(lib.wunet_stft_saved_bytes(R, T, N, H) // 4, dtype=torch.float32, device=dev) if with_backward else None
-            self._check(lib.wunet_stft_forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(clamp), basis.data_ptr(),
-                                               scr.data_ptr(), sv.data_ptr() if sv is not None else None, None, st))
-            scratch.append(scr)
-            saved.append(sv)
-        self._check(lib.wunet_stft_finalize(n, self._ptrs(scratch), R, T, (ctypes.c_int * n)(*[r[0] for r in resolutions]),
-                                            (ctypes.c_int * n)(*[r[1] for r in resolutions]), float(sc_weight), float(mag_weight),
-                                            out.data_ptr(), coefs.data_ptr(), st))
-    return out, coefs, (saved if with_backward else None)
-
-
-def _stft_loss_backward(self, shape, resolutions, coefs, saved, grad_loss, clamp=1e-7):
-    """d loss / d enhanced (a tensor of `shape`) of the `stft_loss_forward` that produced `coefs` and `saved`, times grad_loss (a scalar
-    tensor).  The resolutions are added in their order: one fixed order of sums."""
-    n = len(resolutions)
-    if coefs.dtype != torch.float64 or coefs.numel() != n * STFT_COEFS or not coefs.is_contiguous() or saved is None or len(saved) != n:
-        raise WunetError(f"stft loss: coefs / saved must be those of stft_loss_forward over the same {n} resolutions")
-    dev = coefs.device
-    T = shape[-1]
-    g = torch.empty(shape, dtype=torch.float32, device=dev)
-    R = g.numel() // T
-    gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
-    lib = self.lib
-    with self._device_guard(dev):
-        st = self._stream(dev)
-        for i, (N, H, W) in enumerate(resolutions):
-            if saved[i].numel() * 4 != lib.wunet_stft_saved_bytes(R, T, N, H) or saved[i].device != dev:
-                raise WunetError(f"stft loss: saved[{i}] is not the buffer of resolution {(N, H, W)} on {tuple(shape)}")
-            scr = torch.empty(lib.wunet_stft_scratch_bytes(R, T, N, H, 1) // 4, dtype=torch.float32, device=dev)
-            self._check(lib.wunet_stft_backward(saved[i].data_ptr(), coefs.data_ptr() + 8 * STFT_COEFS * i, gl.data_ptr(), R, T, N, H, W,
-                                                float(clamp), self.stft_basis(N, W, dev).data_ptr(), scr.data_ptr(), g.data_ptr(),
-                                                1 if i else 0, st))
-    return g
-
-
-def _stft_magnitude(self, x, n_fft=320, hop=160, win_length=320):
-    """|STFT| of every row of x (periodic Hann, center=True, reflect padding - torch.stft's conventions): float32 [rows, F, n_fft/2 + 1]."""
-    self._require(x, "x")
-    if x.dtype != torch.float32 or x.dim() < 1 or x.numel() == 0:
-        raise WunetError(f"stft: expected a float32 waveform tensor, got {x.dtype} {tuple(x.shape)}")
-    n_fft, hop, win_length = check_stft_resolution(n_fft, hop, win_length)
-    T = x.shape[-1]
-    R = x.numel() // T
-    dev = x.device
-    if n_fft // 2 > T - 1:
-        raise WunetError(f"stft: reflect padding needs n_fft / 2 <= T - 1 (n_fft {n_fft}, T {T})")
-    F, bins = 1 + T // hop, n_fft // 2 + 1
-    mag = torch.empty(R, F, bins, dtype=torch.float32, device=dev)
-    with self._device_guard(dev):
-        basis = self.stft_basis(n_fft, win_length, dev)
-        self._check(self.lib.wunet_stft_forward(None, x.data_ptr(), R, T, n_fft, hop, win_length, 0.0, basis.data_ptr(), None, None,
-                                                mag.data_ptr(), self._stream(dev)))
-    return mag
-
-
-Engine.stft_basis = _stft_basis
-Engine._stft_pair = _stft_pair
-Engine.stft_loss_forward = _stft_loss_forward
-Engine.stft_loss_backward = _stft_loss_backward
-Engine.stft_magnitude = _stft_magnitude
-
-
-# ---------------------------------------------------------------------- STOI per row (include/wunet_hip.h: wunet_stoi_*)
-STOI_FS = 10000
-_STOI_TAPS = {}                      # sample rate -> (p, q, float32 taps of pystoi's resampler) or None at 10 kHz
-
-
-def stoi_resampler_taps(sample_rate):
-    """pystoi's resampling filter for `sample_rate` -> 10 kHz: (p, q, h) with 10000 / sample_rate = p / q in lowest terms and
-    h[t + L] = kaiser(2 L + 1, 0.1102 (60 - 8.7))[t + L] 2 p fc sinc(2 fc t), fc = 1 / (2 max(p, q)), L = ceil(52 / (28.714 fc / 10)),
-    normalised to sum 1 - computed in float64 with numpy, rounded once to float32, cached per rate.  None at 10 kHz."""
-    fs = int(sample_rate)
-    if fs not in _STOI_TAPS:
-        import math
-        import numpy as np
-        if fs <= 0:
-            raise ValueError(f"stoi: the sample rate must be > 0 (got {sample_rate})")
-        if fs == STOI_FS:
-            _STOI_TAPS[fs] = None
-        else:
-            g = math.gcd(STOI_FS, fs)
-            p, q = STOI_FS // g, fs // g
-            fc = 1.0 / (2.0 * max(p, q))
-            L = int(math.ceil(52.0 / (28.714 * fc / 10.0)))
-            t = np.arange(-L, L + 1, dtype=np.float64)
-            h = np.kaiser(2 * L + 1, 0.1102 * (60.0 - 8.7)) * (2.0 * p * fc * np.sinc(2.0 * fc * t))
-            _STOI_TAPS[fs] = (p, q, (h / h.sum()).astype(np.float32))
-    return _STOI_TAPS[fs]
-
-
-def _stoi_tables(self, sample_rate, device):
-    """The tables of one (sample rate, device) - DFT basis, window, resampler taps - built once: on the first (eager) call, so that a
-    later graph capture sees neither their allocation nor their launch."""
-    key = (int(sample_rate), str(device))
-    tables = self._stoi_tables_cache.get(key)
-    if tables is None:
-        taps = stoi_resampler_taps(sample_rate)
-        nbytes = self.lib.wunet_stoi_tables_bytes(key[0])
-        if nbytes == 0:
-            raise WunetError(f"wunet error -1: {self.lib.wunet_last_error().decode()}")
-        tables = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-        h = torch.from_numpy(taps[2]).to(device) if taps is not None else None
-        with self._device_guard(device):
-            self._check(self.lib.wunet_stoi_tables_build(key[0], h.data_ptr() if h is not None else None, h.numel() if h is not None else 0,
-                                                         tables.data_ptr(), self._stream(device)))
-            if h is not None and not self.host_memory:
-                h.record_stream(torch.cuda.current_stream(device))       # (the copy kernel may still be reading it when h is freed)
-        self._stoi_tables_cache[key] = tables
-    return tables
-
-
-def _stoi(self, clean, estimate, sample_rate=16000, return_frames=False):
-    """include/wunet_hip.h: wunet_stoi_forward.  The last dimension is the utterance, all leading ones are flattened.  Returns float32
-    [rows] (and int32 [rows], the spectral frame count of every row, with return_frames).  Nothing is read back to the host."""
-    self._require(clean, "clean")
-    self._require(estimate, "estimate")
-    if clean.dtype != torch.float32 or estimate.dtype != torch.float32:
-        raise WunetError("stoi: expected float32 waveforms")
-    if clean.shape != estimate.shape or clean.device != estimate.device:
-        raise WunetError(f"stoi: shape / device mismatch {tuple(clean.shape)} vs {tuple(estimate.shape)}")
-    if estimate.dim() < 1 or estimate.numel() == 0:
-        raise WunetError(f"stoi: needs at least one row of at least one sample, got {tuple(estimate.shape)}")
-    fs = int(sample_rate)
-    T = estimate.shape[-1]
-    R = estimate.numel() // T
-    dev = estimate.device
-    tables = self.stoi_tables(fs, dev)
-    nbytes = self.lib.wunet_stoi_scratch_bytes(R, T, fs)
-    if nbytes == 0:
-        raise WunetError(f"wunet error -1: {self.lib.wunet_last_error().decode()}")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    out = torch.empty(R, dtype=torch.float32, device=dev)
-    frames = torch.empty(R, dtype=torch.int32, device=dev) if return_frames else None
-    with self._device_guard(dev):
-        self._check(self.lib.wunet_stoi_forward(clean.data_ptr(), estimate.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
-                                                out.data_ptr(), frames.data_ptr() if frames is not None else None, self._stream(dev)))
-    return (out, frames) if return_frames else out
-
-
-Engine.stoi_tables = _stoi_tables
-Engine.stoi = _stoi
-
-
-def _adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, hyper_dev=None, *,
-               weight_decay=0.0, max_grad_norm=None, lr_dev=None, scratch=None):
-    """One fused Adam step over a list of tensors.  step_dev (int64 device scalar) + hyper_dev (2 floats):
-    the step count lives on the device and the call increments it (capturable in a hipGraph); otherwise `step` is the host's.
-    Keyword arguments (include/wunet_hip.h: wunet_adam_step_ex; with all of them off the call is wunet_adam_step as before):
-    weight_decay - decoupled (AdamW); max_grad_norm - clipping by the global norm inside the step, `scratch` then holds
-    adam_scratch_bytes(len(params)) bytes (p.grad is NOT modified); lr_dev - a float64 device scalar the learning rate is read from.
-    Any of them needs hyper_dev with ADAM_HYPER_FLOATS floats: [2] clip, [3] the norm before clipping, [4] 1 - lr * weight_decay."""
-    ex = bool(weight_decay) or max_grad_norm is not None or lr_dev is not None
-    if ex:
-        clip = float(max_grad_norm) if max_grad_norm is not None else 0.0
-        if max_grad_norm is not None and not clip > 0.0:
-            raise WunetError(f"adam_step: max_grad_norm must be > 0 (got {max_grad_norm}); None turns clipping off")
-        if hyper_dev is None or hyper_dev.dtype != torch.float32 or hyper_dev.numel() < ADAM_HYPER_FLOATS or not hyper_dev.is_contiguous():
-            raise WunetError(f"adam_step: weight_decay / max_grad_norm / lr_dev need hyper_dev with {ADAM_HYPER_FLOATS} float32")
-        if lr_dev is not None and (lr_dev.dtype != torch.float64 or lr_dev.numel() != 1):
-            raise WunetError("adam_step: lr_dev must be ONE float64")
-        if clip > 0.0 and (scratch is None or scratch.numel() * scratch.element_size() < self.adam_scratch_bytes(len(params))):
-            raise WunetError("adam_step: max_grad_norm needs `scratch` of adam_scratch_bytes(len(params)) bytes")
-        extra = [t for t in (step_dev, hyper_dev, lr_dev, scratch) if t is not None]
-        if any(t.device != params[0].device for t in extra):
-            raise WunetError("adam_step: step_dev / hyper_dev / lr_dev / scratch must live on the parameters' device")
-    if self._fast is not None:
-        try:
-            if ex:
-                self._fast.adam_step_ex(params, grads, exp_avg, exp_avg_sq, float(lr), float(beta1), float(beta2), float(eps), int(step),
-                                        float(grad_scale), float(weight_decay), clip, step_dev, hyper_dev, lr_dev, scratch)
-            else:
-                self._fast.adam_step(params, grads, exp_avg, exp_avg_sq, float(lr), float(beta1), float(beta2), float(eps), int(step),
-                                     float(grad_scale), step_dev, hyper_dev)
-        except RuntimeError as e:
-            raise WunetError(str(e).split("\n")[0]) from None
-        return
-    for name, ts in (("param", params), ("grad", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
-        self._require_all(ts, "adam " + name, params[0].device)
-    n = len(params)
-    numels = (ctypes.c_size_t * n)(*[p.numel() for p in params])
-    dev = params[0].device
-    ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
-    with self._device_guard(dev):
+    # ------------------------------------------------------------------ fused Adam, data input
+    def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, hyper_dev=None, *,
+                  weight_decay=0.0, max_grad_norm=None, lr_dev=None, scratch=None):
+        """One fused Adam step over a list of tensors.  step_dev (int64 device scalar) + hyper_dev (2 floats):
+        the step count lives on the device and the call increments it (capturable in a hipGraph); otherwise `step` is the host's.
+        Keyword arguments (include/wunet_hip.h: wunet_adam_step_ex; with all of them off the call is wunet_adam_step as before):
+        weight_decay - decoupled (AdamW); max_grad_norm - clipping by the global norm inside the step, `scratch` then holds
+        adam_scratch_bytes(len(params)) bytes (p.grad is NOT modified); lr_dev - a float64 device scalar the learning rate is read from.
+        Any of them needs hyper_dev with ADAM_HYPER_FLOATS floats: [2] clip, [3] the norm before clipping, [4] 1 - lr * weight_decay."""
+        ex = bool(weight_decay) or max_grad_norm is not None or lr_dev is not None
         if ex:
-            self._check(self.lib.wunet_adam_step_ex(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg), self._ptrs(exp_avg_sq),
-                                                    numels, float(lr), float(beta1), float(beta2), float(eps), int(step),
-                                                    float(grad_scale), float(weight_decay), clip, ptr(step_dev), ptr(hyper_dev),
-                                                    ptr(lr_dev), ptr(scratch), self._stream(dev)))
-        else:
-            self._check(self.lib.wunet_adam_step(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg),
-                                                 self._ptrs(exp_avg_sq), numels, float(lr), float(beta1), float(beta2),
-                                                 float(eps), int(step), float(grad_scale), ptr(step_dev), ptr(hyper_dev), self._stream(dev)))
+            clip = float(max_grad_norm) if max_grad_norm is not None else 0.0
+            if max_grad_norm is not None and not clip > 0.0:
+                raise WunetError(f"adam_step: max_grad_norm must be > 0 (got {max_grad_norm}); None turns clipping off")
+            if hyper_dev is None or hyper_dev.dtype != torch.float32 or hyper_dev.numel() < ADAM_HYPER_FLOATS or not hyper_dev.is_contiguous():
+                raise WunetError(f"adam_step: weight_decay / max_grad_norm / lr_dev need hyper_dev with {ADAM_HYPER_FLOATS} float32")
+            if lr_dev is not None and (lr_dev.dtype != torch.float64 or lr_dev.numel() != 1):
+                raise WunetError("adam_step: lr_dev must be ONE float64")
+            if clip > 0.0 and (scratch is None or scratch.numel() * scratch.element_size() < self.adam_scratch_bytes(len(params))):
+                raise WunetError("adam_step: max_grad_norm needs `scratch` of adam_scratch_bytes(len(params)) bytes")
+            extra = [t for t in (step_dev, hyper_dev, lr_dev, scratch) if t is not None]
+            if any(t.device != params[0].device for t in extra):
+                raise WunetError("adam_step: step_dev / hyper_dev / lr_dev / scratch must live on the parameters' device")
+        if self._fast is not None:
+            try:
+                if ex:
+                    self._fast.adam_step_ex(params, grads, exp_avg, exp_avg_sq, float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                            float(grad_scale), float(weight_decay), clip, step_dev, hyper_dev, lr_dev, scratch)
+                else:
+                    self._fast.adam_step(params, grads, exp_avg, exp_avg_sq, float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                         float(grad_scale), step_dev, hyper_dev)
+            except RuntimeError as e:
+                raise WunetError(str(e).split("\n")[0]) from None
+            return
+        for name, ts in (("param", params), ("grad", grads), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
+            self._require_all(ts, "adam " + name, params[0].device)
+        n = len(params)
+        numels = (ctypes.c_size_t * n)(*[p.numel() for p in params])
+        dev = params[0].device
+        ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
+        with self._device_guard(dev):
+            if ex:
+                self._check(self.lib.wunet_adam_step_ex(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg), self._ptrs(exp_avg_sq),
+                                                        numels, float(lr), float(beta1), float(beta2), float(eps), int(step),
+                                                        float(grad_scale), float(weight_decay), clip, ptr(step_dev), ptr(hyper_dev),
+                                                        ptr(lr_dev), ptr(scratch), self._stream(dev)))
+            else:
+                self._check(self.lib.wunet_adam_step(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg),
+                                                     self._ptrs(exp_avg_sq), numels, float(lr), float(beta1), float(beta2),
+                                                     float(eps), int(step), float(grad_scale), ptr(step_dev), ptr(hyper_dev), self._stream(dev)))
 
+    def adam_scratch_bytes(self, n_tensors):
+        """Device bytes of the partial sums of the gradient norm (adam_step(max_grad_norm=...)) over n_tensors tensors."""
+        return int(self.lib.wunet_adam_scratch_bytes(int(n_tensors)))
 
-def _adam_scratch_bytes(self, n_tensors):
-    """Device bytes of the partial sums of the gradient norm (adam_step(max_grad_norm=...)) over n_tensors tensors."""
-    return int(self.lib.wunet_adam_scratch_bytes(int(n_tensors)))
+    def crop_windows(self, mixture_flat, clean_flat, starts, mixture, clean):
+        """mixture[b, 0, :] = mixture_flat[starts[b] : starts[b] + L], clean likewise (one launch for the batch)."""
+        for t in (mixture_flat, clean_flat, starts, mixture, clean):
+            self._require(t, "crop tensor")
+        if starts.dtype != torch.int64 or mixture_flat.dtype != torch.float32 or mixture.dtype != torch.float32:
+            raise WunetError("crop_windows: float32 arrays and int64 starts expected")
+        if mixture_flat.numel() != clean_flat.numel() or mixture.shape != clean.shape or starts.numel() != mixture.shape[0]:
+            raise WunetError("crop_windows: shape mismatch")
+        B, L = mixture.shape[0], mixture.shape[-1]
+        with self._device_guard(mixture.device):
+            self._check(self.lib.wunet_crop_windows(mixture_flat.data_ptr(), clean_flat.data_ptr(), starts.data_ptr(), mixture_flat.numel(),
+                                                    B, L, mixture.data_ptr(), clean.data_ptr(), self._stream(mixture.device)))
 
-
-ADAM_HYPER_FLOATS = 8                # WUNET_ADAM_HYPER_FLOATS of include/wunet_hip.h
-Engine.adam_scratch_bytes = _adam_scratch_bytes
-Engine.adam_step = _adam_step
-
-
-def _crop_windows(self, mixture_flat, clean_flat, starts, mixture, clean):
-    """mixture[b, 0, :] = mixture_flat[starts[b] : starts[b] + L], clean likewise (one launch for the batch)."""
-    for t in (mixture_flat, clean_flat, starts, mixture, clean):
-        self._require(t, "crop tensor")
-    if starts.dtype != torch.int64 or mixture_flat.dtype != torch.float32 or mixture.dtype != torch.float32:
-        raise WunetError("crop_windows: float32 arrays and int64 starts expected")
-    if mixture_flat.numel() != clean_flat.numel() or mixture.shape != clean.shape or starts.numel() != mixture.shape[0]:
-        raise WunetError("crop_windows: shape mismatch")
-    B, L = mixture.shape[0], mixture.shape[-1]
-    with self._device_guard(mixture.device):
-        self._check(self.lib.wunet_crop_windows(mixture_flat.data_ptr(), clean_flat.data_ptr(), starts.data_ptr(), mixture_flat.numel(),
-                                                B, L, mixture.data_ptr(), clean.data_ptr(), self._stream(mixture.device)))
-
-
-Engine.crop_windows = _crop_windows
-
-
-def _mix_windows(self, clean_flat, noise_flat, rows, params, mixture, clean_out, gains=None, peak_limit=0.99):
-    """include/wunet_hip.h: wunet_mix_windows.  mixture[b, 0, :] = a (c + g n), clean_out[b, 0, :] = a c for the clean window and the
-    circular noise window that rows[b] = (clean start, noise item start, noise item length, noise phase) names, at params[b] =
-    (snr_db, linear level); gains (optional float32 [B, 2]) receives (g, a).  Two launches, nothing read back; the scratch comes from
-    torch's allocator."""
-    f32 = torch.float32
-    if rows.dtype != torch.int64 or any(t.dtype != f32 for t in (clean_flat, noise_flat, params, mixture, clean_out)) or \
-            (gains is not None and gains.dtype != f32):
-        raise WunetError("mix_windows: float32 arrays, params, outputs and gains and int64 rows expected")
-    for t in (clean_flat, noise_flat, rows, params, mixture, clean_out) + ((gains,) if gains is not None else ()):
-        self._require(t, "mix tensor")
-    if clean_flat.dim() != 1 or noise_flat.dim() != 1 or mixture.dim() < 2:
-        raise WunetError("mix_windows: the two arrays must be flat and the outputs [B, ..., L]")
-    B, L = mixture.shape[0], mixture.shape[-1]
-    if mixture.shape != clean_out.shape or mixture.numel() != B * L or tuple(rows.shape) != (B, 4) or tuple(params.shape) != (B, 2) or \
-            (gains is not None and tuple(gains.shape) != (B, 2)):
-        raise WunetError("mix_windows: shape mismatch (rows [B, 4], params [B, 2], gains [B, 2], outputs [B, 1, L])")
-    dev = mixture.device
-    if any(t.device != dev for t in (clean_flat, noise_flat, rows, params, clean_out)) or (gains is not None and gains.device != dev):
-        raise WunetError("mix_windows: every tensor must live on the outputs' device")
-    nbytes = self.lib.wunet_mix_scratch_bytes(B, L)
-    if nbytes == 0:
-        raise WunetError(f"mix_windows: bad shape (batch={B} length={L})")
-    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
-    with self._device_guard(dev):
-        self._check(self.lib.wunet_mix_windows(clean_flat.data_ptr(), clean_flat.numel(), noise_flat.data_ptr(), noise_flat.numel(),
-                                               rows.data_ptr(), params.data_ptr(), float(peak_limit), B, L, scratch.data_ptr(),
-                                               mixture.data_ptr(), clean_out.data_ptr(), gains.data_ptr() if gains is not None else None,
-                                               self._stream(dev)))
-
-
-Engine.mix_windows = _mix_windows
+    def mix_windows(self, clean_flat, noise_flat, rows, params, mixture, clean_out, gains=None, peak_limit=0.99):
+        """include/wunet_hip.h: wunet_mix_windows.  mixture[b, 0, :] = a (c + g n), clean_out[b, 0, :] = a c for the clean window and the
+        circular noise window that rows[b] = (clean start, noise item start, noise item length, noise phase) names, at params[b] =
+        (snr_db, linear level); gains (optional float32 [B, 2]) receives (g, a).  Two launches, nothing read back; the scratch comes from
+        torch's allocator."""
+        f32 = torch.float32
+        if rows.dtype != torch.int64 or any(t.dtype != f32 for t in (clean_flat, noise_flat, params, mixture, clean_out)) or \
+                (gains is not None and gains.dtype != f32):
+            raise WunetError("mix_windows: float32 arrays, params, outputs and gains and int64 rows expected")
+        for t in (clean_flat, noise_flat, rows, params, mixture, clean_out) + ((gains,) if gains is not None else ()):
+            self._require(t, "mix tensor")
+        if clean_flat.dim() != 1 or noise_flat.dim() != 1 or mixture.dim() < 2:
+            raise WunetError("mix_windows: the two arrays must be flat and the outputs [B, ..., L]")
+        B, L = mixture.shape[0], mixture.shape[-1]
+        if mixture.shape != clean_out.shape or mixture.numel() != B * L or tuple(rows.shape) != (B, 4) or tuple(params.shape) != (B, 2) or \
+                (gains is not None and tuple(gains.shape) != (B, 2)):
+            raise WunetError("mix_windows: shape mismatch (rows [B, 4], params [B, 2], gains [B, 2], outputs [B, 1, L])")
+        dev = mixture.device
+        if any(t.device != dev for t in (clean_flat, noise_flat, rows, params, clean_out)) or (gains is not None and gains.device != dev):
+            raise WunetError("mix_windows: every tensor must live on the outputs' device")
+        nbytes = self.lib.wunet_mix_scratch_bytes(B, L)
+        if nbytes == 0:
+            raise WunetError(f"mix_windows: bad shape (batch={B} length={L})")
+        scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_mix_windows(clean_flat.data_ptr(), clean_flat.numel(), noise_flat.data_ptr(), noise_flat.numel(),
+                                                   rows.data_ptr(), params.data_ptr(), float(peak_limit), B, L, scratch.data_ptr(),
+                                                   mixture.data_ptr(), clean_out.data_ptr(), gains.data_ptr() if gains is not None else None,
+                                                   self._stream(dev)))
 
 
 class _CtxHold:
