@@ -1,0 +1,179 @@
+#!/usr/bin/env python
+"""Two builds of the emulator library (tests/emu/libwunet_emu.so) against each other, bit for bit, in one process.
+
+    python tools/emu_lib_ab.py BASE.so [NEW.so]        (NEW defaults to tests/emu/libwunet_emu.so, built if missing)
+
+For a refactor of the host path: both libraries run the case table below through Engine(lib=..., host_memory=True) and every
+result is compared with np.array_equal - output, loss, every parameter gradient, the input gradient, the running statistics and
+num_batches_tracked - and so is the text of wunet_profile_collect with the profiler on (kernel names and launch counts; the
+emulator build reports no flops / bytes).  Planner switches are read when a context is planned: every run gets its own engine.
+Exit status 0: nothing differs."""
+import ctypes
+import importlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+PKG = "wave-u-net-for-speech-enhancement_amd"
+from oracle import plan                                   # noqa: E402
+
+eng_mod = importlib.import_module(PKG + ".engine")
+lib_mod = importlib.import_module(PKG + "._lib")
+model_mod = importlib.import_module(PKG + ".model")
+loss_mod = importlib.import_module(PKG + ".loss")
+
+SWITCHES = ("WUNET_NO_EVOP", "WUNET_NO_SKIP_FUSE", "WUNET_H3U", "WUNET_H3_NOSPLIT", "WUNET_H3_GRID")
+
+
+def masks(n):
+    """The frozen masks of tests/test_frozen_bn_emu.py's kinds: the first layer, a decoder layer's producers (the middle layer feeds
+    decoder 0's upsampled half, encoder n - 1 its skip half), every layer."""
+    nl = 2 * n + 1
+    return {"first": [i == 0 for i in range(nl)], "producer": [i in (n - 1, n) for i in range(nl)], "all": [True] * nl}
+
+
+def cases():
+    """(shape, h3, mode, frozen mask name, switches).  Modes: train (saving forward + backward + input gradient), train_nosave
+    (training forward, save_for_backward 0), eval, eval_cached (a second eval forward with WUNET_FWD_PACKS_VALID)."""
+    out = []
+    # fp32 kernels and the split kernels on the small nets; (2, 24, 1, 1024): conv_first_kernel, every level on the split path
+    for shape in [(2, 4, 2, 32), (3, 8, 3, 64), (2, 24, 1, 1024)]:
+        for h3 in (0, 2):
+            for mode in ("train", "train_nosave", "eval", "eval_cached"):
+                out.append((shape, h3, mode, None, {}))
+    # levels of 1 and 2 samples: the scalar kernels (middle level of 2 samples: (3, 8, 2, 16); of 1: (4, 4, 2, 16))
+    for shape in [(3, 8, 2, 16), (4, 4, 2, 16)]:
+        for mode in ("train", "eval"):
+            out.append((shape, 0, mode, None, {}))
+    # EVOP, the skip hand-off and conv_h3u_kernel, each with its switch
+    for shape, grid in [((3, 24, 3, 2048), ""), ((4, 16, 3, 4096), "8")]:
+        base = {"WUNET_H3_NOSPLIT": "1"}
+        if grid:
+            base["WUNET_H3_GRID"] = grid
+        for sw in [{}, {"WUNET_NO_EVOP": "1"}, {"WUNET_NO_SKIP_FUSE": "1"}, {"WUNET_H3U": "0"}, {"WUNET_H3U": "256,256"}]:
+            for mode in ("eval", "train"):
+                out.append((shape, 2, mode, None, dict(base, **sw)))
+        out.append((shape, 2, "eval_cached", None, base))
+        out.append((shape, 2, "train_nosave", None, dict(base, WUNET_H3U="256,256")))
+    # padded lengths: every conv through conv_reduce_bn_kernel, no EVOP, no conv_h3u_kernel
+    for shape, h3 in [((3, 8, 2, 96), 0), ((3, 8, 2, 96), 2), ((3, 16, 3, 768), 2), ((2, 24, 3, 1536), 2)]:
+        for mode in ("train", "eval"):
+            out.append((shape, h3, mode, None, {}))
+    # bf16 operands
+    for mode in ("train", "eval"):
+        out.append(((3, 24, 3, 2048), 4, mode, None, {"WUNET_H3_NOSPLIT": "1"}))
+    # frozen BatchNorm layers inside a training forward
+    for shape, h3, sw in [((3, 8, 3, 64), 0, {}), ((2, 24, 1, 1024), 2, {}), ((3, 24, 3, 2048), 2, {"WUNET_H3_NOSPLIT": "1"}),
+                          ((3, 24, 3, 2048), 2, {"WUNET_H3_NOSPLIT": "1", "WUNET_H3U": "256,256"})]:
+        for name in ("first", "producer", "all"):
+            out.append((shape, h3, "train", name, sw))
+            out.append((shape, h3, "train_nosave", name, sw))
+    return out
+
+
+def profile_text(lib):
+    buf = ctypes.create_string_buffer(1 << 16)
+    lib.wunet_profile_collect(buf, len(buf))
+    lib.wunet_profile_enable(0)
+    return buf.value.decode()
+
+
+def run_case(lib, shape, h3, mode, mask_name, switches):
+    n, ci, B, T = shape
+    for k in SWITCHES:
+        os.environ.pop(k, None)
+    os.environ.update(switches)
+    eng = eng_mod.Engine(lib=lib, host_memory=True, h3=h3)
+    sd = plan.golden_state(n, ci, 0)
+    noisy, clean = plan.golden_batch(B, T, 0)
+    m = model_mod.Model(n_layers=n, channels_interval=ci, input_grad=True)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()})
+    m._engine_override = eng
+    res = {}
+    lib.wunet_profile_enable(1)
+    try:
+        if mode in ("eval", "eval_cached"):
+            m.eval()
+            params = m._wunet_params()
+            running, nbt = m._wunet_buffers()
+            x = torch.from_numpy(noisy)
+            with torch.no_grad():
+                out, ws = eng.forward(n, ci, x, params, running, nbt, False, False)
+                res["out"] = out.numpy().copy()
+                if mode == "eval_cached":
+                    # the engine only caches device workspaces: the second forward on the first one's packs through the C ABI
+                    out2 = torch.empty_like(x)
+                    with eng._using(n, ci, B, T, x.device) as h:
+                        eng._check(lib.wunet_forward(h, x.data_ptr(), eng._ptrs(params), eng._ptrs(running), eng._ptrs(nbt), 0, 2,
+                                                     ws.data_ptr(), out2.data_ptr(), None))
+                    res["out_cached"] = out2.numpy().copy()
+        else:
+            m.train()
+            if mask_name:
+                for (_, bn), f in zip(m._leaves(), masks(n)[mask_name]):
+                    bn.train(not f)
+            if mode == "train_nosave":
+                with torch.no_grad():
+                    res["out"] = m(torch.from_numpy(noisy)).numpy().copy()
+            else:
+                crit = loss_mod.mse_loss()
+                crit._engine_override = eng
+                x = torch.from_numpy(noisy).requires_grad_(True)
+                out = m(x)
+                lv = crit(torch.from_numpy(clean), out)
+                lv.backward()
+                res["out"] = out.detach().numpy().copy()
+                res["loss"] = np.float64(lv.item())
+                res["grad_input"] = x.grad.numpy().copy()
+                for k, p in m.named_parameters():
+                    res["grad " + k] = p.grad.numpy().copy()
+        for k, v in m.state_dict().items():
+            if "running" in k or "num_batches" in k:
+                res["buffer " + k] = v.numpy().copy()
+    finally:
+        res["profile"] = profile_text(lib)
+    return res
+
+
+def main():
+    if len(sys.argv) < 2:
+        sys.exit(__doc__)
+    base_path = os.path.realpath(sys.argv[1])
+    if len(sys.argv) > 2:
+        new_path = os.path.realpath(sys.argv[2])
+    else:
+        import emu_lib
+        emu_lib.lib()
+        new_path = os.path.realpath(os.path.join(ROOT, "tests", "emu", "libwunet_emu.so"))
+    assert base_path != new_path, "the two libraries are one file"
+    libs = [lib_mod.declare(ctypes.CDLL(p)) for p in (base_path, new_path)]
+    assert libs[0]._handle != libs[1]._handle
+    for L in libs:
+        L.wunet_last_error.restype = ctypes.c_char_p
+        L.wunet_workspace_bytes.restype = ctypes.c_size_t
+    differing, kernels = 0, set()
+    table = cases()
+    for shape, h3, mode, mask_name, switches in table:
+        a, b = (run_case(L, shape, h3, mode, mask_name, switches) for L in libs)
+        bad = [k for k in a if k not in b or not np.array_equal(a[k], b[k])] + [k for k in b if k not in a]
+        kernels.update(ln.split("\t")[0] for ln in b["profile"].splitlines())
+        tag = " ".join(f"{k}={v}" for k, v in switches.items())
+        print(f"{'DIFF' if bad else 'same'}  {shape} h3={h3} {mode}{' frozen=' + mask_name if mask_name else ''} {tag}  "
+              f"[{len(a) - 1} arrays, {len(a['profile'].splitlines())} kernel names]", flush=True)
+        for k in bad:
+            print("      differs:", k)
+            if k == "profile":
+                print("      base:", a[k].replace("\n", " | "))
+                print("      new: ", b[k].replace("\n", " | "))
+        differing += bool(bad)
+    print("kernel names seen:", ", ".join(sorted(kernels)))
+    print(f"{len(table)} cases, {differing} differing")
+    return 1 if differing else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

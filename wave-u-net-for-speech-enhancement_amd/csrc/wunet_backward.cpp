@@ -262,8 +262,7 @@ int finalize_and_gz(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
     if (q.gz_h3) {
         const int c8 = (l.cout + 7) / 8;
         const size_t nt = (size_t)c->B * c8 * (l.L / 4);
-        size_t hb = (nt + WUNET_THREADS - 1) / WUNET_THREADS;
-        if (hb > 8192) hb = 8192;
+        const unsigned hb = capped_blocks(nt, WUNET_THREADS, 8192);
         prof_begin(st, "gz_split_h3_kernel", 0.0, (double)c->B * l.cout * l.L * (q.gz_bytes() + (c->bf ? 2.0 : 4.0)));
         GzHeadArgs hd{};
         if (q.gz_mode != GZ_G) { hd.a = ws + l.a; hd.s = ws + l.s; }
@@ -275,9 +274,9 @@ int finalize_and_gz(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
         }
         // (the source of g is a compile-time mode of the kernel: every load of a thread is issued before its first use)
 #define WUNET_GZ_LAUNCH(FIN_, GM_, BF_)                                                                                                               \
-    WUNET_LAUNCH((gz_split_h3_kernel<FIN_, GM_, BF_>), dim3((unsigned)hb), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z), \
+    WUNET_LAUNCH((gz_split_h3_kernel<FIN_, GM_, BF_>), dim3(hb), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z), \
                  (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), (const float*)(ws + c->bound_off),                 \
-                 ws + c->h3_slot + 8 + 4 * i, reinterpret_cast<wunet_half*>(ws + l.gzh), reinterpret_cast<wunet_half*>(ws + l.gzl),                  \
+                 gz_scale_slot(c, ws, i), reinterpret_cast<wunet_half*>(ws + l.gzh), reinterpret_cast<wunet_half*>(ws + l.gzl),                      \
                  c->B, l.cout, c8, l.L, l.logL, l.Lt, b, hd)
 #define WUNET_GZ_MODE(GM_)                                                                                                                            \
     case GM_:                                                                                                                                         \
@@ -293,9 +292,7 @@ int finalize_and_gz(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
                      (const float*)(ws + l.z), (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), l.cout, l.logL,
                      (size_t)c->B * l.cout * l.L, ws + l.g);
     } else if (!q.gz_in_wgrad) {
-        size_t blocks = (n4 + WUNET_THREADS - 1) / WUNET_THREADS;
-        if (blocks > 8192) blocks = 8192;
-        WUNET_LAUNCH(gz_materialize_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z),
+        WUNET_LAUNCH(gz_materialize_kernel, dim3(capped_blocks(n4, WUNET_THREADS, 8192)), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z),
                      (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), l.cout, l.logL, n4, ws + l.g, l.Lt);   // in place
     }
     WUNET_CHECK_LAUNCH();
@@ -306,9 +303,7 @@ int finalize_and_gz(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
 int sum_dx_splits(const BwdCall& k, const LayerPlan& l)
 {
     const size_t nd = (size_t)k.c->B * l.cin * l.L;
-    size_t blocks = (nd + WUNET_THREADS - 1) / WUNET_THREADS;
-    if (blocks > 2048) blocks = 2048;
-    WUNET_LAUNCH(split_sum_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, k.st, (const float*)(k.ws + k.c->spart_off), l.d.ksplit, nd, k.ws + l.dx, (const float*)nullptr, 1, 0);
+    WUNET_LAUNCH(split_sum_kernel, dim3(capped_blocks(nd, WUNET_THREADS, 2048)), dim3(WUNET_THREADS), 0, k.st, (const float*)(k.ws + k.c->spart_off), l.d.ksplit, nd, k.ws + l.dx, (const float*)nullptr, 1, 0);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
 }
@@ -327,12 +322,14 @@ int data_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
             up.c0 = l.c0; up.up_scale = (float)(l.Lt / 2 - 1) / (float)(l.Lt - 1);
             up.uh_out = ws + l.dxh; up.uh_spill = ws + l.usp;
         }
-        const int rc = launch_conv_h3(l.taps, l.h3d_mrep, l.h3d_mtp, l.h3d_sps, reinterpret_cast<wunet_half*>(ws + l.gzh), reinterpret_cast<wunet_half*>(ws + l.gzl),
-                                      reinterpret_cast<const wunet_half*>(ws + c->h3_wb_hi) + l.h3d_wpk,
-                                      reinterpret_cast<const wunet_half*>(ws + c->h3_wb_lo) + l.h3d_wpk, nullptr, ws + c->h3_slot + 8 + 4 * i,
-                                      ws + c->fslot_off + (size_t)WUNET_SLOT_FLOATS * i + 2,
-                                      dx, nullptr, c->B, l.cin, l.cout, l.h3d_nch, l.L, st, ws + l.gzp, nullptr, nullptr,
-                                      nullptr, c->bf, l.h3d_ntt, nullptr, q.upt ? &up : nullptr);
+        ConvH3Launch h{};
+        h.taps = l.taps; h.mrep = l.h3d_mrep; h.mtiles_p = l.h3d_mtp; h.sps = l.h3d_sps; h.nch = l.h3d_nch; h.ntt = l.h3d_ntt;
+        h.B = c->B; h.rows = l.cin; h.kch = l.cout; h.L = l.L; h.bf = c->bf;
+        h.xh = reinterpret_cast<wunet_half*>(ws + l.gzh); h.xl = reinterpret_cast<wunet_half*>(ws + l.gzl); h.zpad = ws + l.gzp;
+        h.wh = reinterpret_cast<const wunet_half*>(ws + c->h3_wb_hi) + l.h3d_wpk; h.wl = reinterpret_cast<const wunet_half*>(ws + c->h3_wb_lo) + l.h3d_wpk;
+        h.sc = gz_scale_slot(c, ws, i); h.sc2 = w_scale_slot(c, ws, i); h.out = dx;
+        h.upt = q.upt ? &up : nullptr;
+        const int rc = launch_conv_h3(h, st);
         if (rc) return rc;
         WUNET_CHECK_LAUNCH();
     } else if (q.dgrad == DG_SCALAR) {
@@ -381,7 +378,7 @@ int weight_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
     if (l.h3w)
         rc = launch_wgrad_h3(l, reinterpret_cast<const wunet_half*>(ws + l.xh), reinterpret_cast<const wunet_half*>(ws + l.xl),
                              reinterpret_cast<const wunet_half*>(ws + l.gzh), reinterpret_cast<const wunet_half*>(ws + l.gzl),
-                             ws + c->h3_slot + 8 + 4 * i, ws + c->fslot_off + (size_t)WUNET_SLOT_FLOATS * i,
+                             gz_scale_slot(c, ws, i), x_scale_slot(c, ws, i),
                              ws + c->wgpart_off, c->B, sd, c->bf);
     else {
         WgradArgs w = make_wgrad_args(xin, ws + l.g, ws + c->wgpart_off, c->B, l.cin, l.cout, l.L, l.taps, l.w.cps);
@@ -405,19 +402,13 @@ int weight_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
 #endif
         const size_t n4 = ra.part_stride / 4;
         if (ra.splits <= serial_max && (long long)n4 >= serial_min_n4) {
-            size_t blocks = (n4 + WUNET_THREADS - 1) / WUNET_THREADS;
-            if (blocks > 4096) blocks = 4096;
-            WUNET_LAUNCH(wgrad_h3_reduce_serial_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd, ra);
+            WUNET_LAUNCH(wgrad_h3_reduce_serial_kernel, dim3(capped_blocks(n4, WUNET_THREADS, 4096)), dim3(WUNET_THREADS), 0, sd, ra);
         } else {
-            size_t blocks = (n4 + 15) / 16;
-            if (blocks > 4096) blocks = 4096;
-            WUNET_LAUNCH(wgrad_h3_reduce_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd, ra);
+            WUNET_LAUNCH(wgrad_h3_reduce_kernel, dim3(capped_blocks(n4, 16, 4096)), dim3(WUNET_THREADS), 0, sd, ra);
         }
     } else {
-        size_t blocks = (nw / 4 + 15) / 16;                   // 16 float4 groups of outputs per block
-        if (blocks > 4096) blocks = 4096;
-        if (blocks < 1) blocks = 1;
-        WUNET_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, sd,
+        const unsigned blocks = capped_blocks(nw / 4, 16, 4096);                   // 16 float4 groups of outputs per block
+        WUNET_LAUNCH(wgrad_reduce_kernel, dim3(blocks < 1 ? 1 : blocks), dim3(WUNET_THREADS), 0, sd,
                      (const float*)(ws + c->wgpart_off), l.w.rows, nw, k.grads[4 * i]);
     }
     WUNET_CHECK_LAUNCH();

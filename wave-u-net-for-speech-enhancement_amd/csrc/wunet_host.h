@@ -45,6 +45,8 @@ inline int ilog2(long long v) { int r = 0; while ((1LL << r) < v) ++r; return r;
 inline bool is_pow2(long long v) { return v > 0 && (v & (v - 1)) == 0; }
 inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// blocks of a grid-stride launch: one per per_block elements of n, at most cap
+inline unsigned capped_blocks(size_t n, size_t per_block, size_t cap) { const size_t b = (n + per_block - 1) / per_block; return (unsigned)(b < cap ? b : cap); }
 inline int kc_of(int taps) { return taps == 15 ? 4 : 12; }
 
 // Tiling of one implicit-GEMM conv: rows = output channels of the GEMM, kch = its K channels.
@@ -146,14 +148,29 @@ namespace wunet_host {
 void layout_workspace(wunet_ctx* c);
 int launch_split(const float* x, wunet_half* hi, wunet_half* lo, const float* sc, const float* xb0, const float* xb1, float* xsc,
                  int B, int C, int L, hipStream_t st, int bf = 0);
+// the per-layer scale slots of the split kernels inside the workspace: {scale, 1 / scale} of the conv operand and of the weight, the
+// bound of the layer's activation (forward segment, WUNET_SLOT_FLOATS per layer), {scale, 1 / scale} of g_z (backward segment)
+float* x_scale_slot(const wunet_ctx* c, float* ws, int layer);
+float* w_scale_slot(const wunet_ctx* c, float* ws, int layer);
+float* act_bound_slot(const wunet_ctx* c, float* ws, int layer);
+float* gz_scale_slot(const wunet_ctx* c, float* ws, int layer);
 // (op: eval mode, the conv also writes the next encoder layer's operand - ConvH3Args::op_*, conv_h3d_kernel<.., EVOP>)
 struct ConvH3OpOut { wunet_half* h; wunet_half* l; const float* wl1; const float* xmax; float* xsc; int C8; };
 // (upt: training backward of a decoder layer, the rows < c0 stored pulled back through the upsample - ConvH3Args::uh_*, conv_h3d_kernel<.., UPT>)
 struct ConvH3Upt { int c0; float up_scale; float* uh_out; float* uh_spill; };
-int launch_conv_h3(int taps, int mrep, int mtiles_p, int sps, const wunet_half* xh, const wunet_half* xl, const wunet_half* wh,
-                   const wunet_half* wl, const float* bias, const float* sc, const float* sc2, float* out, float* stats, int B, int rows,
-                   int kch, int nch, int L, hipStream_t st, const void* zpad, const float* ev_a = nullptr, const float* ev_s = nullptr,
-                   float* xrows = nullptr, int bf = 0, int ntt = 0, const ConvH3OpOut* op = nullptr, const ConvH3Upt* upt = nullptr);
+// one launch of conv_h3d_kernel; a caller fills what it uses, the rest stays zero
+struct ConvH3Launch {
+    int taps, mrep, mtiles_p, sps, nch, ntt;         // the tiling (plan_h3_conv)
+    int B, rows, kch, L, bf;                         // the GEMM: rows x B*L positions, K = kch channels x taps
+    const wunet_half *xh, *xl, *wh, *wl;             // split operand and weight pack
+    const void* zpad;                                // the operand's zero pad (DMA)
+    const float *bias, *sc, *sc2;                    // sc / sc2: {scale, 1 / scale} of the operand / of the weight
+    float *out, *stats;
+    const float *ev_a, *ev_s; float* xrows;          // eval: BatchNorm scale / shift, the activation bound the epilogue folds its maxima into
+    const ConvH3OpOut* op;
+    const ConvH3Upt* upt;
+};
+int launch_conv_h3(const ConvH3Launch& k, hipStream_t st);
 int launch_conv_h3u(const ConvH3uArgs& a, int mrep, int mtiles_p, int kch, hipStream_t st);
 int launch_wgrad_h3(const LayerPlan& l, const wunet_half* xh, const wunet_half* xl, const wunet_half* gh, const wunet_half* gl,
                     const float* sc, const float* sc2, float* part, int B, hipStream_t st, int bf = 0);

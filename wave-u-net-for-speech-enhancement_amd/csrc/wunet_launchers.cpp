@@ -79,14 +79,16 @@ int launch_wgrad_any(int taps, const WgradArgs& a, const WgradCfg& w, hipStream_
     return 0;
 }
 // ---- fp16-split helpers
+float* x_scale_slot(const wunet_ctx* c, float* ws, int layer) { return ws + c->fslot_off + (ptrdiff_t)WUNET_SLOT_FLOATS * layer; }
+float* w_scale_slot(const wunet_ctx* c, float* ws, int layer) { return x_scale_slot(c, ws, layer) + 2; }
+float* act_bound_slot(const wunet_ctx* c, float* ws, int layer) { return x_scale_slot(c, ws, layer) + 4; }
+float* gz_scale_slot(const wunet_ctx* c, float* ws, int layer) { return ws + c->h3_slot + 8 + 4 * (size_t)layer; }
 int launch_split(const float* x, wunet_half* hi, wunet_half* lo, const float* sc, const float* xb0, const float* xb1, float* xsc,
                  int B, int C, int L, hipStream_t st, int bf)
 {
     const int c8 = (C + 7) / 8;
     const size_t n = (size_t)B * c8 * (L / 4);
-    size_t blocks = (n + WUNET_THREADS - 1) / WUNET_THREADS;
-    if (blocks > 16384) blocks = 16384;
-    WUNET_LAUNCH(split_act_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, x, hi, lo, sc, xb0, xb1, xsc, B, C, c8, L, ilog2(L), bf);
+    WUNET_LAUNCH(split_act_kernel, dim3(capped_blocks(n, WUNET_THREADS, 16384)), dim3(WUNET_THREADS), 0, st, x, hi, lo, sc, xb0, xb1, xsc, B, C, c8, L, ilog2(L), bf);
     return 0;
 }
 // resident conv_h3d blocks the grid is sized for: two per CU (its launch bounds).  Emulator build only: WUNET_H3_GRID overrides
@@ -108,35 +110,35 @@ int h3_grid_cap()
     return 2 * cus[dev];
 #endif
 }
-int launch_conv_h3(int taps, int mrep, int mtiles_p, int sps, const wunet_half* xh, const wunet_half* xl, const wunet_half* wh,
-                   const wunet_half* wl, const float* bias, const float* sc, const float* sc2, float* out, float* stats, int B, int rows,
-                   int kch, int nch, int L, hipStream_t st, const void* zpad, const float* ev_a, const float* ev_s, float* xrows, int bf, int ntt,
-                   const ConvH3OpOut* op, const ConvH3Upt* upt)
+int launch_conv_h3(const ConvH3Launch& k, hipStream_t st)
 {
+    const ConvH3OpOut* const op = k.op;
+    const ConvH3Upt* const upt = k.upt;
+    const int taps = k.taps, mrep = k.mrep, rows = k.rows, kch = k.kch, bf = k.bf;
     // conv_h3d_kernel addresses its DMA pieces as SGPR base + unsigned 32-bit offset: lo plane / lo pack behind the hi one, the zero pad
     // behind both, everything within 4 GiB of the hi arrays
-    const long long xd = bf ? 0 : (const char*)xl - (const char*)xh, wd = bf ? 0 : (const char*)wl - (const char*)wh;
-    const long long zd = (const char*)zpad - (const char*)xh, plane = (long long)B * ((kch + 7) / 8) * L * 16;
-    if (!zpad || xd < 0 || wd < 0 || xd >= (1LL << 31) || wd >= (1LL << 31) || zd < plane + xd || zd + 256 >= (1LL << 32))
+    const long long xd = bf ? 0 : (const char*)k.xl - (const char*)k.xh, wd = bf ? 0 : (const char*)k.wl - (const char*)k.wh;
+    const long long zd = (const char*)k.zpad - (const char*)k.xh, plane = (long long)k.B * ((kch + 7) / 8) * k.L * 16;
+    if (!k.zpad || xd < 0 || wd < 0 || xd >= (1LL << 31) || wd >= (1LL << 31) || zd < plane + xd || zd + 256 >= (1LL << 32))
         return fail(WUNET_E_ARG, "conv_h3d operand layout: lo plane / lo pack / zero pad must lie behind the hi array within 4 GiB");
     char pname[96];
-    const double posn = (double)B * L;
+    const double posn = (double)k.B * k.L;
     ConvH3Args a{};
-    a.xh = xh; a.xl = xl; a.wh = wh; a.wl = wl; a.bias = bias; a.sc = sc; a.sc2 = sc2; a.out = out; a.stats = stats;
-    a.B = B; a.Cout = rows; a.C8 = (kch + 7) / 8; a.NCH = nch; a.L = L; a.logL = ilog2(L);
-    a.ev_a = ev_a; a.ev_s = ev_s; a.xrows = xrows;
+    a.xh = k.xh; a.xl = k.xl; a.wh = k.wh; a.wl = k.wl; a.bias = k.bias; a.sc = k.sc; a.sc2 = k.sc2; a.out = k.out; a.stats = k.stats;
+    a.B = k.B; a.Cout = rows; a.C8 = (kch + 7) / 8; a.NCH = k.nch; a.L = k.L; a.logL = ilog2(k.L);
+    a.ev_a = k.ev_a; a.ev_s = k.ev_s; a.xrows = k.xrows;
     if (op) { a.op_h = op->h; a.op_l = op->l; a.op_wl1 = op->wl1; a.op_xmax = op->xmax; a.op_xsc = op->xsc; a.op_C8 = op->C8; }
-    a.xdelta = (unsigned)xd; a.wdelta = (unsigned)wd; a.zpad = zpad;
-    const int nseg = L >= 256 ? 1 : 256 / L, nstage = h3_stage_count(kch, taps, ntt);
-    a.NS = nstage; a.NFS = ntt ? (a.C8 / 4) * (taps / 5) : nstage;
-    const int ksplit = (nstage + sps - 1) / sps;
-    a.stages_per_split = sps; a.split_stride = (size_t)B * rows * L;
+    a.xdelta = (unsigned)xd; a.wdelta = (unsigned)wd; a.zpad = k.zpad;
+    const int nseg = k.L >= 256 ? 1 : 256 / k.L, nstage = h3_stage_count(kch, taps, k.ntt);
+    a.NS = nstage; a.NFS = k.ntt ? (a.C8 / 4) * (taps / 5) : nstage;
+    const int ksplit = (nstage + k.sps - 1) / k.sps;
+    a.stages_per_split = k.sps; a.split_stride = (size_t)k.B * rows * k.L;
 
-    a.ntiles = (int)((posn + 255) / 256); a.mblocks = mtiles_p / mrep;
+    a.ntiles = (int)((posn + 255) / 256); a.mblocks = k.mtiles_p / mrep;
     a.trace = g_h3_trace;
-    if (op && (ksplit != 1 || nseg != 1 || !ev_a || !xrows)) return fail(WUNET_E_ARG, "conv_h3d EVOP needs an un-split whole-row eval launch");
+    if (op && (ksplit != 1 || nseg != 1 || !k.ev_a || !k.xrows)) return fail(WUNET_E_ARG, "conv_h3d EVOP needs an un-split whole-row eval launch");
     if (upt) {
-        if (ksplit != 1 || nseg != 1 || bf || op || bias || stats || xrows || (rows & 3) || (upt->c0 & 3) || taps != 5 ||
+        if (ksplit != 1 || nseg != 1 || bf || op || k.bias || k.stats || k.xrows || (rows & 3) || (upt->c0 & 3) || taps != 5 ||
             !upt->uh_out || !upt->uh_spill || upt->c0 > rows)
             return fail(WUNET_E_ARG, "conv_h3d UPT needs an un-split whole-row decoder data gradient with rows in groups of four");
         a.uh_c0 = upt->c0; a.uh_up_scale = upt->up_scale; a.uh_out = upt->uh_out; a.uh_spill = upt->uh_spill;
@@ -147,8 +149,8 @@ int launch_conv_h3(int taps, int mrep, int mtiles_p, int sps, const wunet_half* 
     const double upt_bytes = upt ? -2.0 * posn * upt->c0 : 0.0;          // (UPT: the upsampled rows leave at half the length)
     prof_begin(st, pname, 2.0 * posn * rows * kch * taps, (bf ? 2.0 * posn * kch + 4.0 * posn * rows : 4.0 * posn * (rows + kch)) + (op ? 2.0 * posn * rows : 0.0) + upt_bytes);
     // (eval: BatchNorm scale / shift beside the bias in the block's table of per-row constants unless that costs the second block of a CU)
-    a.epi_eval = (xrows && nseg == 1 && 2 * h3d_smem(nseg, mrep, bf, mtiles_p, 1) <= 160u * 1024u) ? 1 : 0;
-    const size_t smem = h3d_smem(nseg, mrep, bf, mtiles_p, a.epi_eval, upt ? 1 : 0);
+    a.epi_eval = (k.xrows && nseg == 1 && 2 * h3d_smem(nseg, mrep, bf, k.mtiles_p, 1) <= 160u * 1024u) ? 1 : 0;
+    const size_t smem = h3d_smem(nseg, mrep, bf, k.mtiles_p, a.epi_eval, upt ? 1 : 0);
     const int nitems = a.ntiles * a.mblocks;
     // resident blocks: two per CU, one for the 16-segment tile (96 KB); a K-split layer whose items x splits fit them runs one item per block
     int gx = h3_grid_cap() / 2 * h3d_blocks_per_cu(nseg, mrep, bf) / ksplit;
@@ -272,7 +274,7 @@ int launch_backward_packs(wunet_ctx* c, const float* const* params, float* ws, h
             d.Cout = l.cout; d.Cin = l.cin; d.taps = l.taps; d.rows = l.cin; d.kch = l.cout; d.mtiles = l.h3d_mtp; d.nch = l.h3d_nch; d.transposed = 1;
             d.ntt = l.h3d_ntt; d.nfull = ((l.cout + 7) / 8) / 4; d.ns = h3_stage_count(l.cout, l.taps, l.h3d_ntt);
             d.wmax = ws + c->wmax_off + (size_t)WUNET_WMAX_PARTS * i;      // the forward's maxima: the weights have not changed since
-            d.wsc = l.h3f ? nullptr : ws + c->fslot_off + (size_t)WUNET_SLOT_FLOATS * i + 2;
+            d.wsc = l.h3f ? nullptr : w_scale_slot(c, ws, i);
             d.bf = c->bf;
         }
         if (n3 > 0) {

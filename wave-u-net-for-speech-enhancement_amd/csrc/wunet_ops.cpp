@@ -18,9 +18,8 @@ int wunet_loss_forward(int kind, const float* clean, const float* enhanced, size
 {
     if (kind < 0 || kind > 2 || !clean || !enhanced || !loss_out || !scratch || n == 0) return fail(WUNET_E_ARG, "bad loss argument");
     hipStream_t st = (hipStream_t)stream;
-    size_t blocks = (n + WUNET_THREADS * 8 - 1) / (WUNET_THREADS * 8);
-    if (blocks > 256) blocks = 256;
-    WUNET_LAUNCH(loss_partial_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, n, (double*)scratch);
+    const unsigned blocks = capped_blocks(n, WUNET_THREADS * 8, 256);
+    WUNET_LAUNCH(loss_partial_kernel, dim3(blocks), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, n, (double*)scratch);
     WUNET_CHECK_LAUNCH();
     WUNET_LAUNCH(loss_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, st, (const double*)scratch, (int)blocks, n, loss_out);
     WUNET_CHECK_LAUNCH();
@@ -31,9 +30,7 @@ int wunet_loss_backward(int kind, const float* clean, const float* enhanced, con
 {
     if (kind < 0 || kind > 2 || !clean || !enhanced || !grad_loss || !grad_enhanced || n == 0) return fail(WUNET_E_ARG, "bad loss argument");
     hipStream_t st = (hipStream_t)stream;
-    size_t blocks = (n + WUNET_THREADS * 4 - 1) / (WUNET_THREADS * 4);
-    if (blocks > 2048) blocks = 2048;
-    WUNET_LAUNCH(loss_bwd_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, grad_loss, n, grad_enhanced);
+    WUNET_LAUNCH(loss_bwd_kernel, dim3(capped_blocks(n, WUNET_THREADS * 4, 2048)), dim3(WUNET_THREADS), 0, st, kind, clean, enhanced, grad_loss, n, grad_enhanced);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
 }
@@ -404,10 +401,8 @@ static void adam_launch_at(int n_tensors, int base, float* const* params, const 
         L.T.n[k] = (unsigned)numels[base + k];
         if (numels[base + k] > nmax) nmax = numels[base + k];
     }
-    size_t bx = (nmax + WUNET_THREADS * 4 - 1) / (WUNET_THREADS * 4);
-    if (bx < 1) bx = 1;
-    if (bx > 256) bx = 256;
-    L.bx = (unsigned)bx;
+    L.bx = capped_blocks(nmax, WUNET_THREADS * 4, 256);
+    if (L.bx < 1) L.bx = 1;
 }
 
 int wunet_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
@@ -583,9 +578,7 @@ static int op_conv_common(const float* x, const float* w, const float* bias, flo
     const ConvArgs a = make_conv_args(x, kch, wpk, split ? nullptr : bias, split ? part : out, nullptr, B, rows, L, K, cfg, nout);
     int rc = launch_conv(K, a, cfg, st);
     if (!rc && split) {
-        size_t blocks = (nout + WUNET_THREADS - 1) / WUNET_THREADS;
-        if (blocks > 2048) blocks = 2048;
-        WUNET_LAUNCH(split_sum_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, (const float*)part, cfg.ksplit, nout, out,
+        WUNET_LAUNCH(split_sum_kernel, dim3(capped_blocks(nout, WUNET_THREADS, 2048)), dim3(WUNET_THREADS), 0, st, (const float*)part, cfg.ksplit, nout, out,
                      bias, rows, ilog2(L));
     }
     hipStreamSynchronize(st);
@@ -619,9 +612,7 @@ int wunet_op_conv1d_wgrad(const float* gz, const float* x, float* dw, int B, int
     const WgradArgs a = make_wgrad_args(x, gz, part, B, Cin, Cout, L, K, cfg.cps);
     int rc = launch_wgrad_any(K, a, cfg, st);
     if (!rc) {
-        size_t blocks = (nw + WUNET_THREADS - 1) / WUNET_THREADS;
-        if (blocks > 2048) blocks = 2048;
-        WUNET_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, (const float*)part, cfg.rows, nw, dw);
+        WUNET_LAUNCH(wgrad_reduce_kernel, dim3(capped_blocks(nw, WUNET_THREADS, 2048)), dim3(WUNET_THREADS), 0, st, (const float*)part, cfg.rows, nw, dw);
     }
     hipStreamSynchronize(st);
     hipFree(part);
@@ -668,9 +659,7 @@ int op_split_operand(const float* x, int B, int C, int L, SplitBuf& sb, float* s
     hipMemsetAsync(static_cast<char*>(sb.buf.p) + 2 * sb.plane, 0, 64, st);
     hipMemsetAsync(slot, 0, WUNET_SLOT_FLOATS * sizeof(float), st);
     const size_t n4 = (size_t)B * C * L / 4;
-    size_t blocks = (n4 + WUNET_THREADS * 4 - 1) / (WUNET_THREADS * 4);
-    if (blocks > 2048) blocks = 2048;
-    WUNET_LAUNCH(act_max_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, x, ones, zeros, C, ilog2(L), n4, slot + 4);
+    WUNET_LAUNCH(act_max_kernel, dim3(capped_blocks(n4, WUNET_THREADS * 4, 2048)), dim3(WUNET_THREADS), 0, st, x, ones, zeros, C, ilog2(L), n4, slot + 4);
     return launch_split(x, sb.h(), sb.l(), nullptr, slot + 4, nullptr, slot, B, C, L, st);
 }
 
@@ -705,14 +694,17 @@ int op_conv_split_common(const float* x, const float* w, const float* bias, floa
         WUNET_LAUNCH(pack_h3_kernel, dim3(64, 1), dim3(WUNET_THREADS), 0, st, tab);
     }
     const bool split = p.ksplit > 1;
-    rc = launch_conv_h3(K, p.mrep, p.mtp, p.sps, xs.h(), xs.l(), whp, wlp, split ? nullptr : bias, xslot, wslot + 2,
-                        split ? part.f() : out, nullptr, B, rows, kch, p.nch, L, st, xs.zpad(), nullptr, nullptr, nullptr, 0, p.ntt);
+    ConvH3Launch h{};
+    h.taps = K; h.mrep = p.mrep; h.mtiles_p = p.mtp; h.sps = p.sps; h.nch = p.nch; h.ntt = p.ntt;
+    h.B = B; h.rows = rows; h.kch = kch; h.L = L;
+    h.xh = xs.h(); h.xl = xs.l(); h.zpad = xs.zpad(); h.wh = whp; h.wl = wlp;
+    h.bias = split ? nullptr : bias; h.sc = xslot; h.sc2 = wslot + 2; h.out = split ? part.f() : out;
+    rc = launch_conv_h3(h, st);
     if (!rc && split) {
-        size_t blocks = (nout + WUNET_THREADS - 1) / WUNET_THREADS;
-        if (blocks > 2048) blocks = 2048;
+        const unsigned blocks = capped_blocks(nout, WUNET_THREADS, 2048);
         const float* partp = part.f();
         const int ks = p.ksplit;
-        WUNET_LAUNCH(split_sum_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, partp, ks, nout, out, bias, rows, ilog2(L));
+        WUNET_LAUNCH(split_sum_kernel, dim3(blocks), dim3(WUNET_THREADS), 0, st, partp, ks, nout, out, bias, rows, ilog2(L));
     }
     hipStreamSynchronize(st);
     if (rc) return rc;
@@ -757,9 +749,7 @@ int wunet_op_conv1d_wgrad_split(const float* gz, const float* x, float* dw, int 
         ra.part = part.f(); ra.part_stride = h3w_part_stride(l); ra.splits = l.h3w_ksplit; ra.dw = dw;
         ra.Cout = Cout; ra.Cin = Cin; ra.taps = K; ra.mrep = l.h3w_mrep; ra.tw = K == 15 ? 8 : 5;
         ra.nblocks = l.h3w_nblocks; ra.mblocks = l.h3w_mblocks; ra.cib = K == 15 ? 32 : 64;
-        size_t blocks = (ra.part_stride / 4 + 15) / 16;
-        if (blocks > 4096) blocks = 4096;
-        WUNET_LAUNCH(wgrad_h3_reduce_kernel, dim3((unsigned)blocks), dim3(WUNET_THREADS), 0, st, ra);
+        WUNET_LAUNCH(wgrad_h3_reduce_kernel, dim3(capped_blocks(ra.part_stride / 4, 16, 4096)), dim3(WUNET_THREADS), 0, st, ra);
     }
     hipStreamSynchronize(st);
     if (rc) return rc;
