@@ -7,6 +7,7 @@ For a refactor of the host path: both libraries run the case table below through
 result is compared with np.array_equal - output, loss, every parameter gradient, the input gradient, the running statistics and
 num_batches_tracked - and so is the text of wunet_profile_collect with the profiler on (kernel names and launch counts; the
 emulator build reports no flops / bytes).  Planner switches are read when a context is planned: every run gets its own engine.
+(A base library from before PlanSwitches reads WUNET_WGRAD_XCD and WUNET_A_CAP once per process: set those outside, one run each.)
 Exit status 0: nothing differs."""
 import ctypes
 import importlib
@@ -26,7 +27,8 @@ lib_mod = importlib.import_module(PKG + "._lib")
 model_mod = importlib.import_module(PKG + ".model")
 loss_mod = importlib.import_module(PKG + ".loss")
 
-SWITCHES = ("WUNET_NO_EVOP", "WUNET_NO_SKIP_FUSE", "WUNET_H3U", "WUNET_H3_NOSPLIT", "WUNET_H3_GRID")
+SWITCHES = ("WUNET_NO_EVOP", "WUNET_NO_SKIP_FUSE", "WUNET_H3U", "WUNET_H3_NOSPLIT", "WUNET_H3_GRID", "WUNET_H3_KTAIL", "WUNET_UPT", "WUNET_NO_E0",
+            "WUNET_H3_ORDER", "WUNET_H3D_ORDER", "WUNET_H3W_ORDER", "WUNET_H3_SPS", "WUNET_H3_OLDSPLIT")
 
 
 def masks(n):
@@ -58,6 +60,15 @@ def cases():
             for mode in ("eval", "train"):
                 out.append((shape, 2, mode, None, dict(base, **sw)))
         out.append((shape, 2, "eval_cached", None, base))
+        # the other planner switches (the two split-K ones without WUNET_H3_NOSPLIT, which would come first)
+        grid_only = {k: v for k, v in base.items() if k != "WUNET_H3_NOSPLIT"}
+        for sw in [{"WUNET_H3_KTAIL": "0"}, {"WUNET_UPT": "0"}, {"WUNET_NO_E0": "1"}, {"WUNET_H3_ORDER": "432"}, {"WUNET_H3D_ORDER": "432"},
+                   {"WUNET_H3W_ORDER": "432"}]:
+            for mode in ("eval", "train"):
+                out.append((shape, 2, mode, None, dict(base, **sw)))
+        for sw in [{"WUNET_H3_SPS": "1"}, {"WUNET_H3_OLDSPLIT": "1"}]:
+            for mode in ("eval", "train"):
+                out.append((shape, 2, mode, None, dict(grid_only, **sw)))
         out.append((shape, 2, "train_nosave", None, dict(base, WUNET_H3U="256,256")))
     # padded lengths: every conv through conv_reduce_bn_kernel, no EVOP, no conv_h3u_kernel
     for shape, h3 in [((3, 8, 2, 96), 0), ((3, 8, 2, 96), 2), ((3, 16, 3, 768), 2), ((2, 24, 3, 1536), 2)]:

@@ -323,7 +323,7 @@ int data_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
             up.uh_out = ws + l.dxh; up.uh_spill = ws + l.usp;
         }
         ConvH3Launch h{};
-        h.taps = l.taps; h.mrep = l.h3d_mrep; h.mtiles_p = l.h3d_mtp; h.sps = l.h3d_sps; h.nch = l.h3d_nch; h.ntt = l.h3d_ntt;
+        h.taps = l.taps; h.mrep = l.hd.mrep; h.mtiles_p = l.hd.mtp; h.sps = l.hd.sps; h.nch = l.hd.nch; h.ntt = l.hd.ntt;
         h.B = c->B; h.rows = l.cin; h.kch = l.cout; h.L = l.L; h.bf = c->bf;
         h.xh = reinterpret_cast<wunet_half*>(ws + l.gzh); h.xl = reinterpret_cast<wunet_half*>(ws + l.gzl); h.zpad = ws + l.gzp;
         h.wh = reinterpret_cast<const wunet_half*>(ws + c->h3_wb_hi) + l.h3d_wpk; h.wl = reinterpret_cast<const wunet_half*>(ws + c->h3_wb_lo) + l.h3d_wpk;
@@ -376,7 +376,7 @@ int weight_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
     }
     int rc;
     if (l.h3w)
-        rc = launch_wgrad_h3(l, reinterpret_cast<const wunet_half*>(ws + l.xh), reinterpret_cast<const wunet_half*>(ws + l.xl),
+        rc = launch_wgrad_h3(l, l.hw, reinterpret_cast<const wunet_half*>(ws + l.xh), reinterpret_cast<const wunet_half*>(ws + l.xl),
                              reinterpret_cast<const wunet_half*>(ws + l.gzh), reinterpret_cast<const wunet_half*>(ws + l.gzl),
                              gz_scale_slot(c, ws, i), x_scale_slot(c, ws, i),
                              ws + c->wgpart_off, c->B, sd, c->bf);
@@ -391,9 +391,9 @@ int weight_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
     WUNET_CHECK_LAUNCH();
     if (l.h3w) {
         WgradH3ReduceArgs ra{};
-        ra.part = ws + c->wgpart_off; ra.part_stride = h3w_part_stride(l); ra.splits = l.h3w_ksplit; ra.dw = k.grads[4 * i];
-        ra.Cout = l.cout; ra.Cin = l.cin; ra.taps = l.taps; ra.mrep = l.h3w_mrep; ra.tw = l.taps == 15 ? 8 : 5;
-        ra.nblocks = l.h3w_nblocks; ra.mblocks = l.h3w_mblocks; ra.cib = l.taps == 15 ? 32 : 64;
+        ra.part = ws + c->wgpart_off; ra.part_stride = h3w_part_stride(l, l.hw); ra.splits = l.hw.ksplit; ra.dw = k.grads[4 * i];
+        ra.Cout = l.cout; ra.Cin = l.cin; ra.taps = l.taps; ra.mrep = l.hw.mrep; ra.tw = l.taps == 15 ? 8 : 5;
+        ra.nblocks = l.hw.nblocks; ra.mblocks = l.hw.mblocks; ra.cib = l.taps == 15 ? 32 : 64;
         // few splits over many outputs: the barrier-free serial form (64, 8192: 6.19 -> 6.13 ms per step in round 1).
         // Emulator-build test hook WUNET_REDUCE_SERIAL = "<max splits>,<min float4 outputs>": tiny shapes reach that kernel
         int serial_max = 64; long long serial_min_n4 = 8192;

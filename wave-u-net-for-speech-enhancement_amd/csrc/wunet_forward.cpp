@@ -200,9 +200,9 @@ int pack_split(const FwdCall& k, hipStream_t pst)
         if (!l.h3f) continue;
         PackH3Desc& d = tab.d[nd++];
         d.w = k.params[4 * i]; d.hi = wh + l.h3f_wpk; d.lo = wl + l.h3f_wpk;
-        d.Cout = l.cout; d.Cin = l.cin; d.taps = l.taps; d.rows = l.cout; d.kch = l.cin; d.mtiles = l.h3f_mtp; d.nch = l.h3f_nch; d.transposed = 0;
+        d.Cout = l.cout; d.Cin = l.cin; d.taps = l.taps; d.rows = l.cout; d.kch = l.cin; d.mtiles = l.hf.mtp; d.nch = l.hf.nch; d.transposed = 0;
         // (conv_h3u_kernel walks whole chunks: the layers it runs in this mode get a pack without K tail - never longer than the one with)
-        d.ntt = (training ? l.h3u_train : l.h3u) ? 0 : l.h3f_ntt; d.nfull = ((l.cin + 7) / 8) / 4; d.ns = h3_stage_count(l.cin, l.taps, d.ntt);
+        d.ntt = (training ? l.h3u_train : l.h3u) ? 0 : l.hf.ntt; d.nfull = ((l.cin + 7) / 8) / 4; d.ns = h3_stage_count(l.cin, l.taps, d.ntt);
         d.wmax = ws + c->wmax_off + (size_t)WUNET_WMAX_PARTS * i; d.wsc = w_scale_slot(c, ws, i);
         d.bf = c->bf;
     }
@@ -401,7 +401,7 @@ int conv(const FwdCall& k, int i, const FwdLayerPlan& q)
             u.oxh = reinterpret_cast<wunet_half*>(ws + l.xh); u.oxl = reinterpret_cast<wunet_half*>(ws + l.xl);
         }
         u.B = c->B; u.Cout = l.cout; u.L = l.L;
-        rc = launch_conv_h3u(u, l.h3f_mrep, l.h3f_mtp, l.cin, st);
+        rc = launch_conv_h3u(u, l.hf.mrep, l.hf.mtp, l.cin, st);
     } else if (q.conv == CV_H3) {
         // fp16-split GEMM: split the materialised input, then 3 MFMA passes on the 2.5 PF pipe
         wunet_half* xh = reinterpret_cast<wunet_half*>(ws + l.xh);
@@ -419,7 +419,7 @@ int conv(const FwdCall& k, int i, const FwdLayerPlan& q)
             opo.xsc = x_scale_slot(c, ws, i + 1); opo.C8 = (nx.cin + 7) / 8;
         }
         ConvH3Launch h{};
-        h.taps = l.taps; h.mrep = l.h3f_mrep; h.mtiles_p = l.h3f_mtp; h.sps = l.h3f_sps; h.nch = l.h3f_nch; h.ntt = l.h3f_ntt;
+        h.taps = l.taps; h.mrep = l.hf.mrep; h.mtiles_p = l.hf.mtp; h.sps = l.hf.sps; h.nch = l.hf.nch; h.ntt = l.hf.ntt;
         h.B = c->B; h.rows = l.cout; h.kch = l.cin; h.L = l.L; h.bf = c->bf;
         h.xh = xh; h.xl = xl; h.wh = wh; h.wl = reinterpret_cast<const wunet_half*>(ws + c->h3_wf_lo) + l.h3f_wpk; h.zpad = ws + l.xzp;
         h.bias = bias; h.sc = x_scale_slot(c, ws, i); h.sc2 = w_scale_slot(c, ws, i); h.out = out; h.stats = stats;

@@ -63,11 +63,49 @@ int launch_wgrad_any(int taps, const WgradArgs& a, const WgradCfg& w, hipStream_
 
 enum { LK_RAW = 0, LK_DECIM = 1, LK_UPCAT = 2 };
 
-struct LayerPlan {
+// Every environment switch of the planner, read once by read_plan_switches() when a context is planned (wunet_create, wunet_set_h3)
+// or a split single-op entry point is called; nothing else in wunet_plan.cpp reads the environment.
+//   variable               effect                                                                            kind
+//   WUNET_H3_ORDER         rows-per-wave preference of conv_h3d_kernel, forward GEMM (levels >= 256 samples)  test hook
+//   WUNET_H3D_ORDER        ... of the data gradient                                                           test hook
+//   WUNET_H3W_ORDER        ... of the split weight gradient                                                   test hook
+//   WUNET_H3_NOSPLIT       no split-K on conv_h3d_kernel (the un-split epilogue on small shapes)              test hook
+//   WUNET_H3_SPS=<n>       K stages per split (tools/conv_bench.py sweeps it per layer)                       measurement hook
+//   WUNET_H3_OLDSPLIT      the split-K rule of rounds 1 - 3                                                   A/B switch
+//   WUNET_H3_KTAIL=0       the K tail as one zero-padded chunk everywhere                                     A/B switch
+//   WUNET_H3U=<e>[,<t>]    conv_h3u_kernel from <e> samples in eval, <t> in training (one number: both; 0: off) A/B switch
+//   WUNET_NO_SKIP_FUSE     the decoder-side operand pass reads the skip itself (eval mode's path)             test hook
+//   WUNET_NO_EVOP          no conv writes the next encoder layer's operand                                    A/B switch
+//   WUNET_NO_E0            the first layer's weight gradient as a GEMM of its own                             A/B switch
+//   WUNET_UPT=0            no data gradient stores its upsampled half at the producer's resolution            A/B switch
+//   WUNET_WGRAD_XCD=0      wgrad_h3d_kernel keeps its 3-D grid                                                A/B switch
+//   WUNET_A_CAP=<n>        most pieces of a channel in the gradient-assembly pass (1 .. 256, default 128)     measurement hook
+struct PlanSwitches {
+    const char *order_f, *order_d, *order_w;      // nullptr: the planner's own order (the text lives in the environment: use it within the call)
+    bool no_split, old_split, ktail_off, no_skip_fuse, no_evop, no_e0, upt_off, wgrad_xcd_off;
+    int sps, h3u_eval, h3u_train, a_cap;          // sps < 1: the planner's rule
+};
+PlanSwitches read_plan_switches();
+
+// Tiling of conv_h3d_kernel for one GEMM (rows x B*L positions, K = kch channels x taps): accumulator rows per wave, padded
+// m-tiles, chunks of 32 K channels, K stages per split and the split count, steps of a K tail stage (0: the last chunk is padded to
+// 32 channels).  Shared by the network planner and the single-op entry points, so a geometry gets the same kernel instantiation either way.
+struct H3ConvPlan { int mrep, mtp, nch, sps, ksplit, ntiles, ntt; };
+H3ConvPlan plan_h3_conv(int B, int L, int rows, int kch, int taps, bool transposed, int bf, const PlanSwitches& sw);
+// Tiling of the split weight gradient: rows per wave, grid, chunks of tp positions per split, the XCD-aware walk (the blocks of one K
+// split on one XCD), and the kernel: dma = wgrad_h3d_kernel (DMA-staged) instead of wgrad_h3_kernel, db = its double-buffered form
+struct H3WgradPlan { int mrep, mblocks, nblocks, ksplit, cps, tp, xcd, dma, db; };
+H3WgradPlan plan_h3_wgrad(int B, int L, int cin, int cout, int taps, int bf, const PlanSwitches& sw);
+
+// what wunet_create sets: the layer as the model defines it
+struct LayerGeom {
     int cin, cout, taps, L, logL, kind;
     int Lt;              // samples of a row that exist: L is the power-of-two row stride, Lt <= L (lengths m*2^n; Lt == L otherwise)
     int src0, src1;      // producer layers (src0 = -1: network input)
     int c0;              // UPCAT: channels from the upsampled branch
+};
+// what layout_workspace decides and allots: all of it written anew on every planning of the context
+struct LayerDecisions {
     ConvCfg f;           // forward conv (rows = cout, K channels = cin)
     ConvCfg d;           // data gradient (rows = cin, K channels = cout)
     WgradCfg w;          // weight gradient
@@ -79,15 +117,12 @@ struct LayerPlan {
     size_t wl1;          // cout absolute row sums of the conv weight (eval mode: the bound conv_h3d_kernel<.., EVOP> scales the next operand by)
     int evop;            // eval mode: this encoder layer's conv also writes the next layer's operand (no prep_h3_kernel<0> for that one)
     // fp16-split path
-    int h3f, h3d;                 // forward conv / data gradient use conv_h3_kernel
-    int h3f_mrep, h3f_mtp, h3f_nch, h3d_mrep, h3d_mtp, h3d_nch;
-    int h3f_ntt, h3d_ntt;    // K tail of conv_h3d_kernel: steps of a tail stage (0: the last chunk is padded to 32 channels)
-    int h3f_sps, h3d_sps;         // K stages per split of conv_h3_kernel (the split count is f.ksplit / d.ksplit)
+    int h3f, h3d, h3w;            // forward conv / data gradient use conv_h3d_kernel, the weight gradient wgrad_h3[d]_kernel
+    H3ConvPlan hf, hd;            // ... their tilings (the split counts also as f.ksplit / d.ksplit)
+    H3WgradPlan hw;
     int first;                    // encoder[0] (Cin = 1): direct fp32 kernel (conv_first_kernel)
     int h3x;                      // the conv input exists only in the split layout (no fp32 xin)
     int skip_from;                // decoder layer: > 0 = its skip half is written by the operand pass of encoder-side layer skip_from
-    int h3w, h3w_mrep, h3w_mblocks, h3w_nblocks, h3w_ksplit, h3w_cps, h3w_tp;   // weight gradient uses wgrad_h3_kernel
-    int h3w_xcd;                  // wgrad_h3d_kernel walks its blocks XCD-aware (the blocks of one K split on one XCD)
     int h3u, h3u_train;           // conv_h3u_kernel (operand pass fused into the conv's loader waves) runs the eval / also the training forward
     int feeds_h3;                 // the layer's activation is the (or a) source of a conv input that exists in the split layout
     size_t xh, xl, xzp;           // split activated input (float offsets): hi plane, lo plane right behind it, then 16 zero bytes (DMA pad)
@@ -96,17 +131,13 @@ struct LayerPlan {
     int upt;                      // a decoder layer whose data gradient stores its upsampled rows at the producer's resolution (conv_h3d_kernel<.., UPT>)
     size_t dxh, usp;              // ... [B][c0][L/2] and the tile-edge terms [2][c0][tiles]
 };
+struct LayerPlan : LayerGeom, LayerDecisions {};
 
-// Tiling of conv_h3d_kernel for one GEMM (rows x B*L positions, K = kch channels x taps): accumulator rows per wave, padded
-// m-tiles, chunks of 32 K channels, K stages per split and the split count.  Shared by the network planner and the
-// single-op entry points, so a geometry gets the same kernel instantiation either way.
-struct H3ConvPlan { int mrep, mtp, nch, sps, ksplit, ntiles, ntt; };
-H3ConvPlan plan_h3_conv(int B, int L, int rows, int kch, int taps, const char* order_env, int bf = 0);
 size_t h3d_smem(int nseg, int mrep, int bf, int mtp, int eval, int upt = 0);           // dynamic LDS of a conv_h3d_kernel block
 int h3d_blocks_per_cu(int nseg, int mrep, int bf);   // resident blocks per CU at that size
 int h3_stage_count(int kch, int taps, int ntt);
-void plan_h3_wgrad(LayerPlan& l, int B);
-size_t h3w_part_stride(const LayerPlan& l);
+size_t h3w_part_stride(const LayerGeom& g, const H3WgradPlan& w);
+size_t h3w_dma_smem(const LayerGeom& g, const H3WgradPlan& w, int bf);     // dynamic LDS of a double-buffered wgrad_h3d_kernel block
 bool up_pairs_regular(int Lin);       // the x2 upsample reads the source pairs ((j-1) >> 1, +1) at this length (fp32 coordinates, host check)
 unsigned pack_gx();
 
@@ -172,7 +203,7 @@ struct ConvH3Launch {
 };
 int launch_conv_h3(const ConvH3Launch& k, hipStream_t st);
 int launch_conv_h3u(const ConvH3uArgs& a, int mrep, int mtiles_p, int kch, hipStream_t st);
-int launch_wgrad_h3(const LayerPlan& l, const wunet_half* xh, const wunet_half* xl, const wunet_half* gh, const wunet_half* gl,
+int launch_wgrad_h3(const LayerGeom& g, const H3WgradPlan& w, const wunet_half* xh, const wunet_half* xl, const wunet_half* gh, const wunet_half* gl,
                     const float* sc, const float* sc2, float* part, int B, hipStream_t st, int bf = 0);
 int launch_backward_packs(wunet_ctx* c, const float* const* params, float* ws, hipStream_t st);
 // the side stream + fork / join events of the CURRENT device (nullptr + error text on failure)

@@ -188,58 +188,44 @@ int launch_conv_h3u(const ConvH3uArgs& a0, int mrep, int mtiles_p, int kch, hipS
     return 0;
 }
 
-// wgrad_h3d_kernel (DMA-staged) runs this layer's weight gradient: whole chunks inside one item (L >= 128), both buffers within
-// the 160 KB
-size_t h3w_dma_smem(const LayerPlan& l, int bf)
-{
-    const int xg = l.taps == 15 ? 4 : 8, tp = l.h3w_tp, npl = bf ? 1 : 2;
-    return (size_t)2 * (npl * (l.h3w_mrep * 2) * (tp + 4) + npl * xg * (tp + 20) + 8) * 16;
-}
-bool h3w_is_dma(const LayerPlan& l, int bf)
-{
-    const int tp = l.h3w_tp, nseg = l.L >= tp ? 1 : tp / l.L;
-    return nseg == 1 && tp == 128 && h3w_dma_smem(l, bf) <= 160 * 1024 && l.h3w_mrep <= (l.taps == 15 ? 6 : 5);
-}
-int launch_wgrad_h3(const LayerPlan& l, const wunet_half* xh, const wunet_half* xl, const wunet_half* gh, const wunet_half* gl,
+// The split weight gradient of one layer on the kernel its tiling names (plan_h3_wgrad): wgrad_h3d_kernel (DMA-staged), single- or
+// double-buffered, else wgrad_h3_kernel
+int launch_wgrad_h3(const LayerGeom& l, const H3WgradPlan& w, const wunet_half* xh, const wunet_half* xl, const wunet_half* gh, const wunet_half* gl,
                     const float* sc, const float* sc2, float* part, int B, hipStream_t st, int bf)
 {
     char pname[96];
     const double posn = (double)B * l.L;
-    const int xg = l.taps == 15 ? 4 : 8, tp = l.h3w_tp, nseg = l.L >= tp ? 1 : tp / l.L;
-    const dim3 grid(l.h3w_ksplit, l.h3w_nblocks, l.h3w_mblocks);
+    const int xg = l.taps == 15 ? 4 : 8, tp = w.tp, nseg = l.L >= tp ? 1 : tp / l.L;
+    const dim3 grid(w.ksplit, w.nblocks, w.mblocks);
     const int npl = bf ? 1 : 2;
-    const size_t smem_d = h3w_dma_smem(l, bf);
     int rc;
-    if (h3w_is_dma(l, bf)) {
-        WgradH3dArgs a{};
+    const auto fill = [&](auto& a) {          // what the two kernels' argument blocks share
         a.xh = xh; a.xl = xl; a.gh = gh; a.gl = gl; a.sc = sc; a.sc2 = sc2; a.part = part; a.B = B; a.Cin = l.cin; a.Cout = l.cout;
         a.XC8 = (l.cin + 7) / 8; a.GC8 = (l.cout + 7) / 8; a.L = l.L; a.logL = l.logL;
-        a.chunks_per_split = l.h3w_cps; a.part_stride = h3w_part_stride(l);
+        a.chunks_per_split = w.cps; a.part_stride = h3w_part_stride(l, w);
+    };
+    snprintf(pname, sizeof pname, "wgrad_h3%s_kernel<%d, %d%s>", w.dma ? "d" : "", l.taps, w.mrep, bf ? ", bf16" : "");
+    prof_begin(st, pname, 2.0 * posn * l.cout * l.cin * l.taps, 4.0 * posn * (l.cout + l.cin));
+    if (w.dma) {
+        WgradH3dArgs a{};
+        fill(a);
         a.cin_active = l.cin;
-        a.ksplit = l.h3w_ksplit; a.nblocks = l.h3w_nblocks; a.mblocks = l.h3w_mblocks;
-        // the blocks of one K split on one XCD where the planner found room (plan_h3_wgrad; WgradH3dArgs::xcd_walk)
-        a.xcd_walk = l.h3w_xcd;
-        snprintf(pname, sizeof pname, bf ? "wgrad_h3d_kernel<%d, %d, bf16>" : "wgrad_h3d_kernel<%d, %d>", l.taps, l.h3w_mrep);
-        prof_begin(st, pname, 2.0 * posn * l.cout * l.cin * l.taps, 4.0 * posn * (l.cout + l.cin));
-        // two blocks per CU with a single buffer where the registers allow it (two independent blocks hide each other's
-        // waits: +18-28 % on those kernels), else one block with double-buffered tiles
-        const bool db = !((l.taps == 5 && l.h3w_mrep <= 4) || (l.taps == 15 && l.h3w_mrep <= 3));
-        const int nyz = l.h3w_nblocks * l.h3w_mblocks;
-        const dim3 grid_x((unsigned)(((l.h3w_ksplit + 7) / 8) * 8 * nyz));
-        rc = wunet_launch_wgrad_h3d(a, l.taps, l.h3w_mrep, db, a.xcd_walk ? grid_x : grid, db ? smem_d : smem_d / 2, st, bf != 0, tp);
+        a.ksplit = w.ksplit; a.nblocks = w.nblocks; a.mblocks = w.mblocks;
+        // the blocks of one K split on one XCD where the planner found room (WgradH3dArgs::xcd_walk)
+        a.xcd_walk = w.xcd;
+        const size_t smem_d = h3w_dma_smem(l, w, bf);
+        const int nyz = w.nblocks * w.mblocks;
+        const dim3 grid_x((unsigned)(((w.ksplit + 7) / 8) * 8 * nyz));
+        rc = wunet_launch_wgrad_h3d(a, l.taps, w.mrep, w.db != 0, a.xcd_walk ? grid_x : grid, w.db ? smem_d : smem_d / 2, st, bf != 0, tp);
     } else {
         WgradH3Args a{};
-        a.xh = xh; a.xl = xl; a.gh = gh; a.gl = gl; a.sc = sc; a.sc2 = sc2; a.part = part; a.B = B; a.Cin = l.cin; a.Cout = l.cout;
-        a.XC8 = (l.cin + 7) / 8; a.GC8 = (l.cout + 7) / 8; a.L = l.L; a.logL = l.logL;
-        a.chunks_per_split = l.h3w_cps; a.part_stride = h3w_part_stride(l);
-        snprintf(pname, sizeof pname, bf ? "wgrad_h3_kernel<%d, %d, bf16>" : "wgrad_h3_kernel<%d, %d>", l.taps, l.h3w_mrep);
-        prof_begin(st, pname, 2.0 * posn * l.cout * l.cin * l.taps, 4.0 * posn * (l.cout + l.cin));
+        fill(a);
         const int xrows = nseg == 1 ? tp + 20 : nseg * (tp / nseg + 16), xpos = ((xrows + 11) / 16) * 16 + 4;
-        const size_t smem = ((size_t)npl * (l.h3w_mrep * 2) * (tp + 4) + (size_t)npl * xg * xpos + 8) * 16;
-        rc = wunet_launch_wgrad_h3(a, l.taps, l.h3w_mrep, nseg, tp, grid, smem, st, bf != 0);
+        const size_t smem = ((size_t)npl * (w.mrep * 2) * (tp + 4) + (size_t)npl * xg * xpos + 8) * 16;
+        rc = wunet_launch_wgrad_h3(a, l.taps, w.mrep, nseg, tp, grid, smem, st, bf != 0);
     }
     prof_end(st);
-    if (rc != 0) return fail(WUNET_E_ARG, "no wgrad_h3 kernel for taps=%d mrep=%d (rc %d)", l.taps, l.h3w_mrep, rc);
+    if (rc != 0) return fail(WUNET_E_ARG, "no wgrad_h3 kernel for taps=%d mrep=%d (rc %d)", l.taps, w.mrep, rc);
     return 0;
 }
 
@@ -271,8 +257,8 @@ int launch_backward_packs(wunet_ctx* c, const float* const* params, float* ws, h
             if (!l.h3d) continue;
             PackH3Desc& d = t3.d[n3++];
             d.w = params[4 * i]; d.hi = wh + l.h3d_wpk; d.lo = wl + l.h3d_wpk;
-            d.Cout = l.cout; d.Cin = l.cin; d.taps = l.taps; d.rows = l.cin; d.kch = l.cout; d.mtiles = l.h3d_mtp; d.nch = l.h3d_nch; d.transposed = 1;
-            d.ntt = l.h3d_ntt; d.nfull = ((l.cout + 7) / 8) / 4; d.ns = h3_stage_count(l.cout, l.taps, l.h3d_ntt);
+            d.Cout = l.cout; d.Cin = l.cin; d.taps = l.taps; d.rows = l.cin; d.kch = l.cout; d.mtiles = l.hd.mtp; d.nch = l.hd.nch; d.transposed = 1;
+            d.ntt = l.hd.ntt; d.nfull = ((l.cout + 7) / 8) / 4; d.ns = h3_stage_count(l.cout, l.taps, l.hd.ntt);
             d.wmax = ws + c->wmax_off + (size_t)WUNET_WMAX_PARTS * i;      // the forward's maxima: the weights have not changed since
             d.wsc = l.h3f ? nullptr : w_scale_slot(c, ws, i);
             d.bf = c->bf;

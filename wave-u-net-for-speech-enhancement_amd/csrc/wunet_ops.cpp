@@ -666,7 +666,7 @@ int op_split_operand(const float* x, int B, int C, int L, SplitBuf& sb, float* s
 int op_conv_split_common(const float* x, const float* w, const float* bias, float* out, int B, int kch, int rows, int Cout, int Cin,
                          int L, int K, int transposed, hipStream_t st)
 {
-    const H3ConvPlan p = plan_h3_conv(B, L, rows, kch, K, transposed ? "WUNET_H3D_ORDER" : "WUNET_H3_ORDER");
+    const H3ConvPlan p = plan_h3_conv(B, L, rows, kch, K, transposed != 0, 0, read_plan_switches());
     SplitBuf xs;
     DevBuf wpk, misc, part;
     const size_t wh_halfs = (size_t)p.mtp * p.nch * K * 512, nout = (size_t)B * rows * L;
@@ -729,26 +729,26 @@ int wunet_op_conv1d_wgrad_split(const float* gz, const float* x, float* dw, int 
 {
     if (op_split_check(B, Cin, Cout, L, K, true)) return WUNET_E_ARG;
     hipStream_t st = (hipStream_t)stream;
-    LayerPlan l{};
+    LayerGeom l{};
     l.cin = Cin; l.cout = Cout; l.taps = K; l.L = L; l.logL = ilog2(L);
-    plan_h3_wgrad(l, B);
+    const H3WgradPlan w = plan_h3_wgrad(B, L, Cin, Cout, K, 0, read_plan_switches());
     SplitBuf xs, gs;
     DevBuf misc, part;
     const int cmax = Cin > Cout ? Cin : Cout;
     // misc: slot of g_z | slot of x | ones | zeros
-    if (!misc.alloc((16 + 2 * (size_t)cmax) * sizeof(float)) || !part.alloc((size_t)l.h3w_ksplit * h3w_part_stride(l) * sizeof(float)))
+    if (!misc.alloc((16 + 2 * (size_t)cmax) * sizeof(float)) || !part.alloc((size_t)w.ksplit * h3w_part_stride(l, w) * sizeof(float)))
         return fail(WUNET_E_RUNTIME, "hipMalloc");
     float* gslot = misc.f(), *xslot = misc.f() + 8, *oz = misc.f() + 16;
     WUNET_LAUNCH(fill_kernel, dim3(4), dim3(WUNET_THREADS), 0, st, oz, (size_t)cmax, 1.0f);
     WUNET_LAUNCH(fill_kernel, dim3(4), dim3(WUNET_THREADS), 0, st, oz + cmax, (size_t)cmax, 0.0f);
     int rc = op_split_operand(gz, B, Cout, L, gs, gslot, oz, oz + cmax, st);
     if (!rc) rc = op_split_operand(x, B, Cin, L, xs, xslot, oz, oz + cmax, st);
-    if (!rc) rc = launch_wgrad_h3(l, xs.h(), xs.l(), gs.h(), gs.l(), gslot, xslot, part.f(), B, st);
+    if (!rc) rc = launch_wgrad_h3(l, w, xs.h(), xs.l(), gs.h(), gs.l(), gslot, xslot, part.f(), B, st);
     if (!rc) {
         WgradH3ReduceArgs ra{};
-        ra.part = part.f(); ra.part_stride = h3w_part_stride(l); ra.splits = l.h3w_ksplit; ra.dw = dw;
-        ra.Cout = Cout; ra.Cin = Cin; ra.taps = K; ra.mrep = l.h3w_mrep; ra.tw = K == 15 ? 8 : 5;
-        ra.nblocks = l.h3w_nblocks; ra.mblocks = l.h3w_mblocks; ra.cib = K == 15 ? 32 : 64;
+        ra.part = part.f(); ra.part_stride = h3w_part_stride(l, w); ra.splits = w.ksplit; ra.dw = dw;
+        ra.Cout = Cout; ra.Cin = Cin; ra.taps = K; ra.mrep = w.mrep; ra.tw = K == 15 ? 8 : 5;
+        ra.nblocks = w.nblocks; ra.mblocks = w.mblocks; ra.cib = K == 15 ? 32 : 64;
         WUNET_LAUNCH(wgrad_h3_reduce_kernel, dim3(capped_blocks(ra.part_stride / 4, 16, 4096)), dim3(WUNET_THREADS), 0, st, ra);
     }
     hipStreamSynchronize(st);

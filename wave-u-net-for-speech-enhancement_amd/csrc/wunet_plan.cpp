@@ -1,5 +1,6 @@
 // Shape planning, workspace layout, context life cycle, error text and the per-launch profiler of libwunet_hip.so
 // (see wunet_host.h for the map of the host side).
+#include <algorithm>
 #include "wunet_host.h"
 #include "wunet_h3_elem.h"      // WUNET_SLOT_FLOATS, WUNET_WMAX_PARTS
 
@@ -205,11 +206,32 @@ WgradCfg plan_wgrad(int B, int L, int cin, int cout, int taps)
 // blocks per layer of the weight-pack launches (grid-stride loops inside)
 unsigned pack_gx() { return 512; }      // (swept 64 .. 1024 in round 1: 6.19 -> 6.13 ms per step at 512)
 
-int pick_mrep_h3(int mtiles, const char* env, const char* dflt)
+// The one place of this file that reads the environment (the table is above PlanSwitches in wunet_host.h)
+PlanSwitches read_plan_switches()
+{
+    const auto is_zero = [](const char* name) { const char* e = getenv(name); return e != nullptr && atoi(e) == 0; };
+    PlanSwitches sw{};
+    sw.order_f = getenv("WUNET_H3_ORDER"); sw.order_d = getenv("WUNET_H3D_ORDER"); sw.order_w = getenv("WUNET_H3W_ORDER");
+    sw.no_split = getenv("WUNET_H3_NOSPLIT") != nullptr; sw.old_split = getenv("WUNET_H3_OLDSPLIT") != nullptr;
+    if (const char* e = getenv("WUNET_H3_SPS")) sw.sps = atoi(e);
+    sw.ktail_off = is_zero("WUNET_H3_KTAIL");
+    sw.h3u_eval = 512; sw.h3u_train = 2048;    // (batch 64, one box - eval: off 1.87 ms, from 2048 1.567, from 512 1.516; training step: off 5.12 / 5.20, from 2048 or 4096 5.08 / 5.15, from 512 5.17: profiles/r5_h3u_threshold_sweep.txt)
+    if (const char* e = getenv("WUNET_H3U")) {
+        int a = 0, b = 0;
+        const int got = sscanf(e, "%d,%d", &a, &b);
+        if (got == 2) { sw.h3u_eval = a; sw.h3u_train = b; }
+        else if (got == 1) sw.h3u_eval = sw.h3u_train = a;      // one number: both thresholds (WUNET_H3U=0 turns the kernel off everywhere)
+    }
+    sw.no_skip_fuse = getenv("WUNET_NO_SKIP_FUSE") != nullptr; sw.no_evop = getenv("WUNET_NO_EVOP") != nullptr; sw.no_e0 = getenv("WUNET_NO_E0") != nullptr;
+    sw.upt_off = is_zero("WUNET_UPT"); sw.wgrad_xcd_off = is_zero("WUNET_WGRAD_XCD");
+    sw.a_cap = getenv("WUNET_A_CAP") ? atoi(getenv("WUNET_A_CAP")) : 128;
+    return sw;
+}
+
+// (ord: the switch's order where one applies - tiny shapes reach every rows-per-wave instantiation - else the planner's)
+int pick_mrep_h3(int mtiles, const char* ord)
 {
     int best = 2, best_pad = 1 << 30;
-    const char* ord = env ? getenv(env) : nullptr;    // test hook (WUNET_H3_ORDER / _H3D_ORDER / _H3W_ORDER): tiny shapes reach every rows-per-wave instantiation
-    if (!ord) ord = dflt;
     for (const char* p = ord; *p; ++p) {
         const int m = *p - '0';
         const int pad = round_up(mtiles, m) - mtiles;
@@ -228,11 +250,19 @@ const char* h3_order(int taps, int L, int ntiles, int mtiles)
 }
 
 // floats of one split's tile-major partial dW (wgrad_h3_kernel epilogue): padded tiles
-size_t h3w_part_stride(const LayerPlan& l)
+size_t h3w_part_stride(const LayerGeom& g, const H3WgradPlan& w)
 {
-    const int tw = l.taps == 15 ? 8 : 5;
-    return (size_t)l.h3w_mblocks * l.h3w_nblocks * WUNET_WAVES * l.h3w_mrep * tw * 256;
+    const int tw = g.taps == 15 ? 8 : 5;
+    return (size_t)w.mblocks * w.nblocks * WUNET_WAVES * w.mrep * tw * 256;
 }
+// both LDS buffers of a wgrad_h3d_kernel block
+size_t h3w_dma_smem(const LayerGeom& g, const H3WgradPlan& w, int bf)
+{
+    const int xg = g.taps == 15 ? 4 : 8, tp = w.tp, npl = bf ? 1 : 2;
+    return (size_t)2 * (npl * (w.mrep * 2) * (tp + 4) + npl * xg * (tp + 20) + 8) * 16;
+}
+// wgrad_h3d_kernel<.., false> (single LDS buffer, two blocks per CU) where its registers allow: k5 up to 4 m-tiles, k15 up to 3
+static bool h3w_regs_allow_two_blocks(int taps, int mrep) { return (taps == 5 && mrep <= 4) || (taps == 15 && mrep <= 3); }
 
 // dynamic LDS of one conv_h3d_kernel block: x tile [planes][4][NSEG * (256 / NSEG + 16)] + W sub-tile [planes][M_REP][5][64] pieces of 16 bytes
 // + the statistics hand-over
@@ -255,14 +285,11 @@ int h3d_blocks_per_cu(int nseg, int mrep, int bf) { return 2 * h3d_smem(nseg, mr
 // persistent blocks walked 112 items, 16 of them two (24 us instead of 13).  Cost of a candidate = rounds x (fixed part of a block:
 // first fetch + epilogue, about 5 us, + 1.8 us per stage) + the partial sums the reduce kernel reads; returns the stages per split
 // (== nstage: no split).
-int h3_stages_per_split(int items, int nstage, int slots)
+int h3_stages_per_split(int items, int nstage, int slots, const PlanSwitches& sw)
 {
-    if (items >= 384 || nstage <= 1 || getenv("WUNET_H3_NOSPLIT")) return nstage;      // (switch: tests reach the un-split epilogue on small shapes)
-    if (const char* e = getenv("WUNET_H3_SPS")) {    // measurement hook (tools/conv_bench.py sweeps it per layer): the stages per split
-        const int v = atoi(e);
-        if (v >= 1) return v < nstage ? v : nstage;
-    }
-    if (getenv("WUNET_H3_OLDSPLIT")) {              // A/B switch: the rule of rounds 1 - 3
+    if (items >= 384 || nstage <= 1 || sw.no_split) return nstage;
+    if (sw.sps >= 1) return sw.sps < nstage ? sw.sps : nstage;
+    if (sw.old_split) {
         int ks = (512 + items - 1) / items;
         if (ks > nstage) ks = nstage;
         return (nstage + ks - 1) / ks;
@@ -284,11 +311,10 @@ int h3_stages_per_split(int items, int nstage, int slots)
 // for 15 taps with any tail (4 t1 steps instead of 15), for 5 taps with one left-over group (2 instead of 5).
 // Returns the steps of a tail stage, 0 without a tail.  WUNET_H3_KTAIL=0 (read when a context is planned): the padded chunk
 // everywhere - the other arm of tests/test_gpu_parity.py::test_k_tail_on_hardware; the two shapes at the register limit always run it
-int h3_tail_steps(int kch, int taps)
+int h3_tail_steps(int kch, int taps, const PlanSwitches& sw)
 {
-    const char* kt = getenv("WUNET_H3_KTAIL");
     const int t1 = ((kch + 7) / 8) & 3;
-    if (kt && atoi(kt) == 0) return 0;
+    if (sw.ktail_off) return 0;
     return taps == 15 ? (t1 ? 4 : 0) : (t1 == 1 ? 2 : 0);
 }
 // stages of the K loop: full chunks * tap groups + tail stages
@@ -298,68 +324,72 @@ int h3_stage_count(int kch, int taps, int ntt)
     return ntt ? (c8 / 4) * (taps / 5) + (c8 & 3) : ((c8 + 3) / 4) * (taps / 5);
 }
 
-H3ConvPlan plan_h3_conv(int B, int L, int rows, int kch, int taps, const char* order_env, int bf)
+H3ConvPlan plan_h3_conv(int B, int L, int rows, int kch, int taps, bool transposed, int bf, const PlanSwitches& sw)
 {
     H3ConvPlan p{};
     const long long posn = (long long)B * L;
     p.ntiles = (int)((posn + 255) / 256);
-    const int ntg = taps / 5, c8 = (kch + 7) / 8, mt = (rows + 15) / 16;
-    // (4 accumulator rows per wave only exist un-segmented: L >= 256)
-    p.mrep = pick_mrep_h3(mt, L >= 256 ? order_env : nullptr, h3_order(taps, L, p.ntiles, mt));
+    const int c8 = (kch + 7) / 8, mt = (rows + 15) / 16;
+    // (4 accumulator rows per wave only exist un-segmented: the switch's order applies from 256 samples)
+    const char* ord = L >= 256 ? (transposed ? sw.order_d : sw.order_f) : nullptr;
+    p.mrep = pick_mrep_h3(mt, ord ? ord : h3_order(taps, L, p.ntiles, mt));
     p.mtp = round_up(mt, p.mrep);
     p.nch = (c8 + 3) / 4;
-    p.ntt = (p.mrep < 4 && L >= 32) ? h3_tail_steps(kch, taps) : 0;      // (WUNET_H3D_HAS_TAIL: the shapes at the register limit go without)
+    p.ntt = (p.mrep < 4 && L >= 32) ? h3_tail_steps(kch, taps, sw) : 0;      // (WUNET_H3D_HAS_TAIL: the shapes at the register limit go without)
     const int ns = h3_stage_count(kch, taps, p.ntt);
     const int nseg = L >= 256 ? 1 : 256 / L;
-    p.sps = h3_stages_per_split(p.ntiles * (p.mtp / p.mrep), ns, 256 * h3d_blocks_per_cu(nseg, p.mrep, bf));
+    p.sps = h3_stages_per_split(p.ntiles * (p.mtp / p.mrep), ns, 256 * h3d_blocks_per_cu(nseg, p.mrep, bf), sw);
     p.ksplit = (ns + p.sps - 1) / p.sps;
-    (void)ntg;
     return p;
 }
 
-// Tiling of the split weight gradient of one layer (fills l.h3w_*)
-void plan_h3_wgrad(LayerPlan& l, int B)
+// Tiling of the split weight gradient of one layer
+H3WgradPlan plan_h3_wgrad(int B, int L, int cin, int cout, int taps, int bf, const PlanSwitches& sw)
 {
-    const int mt = (l.cout + 15) / 16, cib = l.taps == 15 ? 32 : 64;
+    H3WgradPlan w{};
+    const int mt = (cout + 15) / 16, cib = taps == 15 ? 32 : 64;
     // 3 or 2 m-tiles per block: those DMA-staged kernels fit two blocks per CU, and two independent blocks beat taller
     // single blocks (weight gradients 1.25 -> 1.14 ms per step; the register-staged kernel preferred 5-6 m-tiles)
     // per-layer sweep (profiles/r1_h3_rows_per_wave_sweep.txt): 4 where 5 taps divide evenly at >= 256 samples
     // (decoder.7: 79 -> 68 us); 2 on the short 15-tap levels (encoder.6/7/9: 44 -> 39, 32 -> 29, 21 -> 18 us)
     // (round-2 sweep, profiles/r2_wgrad_rows_sweep.txt: 5 m-tiles in one block - no padded rows - win on the 15-tap layer with
     // Cout = 80 .. 72 at >= 1024 samples (encoder.2: 118 -> 106 us) although that kernel runs one block per CU)
-    const char* w_order = (l.taps == 5 && l.L >= 256 && mt % 4 == 0) ? "432" : (l.taps == 15 && l.L <= 256) ? "2" :
-                          (l.taps == 15 && mt == 5 && l.L >= 1024) ? "532" : "32";
-    l.h3w_mrep = pick_mrep_h3(mt, "WUNET_H3W_ORDER", w_order);
-    l.h3w_mblocks = round_up(mt, l.h3w_mrep) / l.h3w_mrep;
-    l.h3w_nblocks = (l.cin + cib - 1) / cib;
+    const char* w_order = (taps == 5 && L >= 256 && mt % 4 == 0) ? "432" : (taps == 15 && L <= 256) ? "2" :
+                          (taps == 15 && mt == 5 && L >= 1024) ? "532" : "32";
+    w.mrep = pick_mrep_h3(mt, sw.order_w ? sw.order_w : w_order);
+    w.mblocks = round_up(mt, w.mrep) / w.mrep;
+    w.nblocks = (cin + cib - 1) / cib;
     // 128 positions per K chunk (256 measured 5-8 % faster for the kernel alone and slower in the concurrent step, 64-position
     // double-buffered chunks neutral: HISTORY.md sections 7, 8)
-    l.h3w_tp = 128;
-    // wgrad_h3d_kernel<.., false> (single LDS buffer, two blocks per CU) where its registers allow: k5 up to 4 m-tiles, k15 up to 3
-    const bool sb2 = l.L >= 128 && ((l.taps == 5 && l.h3w_mrep <= 4) || (l.taps == 15 && l.h3w_mrep <= 3));
-    const long long slots = 256LL * ((l.h3w_mrep <= 2 || sb2) ? 2 : 1);      // resident blocks: launch bounds of the wgrad kernels
-    long long ks = slots / ((long long)l.h3w_mblocks * l.h3w_nblocks);
+    w.tp = 128;
+    // wgrad_h3d_kernel (DMA-staged): whole chunks inside one item (L >= 128), both buffers within the 160 KB.  Two blocks per CU with
+    // a single buffer where the registers allow it (two independent blocks hide each other's waits: +18-28 % on those kernels), else
+    // one block with double-buffered tiles
+    const LayerGeom g{cin, cout, taps, L};
+    const int nseg = L >= w.tp ? 1 : w.tp / L;
+    w.dma = (nseg == 1 && w.tp == 128 && h3w_dma_smem(g, w, bf) <= 160 * 1024 && w.mrep <= (taps == 15 ? 6 : 5)) ? 1 : 0;
+    w.db = h3w_regs_allow_two_blocks(taps, w.mrep) ? 0 : 1;
+    const bool sb2 = L >= 128 && h3w_regs_allow_two_blocks(taps, w.mrep);
+    const long long slots = 256LL * ((w.mrep <= 2 || sb2) ? 2 : 1);      // resident blocks: launch bounds of the wgrad kernels
+    long long ks = slots / ((long long)w.mblocks * w.nblocks);
     if (ks < 1) ks = 1;
-    const long long chunks = ((long long)B * l.L + l.h3w_tp - 1) / l.h3w_tp;
+    const long long chunks = ((long long)B * L + w.tp - 1) / w.tp;
     if (ks > chunks) ks = chunks;
     // XCD-aware walk of wgrad_h3d_kernel (WgradH3dArgs::xcd_walk): the nyz blocks of one K split share an XCD, so an XCD hosts
     // ceil(ks / 8) * nyz blocks - they must fit its share of the resident slots, else some blocks wait for a second round (measured:
     // wgrad_h3d_kernel<5, 3> 404 -> 493 us per step with 66 / 72 blocks on an XCD of 64 slots).  The split count is trimmed to fit when
     // that costs at most 6 % of the blocks; otherwise the layer keeps the 3-D grid.  WUNET_WGRAD_XCD=0: off (A/B switch).
-    {
-        static const bool xcd_off = getenv("WUNET_WGRAD_XCD") != nullptr && atoi(getenv("WUNET_WGRAD_XCD")) == 0;
-        const long long nyz = (long long)l.h3w_mblocks * l.h3w_nblocks, per_xcd = slots / 8;
-        l.h3w_xcd = 0;
-        if (!xcd_off && nyz > 1 && l.L >= 128) {
-            if (((ks + 7) / 8) * nyz <= per_xcd) l.h3w_xcd = 1;
-            else {
-                const long long ks8 = (per_xcd / nyz) * 8;
-                if (ks8 >= 8 && ks8 * 100 >= ks * 94) { ks = ks8; l.h3w_xcd = 1; }
-            }
+    const long long nyz = (long long)w.mblocks * w.nblocks, per_xcd = slots / 8;
+    if (!sw.wgrad_xcd_off && nyz > 1 && L >= 128) {
+        if (((ks + 7) / 8) * nyz <= per_xcd) w.xcd = 1;
+        else {
+            const long long ks8 = (per_xcd / nyz) * 8;
+            if (ks8 >= 8 && ks8 * 100 >= ks * 94) { ks = ks8; w.xcd = 1; }
         }
     }
-    l.h3w_cps = (int)((chunks + ks - 1) / ks);
-    l.h3w_ksplit = (int)((chunks + l.h3w_cps - 1) / l.h3w_cps);
+    w.cps = (int)((chunks + ks - 1) / ks);
+    w.ksplit = (int)((chunks + w.cps - 1) / w.cps);
+    return w;
 }
 
 // The x2 upsample's source pairs as the fused loaders assume them (conv_h3u_kernel, and the gradient-side kernels that gather through
@@ -390,203 +420,215 @@ bool up_pairs_regular(int Lin)
     return seen[Lin] = ok;
 }
 
-void layout_workspace(wunet_ctx* c)
+// conv_h3u_kernel (wunet_h3u.h: the operand pass inside the conv, loader waves beside the MFMA waves) can run decoder layer l: the
+// un-split 5-tap conv on the split kernels at >= 256 samples, whole channel groups on both halves, the regular upsample pairs
+static bool h3u_can_run(const wunet_ctx* c, const LayerPlan& l)
 {
-    const int B = c->B, T = c->T, ci = c->ci;
-    size_t off = 0, wpk = 0, stats_max = 0, spart_max = 0;
+    return l.h3f && l.h3x && l.kind == LK_UPCAT && l.taps == 5 && l.L >= 256 && l.c0 % 8 == 0 && l.cin % 8 == 0 &&
+           l.hf.mrep <= 4 && l.f.ksplit == 1 && !c->bf && !c->padded && up_pairs_regular(l.L / 2);
+}
+
+// Per layer: the kernel family of the forward conv, the data gradient and the weight gradient, and their tilings
+static void decide_layers(wunet_ctx* c, const PlanSwitches& sw)
+{
+    const int B = c->B;
     for (int i = 0; i < c->NL; ++i) {
         LayerPlan& l = c->ly[i];
         l.f = plan_conv(B, l.L, l.cout, l.cin, l.taps);
         l.d = plan_conv(B, l.L, l.cin, l.cout, l.taps);
         l.w = plan_wgrad(B, l.L, l.cin, l.cout, l.taps);
         if (l.L < 4) { l.f.ksplit = 1; l.d.ksplit = 1; }    // levels of 1-2 samples run the scalar kernels of wunet_tiny.h
-        {
-            // auto: only where the fp32 planner would launch an un-split full-width grid (enough 256-position tiles to fill
-            // the chip); forced (2): every level the kernels can run (tests of small shapes)
-            l.first = (i == 0 && l.cin == 1 && l.taps == 15 && l.L >= 256) ? 1 : 0;
-            // fp16-split kernels.  auto (1): levels >= 256 samples where the fp32 planner would launch an un-split
-            // full-width grid (enough 256-position tiles to fill the chip) and the 128- to 16-sample levels of a large
-            // batch (split-K fills the chip there); forced (2): every level the kernels can run (tests of small shapes)
-            const long long posn = (long long)B * l.L;
-            // (the 16-sample level: 20-38 us per step faster on conv_h3d_kernel<., ., 16> than on the fp32 kernels)
-            const int min_l = 16;
-            const bool big = c->h3 && !l.first && l.L >= 16 && posn >= 256 &&
-                             (c->h3 == 2 || (l.L >= 256 ? (l.f.nrep == 4 && l.f.ksplit == 1) : (l.L >= min_l && posn >= 1024)));
-            l.h3f = big ? 1 : 0;
-            // backward: data gradient AND weight gradient together (g_z then only exists in the split layout)
-            l.h3d = (big && i > 0 && l.cin >= 16 && (c->h3 == 2 || l.L < 256 || (l.d.nrep == 4 && l.d.ksplit == 1))) ? 1 : 0;
-            l.h3w = l.h3d;
-            l.h3x = l.h3w;        // ... and so does the conv input (no fp32 xin)
-            if (l.h3f) {
-                const H3ConvPlan p = plan_h3_conv(B, l.L, l.cout, l.cin, l.taps, "WUNET_H3_ORDER", c->bf);
-                l.h3f_mrep = p.mrep; l.h3f_mtp = p.mtp; l.h3f_nch = p.nch; l.h3f_sps = p.sps; l.h3f_ntt = p.ntt;
-                l.f.ksplit = p.ksplit;
-                l.f.grid_x = p.ntiles;                 // one statistics row per tile (f_rows below)
-            }
-            if (l.h3d) {
-                const H3ConvPlan p = plan_h3_conv(B, l.L, l.cin, l.cout, l.taps, "WUNET_H3D_ORDER", c->bf);
-                l.h3d_mrep = p.mrep; l.h3d_mtp = p.mtp; l.h3d_nch = p.nch; l.h3d_sps = p.sps; l.h3d_ntt = p.ntt;
-                l.d.ksplit = p.ksplit;
-            }
-            if (l.first) { l.f.ksplit = 1; l.f.grid_x = (int)(((long long)B * l.L + 1023) / 1024); }   // one statistics row per wave
-            // conv_h3u_kernel (wunet_h3u.h: the operand pass inside the conv, loader waves beside the MFMA waves) for the decoder levels
-            // whose conv is bound by operand bytes, not by the matrix pipe.  WUNET_H3U = "<eval min L>,<train min L>" (0: off), read
-            // when the context is planned
-            {
-                int u_eval = 512, u_train = 2048;    // (batch 64, one box - eval: off 1.87 ms, from 2048 1.567, from 512 1.516; training step: off 5.12 / 5.20, from 2048 or 4096 5.08 / 5.15, from 512 5.17: profiles/r5_h3u_threshold_sweep.txt)
-                if (const char* e = getenv("WUNET_H3U")) {
-                    int a = 0, b = 0;
-                    const int got = sscanf(e, "%d,%d", &a, &b);
-                    if (got == 2) { u_eval = a; u_train = b; }
-                    else if (got == 1) u_eval = u_train = a;      // one number: both thresholds (WUNET_H3U=0 turns the kernel off everywhere)
-                }
-                const bool can = l.h3f && l.h3x && l.kind == LK_UPCAT && l.taps == 5 && l.L >= 256 && l.c0 % 8 == 0 && l.cin % 8 == 0 &&
-                                 l.h3f_mrep <= 4 && l.f.ksplit == 1 && !c->bf && !c->padded && up_pairs_regular(l.L / 2);
-                l.h3u = (can && u_eval > 0 && l.L >= u_eval) ? 1 : 0;
-                l.h3u_train = (can && u_train > 0 && l.L >= u_train) ? 1 : 0;
-            }
-        }
-        l.f_rows = l.h3f ? l.f.grid_x : l.f.grid_x * WUNET_WAVES;
-        l.f_wpk = wpk;
-        wpk += align64((size_t)l.f.mtiles_p * l.f.cp * l.taps * 16);
-        if (l.f.ksplit == 1 && (size_t)l.f_rows * l.cout * 2 > stats_max) stats_max = (size_t)l.f_rows * l.cout * 2;
-        // (a padded length takes every conv but the first through the bias-free buffer and conv_reduce_bn_kernel: its statistics skip
-        // the row padding, the conv kernels need not know)
-        if ((l.f.ksplit > 1 || c->padded) && (size_t)64 * l.cout * 2 > stats_max) stats_max = (size_t)64 * l.cout * 2;
-        if ((l.f.ksplit > 1 || c->padded) && (size_t)l.f.ksplit * B * l.cout * l.L > spart_max) spart_max = (size_t)l.f.ksplit * B * l.cout * l.L;
-        if (l.L < 4 && (size_t)B * l.cout * l.L > spart_max) spart_max = (size_t)B * l.cout * l.L;
-        if (i > 0 && l.d.ksplit > 1 && (size_t)l.d.ksplit * B * l.cin * l.L > spart_max) spart_max = (size_t)l.d.ksplit * B * l.cin * l.L;
-        l.z = off; off += align64((size_t)B * l.cout * l.L);
-        l.a = off; off += align64(l.cout);
-        l.s = off; off += align64(l.cout);
-        l.mean = off; off += align64(l.cout);
-        l.rstd = off; off += align64(l.cout);
-        l.wl1 = off; off += align64(l.cout);
-        l.xin = off; if (i > 0 && !l.h3x) off += align64((size_t)B * l.cin * l.L);   // the conv's activated input, materialised once
-    }
-    // the operand pass of encoder-side layer i (decimation of its producer's activation) also writes that activation at full
-    // resolution into the split input of the decoder layer that concatenates it: one read of the producer's z instead of two
-    for (int i = 0; i < c->NL; ++i) c->ly[i].skip_from = 0;
-    for (int i = 1; i <= c->n; ++i) {
-        const int dj = 2 * c->n - i + 1;
-        LayerPlan& e = c->ly[i];
-        LayerPlan& d = c->ly[dj];
-        if (e.kind == LK_DECIM && d.kind == LK_UPCAT && e.h3x && d.h3x && d.src1 == e.src0 && d.c0 % 8 == 0 && !getenv("WUNET_NO_SKIP_FUSE"))      // (test hook: the decoder-side pass reads the skip itself, eval mode's path)
-            d.skip_from = i;
-    }
-    c->stats_off = off; off += align64(stats_max);
-    c->wpkf_off = off; off += align64(wpk);
-    c->spart_off = off; off += align64(spart_max);
-    // ---- fp16-split path: split activations + forward weight packs live in the forward segment
-    size_t wfh = 0;
-    for (int i = 0; i < c->NL; ++i) {
-        LayerPlan& l = c->ly[i];
-        l.xh = l.xl = l.xzp = 0; l.h3f_wpk = l.h3d_wpk = 0;
+        l.first = (i == 0 && l.cin == 1 && l.taps == 15 && l.L >= 256) ? 1 : 0;
+        // fp16-split kernels.  auto (1): levels >= 256 samples where the fp32 planner would launch an un-split
+        // full-width grid (enough 256-position tiles to fill the chip) and the 128- to 16-sample levels of a large
+        // batch (split-K fills the chip there); forced (2): every level the kernels can run (tests of small shapes)
+        // (the 16-sample level: 20-38 us per step faster on conv_h3d_kernel<., ., 16> than on the fp32 kernels)
+        const long long posn = (long long)B * l.L;
+        const bool big = c->h3 && !l.first && l.L >= 16 && posn >= 256 &&
+                         (c->h3 == 2 || (l.L >= 256 ? (l.f.nrep == 4 && l.f.ksplit == 1) : posn >= 1024));
+        l.h3f = big ? 1 : 0;
+        // backward: data gradient AND weight gradient together (g_z then only exists in the split layout)
+        l.h3d = (big && i > 0 && l.cin >= 16 && (c->h3 == 2 || l.L < 256 || (l.d.nrep == 4 && l.d.ksplit == 1))) ? 1 : 0;
+        l.h3w = l.h3d;
+        l.h3x = l.h3w;        // ... and so does the conv input (no fp32 xin)
         if (l.h3f) {
-            const int c8 = (l.cin + 7) / 8;
-            l.xh = off; off += align64((size_t)B * c8 * l.L * 4);
-            l.xl = off; off += align64((size_t)B * c8 * l.L * 4);
-            l.xzp = off; off += 64;
-            l.h3f_wpk = wfh; wfh += (size_t)l.h3f_mtp * l.h3f_nch * l.taps * 512;
+            l.hf = plan_h3_conv(B, l.L, l.cout, l.cin, l.taps, false, c->bf, sw);
+            l.f.ksplit = l.hf.ksplit;
+            l.f.grid_x = l.hf.ntiles;              // one statistics row per tile (f_rows below)
         }
+        if (l.h3d) {
+            l.hd = plan_h3_conv(B, l.L, l.cin, l.cout, l.taps, true, c->bf, sw);
+            l.d.ksplit = l.hd.ksplit;
+        }
+        if (l.h3w) l.hw = plan_h3_wgrad(B, l.L, l.cin, l.cout, l.taps, c->bf, sw);
+        if (l.first) { l.f.ksplit = 1; l.f.grid_x = (int)(((long long)B * l.L + 1023) / 1024); }   // one statistics row per wave
+        // conv_h3u_kernel for the decoder levels whose conv is bound by operand bytes, not by the matrix pipe (WUNET_H3U: the thresholds)
+        const bool can = h3u_can_run(c, l);
+        l.h3u = (can && sw.h3u_eval > 0 && l.L >= sw.h3u_eval) ? 1 : 0;
+        l.h3u_train = (can && sw.h3u_train > 0 && l.L >= sw.h3u_train) ? 1 : 0;
+        l.f_rows = l.h3f ? l.f.grid_x : l.f.grid_x * WUNET_WAVES;
+        // pieces of a channel's B*L positions, one block of the gradient-assembly pass each: at least 4096 positions, at most 128 pieces
+        // (round 4, with the blocks of one channel adjacent in the grid: 32 / 64 / 128 / 256 pieces -> 5.174 / 5.136 / 5.116 / 5.130 ms
+        // per step; WUNET_A_CAP: measurement hook)
+        const long long sp = posn / 4096;
+        const int a_cap = sw.a_cap < 1 ? 1 : (sw.a_cap > 256 ? 256 : sw.a_cap);      // (hpart2 holds 256 rows)
+        l.a_split = (int)(sp < 1 ? 1 : (sp > a_cap ? a_cap : sp));
     }
-    c->h3_wf_halfs = wfh;
-    c->h3_wf_hi = off; off += align64((wfh + 1) / 2);
-    c->h3_wf_lo = off; off += align64((wfh + 1) / 2);
-    c->fslot_off = off; off += align64((size_t)WUNET_SLOT_FLOATS * c->NL);
-    c->wmax_off = off; off += align64((size_t)WUNET_WMAX_PARTS * c->NL);
-    // eval mode: an encoder level's un-split split conv (15 taps, whole-row tiles) writes the next encoder level's operand in its epilogue
-    // (conv_h3d_kernel<.., EVOP>; WUNET_NO_EVOP=1, read when the context is planned: A/B switch)
-    for (int i = 0; i < c->NL; ++i) c->ly[i].evop = 0;
-    for (int i = 1; i + 1 <= c->n; ++i) {
-        LayerPlan& p = c->ly[i];
-        const LayerPlan& q = c->ly[i + 1];
-        if (p.h3f && !p.first && p.taps == 15 && p.L >= 256 && p.f.ksplit == 1 && p.h3f_mrep <= 4 && q.kind == LK_DECIM && q.src0 == i && q.h3f && q.h3x &&
-            !c->bf && !c->padded && !getenv("WUNET_NO_EVOP"))
-            p.evop = 1;
+    const long long hb = ((long long)B * c->T) / 2048;
+    c->head_blocks = (int)(hb < 1 ? 1 : (hb > 1024 ? 1024 : hb));
+    c->e0 = sw.no_e0 ? 0 : 1;
+}
+
+// The hand-offs between layers, one predicate over the two layers involved each.
+// Skip half: the operand pass of encoder-side layer e (decimation of its producer's activation) also writes that activation at full
+// resolution into the split input of the decoder layer d that concatenates it: one read of the producer's z instead of two
+// (WUNET_NO_SKIP_FUSE: the decoder-side pass reads the skip itself, eval mode's path)
+static bool skip_planned(const LayerPlan& e, const LayerPlan& d) { return e.kind == LK_DECIM && d.kind == LK_UPCAT && e.h3x && d.h3x && d.src1 == e.src0 && d.c0 % 8 == 0; }
+// EVOP, eval mode: encoder level p's un-split split conv (15 taps, whole-row tiles) writes the next encoder level q's operand in its
+// epilogue (conv_h3d_kernel<.., EVOP>)
+static bool evop_planned(const wunet_ctx* c, const LayerPlan& p, const LayerPlan& q, int pi)
+{
+    return p.h3f && !p.first && p.taps == 15 && p.L >= 256 && p.f.ksplit == 1 && p.hf.mrep <= 4 && q.kind == LK_DECIM && q.src0 == pi && q.h3f && q.h3x &&
+           !c->bf && !c->padded;
+}
+// UPT: decoder layer q's data gradient stores the rows of the upsampled half of its input pulled back through the upsample
+// (conv_h3d_kernel<.., UPT>, ConvH3Args::uh_*): un-split whole-row tiles, the producer p on the split kernels
+static bool upt_planned(const wunet_ctx* c, const LayerPlan& q, const LayerPlan& p)
+{
+    return q.kind == LK_UPCAT && q.h3d && q.L >= 256 && q.d.ksplit == 1 && !(q.c0 & 3) && !(q.cin & 3) && q.c0 == p.cout && !c->bf && !c->padded &&
+           p.h3d && p.L >= 128 && up_pairs_regular(q.L / 2);
+}
+static void plan_handoffs(wunet_ctx* c, const PlanSwitches& sw)
+{
+    // skip_from: read by skip_handoff (wunet_forward.cpp), at both ends
+    for (int i = 1; i <= c->n && !sw.no_skip_fuse; ++i) {
+        LayerPlan& d = c->ly[2 * c->n - i + 1];
+        if (skip_planned(c->ly[i], d)) d.skip_from = i;
     }
-    for (int i = 0; i < c->NL; ++i) c->ly[i].feeds_h3 = 0;
+    // evop: read by evop_handoff (wunet_forward.cpp), at both ends
+    for (int i = 1; i + 1 <= c->n && !sw.no_evop; ++i)
+        if (evop_planned(c, c->ly[i], c->ly[i + 1], i)) c->ly[i].evop = 1;
+    // feeds_h3: read by fwd_layer_plan (wunet_forward.cpp) - who measures the bound of an activation that feeds a split operand
     for (int i = 1; i < c->NL; ++i) {
         const LayerPlan& l = c->ly[i];
         if (!l.h3f) continue;
         c->ly[l.src0].feeds_h3 = 1;
         if (l.kind == LK_UPCAT) c->ly[l.src1].feeds_h3 = 1;
     }
-    if (c->padded) {            // padded copies of the caller's tensors (rows of T floats, the caller's hold Tt)
-        c->pad_in = off; off += align64((size_t)B * T);
-        c->pad_out = off; off += align64((size_t)B * T);
-    }
-    c->fwd_floats = off;
+    // upt: read by upt_handoff (wunet_backward.cpp), at both ends
+    for (int i = c->n + 1; i < c->NL && !sw.upt_off; ++i)
+        if (upt_planned(c, c->ly[i], c->ly[c->ly[i].src0])) c->ly[i].upt = 1;
+}
 
-    size_t wpkb = 0, bpart_max = 0, wgpart_max = 0;
+// the workspace as a bump allocator of float offsets, every allotment a multiple of 64 floats
+struct Bump { size_t off; size_t take(size_t floats) { const size_t at = off; off += align64(floats); return at; } };
+
+// floats of BN statistics partials the forward conv of layer l needs: its own rows where it runs un-split, 64 of conv_reduce_bn_kernel
+// (a padded length takes every conv but the first through the bias-free buffer and conv_reduce_bn_kernel: its statistics skip
+// the row padding, the conv kernels need not know)
+static size_t stats_floats(const wunet_ctx* c, const LayerPlan& l) { return (size_t)(l.f.ksplit > 1 ? 64 : std::max(l.f_rows, c->padded ? 64 : 0)) * l.cout * 2; }
+// floats of the bias-free split buffer layer i needs: the forward's split-K slices (a padded length: its one), else the scalar
+// kernels' result; the data gradient's split-K slices
+static size_t spart_floats(const wunet_ctx* c, int i)
+{
+    const LayerPlan& l = c->ly[i];
+    const size_t fwd = (size_t)c->B * l.cout * l.L, bwd = (size_t)c->B * l.cin * l.L;
+    const size_t f = (l.f.ksplit > 1 || c->padded) ? l.f.ksplit * fwd : l.L < 4 ? fwd : 0;
+    return std::max(f, (i > 0 && l.d.ksplit > 1) ? l.d.ksplit * bwd : 0);
+}
+// floats of weight-gradient partials layer l needs: the split kernels' padded tiles, else the fp32 kernel's rows
+static size_t wgpart_floats(const LayerPlan& l) { return l.h3w ? (size_t)l.hw.ksplit * h3w_part_stride(l, l.hw) : (size_t)l.w.rows * l.cout * l.cin * l.taps; }
+// floats of pass A's per-piece partials of layer l (the sums; the maxima in a second region of that size)
+static size_t bpart_floats(const LayerPlan& l) { return (size_t)l.a_split * l.cout * 2; }
+
+// The forward segment [0, fwd_floats): sizes only
+static void allot_forward(wunet_ctx* c)
+{
+    const size_t B = c->B;
+    Bump b{0};
+    size_t wpk = 0, stats_max = 0, spart_max = 0, wfh = 0;
     for (int i = 0; i < c->NL; ++i) {
         LayerPlan& l = c->ly[i];
-        l.g = off; off += align64((size_t)B * l.cout * l.L);
-        l.dx = off; if (i > 0) off += align64((size_t)B * l.cin * l.L);
-        l.k1 = off; off += align64(l.cout);
-        l.k2 = off; off += align64(l.cout);
-        l.k3 = off; off += align64(l.cout);
+        l.f_wpk = wpk;
+        wpk += align64((size_t)l.f.mtiles_p * l.f.cp * l.taps * 16);
+        stats_max = std::max(stats_max, stats_floats(c, l));
+        spart_max = std::max(spart_max, spart_floats(c, i));
+        l.z = b.take(B * l.cout * l.L);
+        for (size_t* v : {&l.a, &l.s, &l.mean, &l.rstd, &l.wl1}) *v = b.take(l.cout);
+        l.xin = b.take(i > 0 && !l.h3x ? B * l.cin * l.L : 0);      // the conv's activated input, materialised once
+    }
+    c->stats_off = b.take(stats_max);
+    c->wpkf_off = b.take(wpk);
+    c->spart_off = b.take(spart_max);
+    // ---- fp16-split path: split activations + forward weight packs live in the forward segment
+    for (int i = 0; i < c->NL; ++i) {
+        LayerPlan& l = c->ly[i];
+        if (!l.h3f) continue;
+        const size_t plane = B * ((l.cin + 7) / 8) * l.L * 4;
+        l.xh = b.take(plane); l.xl = b.take(plane); l.xzp = b.take(64);
+        l.h3f_wpk = wfh; wfh += (size_t)l.hf.mtp * l.hf.nch * l.taps * 512;
+    }
+    c->h3_wf_halfs = wfh;
+    c->h3_wf_hi = b.take((wfh + 1) / 2); c->h3_wf_lo = b.take((wfh + 1) / 2);
+    c->fslot_off = b.take((size_t)WUNET_SLOT_FLOATS * c->NL);
+    c->wmax_off = b.take((size_t)WUNET_WMAX_PARTS * c->NL);
+    if (c->padded) { c->pad_in = b.take(B * c->T); c->pad_out = b.take(B * c->T); }      // padded copies of the caller's tensors (rows of T floats, the caller's hold Tt)
+    c->fwd_floats = b.off;
+}
+
+// The backward segment [fwd_floats, total_floats): sizes only
+static void allot_backward(wunet_ctx* c)
+{
+    const size_t B = c->B;
+    Bump b{c->fwd_floats};
+    size_t wpkb = 0, bpart_max = 0, wgpart_max = 0, wbh = 0;
+    for (int i = 0; i < c->NL; ++i) {
+        LayerPlan& l = c->ly[i];
+        l.g = b.take(B * l.cout * l.L);
+        l.dx = b.take(i > 0 ? B * l.cin * l.L : 0);
+        for (size_t* v : {&l.k1, &l.k2, &l.k3}) *v = b.take(l.cout);
         l.d_wpk = wpkb;
         if (i > 0) wpkb += align64((size_t)l.d.mtiles_p * l.d.cp * l.taps * 16);
-        if (l.h3w) plan_h3_wgrad(l, B);
-        const size_t wg = l.h3w ? (size_t)l.h3w_ksplit * h3w_part_stride(l) : (size_t)l.w.rows * l.cout * l.cin * l.taps;
-        if (wg > wgpart_max) wgpart_max = wg;
-        long long sp = ((long long)B * l.L) / 4096;
-        // pieces of a channel's B*L positions, one block of the gradient-assembly pass each: at least 4096 positions, at most 128 pieces
-        // (round 4, with the blocks of one channel adjacent in the grid: 32 / 64 / 128 / 256 pieces -> 5.174 / 5.136 / 5.116 / 5.130 ms
-        // per step; WUNET_A_CAP: measurement hook)
-        static const int a_cap_env = getenv("WUNET_A_CAP") ? atoi(getenv("WUNET_A_CAP")) : 128;
-        const int a_cap = a_cap_env < 1 ? 1 : (a_cap_env > 256 ? 256 : a_cap_env);      // (hpart2 below holds 256 rows)
-        l.a_split = (int)(sp < 1 ? 1 : (sp > a_cap ? a_cap : sp));
-        if ((size_t)l.a_split * l.cout * 2 > bpart_max) bpart_max = (size_t)l.a_split * l.cout * 2;
+        wgpart_max = std::max(wgpart_max, wgpart_floats(l));
+        bpart_max = std::max(bpart_max, bpart_floats(l));
     }
-    c->bpart_off = off; off += align64(bpart_max);
-    c->bmax_off = off; off += align64(bpart_max);
-    c->bound_off = off; off += align64(4096);
-    c->wgpart_off = off; off += align64(wgpart_max);
-    c->wpkb_off = off; off += align64(wpkb);
-    c->gh_off = off; off += align64((size_t)B * T);
-    {
-        long long hb = ((long long)B * T) / 2048;
-        c->head_blocks = (int)(hb < 1 ? 1 : (hb > 1024 ? 1024 : hb));
-    }
-    c->hpart_off = off; off += align64((size_t)c->head_blocks * 2);
-    c->hpart2_off = off; off += align64((size_t)256 * ci);          // pass A (head mode) partial head-weight gradients [a_split][ci]
-    c->e0part_off = off; off += align64((size_t)256 * ci * 48);     // pass A of the first layer (E0): its weight gradient's partial sums [a_split][ci][48]
-    c->e0 = getenv("WUNET_NO_E0") ? 0 : 1;
-    // ---- fp16-split data gradient: transposed packs, one shared split g_z buffer, scale slot
-    size_t wbh = 0;
+    c->bpart_off = b.take(bpart_max); c->bmax_off = b.take(bpart_max);
+    c->bound_off = b.take(4096);
+    c->wgpart_off = b.take(wgpart_max);
+    c->wpkb_off = b.take(wpkb);
+    c->gh_off = b.take(B * c->T);
+    c->hpart_off = b.take((size_t)c->head_blocks * 2);
+    c->hpart2_off = b.take((size_t)256 * c->ci);          // pass A (head mode) partial head-weight gradients [a_split][ci]
+    c->e0part_off = b.take((size_t)256 * c->ci * 48);     // pass A of the first layer (E0): its weight gradient's partial sums [a_split][ci][48]
+    // ---- fp16-split data gradient: transposed packs, a split g_z buffer per layer (the side stream reads it late), scale slot
     for (int i = 0; i < c->NL; ++i) {
         LayerPlan& l = c->ly[i];
         if (!l.h3d) continue;
-        const int c8 = (l.cout + 7) / 8;
-        l.h3d_wpk = wbh; wbh += (size_t)l.h3d_mtp * l.h3d_nch * l.taps * 512;
-        l.gzh = off; off += align64((size_t)B * c8 * l.L * 4);      // per layer: the side stream reads it late
-        l.gzl = off; off += align64((size_t)B * c8 * l.L * 4);
-        l.gzp = off; off += 64;
+        const size_t plane = B * ((l.cout + 7) / 8) * l.L * 4;
+        l.h3d_wpk = wbh; wbh += (size_t)l.hd.mtp * l.hd.nch * l.taps * 512;
+        l.gzh = b.take(plane); l.gzl = b.take(plane); l.gzp = b.take(64);
     }
-    // ---- UPT: a decoder layer's data gradient stores the rows of the upsampled half of its input pulled back through the upsample
-    // (conv_h3d_kernel<.., UPT>, ConvH3Args::uh_*): un-split whole-row tiles, the producer on the split kernels.  WUNET_UPT=0: off (A/B switch).
-    {
-        const bool upt_off = getenv("WUNET_UPT") != nullptr && atoi(getenv("WUNET_UPT")) == 0;      // (read when a context is planned)
-        for (int i = 0; i < c->NL; ++i) { c->ly[i].upt = 0; c->ly[i].dxh = c->ly[i].usp = 0; }
-        for (int i = c->n + 1; i < c->NL && !upt_off; ++i) {
-            LayerPlan& q = c->ly[i];
-            const LayerPlan& p = c->ly[q.src0];
-            if (q.kind != LK_UPCAT || !q.h3d || q.L < 256 || q.d.ksplit != 1 || (q.c0 & 3) || (q.cin & 3) || q.c0 != p.cout || c->bf || c->padded ||
-                !p.h3d || p.L < 128 || !up_pairs_regular(q.L / 2))
-                continue;
-            q.upt = 1;
-            q.dxh = off; off += align64((size_t)B * q.c0 * (q.L / 2));
-            q.usp = off; off += align64((size_t)2 * q.c0 * (((size_t)B * q.L + 255) / 256));
-        }
+    for (int i = c->n + 1; i < c->NL; ++i) {      // UPT: the half-resolution rows and the tile-edge terms
+        LayerPlan& q = c->ly[i];
+        if (q.upt) { q.dxh = b.take(B * q.c0 * (q.L / 2)); q.usp = b.take((size_t)2 * q.c0 * ((B * q.L + 255) / 256)); }
     }
     c->h3_wb_halfs = wbh;
-    c->h3_wb_hi = off; off += align64((wbh + 1) / 2);
-    c->h3_wb_lo = off; off += align64((wbh + 1) / 2);
-    c->h3_slot = off; off += align64(8 + 4 * (size_t)c->NL);      // 8 zero floats (DMA zero page), then {scale, 1/scale} of g_z per layer (offset 8 + 4*layer)
-    if (c->padded) { c->pad_gout = off; off += align64((size_t)B * T); }
-    c->total_floats = off;
+    c->h3_wb_hi = b.take((wbh + 1) / 2); c->h3_wb_lo = b.take((wbh + 1) / 2);
+    c->h3_slot = b.take(8 + 4 * (size_t)c->NL);      // 8 zero floats (DMA zero page), then {scale, 1/scale} of g_z per layer (offset 8 + 4*layer)
+    if (c->padded) c->pad_gout = b.take(B * c->T);
+    c->total_floats = b.off;
+}
+
+// Plans a context anew (wunet_create, wunet_set_h3): the switches, the layers' own decisions, the hand-offs between them, the two
+// workspace segments.  Everything a planning decides starts from zero, so a second planning leaves nothing of the first.
+void layout_workspace(wunet_ctx* c)
+{
+    const PlanSwitches sw = read_plan_switches();
+    for (LayerPlan& l : c->ly) static_cast<LayerDecisions&>(l) = LayerDecisions{};
+    decide_layers(c, sw);
+    plan_handoffs(c, sw);
+    allot_forward(c);
+    allot_backward(c);
 }
 
 }  // namespace wunet_host
