@@ -318,6 +318,32 @@ int wunet_mix_windows(const float* clean_flat, long long clean_total, const floa
                       float peak_limit, int batch, int length, void* scratch,
                       float* mixture, float* clean_out, float* gains /* [batch][2] or NULL */, void* stream);
 
+/* dst[b][j] = gains[b][1] * src[b][j] over [batch][length]: the level a of a `gains` table that wunet_mix_windows wrote, applied to
+ * another batch - the one float32 multiply that made clean_out, so a target scaled here equals a c bit for bit.  dst == src is
+ * allowed.  16-byte aligned src / dst when length % 4 == 0.  One launch, the mix's shape limits. */
+int wunet_apply_level(const float* src, const float* gains /* [batch][2] */, int batch, int length, float* dst, void* stream);
+
+/* Reverberant speech made on the device (no reference counterpart): row b is a window of the clean array convolved with a room impulse
+ * response out of a second flat float32 array - a per-row FIR as an exact fp32 MFMA GEMM (csrc/wunet_reverb.h).
+ *   x[t] = clean_flat[t] for t >= is and 0 in front of it: `is` is the first sample of the window's item, what lies before belongs to
+ *     another utterance and does not leak in.
+ *   reverberant[b][j] = sum over k < K of h[k] x[cs + j - k],  direct[b][j] = the same sum over k < min(early_taps, K), j < length.
+ *   With a response that starts at its direct path with h[0] = 1 (pack_rir_shard), early_taps = 1 gives the dry window itself and
+ *   early_taps at 50 ms the early-reflections target.
+ * Clamps: cs into [0, clean_total - length], is into [0, cs]; the RIR range [hs, hs + K) is cut to its part inside [0, rir_total) and K
+ * then to WUNET_REVERB_MAX_TAPS.  Nothing outside either array is addressed, and the loads are masked, not multiplied by zero.
+ * A row with K <= 0 is passed through: both outputs are the window's own bits.  Products are exact fp32 and an output is one chain of
+ * fewer than K + 256 fused adds in a fixed order: |out - exact| <= gamma(K + 256) sum |h[k]| |x[cs + j - k]|.
+ * rows: device int64 [batch][4] = window start cs, item start is, RIR start hs, RIR taps K.  early_taps >= 1 is used only when direct
+ * is not NULL.  reverberant / direct receive [batch][1][length] float32 (16-byte aligned when length % 4 == 0).  batch <= 65535,
+ * length <= 2^30.  One launch; everything it depends on is read from device memory, so a captured launch follows its tables.  No
+ * atomics: bit-identical run to run.  Caller-owned memory, no allocation, no synchronisation. */
+#define WUNET_REVERB_MAX_TAPS 16384
+int wunet_reverb_windows(const float* clean_flat, long long clean_total, const float* rir_flat, long long rir_total,
+                         const long long* rows,   /* [batch][4]: window start, clean item start, RIR start, RIR taps */
+                         int early_taps, int batch, int length,
+                         float* reverberant, float* direct /* [batch][1][length] or NULL */, void* stream);
+
 /* Measurement aid (tools/conv_trace.py; no reference counterpart): a device buffer of gridDim.x * 64 uint64 that the DMA-staged
  * conv / data-gradient kernel (conv_h3d_kernel) fills with shader-clock stamps of each block's phases (entry; per K stage: tile
  * landed, W buffer released, MFMAs issued; epilogue done), or NULL (default) to turn the stamps off.  Process-wide. */

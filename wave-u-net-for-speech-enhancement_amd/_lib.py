@@ -23,7 +23,7 @@ EXPORTS = [
     "wunet_stft_basis_bytes", "wunet_stft_basis", "wunet_stft_scratch_bytes", "wunet_stft_saved_bytes", "wunet_stft_forward",
     "wunet_stft_finalize", "wunet_stft_backward",
     "wunet_stoi_tables_bytes", "wunet_stoi_tables_build", "wunet_stoi_scratch_bytes", "wunet_stoi_forward",
-    "wunet_mix_scratch_bytes", "wunet_mix_windows",
+    "wunet_mix_scratch_bytes", "wunet_mix_windows", "wunet_apply_level", "wunet_reverb_windows",
 ]
 
 _vp = ctypes.c_void_p
@@ -102,6 +102,9 @@ def declare(lib):
         lib.wunet_mix_scratch_bytes.argtypes = [_i, _i]
         lib.wunet_mix_scratch_bytes.restype = _sz
         lib.wunet_mix_windows.argtypes = [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _vp, ctypes.c_float, _i, _i, _vp, _vp, _vp, _vp, _vp]
+    if hasattr(lib, "wunet_reverb_windows"):     # (the same)
+        lib.wunet_apply_level.argtypes = [_vp, _vp, _i, _i, _vp, _vp]
+        lib.wunet_reverb_windows.argtypes = [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _i, _vp, _vp, _vp]
     lib.wunet_comm_unique_id.argtypes = [_vp]
     lib.wunet_comm_create.argtypes = [_vp, _i, _i, ctypes.POINTER(_vp)]
     lib.wunet_comm_allreduce_sum.argtypes = [_vp, _vp, _sz, _vp]

@@ -3,6 +3,8 @@
 //   mix_partial_kernel   one pass over both windows: a block reduces one piece of one row to sum c^2, sum n^2 (double), max|c|, max|n|
 //   mix_apply_kernel     every block folds its row's partials in piece order -> g, a (double, rounded once to float32), then
 //                        mixture = a (c + g n), clean_out = a c over its piece
+//   apply_level_kernel   dst = a src for the a of a gains table (wunet_apply_level): the multiply of clean_out, for a target that is not
+//                        the window the mix read
 // The row description is read from device memory (rows[b] = clean start, noise item start, noise item length, noise phase; params[b] =
 // snr_db, level), so a captured pair of launches follows the tables it was captured on.  The sums use block_sum's fixed order and the
 // partials are folded in piece order by every block on its own: no atomics, bit-identical run to run.  Window starts are any sample,
@@ -167,5 +169,24 @@ static __global__ __launch_bounds__(WUNET_THREADS) void mix_apply_kernel(MixArgs
         }
         k += step;
         if (k >= R.nl) k -= R.nl;
+    }
+}
+
+// grid = (pieces of 4 * WUNET_THREADS samples, batch).  dst[b][j] = gains[b][1] * src[b][j]: mix_apply_kernel's one float32 multiply, so a
+// row scaled here equals that kernel's a c bit for bit.  A thread reads its four samples before it writes them: dst == src is allowed.
+static __global__ __launch_bounds__(WUNET_THREADS) void apply_level_kernel(const float* src, const float* gains, int length, float* dst)
+{
+    const int b = blockIdx.y, j0 = 4 * ((int)blockIdx.x * WUNET_THREADS + (int)threadIdx.x);
+    if (j0 >= length) return;
+    const float af = gains[2 * b + 1];
+    const float* s = src + (size_t)b * length;
+    float* d = dst + (size_t)b * length;
+    if ((length & 3) == 0) {
+        wunet_f4 v = wunet_ld4(s + j0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) v[u] = af * v[u];
+        wunet_st4(d + j0, v);
+    } else {
+        for (int u = 0; u < 4 && j0 + u < length; ++u) d[j0 + u] = af * s[j0 + u];
     }
 }

@@ -7,6 +7,7 @@
 #include "wunet_stft.h"
 #include "wunet_stoi.h"
 #include "wunet_mix.h"
+#include "wunet_reverb.h"
 
 using namespace wunet_host;
 
@@ -549,6 +550,48 @@ int wunet_mix_windows(const float* clean_flat, long long clean_total, const floa
     WUNET_CHECK_LAUNCH();
     prof_begin(st, "mix_apply_kernel", 3.0 * n, 4.0 * 4.0 * n);
     WUNET_LAUNCH(mix_apply_kernel, dim3(A.ppr, (unsigned)batch), dim3(WUNET_THREADS), 0, st, A);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// dst = a src with the a that wunet_mix_windows wrote into `gains` (a target that is not the window the mix read, at the mixture's level)
+int wunet_apply_level(const float* src, const float* gains, int batch, int length, float* dst, void* stream)
+{
+    if (mix_shape_check(batch, length)) return WUNET_E_ARG;
+    if (!src || !gains || !dst) return fail(WUNET_E_ARG, "apply_level: null argument");
+    if ((length & 3) == 0 && (((size_t)src | (size_t)dst) & 15)) return fail(WUNET_E_ARG, "apply_level: src and dst need 16-byte alignment when length %% 4 == 0");
+    hipStream_t st = (hipStream_t)stream;
+    const double n = (double)batch * length;
+    prof_begin(st, "apply_level_kernel", n, 4.0 * 2.0 * n);
+    WUNET_LAUNCH(apply_level_kernel, dim3((unsigned)((length + 4 * WUNET_THREADS - 1) / (4 * WUNET_THREADS)), (unsigned)batch), dim3(WUNET_THREADS), 0, st,
+                 src, gains, length, dst);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- data input: reverberant speech (wunet_reverb.h)
+int wunet_reverb_windows(const float* clean_flat, long long clean_total, const float* rir_flat, long long rir_total, const long long* rows,
+                         int early_taps, int batch, int length, float* reverberant, float* direct, void* stream)
+{
+    if (batch < 1 || length < 1) return fail(WUNET_E_ARG, "reverb: batch and length must be >= 1 (got %d x %d)", batch, length);
+    if (batch > 65535 || length > (1 << 30)) return fail(WUNET_E_ARG, "reverb: at most 65535 rows of 2^30 samples per call (got %d x %d)", batch, length);
+    if (clean_total < length) return fail(WUNET_E_ARG, "reverb: the clean array is shorter than one window (clean_total=%lld length=%d)", clean_total, length);
+    if (rir_total < 1) return fail(WUNET_E_ARG, "reverb: the rir array is empty (rir_total=%lld)", rir_total);
+    if (clean_total >= (1LL << 60) || rir_total >= (1LL << 60)) return fail(WUNET_E_ARG, "reverb: array too large");
+    if (!clean_flat || !rir_flat || !rows || !reverberant) return fail(WUNET_E_ARG, "reverb: null argument");
+    if (direct && early_taps < 1) return fail(WUNET_E_ARG, "reverb: early_taps must be >= 1 when direct is given (got %d)", early_taps);
+    if ((length & 3) == 0 && (((size_t)reverberant | (size_t)direct) & 15))
+        return fail(WUNET_E_ARG, "reverb: the outputs need 16-byte alignment when length %% 4 == 0");
+    hipStream_t st = (hipStream_t)stream;
+    ReverbArgs A{};
+    A.clean_flat = clean_flat; A.rir_flat = rir_flat; A.clean_total = clean_total; A.rir_total = rir_total; A.rows = rows;
+    A.early_taps = early_taps; A.length = length; A.reverberant = reverberant; A.direct = direct;
+    const double n = (double)batch * length;
+    // (the taps are the tables': the profiler's FLOP column counts one tap per sample, the bytes the two outputs)
+    prof_begin(st, "reverb_kernel", 2.0 * n, 4.0 * 3.0 * n);
+    WUNET_LAUNCH(reverb_kernel, dim3((unsigned)((length + WUNET_REVERB_CH - 1) / WUNET_REVERB_CH), (unsigned)batch), dim3(WUNET_THREADS), 0, st, A);
     prof_end(st);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;

@@ -664,6 +664,49 @@ class Engine:
                                                    mixture.data_ptr(), clean_out.data_ptr(), gains.data_ptr() if gains is not None else None,
                                                    self._stream(dev)))
 
+    def reverb_windows(self, clean_flat, rir_flat, rows, reverberant, direct=None, early_taps=1):
+        """include/wunet_hip.h: wunet_reverb_windows.  reverberant[b, 0, :] = the clean window that rows[b] = (window start, clean item
+        start, RIR start, RIR taps) names, convolved with its room impulse response (the source is zero in front of the item start);
+        direct (optional, the same shape) receives the first min(early_taps, taps) taps' share.  A row with no taps is passed through.
+        One launch, nothing read back, no scratch."""
+        f32 = torch.float32
+        if rows.dtype != torch.int64 or any(t.dtype != f32 for t in (clean_flat, rir_flat, reverberant)) or \
+                (direct is not None and direct.dtype != f32):
+            raise WunetError("reverb_windows: float32 arrays and outputs and int64 rows expected")
+        for t in (clean_flat, rir_flat, rows, reverberant) + ((direct,) if direct is not None else ()):
+            self._require(t, "reverb tensor")
+        if clean_flat.dim() != 1 or rir_flat.dim() != 1 or reverberant.dim() < 2:
+            raise WunetError("reverb_windows: the two arrays must be flat and the outputs [B, ..., L]")
+        B, L = reverberant.shape[0], reverberant.shape[-1]
+        if reverberant.numel() != B * L or tuple(rows.shape) != (B, 4) or (direct is not None and direct.shape != reverberant.shape):
+            raise WunetError("reverb_windows: shape mismatch (rows [B, 4], outputs [B, 1, L])")
+        dev = reverberant.device
+        if any(t.device != dev for t in (clean_flat, rir_flat, rows)) or (direct is not None and direct.device != dev):
+            raise WunetError("reverb_windows: every tensor must live on the outputs' device")
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_reverb_windows(clean_flat.data_ptr(), clean_flat.numel(), rir_flat.data_ptr(), rir_flat.numel(),
+                                                      rows.data_ptr(), int(early_taps), B, L, reverberant.data_ptr(),
+                                                      direct.data_ptr() if direct is not None else None, self._stream(dev)))
+
+    def apply_level(self, src, gains, dst=None):
+        """include/wunet_hip.h: wunet_apply_level.  dst[b] = gains[b, 1] * src[b] for the [B, 2] gains table that mix_windows wrote - the
+        multiply that made its clean_out.  dst None: in place.  Returns dst."""
+        dst = src if dst is None else dst
+        if any(t.dtype != torch.float32 for t in (src, gains, dst)):
+            raise WunetError("apply_level: float32 src, gains and dst expected")
+        for t in (src, gains, dst):
+            self._require(t, "apply_level tensor")
+        if src.dim() < 2:
+            raise WunetError("apply_level: shape mismatch (src and dst [B, ..., L], gains [B, 2])")
+        B, L = src.shape[0], src.shape[-1]
+        if src.numel() != B * L or dst.shape != src.shape or tuple(gains.shape) != (B, 2):
+            raise WunetError("apply_level: shape mismatch (src and dst [B, ..., L], gains [B, 2])")
+        if gains.device != src.device or dst.device != src.device:
+            raise WunetError("apply_level: every tensor must live on one device")
+        with self._device_guard(src.device):
+            self._check(self.lib.wunet_apply_level(src.data_ptr(), gains.data_ptr(), B, L, dst.data_ptr(), self._stream(src.device)))
+        return dst
+
 
 class _CtxHold:
     """`with engine._using(shape...) as handle`: the context cannot be evicted while the block runs."""

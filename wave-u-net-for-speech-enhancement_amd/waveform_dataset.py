@@ -22,6 +22,9 @@ Two pieces, both float32 mono like the reference's items:
 * `pack_mono_shard` + `MixLoader` - mixtures made on the device: a clean corpus and a noise corpus, each one flat float32 shard in
   HBM, combined per row at a freshly drawn SNR and level every step (include/wunet_hip.h: wunet_mix_windows - two launches per
   batch).  The host draws integers and a few floats per batch; the same batch contract comes out.
+
+* `pack_rir_shard` + `MixLoader(rir_prefix=...)` - reverberant speech: a third resident shard of room impulse responses, every clean
+  window convolved with a drawn response on the device before the noise is added (wunet_reverb_windows, one more launch).
 """
 import json
 import os
@@ -257,6 +260,40 @@ def pack_mono_shard(list_file, prefix, limit=None, offset=0):
     return len(names)
 
 
+RIR_MAX_TAPS = 16384          # include/wunet_hip.h: WUNET_REVERB_MAX_TAPS
+
+
+def pack_rir_shard(list_file, prefix, max_taps=8192, limit=None, offset=0):
+    """Room impulse responses for MixLoader(rir_prefix=...): pack_mono_shard's list handling (one path per line) and files (`<prefix>.f32`,
+    `<prefix>.index.json` with the same keys), but every response is cut to start at its direct path and scaled to it: with
+    p = argmax |h| the stored item is h[p : p + max_taps] / h[p], so h[0] == 1.0.  The propagation delay is gone - a dry target stays
+    time-aligned with the reverberant signal - and so is the response's own gain.  Returns the number of items."""
+    if not 1 <= max_taps <= RIR_MAX_TAPS:
+        raise ValueError(f"max_taps must be in [1, {RIR_MAX_TAPS}], got {max_taps}")
+    with open(os.path.abspath(os.path.expanduser(list_file)), "r") as f:
+        paths = [ln.strip() for ln in f][offset:]
+    paths = [p for p in (paths[:limit] if limit else paths) if p]
+    names, starts, lengths, rate, pos = [], [], [], None, 0
+    with open(prefix + ".f32", "wb") as out:
+        for path in paths:
+            h, r = read_wav(path)
+            if rate is not None and rate != r:
+                raise ValueError(f"mixed sample rates: {path} ({r} vs {rate})")
+            rate = r
+            p = int(np.argmax(np.abs(h))) if len(h) else 0
+            if len(h) == 0 or h[p] == 0.0:
+                raise ValueError(f"{path}: an all-zero impulse response")
+            h = (h[p:p + max_taps] / h[p]).astype(np.float32)
+            out.write(h.tobytes())
+            names.append(os.path.splitext(os.path.basename(path))[0])
+            starts.append(pos)
+            lengths.append(len(h))
+            pos += len(h)
+    with open(prefix + ".index.json", "w") as f:
+        json.dump({"names": names, "starts": starts, "lengths": lengths, "sample_rate": rate}, f)
+    return len(names)
+
+
 class MixLoader:
     """Batches of noisy mixtures made on the device from a clean shard and a noise shard that live in device memory.
 
@@ -269,10 +306,27 @@ class MixLoader:
     stays.  `clean_prefix` is a mono shard (pack_mono_shard) or a pair shard (pack_shard: its `.clean.f32` is used).  `last_draw`
     keeps the host tables and the device gains of the last batch: {"rows": int64 [B,4], "params": float32 [B,2], "gains": [B,2]}.
     There is no host implementation of the mix: device="cpu" needs an engine (the tests inject the emulator's).  Every rank of a
-    data-parallel job passes its own `seed` (e.g. seed + rank)."""
+    data-parallel job passes its own `seed` (e.g. seed + rank).
+
+    Reverberant speech (`rir_prefix`, a pack_rir_shard shard at the same sample rate; without it nothing below applies and the batches
+    are what they were).  Per row a response is drawn as well, from the same generator and after the batch's draws above: a seed starts
+    with the same rows and params with and without it, and then moves on by two more draws per batch.  With probability `p_reverb` the
+    clean window is convolved with the response on the device before the noise
+    is added (wunet_reverb_windows; what precedes the window inside its item reverberates into it, what precedes the item does not).
+    The mix then runs on the reverberant window r: the SNR is 10 log10(sum r^2 / sum (g n)^2), the peak guard bounds the mixture
+    a (r + g n).  The second element of a batch is the target, at the mixture's level a:
+      target="dry"          a c, the clean window itself (the response's first tap: h[0] = 1 in a packed shard)
+      target="early"        a (h[:E] * c), the direct path and the early reflections, E = round(early_ms sample_rate / 1000) taps
+      target="reverberant"  a r: denoising only
+    The guard looks at r and the noise; a dry or early target is NOT guarded and can exceed peak_limit where the response attenuates
+    (|r| well below |c|).  `last_draw` gains "rir_rows" (int64 [B,4]: window start, item start, RIR start, RIR taps - 0 for a dry row)
+    and "reverberant" (a r, [B,1,L]).  Four launches per batch."""
+
+    TARGETS = ("dry", "early", "reverberant")
 
     def __init__(self, clean_prefix, noise_prefix, batch_size, sample_length=16384, snr_db=(0.0, 20.0), level_db=None, peak_limit=0.99,
-                 p_clean=0.0, device="cpu", seed=0, steps_per_epoch=None, engine=None):
+                 p_clean=0.0, device="cpu", seed=0, steps_per_epoch=None, engine=None, rir_prefix=None, p_reverb=1.0, target="dry",
+                 early_ms=50.0):
         self.device = torch.device(device)
         if self.device.type != "cuda" and engine is None:
             raise ValueError("MixLoader mixes on the device: device='cpu' needs an engine (there is no host implementation of the mix)")
@@ -304,9 +358,31 @@ class MixLoader:
         self.gen = torch.Generator().manual_seed(seed)
         self.engine = engine
         self.last_draw = None
+        self.rir = None
+        if rir_prefix is not None:
+            self._init_rir(rir_prefix, p_reverb, target, early_ms)
 
     UPLOAD_CHUNK = ShardLoader.UPLOAD_CHUNK
     _resident = ShardLoader._resident
+
+    def _init_rir(self, rir_prefix, p_reverb, target, early_ms):
+        if target not in self.TARGETS:
+            raise ValueError(f"target must be one of {self.TARGETS}, got {target!r}")
+        ridx = json.load(open(rir_prefix + ".index.json"))
+        if ridx["sample_rate"] != self.sample_rate:
+            raise ValueError(f"clean and RIR sample rates differ: {self.sample_rate} vs {ridx['sample_rate']}")
+        self.early_taps = int(round(float(early_ms) * self.sample_rate / 1000.0)) if target == "early" else 1
+        if self.early_taps < 1:
+            raise ValueError(f"early_ms={early_ms} is less than one tap at {self.sample_rate} Hz")
+        if not 0.0 <= float(p_reverb) <= 1.0:
+            raise ValueError(f"p_reverb must be in [0, 1], got {p_reverb}")
+        rstarts, rlengths = np.asarray(ridx["starts"], np.int64), np.asarray(ridx["lengths"], np.int64)
+        rusable = np.nonzero(rlengths >= 1)[0]
+        if len(rusable) == 0:
+            raise ValueError("the RIR shard has no item of at least one sample")
+        self.rir = self._resident(rir_prefix + ".f32", int(rstarts[-1] + rlengths[-1]))
+        self.rir_usable, self.rir_starts, self.rir_lengths = torch.from_numpy(rusable), torch.from_numpy(rstarts), torch.from_numpy(rlengths)
+        self.target, self.p_reverb = target, float(p_reverb)
 
     def __len__(self):
         return self.steps
@@ -347,9 +423,43 @@ class MixLoader:
                                 gains, peak_limit=self.peak_limit)
         return mixture, clean, gains
 
+    def draw_rir(self, pick, rows):
+        """rir_rows int64 [B,4] of the batch that draw() just drew: window start, clean item start, RIR start, RIR taps (0: the row stays
+        dry).  Its two draws come after all of draw()'s."""
+        B, gen = self.batch_size, self.gen
+        rpick = self.rir_usable[torch.randint(len(self.rir_usable), (B,), generator=gen)]
+        taps = self.rir_lengths[rpick]
+        u = torch.rand(B, generator=gen, dtype=torch.float64)
+        taps = torch.where(u < self.p_reverb, taps, torch.zeros_like(taps))
+        return torch.stack([rows[:, 0], self.starts[pick], self.rir_starts[rpick], taps], dim=1).contiguous()
+
+    def mix_reverberant(self, rows, params, rir_rows):
+        """The batch that the three host tables describe: (mixture, target, gains, a r).  One linear chain of four launches: the reverb
+        into a staged batch (and, for a dry / early target, the staged direct part), the mix's two with the staged batch as their clean
+        array, and the target's level."""
+        if self.engine is None:
+            from .engine import default_engine
+            self.engine = default_engine()
+        B, L, dev = rows.shape[0], self.sample_length, self.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)          # noqa: E731
+        staged, mixture, reverberant, gains = new(B, 1, L), new(B, 1, L), new(B, 1, L), new(B, 2)
+        direct = None if self.target == "reverberant" else new(B, 1, L)
+        self.engine.reverb_windows(self.clean, self.rir, rir_rows.to(dev, non_blocking=True), staged, direct, early_taps=self.early_taps)
+        staged_rows = rows.clone()
+        staged_rows[:, 0] = torch.arange(B, dtype=torch.int64) * L
+        self.engine.mix_windows(staged.view(-1), self.noise, staged_rows.to(dev, non_blocking=True), params.to(dev, non_blocking=True), mixture,
+                                reverberant, gains, peak_limit=self.peak_limit)
+        target = reverberant if direct is None else self.engine.apply_level(direct, gains)
+        return mixture, target, gains, reverberant
+
     def __iter__(self):
         for _ in range(self.steps):
             pick, rows, params = self.draw()
-            mixture, clean, gains = self.mix(rows, params)
-            self.last_draw = {"rows": rows, "params": params, "gains": gains}
+            if self.rir is None:
+                mixture, clean, gains = self.mix(rows, params)
+                self.last_draw = {"rows": rows, "params": params, "gains": gains}
+            else:
+                rir_rows = self.draw_rir(pick, rows)
+                mixture, clean, gains, reverberant = self.mix_reverberant(rows, params, rir_rows)
+                self.last_draw = {"rows": rows, "params": params, "gains": gains, "rir_rows": rir_rows, "reverberant": reverberant}
             yield mixture, clean, [self.names[i] for i in pick.tolist()]
