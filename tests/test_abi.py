@@ -82,7 +82,7 @@ def test_loader_prefetch_registers_are_untouched_until_their_wait():
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_h3u_isa.py")], capture_output=True, text=True, timeout=600)
-    # conv_h3u_kernel<NTG, COPY>: three tap groupings x (eval: no operand copy | training: the loaders' stores counted in their waits)
+    # conv_h3u_kernel<M_REP, COPY>: three row-block heights (M_REP = 2, 3, 4 m-tiles of 16 rows) x (eval: no operand copy | training: the loaders' stores counted in their waits)
     assert p.returncode == 0 and "6 kernels checked, 0 problems" in p.stdout, p.stdout[-2000:] + p.stderr[-500:]
 
 

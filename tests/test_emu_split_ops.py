@@ -1,4 +1,4 @@
-"""Single-op parity of the fp16-split kernels (conv_h3_kernel, wgrad_h3d_kernel, wgrad_h3_kernel) through the C ABI's
+"""Single-op parity of the fp16-split kernels (conv_h3d_kernel, wgrad_h3d_kernel, wgrad_h3_kernel) through the C ABI's
 wunet_op_*_split entry points, on the CPU fiber emulator at small geometries that reach every tile shape: un-segmented tiles
 (L >= 256), 2 .. 16 items per tile (L = 128 .. 16), split-K, channel counts that are not multiples of 8 / 16 / 32, and operands
 whose magnitudes sit far from 1 (the device-derived power-of-two scales).  The cases are the table of tests/split_op_cases.py, which

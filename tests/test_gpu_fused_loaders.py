@@ -8,7 +8,10 @@ next level's operand written by the conv's epilogue, :83-86) - pinned on the har
         on the same operand values -> the same z up to the operand scale's binade (EVOP scales by a rigorous bound instead of the
         measured maximum: 22-bit operands either way, so 'equal' means 2e-6 of the layer's maximum, and bit-equal for conv_h3u in training);
   (iv)  a length that is not a power of two (12288 = 3 * 2^12: padded rows - the planner must NOT take the fused loaders there) and a
-        ragged batch (B = 5: the last tile rows of the grid are partly outside the batch)."""
+        ragged batch (B = 5: the last tile rows of the grid are partly outside the batch);
+  (v)   a 3-level net of 32-channel steps: its last decoder layer (32 rows = one whole row block of conv_h3u_kernel<2>, consumer = the head:
+        neither statistics nor an activation bound in eval mode) takes the un-guarded, statistics-free copy of the row epilogue, which no
+        layer of the BASELINE net does in conv_h3u_kernel (24 rows there: the guarded copy)."""
 import ctypes
 import importlib
 import os
@@ -37,7 +40,8 @@ def dev():
 def _engine(env):
     """A private engine whose contexts are planned under `env` (the planner reads WUNET_H3U / WUNET_NO_EVOP when a context is created)."""
     eng_mod = importlib.import_module(PKG_NAME + ".engine")
-    e = eng_mod.Engine()
+    with _planned_under(env):                   # (WUNET_H3 is read when the engine is made)
+        e = eng_mod.Engine()
     e._plan_env = dict(env)
     return e
 
@@ -84,10 +88,10 @@ def _reference_layers(sd_np, noisy, training):
     return acts
 
 
-def _run(engine, env, pkg, dev, noisy, training):
-    """One forward on `engine` (contexts planned under env): (kernel names, {layer: z})."""
-    sd = plan.golden_state(N, CI, 0)
-    m = pkg.Model(n_layers=N, channels_interval=CI)
+def _run(engine, env, pkg, dev, noisy, training, n=N, ci=CI):
+    """One forward on `engine` (contexts planned under env): (kernel names, {layer: z} - of the BASELINE net only -, output)."""
+    sd = plan.golden_state(n, ci, 0)
+    m = pkg.Model(n_layers=n, channels_interval=ci)
     m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in sd.items()})
     m.to(dev).train(training)
     running, nbt = m._wunet_buffers()
@@ -98,14 +102,14 @@ def _run(engine, env, pkg, dev, noisy, training):
     with _planned_under(env):
         lib.wunet_profile_enable(1)
         try:
-            out, ws = engine.forward(N, CI, x, params, running, nbt, training, False)
+            out, ws = engine.forward(n, ci, x, params, running, nbt, training, False)
             torch.cuda.synchronize()
             buf = ctypes.create_string_buffer(1 << 16)
             lib.wunet_profile_collect(buf, len(buf))
         finally:
             lib.wunet_profile_enable(0)
         names = [ln.split("\t")[0] for ln in buf.value.decode().strip().splitlines()]
-        zs = {i: engine.layer_output(N, CI, B, T, ws, i).clone() for i in DEC + ENC}
+        zs = {i: engine.layer_output(n, ci, B, T, ws, i).clone() for i in (DEC + ENC if n == N else [])}
     return names, zs, out
 
 
@@ -142,21 +146,24 @@ def test_fused_loader_kernels_run_and_match_at_batch_64(pkg, dev, training):
     assert (out - out0).abs().max().item() < 2e-6
 
 
-@pytest.mark.parametrize("B,T", [(5, 16384), (8, 12288)], ids=["ragged_batch", "padded_rows"])
-def test_fused_loaders_on_ragged_and_padded_shapes(pkg, dev, B, T):
+# (the small net: on the split kernels although its grids do not fill the chip, and without split-K - the two-kernel path it is compared
+#  with would otherwise add its K slices in another order)
+@pytest.mark.parametrize("n,ci,B,T,env", [(N, CI, 5, 16384, {}), (N, CI, 8, 12288, {}), (3, 32, 2, 1024, {"WUNET_H3": "2", "WUNET_H3_NOSPLIT": "1"})],
+                         ids=["ragged_batch", "padded_rows", "whole_row_block_without_statistics"])
+def test_fused_loaders_on_ragged_and_padded_shapes(pkg, dev, n, ci, B, T, env):
     noisy, _ = plan.golden_batch(B, T, 7)
-    names, zs, out = _run(_engine({}), {}, pkg, dev, noisy, False)
+    names, zs, out = _run(_engine(env), env, pkg, dev, noisy, False, n, ci)
     padded = T & (T - 1) != 0
     if padded:       # rows padded to the next power of two: the fused loaders know no row padding - the planner must not use them
         assert not any(nm.startswith("conv_h3u_kernel") or nm.endswith(", evop>") for nm in names), sorted(set(names))
     else:
         assert any(nm.startswith("conv_h3u_kernel") for nm in names), sorted(set(names))
-    sd = torch_port.state_to_torch(plan.golden_state(N, CI, 0))
+    sd = torch_port.state_to_torch(plan.golden_state(n, ci, 0))
     with torch.no_grad():
-        ref = torch_port.forward(sd, torch.from_numpy(noisy), N, CI, False)
+        ref = torch_port.forward(sd, torch.from_numpy(noisy), n, ci, False)
     assert (out.cpu() - ref).abs().max().item() < 1e-4
-    off = {"WUNET_H3U": "0,0", "WUNET_NO_EVOP": "1"}
-    _, _, out0 = _run(_engine(off), off, pkg, dev, noisy, False)
+    off = dict(env, WUNET_H3U="0,0", WUNET_NO_EVOP="1")
+    _, _, out0 = _run(_engine(off), off, pkg, dev, noisy, False, n, ci)
     assert (out - out0).abs().max().item() < 2e-6
 
 

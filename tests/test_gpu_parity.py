@@ -555,7 +555,7 @@ def _profiled_kernels(lib, fn):
 
 @pytest.mark.parametrize("prefix,Cin,Cout,K,L", _baseline_split_layers())
 def test_split_ops_at_baseline_geometries(engine, dev, prefix, Cin, Cout, K, L):
-    """conv_h3_kernel (forward conv and data gradient), wgrad_h3d_kernel / wgrad_h3_kernel (weight gradient) through
+    """conv_h3d_kernel (forward conv and data gradient), wgrad_h3d_kernel / wgrad_h3_kernel (weight gradient) through
     wunet_op_*_split with the planner's tiling for the geometry, batch 64, against F.conv1d and its autograd in float64 on the
     host (the reference's op, model/unet_basic.py:10,23, at twice the precision).  Conv and data gradient are checked on three
     batch items (frames are independent: the other 61 only cost host time), the weight gradient - a sum over all frames - in

@@ -55,7 +55,7 @@ struct FwdLayerPlan {
     bool save_operand;  // conv_h3u_kernel writes its operand out: the weight gradient reads the split operand
     // A layer whose activation feeds split operands and has no bound from batch statistics (eval mode, a frozen layer): its
     // consumers' operand scale comes from the measured maximum of |a z + s|.  The large producers (conv_first_kernel, un-split
-    // conv_h3_kernel) take it in their epilogue - the BatchNorm coefficients only depend on the running statistics, so they are
+    // conv_h3d_kernel) take it in their epilogue - the BatchNorm coefficients only depend on the running statistics, so they are
     // finalised BEFORE the conv; a split layer's conv_reduce_bn_kernel takes it; the small ones get a pass of act_max_kernel over z.
     // (a frozen layer: a / s are there from the launch ahead of the chain; its bound is measured behind the conv)
     int bound;

@@ -28,7 +28,8 @@ static __device__ __attribute__((aligned(16))) const unsigned wunet_zero16[8] = 
 // Optional split-K over gridDim.y (short levels: too few position tiles to fill the chip): bias-free partial results
 // [split][B][Cout][L], summed by conv_reduce_bn_kernel / split_sum_kernel like the fp32 path.  Per stage the block stages the W sub-tile (and, for
 // the first tap group of a chunk, the x tile: 4 channel groups x 272 columns, hi and lo) and each wave issues
-// 5 taps x M_REP x 4 tiles x 3 MFMAs.  The kernel is conv_h3d_kernel (wunet_h3d.h); its register-staged predecessor and the
+// 5 taps x M_REP x 4 tiles x 3 MFMAs.  The kernel is conv_h3d_kernel (wunet_h3d.h; what its MFMA waves share with conv_h3u_kernel:
+// wunet_h3_mma.h); its register-staged predecessor and the
 // paired-tile variant of round 1 / 2 are gone (measurements: HISTORY.md sections 7, 8).
 struct ConvH3Args {
     const wunet_half* xh; const wunet_half* xl;   // [B][C8][L][8]
@@ -96,6 +97,22 @@ struct WgradH3Args {
     int B, Cin, Cout, XC8, GC8, L, logL, chunks_per_split;
     size_t part_stride;                           // floats between two splits' partial results
 };
+
+// The partial dW of one block of either kernel below (split split_, block block_ = co block x ci blocks + ci block), tile-major:
+// [split][co block][ci block][wave][mt][tw][lane][4 rows] - every store is a contiguous KiB per wave (the dW layout [co][ci][tap] would
+// be 64 scattered dwords per store); wgrad_h3_reduce_kernel sums the splits in this layout and scatters only the final dW.
+// (A macro with named operands, not a function: as a function it changed the register allocation of all 108 instantiations.)
+#define WUNET_WH3_STORE_PART(M_REP_, TW_, A_, acc_, split_, block_, wave_, lane_)                                 \
+    {                                                                                                             \
+        const float inv = (A_).sc[1], inv2 = (A_).sc2[1];                                                         \
+        float* part = (A_).part + (size_t)(split_) * (A_).part_stride + (((block_) * WUNET_WAVES + (wave_)) * ((M_REP_) * (TW_))) * 256 + (lane_) * 4; \
+        _Pragma("unroll") for (int mt = 0; mt < (M_REP_); ++mt)                                                   \
+            _Pragma("unroll") for (int tw = 0; tw < (TW_); ++tw) {                                                \
+                wunet_f4 o;                                                                                       \
+                _Pragma("unroll") for (int r = 0; r < 4; ++r) o[r] = acc_[mt][tw][r] * inv * inv2;                \
+                wunet_st4(part + (mt * (TW_) + tw) * 256, o);                                                     \
+            }                                                                                                     \
+    }
 
 template <int TAPS, int M_REP, int NSEG, int TP, bool BF = false>
 __global__ __launch_bounds__(WUNET_THREADS, (M_REP <= 2 ? 2 : 1)) void wgrad_h3_kernel(WgradH3Args A)
@@ -223,21 +240,7 @@ __global__ __launch_bounds__(WUNET_THREADS, (M_REP <= 2 ? 2 : 1)) void wgrad_h3_
     }
 #undef WUNET_WH3_PREFETCH
 
-    // partial result, tile-major: [split][co block][ci block][wave][mt][tw][lane][4 rows] - every store is a contiguous
-    // KiB per wave (the dW layout [co][ci][tap] would be 64 scattered dwords per store); wgrad_h3_reduce_kernel sums the
-    // splits in this layout and scatters only the final dW
-    const float inv = A.sc[1], inv2 = A.sc2[1];
-    float* part = A.part + (size_t)blockIdx.x * A.part_stride
-                + ((((size_t)blockIdx.z * gridDim.y + blockIdx.y) * WUNET_WAVES + wave) * (M_REP * TW)) * 256 + lane * 4;
-#pragma unroll
-    for (int mt = 0; mt < M_REP; ++mt)
-#pragma unroll
-        for (int tw = 0; tw < TW; ++tw) {
-            wunet_f4 o;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] = acc[mt][tw][r] * inv * inv2;
-            wunet_st4(part + (mt * TW + tw) * 256, o);
-        }
+    WUNET_WH3_STORE_PART(M_REP, TW, A, acc, blockIdx.x, (size_t)blockIdx.z * gridDim.y + blockIdx.y, wave, lane)
 }
 
 // ---------------------------------------------------------------------------- weight gradient, DMA staging
@@ -421,16 +424,5 @@ __global__ __launch_bounds__(WUNET_THREADS, ((DB && TP == 128) ? 1 : 2)) void wg
     }
 #undef WUNET_WH3D_DMA
 
-    const float inv = A.sc[1], inv2 = A.sc2[1];
-    float* part = A.part + (size_t)bx * A.part_stride
-                + ((((size_t)bz * (A.xcd_walk ? (unsigned)A.nblocks : gridDim.y) + by) * WUNET_WAVES + wave) * (M_REP * TW)) * 256 + lane * 4;
-#pragma unroll
-    for (int mt = 0; mt < M_REP; ++mt)
-#pragma unroll
-        for (int tw = 0; tw < TW; ++tw) {
-            wunet_f4 o;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[r] = acc[mt][tw][r] * inv * inv2;
-            wunet_st4(part + (mt * TW + tw) * 256, o);
-        }
+    WUNET_WH3_STORE_PART(M_REP, TW, A, acc, bx, (size_t)bz * (A.xcd_walk ? (unsigned)A.nblocks : gridDim.y) + by, wave, lane)
 }

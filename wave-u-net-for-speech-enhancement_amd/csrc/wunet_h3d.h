@@ -1,5 +1,6 @@
-// conv_h3d_kernel: the GEMM of conv_h3_kernel (same LDS images, same fragments, same order of the MFMAs of every accumulator:
-// bit-identical results) with the staging rebuilt around the LDS-DMA engine so that a block fetches while it computes:
+// conv_h3d_kernel: the split conv / data-gradient GEMM of wunet_h3.h, its staging built around the LDS-DMA engine so that a block
+// fetches while it computes.  The arithmetic of its MFMA waves - fragments, MFMA order of every accumulator, row epilogue - is the code
+// of wunet_h3_mma.h, which conv_h3u_kernel runs too (bit-identical results).  The staging:
 //   * the x tile is staged by global_load_lds_dwordx4 as well - the de-interleave of the columns is done by the per-lane SOURCE
 //     address (lane i's 16 bytes always land at wave base + 16 i); halo pieces outside the item and channel groups beyond C8 fetch
 //     a 16-byte zero page.  No staging registers, no ds_write pass, no selects.
@@ -20,7 +21,7 @@
 // The MFMAs of a tap are issued pass-major (all accumulators' lo*hi, then hi*lo, then hi*hi): 4*M_REP independent MFMAs between two
 // MFMAs on the same accumulator instead of hipcc's back-to-back chains.
 #pragma once
-#include "wunet_h3.h"
+#include "wunet_h3_mma.h"
 // WUNET_ABL: ablation builds of tools/conv_ablation.sh (parts of the kernel compiled out, bits listed there); 0 in the product
 #ifndef WUNET_ABL
 #define WUNET_ABL 0
@@ -176,11 +177,7 @@ __global__ __launch_bounds__(WUNET_THREADS, 2) void conv_h3d_kernel(ConvH3Args A
     constexpr int NTT = (TAPS + 3) / 4;            // steps of a tail stage
     // the epilogue's per-row constants once per block, not one global round trip per work item; the un-scale of operand and weights
     // (two powers of two: their product is exact) likewise
-    for (int c = threadIdx.x; EPI_LDS && c < ER; c += WUNET_THREADS) {
-        const bool in = c < A.Cout;
-        epi[c] = (in && A.bias && gridDim.y == 1) ? A.bias[c] : 0.0f;
-        if (A.epi_eval) { epi[ER + c] = in ? A.ev_a[c] : 0.0f; epi[2 * ER + c] = in ? A.ev_s[c] : 0.0f; }
-    }
+    if (EPI_LDS) WUNET_H3_EPI_FILL(A, epi, ER, gridDim.y == 1, A.epi_eval, true, threadIdx.x, WUNET_THREADS)
     const float inv12 = (A.sc ? A.sc[1] : 1.0f) * (A.sc2 ? A.sc2[1] : 1.0f);
     if (EPI_LDS) wunet_wait_lds_barrier();
     int stamp = 0;
@@ -254,24 +251,15 @@ __global__ __launch_bounds__(WUNET_THREADS, 2) void conv_h3d_kernel(ConvH3Args A
         }                                                                                                         \
     }
             wunet_h8 ah[2][M_REP], al[2][M_REP];
-#define WUNET_H3D_LOAD_A(BUF_, TL_)                                                                               \
-    _Pragma("unroll") for (int mt = 0; mt < M_REP; ++mt) {                                                        \
-        ah[BUF_][mt] = wunet_ldh8(ws + ((mt * TG + (TL_)) * 64) * 8 + aoff);                                      \
-        if (!BF) al[BUF_][mt] = wunet_ldh8(ws + ((M_REP + mt) * TG + (TL_)) * 64 * 8 + aoff);                     \
-    }
-#define WUNET_H3D_PASS(WHICH_, BUF_, TL_)                                                                         \
-    if (!(WUNET_ABL & 1) && !((WUNET_ABL & 512) && (WHICH_) == 0)) _Pragma("unroll") for (int mt = 0; mt < M_REP; ++mt)                                                          \
-        _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                                        \
-            if (BF) { if ((WHICH_) == 2) acc[mt][nt] = wunet_mfma16b(ah[BUF_][mt], fh[(TL_) + nt], acc[mt][nt]); } \
-            else if ((WHICH_) == 0) acc[mt][nt] = wunet_mfma16h(al[BUF_][mt], fh[(TL_) + nt], acc[mt][nt]);       \
-            else if ((WHICH_) == 1) acc[mt][nt] = wunet_mfma16h(ah[BUF_][mt], fl[(TL_) + nt], acc[mt][nt]);       \
-            else acc[mt][nt] = wunet_mfma16h(ah[BUF_][mt], fh[(TL_) + nt], acc[mt][nt]);                          \
-        }
+            // (wunet_h3_mma.h; the ablation bits of this kernel: 1 no MFMAs, 512 no lo*hi pass)
+#define WUNET_H3D_LOAD_A(TL_) WUNET_H3_LOAD_A(M_REP, TG, BF, ws, aoff, TL_, ah[(TL_) & 1], al[(TL_) & 1])
+#define WUNET_H3D_PASS(WHICH_, TL_)                                                                               \
+    if (!(WUNET_ABL & 1) && !((WUNET_ABL & 512) && (WHICH_) == 0)) WUNET_H3_PASS(WHICH_, M_REP, BF, acc, ah[(TL_) & 1], al[(TL_) & 1], fh, fl, TL_)
             // After the B fragments: the x tile is free once every wave holds them; the prefetch of the next step's A fragments is
             // ISSUED at the fence, not sunk to its first use; with the last A fragments of the stage in flight the W sub-tile is free
             // once every wave has them.  A tail stage runs the first NTT steps only.
             WUNET_H3D_LOAD_F(true)
-            WUNET_H3D_LOAD_A(0, 0)
+            WUNET_H3D_LOAD_A(0)
             if (x_next) {
                 wunet_wait_lds_barrier();
                 if (last) { WUNET_H3D_ISSUE_X(nb, nl0, nch) } else { WUNET_H3D_ISSUE_X(b, l0, nch) }
@@ -287,14 +275,12 @@ __global__ __launch_bounds__(WUNET_THREADS, 2) void conv_h3d_kernel(ConvH3Args A
 #define WUNET_H3D_STEP(TL_)                                                                                       \
     {                                                                                                             \
         constexpr int tl = (TL_);                                                                                 \
-        if (tl + 1 < TG) {                                                                                        \
-            if (tl & 1) { WUNET_H3D_LOAD_A(0, tl + 1) } else { WUNET_H3D_LOAD_A(1, tl + 1) }                      \
-        }                                                                                                         \
+        if (tl + 1 < TG) { WUNET_H3D_LOAD_A(tl + 1) }                                                             \
         wunet_sched_fence();                                                                                      \
-        if (tl & 1) { WUNET_H3D_PASS(0, 1, tl) } else { WUNET_H3D_PASS(0, 0, tl) }                                \
+        WUNET_H3D_PASS(0, tl)                                                                                     \
         if (tl == TG - 2) WUNET_H3D_RELEASE_W()                                                                   \
         else if (TG - 2 >= NTT && tl == NTT - 2) { if (tail) WUNET_H3D_RELEASE_W() }                              \
-        if (tl & 1) { WUNET_H3D_PASS(1, 1, tl) WUNET_H3D_PASS(2, 1, tl) } else { WUNET_H3D_PASS(1, 0, tl) WUNET_H3D_PASS(2, 0, tl) } \
+        WUNET_H3D_PASS(1, tl) WUNET_H3D_PASS(2, tl)                                                               \
     }
             // (the steps a tail stage skips behind ONE uniform branch; TG - 2 >= NTT, 5 taps: the W sub-tile of a full stage is
             // released inside them, that of a tail stage at its step NTT - 2)
@@ -315,85 +301,18 @@ __global__ __launch_bounds__(WUNET_THREADS, 2) void conv_h3d_kernel(ConvH3Args A
 #undef WUNET_H3D_LOAD_F
 #undef WUNET_H3D_PASS
 
-        // ---- epilogue (conv_h3_kernel's): un-scale, bias, store, BN statistics of the bias-free conv; a K split stores its
+        // ---- epilogue (wunet_h3_mma.h): un-scale, bias, store, BN statistics of the bias-free conv; a K split stores its
         // bias-free partial sum (statistics then come from the reduce kernel).  The DMAs of the next item's first stage are in flight.
         wunet_setprio(0);
         float* outp = A.out + (size_t)blockIdx.y * A.split_stride;
         const int bo = b + lseg;
         float amax = 0.0f;
-        // the per-row constants in ONE batch of loads: loaded row by row where they are used, each load was waited for with
-        // vmcnt(0) - i.e. together with the previous row's store - and the 4*M_REP serialised round trips were a third of a shallow
-        // layer's block time (phase stamps, tools/conv_bench.py --trace)
         float bvs[M_REP][4];
-#pragma unroll
-        for (int mt = 0; mt < M_REP; ++mt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int co = (mt0 + mt) * 16 + q * 4 + r;
-                bvs[mt][r] = EPI_LDS ? epi[co] : (A.bias && !split && co < A.Cout) ? A.bias[co] : 0.0f;
-            }
+        WUNET_H3_ROW_BIAS(M_REP, EPI_LDS, A, bvs, mt0, q, A.bias && !split, epi)
         // row (mt, r) of this lane: prow + (mt * 16 + r) * L  (uniform strides: no 64-bit multiply per row)
         float* const prow = outp + ((size_t)bo * A.Cout + mt0 * 16 + q * 4) * L + (l0 + ll0);
         const bool want_stats = A.stats && !split;
         const bool full = (mt0 + M_REP) * 16 <= A.Cout && (NSEG == 1 || b + NSEG <= A.B);     // no row / item of the tile outside the tensor
-        // STATS_: Sigma, Sigma^2 of the bias-free conv per row; GUARD_: rows beyond Cout / items beyond B exist; EVAL_: the activation
-        // bound of eval mode.  Copies of the loop behind uniform branches: the un-guarded, statistics-free one (data gradients, K
-        // splits) is half the instructions
-#define WUNET_H3D_ROWS(STATS_, GUARD_, EVAL_)                                                                     \
-    float eas[M_REP][4], ess[M_REP][4];                                                                           \
-    if (EVAL_) {                                                  /* one batch of loads, like the biases */      \
-        _Pragma("unroll") for (int mt = 0; mt < M_REP; ++mt)                                                      \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                       \
-                const int co = (mt0 + mt) * 16 + q * 4 + r;                                                       \
-                eas[mt][r] = (EPI_LDS && A.epi_eval) ? epi[ER + co] : co < A.Cout ? A.ev_a[co] : 0.0f;            \
-                ess[mt][r] = (EPI_LDS && A.epi_eval) ? epi[2 * ER + co] : co < A.Cout ? A.ev_s[co] : 0.0f;        \
-            }                                                                                                     \
-    }                                                                                                             \
-    _Pragma("unroll") for (int mt = 0; mt < M_REP; ++mt) {                                                        \
-        float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};                                         \
-        float ye[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};   /* EVOP: the activation at the lane's two even samples, rows r */ \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                           \
-            const int co = (mt0 + mt) * 16 + q * 4 + r;                                                           \
-            const float bv = bvs[mt][r];                                                                          \
-            wunet_f4 o;                                                                                           \
-            _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                                    \
-                const float vv = acc[mt][nt][r] * inv12;                                                     \
-                if (STATS_) { s1[r] += vv; s2[r] = fmaf(vv, vv, s2[r]); }                                                    \
-                o[nt] = vv + bv;                                                                                  \
-            }                                                                                                     \
-            if ((!(GUARD_) || (co < A.Cout && bo < A.B)) && (!(WUNET_ABL & 4) || o[0] == 123.456f)) {                                                         \
-                wunet_st4(prow + (size_t)(mt * 16 + r) * L, o);                                                   \
-                if (EVAL_) {                                                                                      \
-                    const float ea = eas[mt][r], es = ess[mt][r];                                                 \
-                    _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) amax = fmaxf(amax, fabsf(ea * o[nt] + es));  \
-                    if (EVOP) { ye[0][r] = wunet_lrelu(ea * o[0] + es); ye[1][r] = wunet_lrelu(ea * o[2] + es); } \
-                }                                                                                                 \
-            }                                                                                                     \
-        }                                                                                                         \
-        if (EVOP && (EVAL_)) {         /* rows q*4 .. q*4+3 = half of the 16-byte piece of channel group 2 (mt0 + mt) + (q >> 1) */ \
-            const int c8o = (mt0 + mt) * 2 + (q >> 1);                                                            \
-            if (c8o < A.op_C8 && bo < A.B) {                                                                      \
-                _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                   \
-                    wunet_half hh[4], ll[4];                                                                      \
-                    _Pragma("unroll") for (int r = 0; r < 4; ++r) wunet_split_h(op_scale * ye[j][r], hh[r], ll[r]); \
-                    const size_t oo = ((((size_t)bo * A.op_C8 + c8o) << (A.logL - 1)) + (size_t)(((l0 + ll0) >> 1) + j)) * 8 + (q & 1) * 4; \
-                    wunet_sth4(A.op_h + oo, hh);                                                                  \
-                    wunet_sth4(A.op_l + oo, ll);                                                                  \
-                }                                                                                                 \
-            }                                                                                                     \
-        }                                                                                                         \
-        if (STATS_) {                                                                                             \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                       \
-                s1[r] = wunet_row16_sum(s1[r]);                                                                   \
-                s2[r] = wunet_row16_sum(s2[r]);                                                                   \
-                if (i16 == 0) {                               /* per-wave sums of row mt*16 + q*4 + r -> LDS */   \
-                    float* rp = red + ((wave * M_REP + mt) * 16 + q * 4 + r) * 2;                                 \
-                    rp[0] = s1[r];                                                                                \
-                    rp[1] = s2[r];                                                                                \
-                }                                                                                                 \
-            }                                                                                                     \
-        }                                                                                                         \
-    }
         if (UPT) {
             // ---- UPT (ConvH3Args::uh_out): the rows through the x2 upsample are stored pulled back to the producer's resolution
             // (per-row addresses below = one per-lane base + offsets that are the same in every lane, and the bases derive from values made
@@ -474,11 +393,25 @@ __global__ __launch_bounds__(WUNET_THREADS, 2) void conv_h3d_kernel(ConvH3Args A
                     wunet_sched_fence();              // (one pair of rows at a time)
                 }
             }
-        } else
-        if (A.xrows) { WUNET_H3D_ROWS(false, true, true) }          // eval mode: the maximum of the activation bound instead of statistics
-        else if (want_stats) { if (full) { WUNET_H3D_ROWS(true, false, false) } else { WUNET_H3D_ROWS(true, true, false) } }
-        else { if (full) { WUNET_H3D_ROWS(false, false, false) } else { WUNET_H3D_ROWS(false, true, false) } }
-#undef WUNET_H3D_ROWS
+        } else {
+            // EVOP: rows q*4 .. q*4+3 = half of the 16-byte piece of channel group 2 (mt0 + mt) + (q >> 1) of the consumer's operand
+#define WUNET_H3D_EVOP_STORE(mt_, ye_)                                                                            \
+    {                                                                                                             \
+        const int c8o = (mt0 + (mt_)) * 2 + (q >> 1);                                                             \
+        if (c8o < A.op_C8 && bo < A.B) {                                                                          \
+            _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                       \
+                wunet_half hh[4], ll[4];                                                                          \
+                _Pragma("unroll") for (int r = 0; r < 4; ++r) wunet_split_h(op_scale * ye_[j][r], hh[r], ll[r]);  \
+                const size_t oo = ((((size_t)bo * A.op_C8 + c8o) << (A.logL - 1)) + (size_t)(((l0 + ll0) >> 1) + j)) * 8 + (q & 1) * 4; \
+                wunet_sth4(A.op_h + oo, hh);                                                                      \
+                wunet_sth4(A.op_l + oo, ll);                                                                      \
+            }                                                                                                     \
+        }                                                                                                         \
+    }
+            WUNET_H3_EPILOGUE(EVOP, WUNET_H3D_EVOP_STORE, M_REP, A, acc, bvs, inv12, prow, mt0, q, i16, wave, bo < A.B, (WUNET_ABL & 4) != 0,
+                              epi, ER, EPI_LDS && A.epi_eval, red, amax, want_stats, full)
+#undef WUNET_H3D_EVOP_STORE
+        }
         if (A.xrows) {                            // eval: block maximum of the activation bound (max is order independent)
 #pragma unroll
             for (int m = 1; m < 64; m <<= 1) amax = fmaxf(amax, wunet_shfl_xor(amax, m));
@@ -487,24 +420,9 @@ __global__ __launch_bounds__(WUNET_THREADS, 2) void conv_h3d_kernel(ConvH3Args A
             wunet_wait_lds_barrier();
             if (tid == 0) amax_run = fmaxf(amax_run, fmaxf(fmaxf(rp[0], rp[1]), fmaxf(rp[2], rp[3])));
         }
-        // one statistics row per tile (256 positions): the four waves' sums are added in wave order
         if (A.stats && !split) {
             wunet_wait_lds_barrier();
-            if (tid < M_REP * 16) {
-                const float* rp = red + tid * 2;
-                float t1 = 0.0f, t2 = 0.0f;
-#pragma unroll
-                for (int w = 0; w < WUNET_WAVES; ++w) {
-                    t1 += rp[w * M_REP * 32];
-                    t2 += rp[w * M_REP * 32 + 1];
-                }
-                const int co = mt0 * 16 + tid;
-                if (co < A.Cout) {
-                    float* stp = A.stats + ((size_t)co * A.ntiles + tile) * 2;
-                    stp[0] = t1;
-                    stp[1] = t2;
-                }
-            }
+            wunet_h3_stats_row<M_REP>(red, tid, mt0, A.Cout, A.stats, A.ntiles, tile);
         }
         WUNET_H3D_STAMP(stamp) ++stamp;
         if (!more) break;

@@ -6,8 +6,8 @@
 // the hi / lo split all happen on the way into LDS.  prep_h3_kernel disappears for the layer and the conv reads 2 (upsampled
 // half) or 4 (skip half) bytes per operand value instead of 4 + 4.
 //
-// Work split inside the block (512 threads, one block per CU): WAVE SPECIALISATION.  Waves 0-3 are the conv_h3d_kernel MFMA
-// waves (same LDS images, same fragments, same MFMA order per accumulator); waves 4-7 are loaders - loader wave w owns channel
+// Work split inside the block (512 threads, one block per CU): WAVE SPECIALISATION.  Waves 0-3 are MFMA waves and run the code
+// conv_h3d_kernel's waves run (wunet_h3_mma.h: same LDS images, fragments, MFMA order per accumulator, row epilogue); waves 4-7 are loaders - loader wave w owns channel
 // group w of the stage's chunk of 32 channels: global loads -> VALU -> ds_write_b128 of the NEXT stage's x tile, and the LDS-DMA
 // of the next W sub-tile.  Every SIMD hosts one MFMA wave and one loader wave, so the matrix pipe and the vector ALU / memory
 // pipes of a SIMD are fed by different instruction streams and overlap without any software pipelining inside a wave.  x tile
@@ -19,7 +19,7 @@
 // instantiation only the first tile of a row takes, the operand scale folded into the BatchNorm coefficients, nothing for empty channel
 // groups - and what remains of a stage is mostly the 17 memory instructions per wave (~100 cycles each at the CU's shared address path).
 #pragma once
-#include "wunet_h3.h"
+#include "wunet_h3_mma.h"
 // WUNET_H3U_ABL: ablation builds of tools/h3u_ablation.sh (parts of the kernel compiled out: 1 no global loads, 4 no MFMAs, 8 no W DMA,
 // 16 no conversion at all (no LDS writes), 32 no fragment reads and no MFMAs, 64 the loads kept alive but nothing converted, 128 no LDS writes);
 // 0 in the product
@@ -446,12 +446,7 @@ __global__ __launch_bounds__(2 * WUNET_THREADS, 1) void conv_h3u_kernel(ConvH3uA
     }
     // (from global memory they were one memory round trip per work item with the matrix pipe idle: this kernel has no second block on the
     //  CU to fill it)
-    for (int c = tid; c < ER; c += 2 * WUNET_THREADS) {
-        const bool in = c < A.Cout;
-        epi[c] = (in && A.bias) ? A.bias[c] : 0.0f;
-        epi[ER + c] = (in && A.xrows) ? A.ev_a[c] : 0.0f;
-        epi[2 * ER + c] = (in && A.xrows) ? A.ev_s[c] : 0.0f;
-    }
+    WUNET_H3_EPI_FILL(A, epi, ER, true, true, A.xrows, tid, 2 * WUNET_THREADS)
     __syncthreads();
     // Both roles run the SAME sequence of workgroup barriers: one per stage (the stage's buffers are complete - the loaders waited for
     // their DMA pieces and LDS writes - and every MFMA wave has read the last fragment of the previous stage, whose buffers the
@@ -580,7 +575,7 @@ __global__ __launch_bounds__(2 * WUNET_THREADS, 1) void conv_h3u_kernel(ConvH3uA
         return;
     }
 
-    // ================================================================ MFMA waves (conv_h3d_kernel's fragments and MFMA order)
+    // ================================================================ MFMA waves (fragments, MFMA order and epilogue: wunet_h3_mma.h)
     const int q = lane >> 4, i16 = lane & 15;
     const int ll0 = cw * 64 + i16 * 4;            // this lane's 4 positions cw*64 + 4*i16 .. +3
     const int boff = (q * COLS + (ll0 >> 2)) * 8;
@@ -612,117 +607,46 @@ __global__ __launch_bounds__(2 * WUNET_THREADS, 1) void conv_h3u_kernel(ConvH3uA
                 fl[e] = wunet_ldh8(xs + 4 * COLS * 8 + boff + po);
             }
             wunet_h8 ah[2][M_REP], al[2][M_REP];
-#define WUNET_H3U_LOAD_A(BUF_, TL_)                                                                               \
-    _Pragma("unroll") for (int mt = 0; mt < M_REP; ++mt) {                                                        \
-        ah[BUF_][mt] = wunet_ldh8(ws + ((mt * TG + (TL_)) * 64) * 8 + aoff);                                      \
-        al[BUF_][mt] = wunet_ldh8(ws + ((M_REP + mt) * TG + (TL_)) * 64 * 8 + aoff);                              \
-    }
-#define WUNET_H3U_PASS(WHICH_, BUF_, TL_)                                                                         \
-    _Pragma("unroll") for (int mt = 0; mt < M_REP; ++mt)                                                          \
-        _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                                        \
-            if (WUNET_H3U_ABL & 4) { if ((WHICH_) == 0 && (TL_) == 0) acc[mt][nt][0] += (float)al[BUF_][mt][0] + (float)fh[nt][0] + (float)ah[BUF_][mt][1] + (float)fl[nt][1]; } \
-            else if ((WHICH_) == 0) acc[mt][nt] = wunet_mfma16h(al[BUF_][mt], fh[(TL_) + nt], acc[mt][nt]);       \
-            else if ((WHICH_) == 1) acc[mt][nt] = wunet_mfma16h(ah[BUF_][mt], fl[(TL_) + nt], acc[mt][nt]);       \
-            else acc[mt][nt] = wunet_mfma16h(ah[BUF_][mt], fh[(TL_) + nt], acc[mt][nt]);                          \
-        }
-#define WUNET_H3U_STEP(TL_)                                                                                       \
-    {                                                                                                             \
-        constexpr int tl = (TL_);                                                                                 \
-        if (tl + 1 < TG) {                                                                                        \
-            if (tl & 1) { WUNET_H3U_LOAD_A(0, tl + 1) } else { WUNET_H3U_LOAD_A(1, tl + 1) }                      \
-        }                                                                                                         \
-        wunet_sched_fence();                                                                                      \
-        if (tl & 1) { WUNET_H3U_PASS(0, 1, tl) WUNET_H3U_PASS(1, 1, tl) WUNET_H3U_PASS(2, 1, tl) }               \
-        else { WUNET_H3U_PASS(0, 0, tl) WUNET_H3U_PASS(1, 0, tl) WUNET_H3U_PASS(2, 0, tl) }                      \
-    }
-            WUNET_H3U_LOAD_A(0, 0)
-            WUNET_H3U_STEP(0) WUNET_H3U_STEP(1) WUNET_H3U_STEP(2) WUNET_H3U_STEP(3) WUNET_H3U_STEP(4)
-#undef WUNET_H3U_STEP
-#undef WUNET_H3U_PASS
-#undef WUNET_H3U_LOAD_A
+            // the plain five steps: the A fragments are read one tap ahead, three passes per tap (ablation 4: no MFMAs, the fragments kept alive)
+            WUNET_H3_LOAD_A(M_REP, TG, false, ws, aoff, 0, ah[0], al[0])
+#pragma unroll
+            for (int tl = 0; tl < TG; ++tl) {
+                if (tl + 1 < TG) { WUNET_H3_LOAD_A(M_REP, TG, false, ws, aoff, tl + 1, ah[(tl + 1) & 1], al[(tl + 1) & 1]) }
+                wunet_sched_fence();
+                if (WUNET_H3U_ABL & 4) {
+                    if (tl == 0) {
+#pragma unroll
+                        for (int mt = 0; mt < M_REP; ++mt)
+#pragma unroll
+                            for (int nt = 0; nt < 4; ++nt) acc[mt][nt][0] += (float)al[0][mt][0] + (float)fh[nt][0] + (float)ah[0][mt][1] + (float)fl[nt][1];
+                    }
+                } else {
+                    WUNET_H3_PASS(0, M_REP, false, acc, ah[tl & 1], al[tl & 1], fh, fl, tl)
+                    WUNET_H3_PASS(1, M_REP, false, acc, ah[tl & 1], al[tl & 1], fh, fl, tl)
+                    WUNET_H3_PASS(2, M_REP, false, acc, ah[tl & 1], al[tl & 1], fh, fl, tl)
+                }
+            }
             par ^= 1;
         }
 
-        // ---- epilogue (conv_h3d_kernel's): un-scale, bias, store, BatchNorm statistics of the bias-free conv / eval activation bound.
-        // The loaders are filling the next item's first buffers meanwhile.
+        // ---- epilogue (wunet_h3_mma.h, an un-segmented tile whose table holds the eval parts): un-scale, bias, store, BatchNorm statistics
+        // of the bias-free conv / eval activation bound.  The loaders are filling the next item's first buffers meanwhile.
         {
             float amax = 0.0f;
             float bvs[M_REP][4];
-#pragma unroll
-            for (int mt = 0; mt < M_REP; ++mt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) bvs[mt][r] = epi[(mt0 + mt) * 16 + q * 4 + r];
+            WUNET_H3_ROW_BIAS(M_REP, true, A, bvs, mt0, q, false, epi)
             float* const prow = A.out + ((size_t)b * A.Cout + mt0 * 16 + q * 4) * L + (l0 + ll0);
             const bool full = (mt0 + M_REP) * 16 <= A.Cout;
-#define WUNET_H3U_ROWS(STATS_, GUARD_, EVAL_)                                                                     \
-    float eas[M_REP][4], ess[M_REP][4];                                                                           \
-    if (EVAL_) {                                                                                                  \
-        _Pragma("unroll") for (int mt = 0; mt < M_REP; ++mt)                                                      \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                       \
-                const int co = (mt0 + mt) * 16 + q * 4 + r;                                                       \
-                eas[mt][r] = epi[ER + co];                                                                        \
-                ess[mt][r] = epi[2 * ER + co];                                                                    \
-            }                                                                                                     \
-    }                                                                                                             \
-    _Pragma("unroll") for (int mt = 0; mt < M_REP; ++mt) {                                                        \
-        float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};                                         \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                           \
-            const int co = (mt0 + mt) * 16 + q * 4 + r;                                                           \
-            const float bv = bvs[mt][r];                                                                          \
-            wunet_f4 o;                                                                                           \
-            _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) {                                                    \
-                const float vv = acc[mt][nt][r] * inv12;                                                          \
-                if (STATS_) { s1[r] += vv; s2[r] = fmaf(vv, vv, s2[r]); }                                         \
-                o[nt] = vv + bv;                                                                                  \
-            }                                                                                                     \
-            if (!(GUARD_) || co < A.Cout) {                                                                       \
-                wunet_st4(prow + (size_t)(mt * 16 + r) * L, o);                                                   \
-                if (EVAL_) {                                                                                      \
-                    const float ea = eas[mt][r], es = ess[mt][r];                                                 \
-                    _Pragma("unroll") for (int nt = 0; nt < 4; ++nt) amax = fmaxf(amax, fabsf(ea * o[nt] + es));  \
-                }                                                                                                 \
-            }                                                                                                     \
-        }                                                                                                         \
-        if (STATS_) {                                                                                             \
-            _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                       \
-                s1[r] = wunet_row16_sum(s1[r]);                                                                   \
-                s2[r] = wunet_row16_sum(s2[r]);                                                                   \
-                if (i16 == 0) {                                                                                   \
-                    float* rp = red + ((cw * M_REP + mt) * 16 + q * 4 + r) * 2;                                   \
-                    rp[0] = s1[r];                                                                                \
-                    rp[1] = s2[r];                                                                                \
-                }                                                                                                 \
-            }                                                                                                     \
-        }                                                                                                         \
-    }
-            if (A.xrows) { WUNET_H3U_ROWS(false, true, true) }
-            else if (want_stats) { if (full) { WUNET_H3U_ROWS(true, false, false) } else { WUNET_H3U_ROWS(true, true, false) } }
-            else { if (full) { WUNET_H3U_ROWS(false, false, false) } else { WUNET_H3U_ROWS(false, true, false) } }
-#undef WUNET_H3U_ROWS
+            WUNET_H3_EPILOGUE(false, WUNET_H3_NO_EVOP, M_REP, A, acc, bvs, inv12, prow, mt0, q, i16, cw, true, false, epi, ER, true, red, amax, want_stats, full)
             if (A.xrows) {                        // eval: the wave's running maximum of the activation bound (no hand-over: one atomic per wave at the end)
 #pragma unroll
                 for (int m = 1; m < 64; m <<= 1) amax = fmaxf(amax, wunet_shfl_xor(amax, m));
                 amax_run = fmaxf(amax_run, amax);
             }
         }
-        // one statistics row per tile (256 positions): the four MFMA waves' sums are added in wave order
         if (want_stats) {
             wunet_wait_lds_barrier();
-            if (tid < M_REP * 16) {
-                const float* rp = red + tid * 2;
-                float t1 = 0.0f, t2 = 0.0f;
-#pragma unroll
-                for (int w = 0; w < WUNET_WAVES; ++w) {
-                    t1 += rp[w * M_REP * 32];
-                    t2 += rp[w * M_REP * 32 + 1];
-                }
-                const int co = mt0 * 16 + tid;
-                if (co < A.Cout) {
-                    float* stp = A.stats + ((size_t)co * A.ntiles + tile) * 2;
-                    stp[0] = t1;
-                    stp[1] = t2;
-                }
-            }
+            wunet_h3_stats_row<M_REP>(red, tid, mt0, A.Cout, A.stats, A.ntiles, tile);
         }
     }
     if (A.xrows && lane == 0) wunet_atomic_absmax(A.xrows, amax_run);      // one atomic per MFMA wave into the layer's xb slot
