@@ -220,6 +220,35 @@ size_t wunet_stoi_scratch_bytes(size_t rows, size_t row_len, int fs);
 int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
                        float* out, int* frames_out, void* stream);
 
+/* STOI as a training loss (Fu et al. 2018, "End-to-end waveform utterance enhancement ... based on STOI"): loss = -(1 / rows) sum_row s_row
+ * with s_row the row's score exactly as wunet_stoi_forward defines it - a row with fewer than 30 spectral frames contributes the
+ * constant 1e-5 and no gradient - the mean taken in double over the double row scores, in row order, and rounded once.  The tables
+ * are those of wunet_stoi_tables_build.
+ *   wunet_stoi_loss_forward: the launch sequence of wunet_stoi_forward, which also keeps in `saved`
+ *     (>= wunet_stoi_loss_saved_bytes(..)) what the backward needs: the kept-frame table, its inverse and the counts, the band powers of
+ *     both signals, re and im of the estimate.  per_row_out (NULL or [rows] float32) receives s_row, frames_out (NULL or [rows] int32)
+ *     the spectral frame counts.
+ *   wunet_stoi_loss_backward: grad_estimate = grad_loss[0] * d loss / d estimate, written for EVERY sample of every row (rows without
+ *     a segment and samples outside every kept frame get exact zeros: no memset needed).  It inverts the chain stage by stage -
+ *     segments -> band magnitudes -> adjoint DFT GEMM -> silence-free signal and frames -> transposed resampling filter - each stage a
+ *     gather.  Conventions of the derivative:
+ *       - the silent-frame mask depends on `clean` only and is a constant; there is no gradient with respect to `clean`;
+ *       - min(alpha y, clip x) passes the gradient through alpha y where alpha y < clip x and nothing otherwise; the alpha y branch
+ *         includes the dependence of alpha = |x| / (|y| + eps) on every y of the segment;
+ *       - ONE departure from autograd: where a band magnitude of the estimate is exactly 0, that (frame, band) passes no gradient
+ *         (autograd: NaN - an all-zero estimate gets a zero gradient here).  Likewise a segment whose clipped, centred estimate is all 0
+ *         drops the derivative of its norm.  An all-zero clean row gives an all-zero gradient.
+ *   scratch: >= wunet_stoi_loss_scratch_bytes(..) device bytes for either call (the two calls may use different buffers), no memset.
+ * fp32 operands and fp32 MFMA accumulation, every reduction in double and in one fixed order, no atomics: bit-identical run to run.
+ * Caller-owned memory; tables, scratch and saved 16-byte aligned, the waveforms and the gradient 4-byte aligned; no allocation, no
+ * synchronisation, no host read-back: both calls can be captured.  rows <= 65535; argument errors are WUNET_E_ARG with a message. */
+size_t wunet_stoi_loss_scratch_bytes(size_t rows, size_t row_len, int fs);
+size_t wunet_stoi_loss_saved_bytes(size_t rows, size_t row_len, int fs);
+int wunet_stoi_loss_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                            void* saved, float* loss_out, float* per_row_out, int* frames_out, void* stream);
+int wunet_stoi_loss_backward(const void* saved, const float* grad_loss, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                             float* grad_estimate, void* stream);
+
 /* replaces optimizer.step() of torch.optim.Adam(params, lr, betas) as the reference builds it
  * (train.py:31-35; eps, weight_decay=0, amsgrad=False fixed by the reference's call) for n_tensors tensors in one
  * or two launches.  step is the 1-based step count AFTER the increment (torch's state["step"]).  numels: host array.

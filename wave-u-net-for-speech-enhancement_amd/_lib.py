@@ -23,6 +23,7 @@ EXPORTS = [
     "wunet_stft_basis_bytes", "wunet_stft_basis", "wunet_stft_scratch_bytes", "wunet_stft_saved_bytes", "wunet_stft_forward",
     "wunet_stft_finalize", "wunet_stft_backward",
     "wunet_stoi_tables_bytes", "wunet_stoi_tables_build", "wunet_stoi_scratch_bytes", "wunet_stoi_forward",
+    "wunet_stoi_loss_scratch_bytes", "wunet_stoi_loss_saved_bytes", "wunet_stoi_loss_forward", "wunet_stoi_loss_backward",
     "wunet_mix_scratch_bytes", "wunet_mix_windows", "wunet_apply_level", "wunet_reverb_windows",
 ]
 
@@ -74,6 +75,13 @@ def declare(lib):
         lib.wunet_stoi_scratch_bytes.argtypes = [_sz, _sz, _i]
         lib.wunet_stoi_scratch_bytes.restype = _sz
         lib.wunet_stoi_forward.argtypes = [_vp, _vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp]
+    if hasattr(lib, "wunet_stoi_loss_forward"):
+        lib.wunet_stoi_loss_scratch_bytes.argtypes = [_sz, _sz, _i]
+        lib.wunet_stoi_loss_scratch_bytes.restype = _sz
+        lib.wunet_stoi_loss_saved_bytes.argtypes = [_sz, _sz, _i]
+        lib.wunet_stoi_loss_saved_bytes.restype = _sz
+        lib.wunet_stoi_loss_forward.argtypes = [_vp, _vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        lib.wunet_stoi_loss_backward.argtypes = [_vp, _vp, _sz, _sz, _i, _vp, _vp, _vp, _vp]
     lib.wunet_layer_info.argtypes = [_vp, _i, ctypes.POINTER(_sz), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     lib.wunet_num_conv_layers.argtypes = [_vp]
     for name in ("wunet_op_conv1d", "wunet_op_conv1d_split"):

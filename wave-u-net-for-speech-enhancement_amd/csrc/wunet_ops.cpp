@@ -329,23 +329,25 @@ size_t wunet_stoi_scratch_bytes(size_t rows, size_t row_len, int fs)
     return s.bytes;
 }
 
-int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
-                       float* out, int* frames_out, void* stream)
+namespace {
+struct StoiBuffers {
+    int *nk, *kept, *inv;   // inv: nullptr for the metric
+    double* energy;
+    float* res;             // [2][rows][Tr], used where the rate is not 10 kHz
+    float* pw;              // [2][M][BP]
+    float* reim;            // nullptr for the metric: the spectrum kernel then keeps the powers only
+    double* part;
+};
+
+// resampling, mask, spectra and segment sums of both entry points: everything but the final kernel
+int stoi_enqueue(const float* clean, const float* estimate, size_t rows, size_t row_len, const StoiShape& s, const float* tables, const StoiBuffers& B,
+                 hipStream_t st)
 {
-    StoiShape s{};
-    if (stoi_shape(rows, row_len, fs, s)) return WUNET_E_ARG;
-    if (!clean || !estimate || !tables || !scratch || !out || ((size_t)tables & 15) || ((size_t)scratch & 15))
-        return fail(WUNET_E_ARG, "stoi: null argument (or tables / scratch that are not 16-byte aligned)");
-    hipStream_t st = (hipStream_t)stream;
-    char* sc = (char*)scratch;
-    int* nk = (int*)(sc + s.o_nk);
-    int* kept = (int*)(sc + s.o_kept);
-    double* part = (double*)(sc + s.o_part);
     const float* w = tables + WUNET_STOI_TAB_W;
     const float* x[2] = {clean, estimate};
     if (s.L && s.Tr > 0) {
         StoiResampleArgs R{};
-        R.in[0] = clean; R.in[1] = estimate; R.taps = tables + WUNET_STOI_TAB_TAPS; R.out = (float*)(sc + s.o_res);
+        R.in[0] = clean; R.in[1] = estimate; R.taps = tables + WUNET_STOI_TAB_TAPS; R.out = B.res;
         R.T = row_len; R.Tr = s.Tr; R.rows = rows; R.p = s.p; R.q = s.q; R.L = s.L;
         const unsigned per = WUNET_THREADS * WUNET_STOI_RPT;
         prof_begin(st, "stoi_resample_kernel", 2.0 * 2.0 * rows * s.Tr * ((2.0 * s.L + 1.0) / s.p), 4.0 * 2.0 * rows * (row_len + s.Tr));
@@ -356,30 +358,177 @@ int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, s
     }
     if (s.F0 > 0) {
         StoiMaskArgs K{};
-        K.x = x[0]; K.w = w; K.Tr = s.Tr; K.F0 = s.F0; K.energy = (double*)(sc + s.o_energy); K.kept = kept; K.nk = nk;
+        K.x = x[0]; K.w = w; K.Tr = s.Tr; K.F0 = s.F0; K.energy = B.energy; K.kept = B.kept; K.nk = B.nk; K.inv = B.inv;
         WUNET_LAUNCH(stoi_mask_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), 0, st, K);
         WUNET_CHECK_LAUNCH();
     }
     if (s.nblk > 0) {       // (fewer than 30 frames at the most: no row has a segment, the final kernel alone writes 1e-5)
         StoiSpecArgs P{};
-        P.x[0] = x[0]; P.x[1] = x[1]; P.basis = tables; P.w = w; P.kept = kept; P.nk = nk; P.Tr = s.Tr; P.M = s.M; P.Fmax = s.Fmax; P.F0 = s.F0;
-        P.pw = (float*)(sc + s.o_pw);
+        P.x[0] = x[0]; P.x[1] = x[1]; P.basis = tables; P.w = w; P.kept = B.kept; P.nk = B.nk; P.Tr = s.Tr; P.M = s.M; P.Fmax = s.Fmax; P.F0 = s.F0;
+        P.pw = B.pw; P.reim = B.reim;
         const unsigned mtiles = (s.M + WUNET_STFT_FM - 1) / WUNET_STFT_FM;
+        const dim3 grid(mtiles, WUNET_STOI_BP / WUNET_STFT_BN);
         // (profiler: 2 flops x frames x 256 x 2 BP columns per signal, at the largest frame count; the signals once, the powers written)
-        prof_begin(st, "stoi_spec_kernel", 2.0 * 2.0 * s.M * WUNET_STOI_N * 2.0 * WUNET_STOI_BP, 4.0 * (2.0 * rows * s.Tr + 2.0 * s.M * WUNET_STOI_BP));
-        WUNET_LAUNCH(stoi_spec_kernel, dim3(mtiles, WUNET_STOI_BP / WUNET_STFT_BN), dim3(WUNET_THREADS), 0, st, P);
+        if (B.reim) {
+            prof_begin(st, "stoi_spec_kernel<save>", 2.0 * 2.0 * s.M * WUNET_STOI_N * 2.0 * WUNET_STOI_BP, 4.0 * (2.0 * rows * s.Tr + 4.0 * s.M * WUNET_STOI_BP));
+            WUNET_LAUNCH(stoi_spec_kernel<true>, grid, dim3(WUNET_THREADS), 0, st, P);
+        } else {
+            prof_begin(st, "stoi_spec_kernel", 2.0 * 2.0 * s.M * WUNET_STOI_N * 2.0 * WUNET_STOI_BP, 4.0 * (2.0 * rows * s.Tr + 2.0 * s.M * WUNET_STOI_BP));
+            WUNET_LAUNCH(stoi_spec_kernel<false>, grid, dim3(WUNET_THREADS), 0, st, P);
+        }
         prof_end(st);
         WUNET_CHECK_LAUNCH();
         StoiSegArgs G{};
-        G.pw = P.pw; G.nk = nk; G.M = s.M; G.Fmax = s.Fmax; G.nblk = s.nblk; G.clip = 1.0 + std::pow(10.0, 15.0 / 20.0); G.part = part;
+        G.pw = P.pw; G.nk = B.nk; G.M = s.M; G.Fmax = s.Fmax; G.nblk = s.nblk; G.clip = 1.0 + std::pow(10.0, 15.0 / 20.0); G.part = B.part;
         prof_begin(st, "stoi_segment_kernel", 0.0, 4.0 * 2.0 * s.M * WUNET_STOI_BP);
         WUNET_LAUNCH(stoi_segment_kernel, dim3(s.nblk, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
         prof_end(st);
         WUNET_CHECK_LAUNCH();
     }
-    WUNET_LAUNCH(stoi_final_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), 0, st, (const double*)part, (const int*)(s.F0 > 0 ? nk : nullptr), s.nblk,
-                 out, frames_out);
+    return WUNET_OK;
+}
+
+// the loss: what the backward needs (saved) and the scratch of either direction, byte offsets
+struct StoiLossShape {
+    StoiShape s;
+    size_t v_nk, v_kept, v_inv, v_pw, v_reim, saved_bytes;
+    size_t f_energy, f_res, f_part, f_score;            // forward
+    size_t b_gr, b_fg, b_g10k;                          // backward
+    size_t scratch_bytes;
+};
+
+int stoi_loss_shape(size_t rows, size_t T, int fs, StoiLossShape& l)
+{
+    if (stoi_shape(rows, T, fs, l.s)) return WUNET_E_ARG;
+    const StoiShape& s = l.s;
+    size_t o = 0;
+    auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 15) & ~(size_t)15; return at; };
+    const size_t spectra = s.nblk ? (size_t)2 * s.M * WUNET_STOI_BP * sizeof(float) : 0;
+    l.v_nk = take(rows * sizeof(int));
+    l.v_kept = take(rows * s.F0 * sizeof(int));
+    l.v_inv = take(rows * s.F0 * sizeof(int));
+    l.v_pw = take(spectra);
+    l.v_reim = take(spectra);
+    l.saved_bytes = o;
+    o = 0;
+    l.f_energy = take(rows * s.F0 * sizeof(double));
+    l.f_res = take(s.L ? 2 * rows * s.Tr * sizeof(float) : 0);
+    l.f_part = take(rows * s.nblk * sizeof(double));
+    l.f_score = take(rows * sizeof(double));
+    const size_t fwd = o;
+    o = 0;
+    l.b_gr = take(s.nblk ? (size_t)s.M * WUNET_STOI_BANDS * sizeof(double) : 0);
+    l.b_fg = take(s.nblk ? (size_t)s.M * WUNET_STOI_N * sizeof(float) : 0);
+    l.b_g10k = take(s.L ? rows * s.Tr * sizeof(float) : 0);
+    l.scratch_bytes = o > fwd ? o : fwd;
+    return 0;
+}
+}  // namespace
+
+int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                       float* out, int* frames_out, void* stream)
+{
+    StoiShape s{};
+    if (stoi_shape(rows, row_len, fs, s)) return WUNET_E_ARG;
+    if (!clean || !estimate || !tables || !scratch || !out || ((size_t)tables & 15) || ((size_t)scratch & 15))
+        return fail(WUNET_E_ARG, "stoi: null argument (or tables / scratch that are not 16-byte aligned)");
+    hipStream_t st = (hipStream_t)stream;
+    char* sc = (char*)scratch;
+    StoiBuffers B{};
+    B.nk = (int*)(sc + s.o_nk); B.kept = (int*)(sc + s.o_kept); B.energy = (double*)(sc + s.o_energy); B.res = (float*)(sc + s.o_res);
+    B.pw = (float*)(sc + s.o_pw); B.part = (double*)(sc + s.o_part);
+    if (const int rc = stoi_enqueue(clean, estimate, rows, row_len, s, tables, B, st)) return rc;
+    WUNET_LAUNCH(stoi_final_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), 0, st, (const double*)B.part, (const int*)(s.F0 > 0 ? B.nk : nullptr), s.nblk,
+                 out, frames_out, (double*)nullptr);
     WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+size_t wunet_stoi_loss_scratch_bytes(size_t rows, size_t row_len, int fs)
+{
+    StoiLossShape l{};
+    if (stoi_loss_shape(rows, row_len, fs, l)) return 0;
+    return l.scratch_bytes;
+}
+
+size_t wunet_stoi_loss_saved_bytes(size_t rows, size_t row_len, int fs)
+{
+    StoiLossShape l{};
+    if (stoi_loss_shape(rows, row_len, fs, l)) return 0;
+    return l.saved_bytes;
+}
+
+int wunet_stoi_loss_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                            void* saved, float* loss_out, float* per_row_out, int* frames_out, void* stream)
+{
+    StoiLossShape l{};
+    if (stoi_loss_shape(rows, row_len, fs, l)) return WUNET_E_ARG;
+    if (!clean || !estimate || !tables || !scratch || !saved || !loss_out || ((size_t)tables & 15) || ((size_t)scratch & 15) || ((size_t)saved & 15))
+        return fail(WUNET_E_ARG, "stoi loss: null argument (or tables / scratch / saved that are not 16-byte aligned)");
+    const StoiShape& s = l.s;
+    hipStream_t st = (hipStream_t)stream;
+    char *sc = (char*)scratch, *sv = (char*)saved;
+    StoiBuffers B{};
+    B.nk = (int*)(sv + l.v_nk); B.kept = (int*)(sv + l.v_kept); B.inv = (int*)(sv + l.v_inv); B.pw = (float*)(sv + l.v_pw); B.reim = (float*)(sv + l.v_reim);
+    B.energy = (double*)(sc + l.f_energy); B.res = (float*)(sc + l.f_res); B.part = (double*)(sc + l.f_part);
+    double* score = (double*)(sc + l.f_score);
+    if (const int rc = stoi_enqueue(clean, estimate, rows, row_len, s, tables, B, st)) return rc;
+    WUNET_LAUNCH(stoi_final_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), 0, st, (const double*)B.part, (const int*)(s.F0 > 0 ? B.nk : nullptr), s.nblk,
+                 per_row_out, frames_out, score);
+    WUNET_CHECK_LAUNCH();
+    WUNET_LAUNCH(stoi_loss_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, st, (const double*)score, (unsigned)rows, loss_out);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_stoi_loss_backward(const void* saved, const float* grad_loss, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                             float* grad_estimate, void* stream)
+{
+    StoiLossShape l{};
+    if (stoi_loss_shape(rows, row_len, fs, l)) return WUNET_E_ARG;
+    if (!saved || !grad_loss || !tables || !scratch || !grad_estimate || ((size_t)tables & 15) || ((size_t)scratch & 15) || ((size_t)saved & 15))
+        return fail(WUNET_E_ARG, "stoi loss: null argument (or tables / scratch / saved that are not 16-byte aligned)");
+    const StoiShape& s = l.s;
+    hipStream_t st = (hipStream_t)stream;
+    char* sc = (char*)scratch;
+    const char* sv = (const char*)saved;
+    const int* nk = (const int*)(sv + l.v_nk);
+    float* fg = (float*)(sc + l.b_fg);
+    float* g10k = s.L ? (float*)(sc + l.b_g10k) : grad_estimate;
+    if (s.nblk > 0) {
+        StoiSegBwdArgs G{};
+        G.pw = (const float*)(sv + l.v_pw); G.nk = nk; G.gl = grad_loss; G.M = s.M; G.Fmax = s.Fmax; G.clip = 1.0 + std::pow(10.0, 15.0 / 20.0);
+        G.inv_rows = 1.0 / (double)rows; G.gr = (double*)(sc + l.b_gr);
+        prof_begin(st, "stoi_segment_bwd_kernel", 0.0, 4.0 * 2.0 * s.M * WUNET_STOI_BP + 8.0 * s.M * WUNET_STOI_BANDS);
+        WUNET_LAUNCH(stoi_segment_bwd_kernel, dim3((s.Fmax + WUNET_STOI_FB - 1) / WUNET_STOI_FB, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
+        prof_end(st);
+        WUNET_CHECK_LAUNCH();
+        StoiSpecBwdArgs P{};
+        P.reim = (const float*)(sv + l.v_reim); P.gr = G.gr; P.basis = tables; P.nk = nk; P.M = s.M; P.Fmax = s.Fmax; P.fg = fg;
+        const unsigned mtiles = (s.M + WUNET_STFT_FM - 1) / WUNET_STFT_FM;
+        prof_begin(st, "stoi_spec_bwd_kernel", 2.0 * s.M * WUNET_STOI_N * 2.0 * WUNET_STOI_BP, 4.0 * (2.0 * s.M * WUNET_STOI_BP + (double)s.M * WUNET_STOI_N));
+        WUNET_LAUNCH(stoi_spec_bwd_kernel, dim3(2 * mtiles), dim3(WUNET_THREADS), 0, st, P);
+        prof_end(st);
+        WUNET_CHECK_LAUNCH();
+    }
+    {
+        StoiUnframeArgs U{};
+        U.fg = fg; U.w = tables + WUNET_STOI_TAB_W; U.inv = (const int*)(sv + l.v_inv); U.nk = s.nblk > 0 ? nk : nullptr; U.g = g10k;
+        U.Tr = s.Tr; U.total = rows * s.Tr; U.Fmax = s.Fmax; U.F0 = s.F0;
+        prof_begin(st, "stoi_unframe_kernel", 0.0, 4.0 * ((double)s.M * WUNET_STOI_N + rows * s.Tr));
+        WUNET_LAUNCH(stoi_unframe_kernel, dim3((unsigned)((U.total + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st, U);
+        prof_end(st);
+        WUNET_CHECK_LAUNCH();
+    }
+    if (s.L) {
+        StoiResampleBwdArgs R{};
+        R.gy = g10k; R.taps = tables + WUNET_STOI_TAB_TAPS; R.gx = grad_estimate; R.T = row_len; R.Tr = s.Tr; R.p = s.p; R.q = s.q; R.L = s.L;
+        const unsigned per = WUNET_THREADS * WUNET_STOI_RPT;
+        prof_begin(st, "stoi_resample_bwd_kernel", 2.0 * rows * row_len * ((2.0 * s.L + 1.0) / s.q), 4.0 * rows * (row_len + s.Tr));
+        WUNET_LAUNCH(stoi_resample_bwd_kernel, dim3((unsigned)((row_len + per - 1) / per), (unsigned)rows), dim3(WUNET_THREADS), 0, st, R);
+        prof_end(st);
+        WUNET_CHECK_LAUNCH();
+    }
     return WUNET_OK;
 }
 

@@ -101,6 +101,7 @@ def check_stft_resolution(n_fft, hop, win_length):
 
 # ---------------------------------------------------------------------- STOI per row (include/wunet_hip.h: wunet_stoi_*)
 STOI_FS = 10000
+STOI_MAX_TAPS = 4096                 # WUNET_STOI_MAX_TAPS of csrc/wunet_stoi.h
 _STOI_TAPS = {}                      # sample rate -> (p, q, float32 taps of pystoi's resampler) or None at 10 kHz
 
 
@@ -125,6 +126,17 @@ def stoi_resampler_taps(sample_rate):
             h = np.kaiser(2 * L + 1, 0.1102 * (60.0 - 8.7)) * (2.0 * p * fc * np.sinc(2.0 * fc * t))
             _STOI_TAPS[fs] = (p, q, (h / h.sum()).astype(np.float32))
     return _STOI_TAPS[fs]
+
+
+def check_stoi_rate(sample_rate):
+    """The sample rates wunet_stoi_* accept (what wunet_stoi_tables_bytes refuses with 0): > 0 and a resampling filter of at most
+    STOI_MAX_TAPS taps."""
+    fs = int(sample_rate)
+    taps = stoi_resampler_taps(fs)
+    if taps is not None and len(taps[2]) > STOI_MAX_TAPS:
+        raise ValueError(f"stoi: {fs} Hz is {taps[1]} / {taps[0]} of 10 kHz and needs {len(taps[2])} filter taps; at most {STOI_MAX_TAPS} "
+                         "are supported (max(p, q) <= 56)")
+    return fs
 
 
 ADAM_HYPER_FLOATS = 8                # WUNET_ADAM_HYPER_FLOATS of include/wunet_hip.h
@@ -565,6 +577,43 @@ class Engine:
             self._check(self.lib.wunet_stoi_forward(clean.data_ptr(), estimate.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
                                                     out.data_ptr(), frames.data_ptr() if frames is not None else None, self._stream(dev)))
         return (out, frames) if return_frames else out
+
+    def stoi_loss_forward(self, clean, enhanced, sample_rate=16000, per_row=False, with_backward=True):
+        """include/wunet_hip.h: wunet_stoi_loss_forward.  The last dimension is the utterance, all leading ones are flattened.  Returns
+        (loss, saved, per_row): loss - device scalar, -mean of the rows' STOI; saved - the buffer `stoi_loss_backward` needs (kept even
+        with with_backward=False: the forward writes its spectra there); per_row - float32 [rows] with per_row=True, else None."""
+        R, T, dev = self._wave_pair("stoi loss", clean, enhanced)
+        fs = int(sample_rate)
+        tables = self.stoi_tables(fs, dev)
+        lib = self.lib
+        scratch = torch.empty(self._sized(lib.wunet_stoi_loss_scratch_bytes(R, T, fs)) // 8, dtype=torch.float64, device=dev)
+        saved = torch.empty(self._sized(lib.wunet_stoi_loss_saved_bytes(R, T, fs)) // 4, dtype=torch.float32, device=dev)
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        rows = torch.empty(R, dtype=torch.float32, device=dev) if per_row else None
+        with self._device_guard(dev):
+            self._check(lib.wunet_stoi_loss_forward(clean.data_ptr(), enhanced.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
+                                                    saved.data_ptr(), out.data_ptr(), rows.data_ptr() if rows is not None else None, None,
+                                                    self._stream(dev)))
+        return out, (saved if with_backward else None), rows
+
+    def stoi_loss_backward(self, shape, saved, grad_loss, sample_rate=16000):
+        """d loss / d enhanced (a tensor of `shape`, every sample written) of the `stoi_loss_forward` that produced `saved`, times
+        grad_loss (a scalar tensor)."""
+        fs = int(sample_rate)
+        T = shape[-1]
+        dev = saved.device
+        g = torch.empty(shape, dtype=torch.float32, device=dev)
+        R = g.numel() // T
+        lib = self.lib
+        if saved.dtype != torch.float32 or not saved.is_contiguous() or saved.numel() * 4 != lib.wunet_stoi_loss_saved_bytes(R, T, fs):
+            raise WunetError(f"stoi loss: saved is not the buffer of stoi_loss_forward on {tuple(shape)} at {fs} Hz")
+        tables = self.stoi_tables(fs, dev)
+        scratch = torch.empty(self._sized(lib.wunet_stoi_loss_scratch_bytes(R, T, fs)) // 8, dtype=torch.float64, device=dev)
+        gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+        with self._device_guard(dev):
+            self._check(lib.wunet_stoi_loss_backward(saved.data_ptr(), gl.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
+                                                     g.data_ptr(), self._stream(dev)))
+        return g
 
     # ------------------------------------------------------------------ fused Adam, data input
     def adam_step(self, params, grads, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, step, grad_scale=1.0, step_dev=None, hyper_dev=None, *,

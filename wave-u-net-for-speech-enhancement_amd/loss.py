@@ -18,11 +18,19 @@ to train on a waveform term plus the spectral one:
 
     "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "weighted_loss",
                       "args": {"terms": [["l1_loss", 1.0], ["stft_loss", 0.5, {"fft_sizes": [1024, 2048, 512]}]]}}
+
+`stoi_loss` (no reference counterpart): minus the mean over the utterances of the batch of STOI, the score the reference picks its best
+checkpoint by, exactly as `metrics.stoi` computes it (include/wunet_hip.h: wunet_stoi_loss_*); gradient with respect to `enhanced`
+only, zero where a band magnitude of the estimate is exactly 0 (autograd: NaN) and for rows with fewer than 30 spectral frames.  STOI
+ignores level, and phase below its 26 ms frames, so it is usually one term beside a waveform one:
+
+    "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "weighted_loss",
+                      "args": {"terms": [["l1_loss", 1.0], ["stoi_loss", 0.25, {"sample_rate": 16000}]]}}
 """
 import torch
 import torch.nn as nn
 
-from .engine import STFT_MAX_RESOLUTIONS, check_stft_resolution, default_engine
+from .engine import STFT_MAX_RESOLUTIONS, check_stft_resolution, check_stoi_rate, default_engine
 
 
 class _LossFn(torch.autograd.Function):
@@ -155,6 +163,44 @@ def stft_loss(fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths
     return HipStftLoss(fft_sizes, hop_sizes, win_lengths, sc_weight, mag_weight, clamp)
 
 
+class _StoiLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, sample_rate, engine, clean, enhanced):
+        if clean.requires_grad:                 # (before anything runs)
+            raise NotImplementedError("stoi_loss: no gradient with respect to `clean` (the target also sets the silent-frame mask and "
+                                      "the clipping level, so it is not minus the gradient of `enhanced`): detach it")
+        clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
+        loss, saved, _ = engine.stoi_loss_forward(clean_c, enh_c, sample_rate)
+        ctx.sample_rate, ctx.engine, ctx.shape = sample_rate, engine, tuple(enh_c.shape)
+        ctx.save_for_backward(saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        saved, = ctx.saved_tensors
+        g = ctx.engine.stoi_loss_backward(ctx.shape, saved, grad_loss, ctx.sample_rate) if ctx.needs_input_grad[3] else None
+        return None, None, None, g
+
+
+class HipStoiLoss(nn.Module):
+    """loss(clean, enhanced) -> -mean over rows of STOI (pystoi, extended=False) at `sample_rate`; the last dimension is the utterance.
+    Gradient with respect to `enhanced` only.  The first call on a device builds the rate's tables: capture a step graph after one
+    eager call, as for stft_loss."""
+
+    def __init__(self, sample_rate=16000):
+        super().__init__()
+        self.sample_rate = check_stoi_rate(sample_rate)
+        self._engine_override = None
+
+    def forward(self, clean, enhanced):
+        engine = self._engine_override if self._engine_override is not None else default_engine()
+        return _StoiLossFn.apply(self.sample_rate, engine, clean, enhanced)
+
+
+def stoi_loss(sample_rate=16000):
+    return HipStoiLoss(sample_rate)
+
+
 class WeightedLoss(nn.Module):
     """The weighted sum of several of this module's losses: terms = [[factory_name, weight, args?], ...]; plain autograd over the
     terms' own functions."""
@@ -184,7 +230,7 @@ class WeightedLoss(nn.Module):
         return total
 
 
-_FACTORIES = ("mse_loss", "l1_loss", "smooth_l1_loss", "si_sdr_loss", "snr_loss", "stft_loss")
+_FACTORIES = ("mse_loss", "l1_loss", "smooth_l1_loss", "si_sdr_loss", "snr_loss", "stft_loss", "stoi_loss")
 
 
 def weighted_loss(terms):
