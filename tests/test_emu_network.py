@@ -467,3 +467,32 @@ def test_first_layer_weight_gradient_from_the_gradient_assembly_sums(monkeypatch
     for kk, g in got[""][1].items():            # nothing else moves
         if kk != k:
             assert np.array_equal(g, got["1"][1][kk]), kk
+
+
+@pytest.fixture(scope="module")
+def bwd_switch_baselines():
+    return {}
+
+
+@pytest.mark.parametrize("switch", ["no_enc_gz", "pa_swap_off"])
+@pytest.mark.parametrize("shape", ["n3_unsplit", "n4_split"])
+def test_backward_elementwise_switches_change_no_bit(monkeypatch, bwd_switch_baselines, shape, switch):
+    """WUNET_NO_ENC_GZ=1 (an encoder layer's g written by pass A and read back instead of re-formed by gz_split_h3_kernel's ENC mode) and
+    WUNET_PA_SWAP=0 (pass A on the (channels, pieces) grid) against the same step without them, two engines in one process: the output, the
+    loss, every parameter gradient and the input gradient bit for bit, and the same kernel names - pass A and the other kernels that form g and g_z call one
+    copy of the arithmetic (wunet_dev.h: wunet_enc_combine, wunet_lrelu_bwd, wunet_gz); gz_split_h3_kernel has it written out a second time, and
+    this test is what holds the two together."""
+    import bwd_switch_cases as cases
+    eng_mod = importlib.import_module(PKG_NAME + ".engine")
+    lib_mod = importlib.import_module(PKG_NAME + "._lib")
+    cfg, env = cases.SHAPES[shape]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for name, _ in cases.SWITCHES.values():
+        monkeypatch.delenv(name, raising=False)
+    make = lambda: eng_mod.Engine(lib=lib_mod.declare(emu_lib.lib()), host_memory=True, h3=2)
+    if shape not in bwd_switch_baselines:
+        bwd_switch_baselines[shape] = cases.train_step(make, torch.device("cpu"), cfg)
+    assert any(k.startswith("pass_a_kernel<ENC") for k in bwd_switch_baselines[shape][1]) and "gz_split_h3_kernel" in bwd_switch_baselines[shape][1]
+    monkeypatch.setenv(*cases.SWITCHES[switch])
+    cases.assert_same_step(bwd_switch_baselines[shape], cases.train_step(make, torch.device("cpu"), cfg), (shape, switch))

@@ -238,6 +238,37 @@ def test_full_size_properties(pkg, dev):
             assert (post[k].cpu() - tsd[k]).abs().max().item() < 1e-5, k
 
 
+@pytest.fixture(scope="module")
+def bwd_switch_baselines():
+    return {}
+
+
+@pytest.mark.parametrize("switch", ["no_enc_gz", "pa_swap_off"])
+@pytest.mark.parametrize("shape", ["n3_unsplit", "n4_split"])
+def test_backward_elementwise_switches_change_no_bit(monkeypatch, dev, bwd_switch_baselines, shape, switch):
+    """WUNET_NO_ENC_GZ=1 and WUNET_PA_SWAP=0 against the same step without them, two engines in one process (tests/bwd_switch_cases.py; the
+    emulator's form is in test_emu_network.py): the output, the loss, every parameter gradient and the input gradient bit for bit on the
+    hardware, where hipcc's contraction of the shared helpers is what is tested, and the same kernel names."""
+    import bwd_switch_cases as cases
+    eng_mod = importlib.import_module(PKG_NAME + ".engine")
+    cfg, env = cases.SHAPES[shape]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    for name, _ in cases.SWITCHES.values():
+        monkeypatch.delenv(name, raising=False)
+    make = lambda: eng_mod.Engine(h3=2)
+    if shape not in bwd_switch_baselines:
+        bwd_switch_baselines[shape] = cases.train_step(make, dev, cfg)
+    assert any(k.startswith("pass_a_kernel<ENC") for k in bwd_switch_baselines[shape][1]) and "gz_split_h3_kernel" in bwd_switch_baselines[shape][1]
+    monkeypatch.setenv(*cases.SWITCHES[switch])
+    other = cases.train_step(make, dev, cfg)
+    cases.assert_same_step(bwd_switch_baselines[shape], other, (shape, switch))
+    if (shape, switch) == ("n3_unsplit", "no_enc_gz"):
+        # the switch took effect (the names cannot tell): pass A now stores the encoder layers' g, 4 bytes per element more in the profiler's
+        # count.  (That WUNET_PA_SWAP reaches the context: tests/test_plan_invariants.py; the grid's order is not visible to the profiler.)
+        assert other[1]["pass_a_kernel<ENC>"] > bwd_switch_baselines[shape][1]["pass_a_kernel<ENC>"]
+
+
 @pytest.mark.parametrize("mode,n,ci,B,T", [(1, 4, 8, 2, 256), (2, 3, 16, 4, 2048)])
 def test_backward_range_equals_full(pkg, dev, mode, n, ci, B, T):
     """wunet_backward_range in buckets (the RCCL-overlap path) == one wunet_backward call, bit for bit - on the fp32

@@ -30,5 +30,14 @@ def test_plan_invariants():
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-4000:]
     assert r.stdout == ""
-    # 5 settings of wunet_set_h3 x 17 switch sets per shape, none refused
-    assert f"{len(SHAPES) * 5 * 17} contexts" in r.stderr and " 0 violations" in r.stderr, r.stderr[-400:]
+    # 5 settings of wunet_set_h3 x 19 switch sets per shape (WUNET_NO_ENC_GZ and WUNET_PA_SWAP are planner switches too), none refused
+    assert f"{len(SHAPES) * 5 * 19} contexts" in r.stderr and " 0 violations" in r.stderr, r.stderr[-400:]
+    # the backward's two A/B switches reach the planned context (the dump names them where one is off) and nothing else sets them
+    r = subprocess.run([os.path.join(_EMU, "plan_dump"), "--shape", "3", "24", "3", "2048", "--shape", "4", "16", "3", "4096"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    ctx = [ln for ln in r.stdout.splitlines() if ln.startswith("ctx ")]
+    assert len(ctx) == 2 * 5 * 19
+    for ln in ctx:
+        want = {"switches=[WUNET_NO_ENC_GZ=1]": " enc_gz=0 pa_swap=1", "switches=[WUNET_PA_SWAP=0]": " enc_gz=1 pa_swap=0"}
+        hit = [v for k, v in want.items() if k in ln]
+        assert (hit[0] in ln) if hit else ("enc_gz=" not in ln and "pa_swap=" not in ln), ln[:200]

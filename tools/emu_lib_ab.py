@@ -7,7 +7,9 @@ For a refactor of the host path: both libraries run the case table below through
 result is compared with np.array_equal - output, loss, every parameter gradient, the input gradient, the running statistics and
 num_batches_tracked - and so is the text of wunet_profile_collect with the profiler on (kernel names and launch counts; the
 emulator build reports no flops / bytes).  Planner switches are read when a context is planned: every run gets its own engine.
-(A base library from before PlanSwitches reads WUNET_WGRAD_XCD and WUNET_A_CAP once per process: set those outside, one run each.)
+(A base library from before PlanSwitches reads WUNET_WGRAD_XCD and WUNET_A_CAP once per process: set those outside, one run each.
+One from before WUNET_NO_ENC_GZ and WUNET_PA_SWAP joined them reads those two at its first backward and keeps them: its runs of their
+cases have them unset - the results are to be the same bits either way.)
 Exit status 0: nothing differs."""
 import ctypes
 import importlib
@@ -28,7 +30,7 @@ model_mod = importlib.import_module(PKG + ".model")
 loss_mod = importlib.import_module(PKG + ".loss")
 
 SWITCHES = ("WUNET_NO_EVOP", "WUNET_NO_SKIP_FUSE", "WUNET_H3U", "WUNET_H3_NOSPLIT", "WUNET_H3_GRID", "WUNET_H3_KTAIL", "WUNET_UPT", "WUNET_NO_E0",
-            "WUNET_H3_ORDER", "WUNET_H3D_ORDER", "WUNET_H3W_ORDER", "WUNET_H3_SPS", "WUNET_H3_OLDSPLIT")
+            "WUNET_H3_ORDER", "WUNET_H3D_ORDER", "WUNET_H3W_ORDER", "WUNET_H3_SPS", "WUNET_H3_OLDSPLIT", "WUNET_NO_ENC_GZ", "WUNET_PA_SWAP")
 
 
 def masks(n):
@@ -70,6 +72,12 @@ def cases():
             for mode in ("eval", "train"):
                 out.append((shape, 2, mode, None, dict(grid_only, **sw)))
         out.append((shape, 2, "train_nosave", None, dict(base, WUNET_H3U="256,256")))
+        # the backward's two elementwise switches, un-split (GZ_ENC recompute, or g stored and read back) and with split-K data gradients
+        # (pass A adds the partials itself; (4, 16, 3, 4096): pieces > 1, the swapped grid)
+        for sw in [{"WUNET_NO_ENC_GZ": "1"}, {"WUNET_PA_SWAP": "0"}, {"WUNET_NO_ENC_GZ": "1", "WUNET_PA_SWAP": "0"}]:
+            out.append((shape, 2, "train", None, dict(base, **sw)))
+            out.append((shape, 2, "train", None, dict(grid_only, **sw)))
+        out.append((shape, 2, "train", None, grid_only))
     # padded lengths: every conv through conv_reduce_bn_kernel, no EVOP, no conv_h3u_kernel
     for shape, h3 in [((3, 8, 2, 96), 0), ((3, 8, 2, 96), 2), ((3, 16, 3, 768), 2), ((2, 24, 3, 1536), 2)]:
         for mode in ("train", "eval"):

@@ -26,6 +26,7 @@ static const char* const kSwitchSets[] = {
     "", "WUNET_H3_NOSPLIT=1", "WUNET_H3_SPS=1", "WUNET_H3_SPS=2", "WUNET_H3_OLDSPLIT=1", "WUNET_H3_KTAIL=0", "WUNET_H3_ORDER=432",
     "WUNET_H3D_ORDER=432", "WUNET_H3W_ORDER=432", "WUNET_H3_ORDER=432 WUNET_H3D_ORDER=432 WUNET_H3W_ORDER=432", "WUNET_H3U=0",
     "WUNET_H3U=256,256", "WUNET_H3U=512", "WUNET_NO_SKIP_FUSE=1", "WUNET_NO_EVOP=1", "WUNET_NO_E0=1", "WUNET_UPT=0",
+    "WUNET_NO_ENC_GZ=1", "WUNET_PA_SWAP=0",
 };
 
 // sets (on) or clears the variables of one switch set ("NAME=VALUE NAME=VALUE")
@@ -104,6 +105,8 @@ static std::string dump(const wunet_ctx* c, int length, int h3, const char* set)
              " fwd_floats=%zu total_floats=%zu h3_wf_halfs=%zu h3_wb_halfs=%zu", c->n, c->ci, c->B, length, h3, set, c->T, (int)c->padded, c->h3, c->bf,
              c->e0, c->head_blocks, c->fwd_floats, c->total_floats, c->h3_wf_halfs, c->h3_wb_halfs);
     out += b;
+    // (the backward's two A/B switches where one is off: a dump from before they were planner switches has neither field)
+    if (!c->enc_gz || !c->pa_swap) out += " enc_gz=" + std::to_string(c->enc_gz) + " pa_swap=" + std::to_string(c->pa_swap);
     size_t split = 0;
     for (const Off& o : offsets_in_order(c, &split))
         if (o.name.find('[') == std::string::npos) out += " " + o.name + "=" + std::to_string(o.at);

@@ -38,20 +38,6 @@ bool dx_stays_split(const wunet_ctx* c, int i)
     return l.d.ksplit > 1 && l.L >= 4 && c->ly[i - 1].L >= 4;       // (neither end on the scalar kernels of the 1-2-sample levels)
 }
 
-// ---- A/B switches of the backward's elementwise passes, read once per process
-// WUNET_NO_ENC_GZ=1: the encoder layers' g written by pass A and read back instead of recomputed by gz_split_h3_kernel
-bool enc_gz_off()
-{
-    static const bool off = getenv("WUNET_NO_ENC_GZ") != nullptr;
-    return off;
-}
-// WUNET_PA_SWAP=0: pass A on the (channels, pieces) grid of rounds 1 - 3
-bool pa_swap_on()
-{
-    static const int on = getenv("WUNET_PA_SWAP") ? atoi(getenv("WUNET_PA_SWAP")) : 1;
-    return on != 0;
-}
-
 // a level of < 4 samples: the scalar kernels (g_z written in place of g)
 bool bwd_tiny(const wunet_ctx* c, int i) { return c->ly[i].L < 4; }
 // a whole channel in one pass of one block (the levels of <= 16 samples at batch 64)
@@ -73,7 +59,8 @@ bool upt_handoff_sound(const wunet_ctx* c, int q)
 }
 
 // How the backward runs layer i: which kernels, who reads what, and so where its g_z ends up.  The one place where these decisions are
-// made - a function of the context and the layer alone (the frozen mask is run-time state and not part of it) - for the stages of
+// made - a function of the context and the layer alone (the frozen mask is run-time state and not part of it; the A/B switches were read when
+// the context was planned) - for the stages of
 // backward_range_impl and for wunet_backward_input, which reads the first layer's g_z in whatever form that backward left it
 // (first_layer_gz_source).
 enum { DG_NONE = 0, DG_H3 = 1, DG_SCALAR = 2, DG_FP32 = 3 };
@@ -132,12 +119,12 @@ BwdLayerPlan bwd_layer_plan(const wunet_ctx* c, int i)
         // mode) from them instead of written here and read back (WUNET_NO_ENC_GZ=1: A/B switch)
         q.g1_split = dx_stays_split(c, i + 1);
         q.pa_mode = A_ENC; q.pa_name = q.e0 ? "pass_a_kernel<ENC, e0>" : "pass_a_kernel<ENC>"; q.g_src_bytes = 6.0; q.gz_mode = GZ_ENC;
-        q.stores_g = !(!enc_gz_off() && recompute && !q.g1_split) && !q.e0;
+        q.stores_g = !(c->enc_gz && recompute && !q.g1_split) && !q.e0;
     }
     if (q.stores_g) q.gz_mode = GZ_G;
     // grid (pieces, channels): consecutive blocks walk consecutive pieces of ONE channel row (rounds 1 - 3 had (channels, pieces):
     // neighbours 4 L bytes apart; 5.156 -> 5.139 ms per step; WUNET_PA_SWAP=0: A/B switch)
-    q.swap = pa_swap_on() && l.a_split > 1 && !q.tiny;        // (pass_a_scalar_kernel reads its channel from blockIdx.x)
+    q.swap = c->pa_swap && l.a_split > 1 && !q.tiny;        // (pass_a_scalar_kernel reads its channel from blockIdx.x)
     // (short levels on the split kernels: the finalize runs in the prologue of gz_split_h3_kernel's blocks instead of a launch of its own)
     q.fin_in_gz = !q.fuse && q.gz_h3 && l.a_split * l.cout <= WUNET_GZ_FIN_LOADS && l.cout <= WUNET_GZ_FIN_C;
     q.dgrad = i == 0 ? DG_NONE : l.h3d ? DG_H3 : q.tiny ? DG_SCALAR : DG_FP32;      // (not needed for the first layer)
@@ -153,6 +140,14 @@ int first_layer_gz_source(const wunet_ctx* c)
 {
     const BwdLayerPlan q = bwd_layer_plan(c, 0);
     return q.e0 ? IG_ENC : q.gz_in_wgrad ? IG_G : IG_GZ;
+}
+
+// the source of encoder layer i's g (0 <= i < n): the skip rows of its decoder partner's data gradient, the next encoder layer's data gradient -
+// for pass A, gz_split_h3_kernel's ENC mode and input_grad_kernel<IG_ENC> alike
+WunetEncSrc enc_grad_source(const wunet_ctx* c, float* ws, int i)
+{
+    const LayerPlan& dc = c->ly[2 * c->n - i];
+    return WunetEncSrc{ws + dc.dx, ws + c->ly[i + 1].dx, dc.cin, dc.c0};
 }
 
 // what every stage of one backward call shares
@@ -193,7 +188,7 @@ int head_backward(const BwdCall& k, void* workspace, const float* enhanced, cons
 int pass_a(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
 {
     wunet_ctx* c = k.c; float* ws = k.ws; const hipStream_t st = k.st;
-    const int NL = c->NL, n = c->n;
+    const int NL = c->NL;
     const LayerPlan& l = c->ly[i];
     PassAArgs p{};
     p.z = ws + l.z; p.a = ws + l.a; p.s = ws + l.s; p.mean = ws + l.mean; p.rstd = ws + l.rstd;
@@ -223,11 +218,10 @@ int pass_a(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
         else if (q.fuse) WUNET_LAUNCH((pass_a_kernel<A_UP, true>), ga, dim3(WUNET_THREADS), 0, st, p);
         else WUNET_LAUNCH(pass_a_kernel<A_UP>, ga, dim3(WUNET_THREADS), 0, st, p);
     } else {
-        const LayerPlan& dc = c->ly[2 * n - i];
         const LayerPlan& nx = c->ly[i + 1];
-        p.g0 = ws + dc.dx; p.Cg0 = dc.cin; p.coff = dc.c0; p.g1 = ws + nx.dx;
+        p.enc = enc_grad_source(c, ws, i);
         if (q.g1_split) {
-            p.g1 = ws + c->spart_off; p.g1_splits = nx.d.ksplit; p.g1_stride = (size_t)c->B * nx.cin * nx.L;
+            p.enc.ge = ws + c->spart_off; p.g1_splits = nx.d.ksplit; p.g1_stride = (size_t)c->B * nx.cin * nx.L;
         }
         if (q.e0) { p.x0 = k.noisy; p.e0rows = ws + c->e0part_off; }
         if (q.tiny) WUNET_LAUNCH(pass_a_scalar_kernel<A_ENC>, ga, dim3(WUNET_THREADS), 0, st, p);
@@ -268,10 +262,7 @@ int finalize_and_gz(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
         if (q.gz_mode != GZ_G) { hd.a = ws + l.a; hd.s = ws + l.s; }
         if (q.gz_mode == GZ_HEAD) { hd.gh = ws + c->gh_off; hd.wh = k.params[4 * c->NL]; }
         if (q.gz_mode == GZ_UPH) hd.gq = ws + c->ly[i + 1].dxh;
-        if (q.gz_mode == GZ_ENC) {
-            const LayerPlan& dc = c->ly[2 * c->n - i];
-            hd.gd = ws + dc.dx; hd.Cg0 = dc.cin; hd.coff = dc.c0; hd.ge = ws + c->ly[i + 1].dx;
-        }
+        if (q.gz_mode == GZ_ENC) hd.enc = enc_grad_source(c, ws, i);
         // (the source of g is a compile-time mode of the kernel: every load of a thread is issued before its first use)
 #define WUNET_GZ_LAUNCH(FIN_, GM_, BF_)                                                                                                               \
     WUNET_LAUNCH((gz_split_h3_kernel<FIN_, GM_, BF_>), dim3(hb), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z), \
@@ -535,8 +526,7 @@ int wunet_backward_input(wunet_ctx* c, const float* noisy, const float* const* p
     A.B = c->B; A.C = l.cout; A.L = l.L; A.Lt = l.Lt; A.Tt = c->Tt;
     A.vec = (reinterpret_cast<size_t>(grad_noisy) & 15) == 0 && (c->Tt & 3) == 0;
     if (src == IG_ENC) {
-        const LayerPlan& dc = c->ly[2 * c->n];
-        A.a = ws + l.a; A.s = ws + l.s; A.gd = ws + dc.dx; A.Cg0 = dc.cin; A.coff = dc.c0; A.ge = ws + c->ly[1].dx;
+        A.a = ws + l.a; A.s = ws + l.s; A.enc = enc_grad_source(c, ws, 0);
     } else {
         A.g = ws + l.g;
     }

@@ -247,6 +247,55 @@ __device__ __forceinline__ void wunet_atomic_absmax(float* slot, float v)
 // LeakyReLU(0.1): slope < 1 so max(v, 0.1 v) is exact and branch-free
 __device__ __forceinline__ float wunet_lrelu(float v) { return fmaxf(v, WUNET_SLOPE * v); }
 
+// ---- the backward's gradient assembly: the kernels that form g or g_z - pass A, pass_a_scalar_kernel, gz_materialize_kernel,
+// gz_scalar_kernel, input_grad_kernel, the first layer's weight gradient - call these; the recompute modes rely on all of them agreeing bit for
+// bit.  ONE EXCEPTION: gz_split_h3_kernel (wunet_h3_elem.h, phase 2) has the same arithmetic written out by hand, because hipcc contracts
+// its loop differently through the helpers.  Whoever edits one of wunet_enc_combine, wunet_lrelu_bwd, wunet_gz edits that copy too.
+// LeakyReLU' on the gradient g of an activation whose pre-activation was a z + s (BatchNorm folded to scale / shift)
+__device__ __forceinline__ float wunet_lrelu_bwd(float a, float s, float z, float g)
+{
+    if (!(a * z + s > 0.0f)) g *= WUNET_SLOPE;
+    return g;
+}
+// (four samples, multiplied in place under the test: input_grad_kernel<IG_ENC>)
+__device__ __forceinline__ wunet_f4 wunet_lrelu_bwd(float a, float s, wunet_f4 z, wunet_f4 g)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (!(a * z[j] + s > 0.0f)) g[j] *= WUNET_SLOPE;
+    return g;
+}
+// g_z = k1 g + k2 z + k3: BatchNorm backward folded to three per-channel coefficients (bn_bwd_fold, wunet_elementwise.h)
+__device__ __forceinline__ float wunet_gz(float k1, float k2, float k3, float g, float z) { return k1 * g + k2 * z + k3; }
+__device__ __forceinline__ wunet_f4 wunet_gz(float k1, float k2, float k3, wunet_f4 g, wunet_f4 z)
+{
+    wunet_f4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = wunet_gz(k1, k2, k3, g[j], z[j]);
+    return o;
+}
+// The source of an encoder layer's g (channel c of C, row stride L): the skip rows of its decoder partner's data gradient gd [B][Cg0][L]
+// from channel coff, plus the next encoder layer's data gradient ge [B][C][L/2] zero-stuffed onto the even positions (skip + decimation^T).
+// Filled by enc_grad_source (wunet_backward.cpp).  Four samples from l (a multiple of 4): one 16-byte load, one float2 load, the combine;
+// the loads are apart from the combine so that a caller issues all its loads before the first use.
+struct WunetEncSrc { const float* gd; const float* ge; int Cg0, coff; };
+__device__ __forceinline__ const float* wunet_enc_skip_at(const WunetEncSrc& S, int b, int c, int L, int l) { return S.gd + ((size_t)b * S.Cg0 + S.coff + c) * L + l; }
+__device__ __forceinline__ const float* wunet_enc_half_at(const WunetEncSrc& S, int b, int C, int c, int L, int l) { return S.ge + ((size_t)b * C + c) * (L >> 1) + (l >> 1); }
+__device__ __forceinline__ wunet_f4 wunet_enc_skip4(const WunetEncSrc& S, int b, int c, int L, int l) { return wunet_ld4(wunet_enc_skip_at(S, b, c, L, l)); }
+__device__ __forceinline__ float2 wunet_enc_half2(const WunetEncSrc& S, int b, int C, int c, int L, int l) { return *reinterpret_cast<const float2*>(wunet_enc_half_at(S, b, C, c, L, l)); }
+__device__ __forceinline__ wunet_f4 wunet_enc_combine(wunet_f4 d, float2 e)
+{
+    d[0] += e.x; d[2] += e.y;        // g = {d0 + e.x, d1, d2 + e.y, d3}
+    return d;
+}
+// one sample (the scalar kernels)
+__device__ __forceinline__ float wunet_enc_g1(const WunetEncSrc& S, int b, int C, int c, int L, int l)
+{
+    float g = *wunet_enc_skip_at(S, b, c, L, l);
+    if ((l & 1) == 0) g += *wunet_enc_half_at(S, b, C, c, L, l);
+    return g;
+}
+
 // ATen upsample_linear1d(align_corners=True) source coordinate, fp32 arithmetic on purpose
 // (reference model/unet_basic.py:93 -> ATen UpSample.h area_pixel_compute_source_index +
 // guard_index_and_lambda).  scale = (float)(Lin-1)/(Lout-1) is computed on the host the same way.

@@ -484,6 +484,44 @@ static __global__ __launch_bounds__(WUNET_THREADS) void rows_sum_kernel(const fl
     }
 }
 
+// ---------------------------------------------------------------------------- BN backward finalize
+// bn_finalize_bwd_kernel (behind pass A, below): grid = C.  dgamma = sum g*xhat, dbeta = sum g, and the folded coefficients of
+// g_z = gamma*rstd*(g - mean(g) - xhat*mean(g*xhat)) = k1*g + k2*z + k3.
+// A frozen layer (BatchNorm on the running statistics, wunet_set_bn_frozen; mean / rstd hold running_mean / 1/sqrt(running_var + eps)):
+// y = a z + const, so g_z = a g - k1 = a, k2 = k3 = 0 - and the conv bias gets a sum g (batch statistics cancel it).
+struct BnBwdArgs {
+    const float* part; int rows;
+    const float* gamma; const float* mean; const float* rstd;
+    float* dgamma; float* dbeta;
+    float* dbias;        // conv bias feeding batch-statistics BN: exact zero gradient; frozen: a sum g
+    float* k1; float* k2; float* k3;
+    int C; double count;
+    const float* pmax;   // nullptr or pass A's [rows][C][2] maxima
+    float* bound;        // [C]: |k1| max|g| + |a m2 rstd| max|z - mean| + |a m1|  >=  max |g_z| of the channel
+    const float* e0rows; // nullptr, or the first layer's [rows][C][48] partial sums (pass_a_kernel<.., E0>): its weight gradient is finished here
+    float* dw0;          // [C][15]: dW[c][k] = k1 sum g x + k2 sum z x + k3 sum x
+    int frozen;          // the layer's BatchNorm ran on the running statistics
+};
+
+// The fold itself, for every kernel that finishes a channel's BatchNorm backward (bn_finalize_bwd_kernel, pass A's FUSE tail,
+// gz_split_h3_kernel's FIN prologue): s1 = sum g, s2 = sum g xhat over `count` values; mg, mz: the channel's max |g|, max |z - mean| (for
+// the bound; 0 where nobody reads it).
+struct BnBwdFold { float k1, k2, k3, dgamma, dbeta, dbias, bound; };
+__device__ __forceinline__ BnBwdFold bn_bwd_fold(float gamma, float rstd, float mean, double s1, double s2, double count, int frozen, float mg, float mz)
+{
+    const double m1 = frozen ? 0.0 : s1 / count, m2 = frozen ? 0.0 : s2 / count;
+    const double a = (double)gamma * (double)rstd;
+    BnBwdFold f;
+    f.k1 = (float)a;
+    f.k2 = (float)(-a * m2 * (double)rstd);
+    f.k3 = (float)(a * m2 * (double)rstd * (double)mean - a * m1);
+    f.dgamma = (float)s2;
+    f.dbeta = (float)s1;
+    f.dbias = frozen ? (float)(a * s1) : 0.0f;
+    f.bound = (float)(fabs(a) * (double)mg + fabs(a * m2 * (double)rstd) * (double)mz + fabs(a * m1));
+    return f;
+}
+
 // ---------------------------------------------------------------------------- pass A (gradient assembly)
 // Builds g_pre = dL/d(BN output) of one layer from its consumers' data gradients, applies the
 // LeakyReLU derivative, writes g_pre and the partial sums  sum g_pre, sum g_pre*xhat  per channel.
@@ -492,75 +530,11 @@ static __global__ __launch_bounds__(WUNET_THREADS) void rows_sum_kernel(const fl
 //   A_ENC  : g_y[b,c,l] = dXdec[b, coff+c, l] + (l even ? dXenc[b,c,l/2] : 0)   (skip + decimation^T)
 // grid = (C, nsplit); part[split][C][2].
 //   A_UPH  : g_y[b,c,i] = dXh[b,c,i] (+ the tile-edge terms): the next decoder layer's data gradient arrives already pulled back through
-//            the upsample (conv_h3d_kernel<.., 3>, ConvH3Args::uh_*) - a plain elementwise pass
+//            the upsample (conv_h3d_kernel<.., 3>, ConvH3Args::uh_*) - a plain elementwise pass.  The tile-edge terms (ConvH3Args::uh_spill
+//            [2][C][ntiles]; a tile = 128 inputs of one row): input l, the first of a tile, is owed sp[0][c][tile - 1]; the last of a tile
+//            sp[1][c][tile + 1]; row ends nothing (exact zeros, but the neighbour tile may not exist).  This pass adds them and writes the two
+//            completed values back into dXh, so that gz_split_h3_kernel's UPH mode reads finished values with nothing conditional among its loads.
 enum { A_HEAD = 0, A_UP = 1, A_ENC = 2, A_UPH = 3 };
-
-// The tile-edge terms of a half-resolution data gradient (ConvH3Args::uh_spill [2][C][ntiles]; a tile = 128 inputs of one row): input l, the
-// first of a tile, is owed sp[0][c][tile - 1]; the last of a tile sp[1][c][tile + 1].  g: the four inputs l .. l + 3 (l a multiple of 4) of
-// channel c, item b; tpr = tiles per row.  Row ends are owed nothing (the terms there are exact zeros, but the neighbour tile may not exist).
-// pass_a_kernel<A_UPH> - one channel per thread, no loads to batch - adds them and writes the two completed values back into the array, so the
-// second reader (gz_split_h3_kernel's UPH mode, eight channels per thread) reads finished values with nothing conditional among its loads.
-__device__ __forceinline__ void wunet_uph_edges(const float* sp, int C, int ntiles, int tpr, int b, int c, int l, int L, float* gq_at_l, float& g_first, float& g_last)
-{
-    const int tile = b * tpr + (l >> 7);
-    if ((l & 127) == 0 && l > 0) { g_first += sp[(size_t)c * ntiles + tile - 1]; gq_at_l[0] = g_first; }
-    if ((l & 127) == 124 && l + 4 < L) { g_last += sp[((size_t)C + c) * ntiles + tile + 1]; gq_at_l[3] = g_last; }
-}
-
-// Transposed x2 upsample of ONE row, four inputs at a time, for callers that walk several channels at the same positions (gz_split_h3_kernel's
-// UP mode: 8 channels per thread): the coordinates of outputs 2l - 1 .. 2l + 8 once (wunet_upT_coords), then per row the ten data-gradient
-// values and sixteen multiply-adds (wunet_upT_row) - pass_a_kernel<A_UP>'s arithmetic in pass_a_kernel's order: input i receives, in ascending
-// j, l1(2i-1) d[2i-1] + l1(2i) d[2i] + l0(2i+1) d[2i+1] + l0(2i+2) d[2i+2].  `fast`: interior positions whose outputs read the regular
-// source pairs ((j-1) >> 1, +1) (checked against ATen's fp32 coordinates); the row ends take the general form.
-struct WunetUpT { float c0[10], c1[10]; bool fast; };
-__device__ __forceinline__ void wunet_upT_coords(int l, int Lt, float up_scale, WunetUpT& U)
-{
-    const int j0 = 2 * l - 4;
-    U.fast = l >= 4 && l + 8 <= Lt;
-    if (U.fast) {
-#pragma unroll
-        for (int k = 3; k <= 12; ++k) {
-            int i0, i1;
-            wunet_up_coord(j0 + k, Lt, up_scale, i0, i1, U.c0[k - 3], U.c1[k - 3]);
-            U.fast = U.fast && i0 == ((j0 + k - 1) >> 1) && i1 == i0 + 1;
-        }
-    }
-}
-// row: the data gradient of one (item, channel) at 2L samples (row stride Lo = 2L, Lot = 2 Lt of them exist); g: inputs l .. l + 3
-__device__ __forceinline__ void wunet_upT_row(const float* row, int l, int Lo, int Lot, int Lt, float up_scale, const WunetUpT& U, float (&g)[4])
-{
-    const int j0 = 2 * l - 4;
-    g[0] = g[1] = g[2] = g[3] = 0.0f;
-    if (U.fast) {
-        const float dm = row[j0 + 3];
-        const wunet_f4 da = wunet_ld4(row + j0 + 4), db = wunet_ld4(row + j0 + 8);
-        const float dl = row[j0 + 12];
-        const float d[10] = {dm, da[0], da[1], da[2], da[3], db[0], db[1], db[2], db[3], dl};      // outputs 2l - 1 .. 2l + 8
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            g[m] += U.c1[2 * m] * d[2 * m];
-            g[m] += U.c1[2 * m + 1] * d[2 * m + 1];
-            g[m] += U.c0[2 * m + 2] * d[2 * m + 2];
-            g[m] += U.c0[2 * m + 3] * d[2 * m + 3];
-        }
-        return;
-    }
-#pragma unroll
-    for (int k = 2; k <= 12; ++k) {                   // j = 2l-2 .. 2l+8, ascending like ATen's backward loop
-        const int j = j0 + k;
-        if (j >= 0 && j < Lot) {
-            const float dv = row[j];
-            int i0, i1; float l0, l1;
-            wunet_up_coord(j, Lt, up_scale, i0, i1, l0, l1);
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                const float w = (i0 == l + m ? l0 : 0.0f) + (i1 == l + m ? l1 : 0.0f);
-                g[m] += w * dv;
-            }
-        }
-    }
-    (void)Lo;
-}
 
 struct PassAArgs {
     const float* z;      // [B][C][L]
@@ -572,12 +546,16 @@ struct PassAArgs {
     float* part;         // [nsplit][C][2]
     float* pmax;         // nullptr or [nsplit][C][2]: max |g_pre|, max |z - mean| (bound of |g_z| for the fp16-split scale)
     float* hpart;        // HEAD: [nsplit][C] partial head-weight gradients  sum gh * act(z_c)  (same pass over z and gh)
-    const float* g0;     // HEAD: gh [B][L];  UP: dX [B][Cg0][2L];  ENC: dXdec [B][Cg0][L];  UPH: dXh [B][C][L] (its tile-edge values are completed IN PLACE)
-    const float* g1;     // HEAD: wh;         ENC: dXenc [B][C][L/2]
-    int Cg0;             // channel count of the g0 tensor
-    int g1_splits;       // ENC: > 1 - g1 points at the split-K partials of the data gradient (g1_stride floats apart): this pass is their
-    size_t g1_stride;    //      only reader and adds them itself, in split order, instead of a split_sum_kernel launch in front of it
-    int coff;            // ENC: channel offset of the skip part inside dXdec
+    union {              // the source of g, by mode
+        struct {
+            const float* g0;     // HEAD: gh [B][L];  UP: dX [B][Cg0][2L];  UPH: dXh [B][C][L] (its tile-edge values are completed IN PLACE)
+            const float* g1;     // HEAD: wh
+            int Cg0;             // UP: channel count of the g0 tensor
+        };
+        WunetEncSrc enc;         // ENC: dXdec's skip rows and dXenc
+    };
+    size_t g1_stride;    // ENC: g1_splits > 1 - enc.ge points at the split-K partials of the data gradient (g1_stride floats apart): this pass is
+    int g1_splits;       //      their only reader and adds them itself, in split order, instead of a split_sum_kernel launch in front of it
     int B, C, L, logL;
     float up_scale;      // UP: (float)(Lt-1)/(2Lt-1)
     int swap;            // grid = (splits, C) instead of (C, splits)
@@ -627,7 +605,7 @@ __device__ __forceinline__ void block_reduce_pass_a(double& s1, double& s2, doub
 template <int MODE, bool E0 = false>
 struct PassALoads {
     wunet_f4 z, g;                       // z; HEAD: gh, UPH: dXh, ENC: dXdec
-    float e0, e1;                        // ENC: dXenc at l/2, l/2 + 1 (the split-K partials already added, in split order)
+    float e0, e1;                        // ENC: dXenc at l/2, l/2 + 1 (the split-K partials already added, in split order); UPH: the two tile-edge terms
     float d[MODE == A_UP ? 13 : 1];      // UP: dX at 2l - 4 .. 2l + 8
     wunet_f4 xw[E0 ? 5 : 1];             // E0: the input waveform at l - 8 .. l + 11
     size_t zi; int b, l;
@@ -672,7 +650,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
         t.e0 = t.e1 = 0.0f;
         if (MODE == A_HEAD) t.g = wunet_ld4(A.g0 + (size_t)b * A.L + l);
         else if (MODE == A_UPH) {
-            // the tile-edge terms (wunet_uph_edges) with the trip's other loads: clamped indices, the values of the lanes that are owed nothing
+            // the two tile-edge terms a thread may owe, with the trip's other loads: clamped indices, the values of the lanes that are owed nothing
             // are not used (as a conditional load inside the trip, every wave - each spans two tiles - waited for all its loads there)
             t.g = wunet_ld4(A.g0 + t.zi);
             const int tile = b * A.tpr + (l >> 7);
@@ -680,8 +658,8 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
             t.e1 = A.sp[((size_t)A.C + c) * A.ntiles + (tile + 1 < A.ntiles ? tile + 1 : tile)];
         }
         else if (MODE == A_ENC) {
-            t.g = wunet_ld4(A.g0 + ((size_t)b * A.Cg0 + A.coff + c) * A.L + l);
-            const float* ge = A.g1 + ((size_t)b * A.C + c) * (A.L >> 1) + (l >> 1);
+            t.g = wunet_enc_skip4(A.enc, b, c, A.L, l);
+            const float* ge = wunet_enc_half_at(A.enc, b, A.C, c, A.L, l);
             float e0, e1;
             if (G1S) {                                        // (four loads in flight, the order of split_sum_kernel's additions)
                 e0 = e1 = 0.0f;
@@ -705,7 +683,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
                     e0 += k + 1 <= last ? t1.x : 0.0f; e1 += k + 1 <= last ? t1.y : 0.0f;
                     e0 += k + 2 <= last ? t2.x : 0.0f; e1 += k + 2 <= last ? t2.y : 0.0f;
                 }
-            } else { const float2 tt = *reinterpret_cast<const float2*>(ge); e0 = tt.x; e1 = tt.y; }
+            } else { const float2 tt = wunet_enc_half2(A.enc, b, A.C, c, A.L, l); e0 = tt.x; e1 = tt.y; }
             t.e0 = e0; t.e1 = e1;
             if (E0) {
                 // l and L are multiples of 4: an aligned 16-byte piece of the row lies wholly inside [0, L) or wholly outside (zero padding of the conv)
@@ -748,7 +726,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
         } else if (MODE == A_UPH) {
             float* const gq = const_cast<float*>(A.g0) + t.zi;
             g[0] = t.g[0]; g[1] = t.g[1]; g[2] = t.g[2]; g[3] = t.g[3];
-            // wunet_uph_edges on the values loaded above: the first input of a tile is owed sp[0][c][tile - 1], the last sp[1][c][tile + 1]; row ends nothing
+            // the tile-edge terms loaded above: the first input of a tile is owed sp[0][c][tile - 1], the last sp[1][c][tile + 1]; row ends nothing
             // (selects, not branches around the additions: hipcc sinks a load whose only use is conditional back into the branch)
             const bool first = (l & 127) == 0 && l > 0, last = (l & 127) == 124 && l + 4 < A.L;
             g[0] += first ? t.e0 : 0.0f;
@@ -756,7 +734,8 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
             if (first) gq[0] = g[0];
             if (last) gq[3] = g[3];
         } else if (MODE == A_ENC) {
-            g[0] = t.g[0] + t.e0; g[1] = t.g[1]; g[2] = t.g[2] + t.e1; g[3] = t.g[3];
+            const wunet_f4 ge = wunet_enc_combine(t.g, float2{t.e0, t.e1});
+            g[0] = ge[0]; g[1] = ge[1]; g[2] = ge[2]; g[3] = ge[3];
         } else {
             // transpose of ATen's upsample_linear1d: output j contributes l0 to input i0(j) and l1 to i1(j), with the
             // fp32-computed coordinates; inputs l..l+3 can only be hit by outputs j in [2l-2, 2l+8], walked in
@@ -806,8 +785,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
         wunet_f4 go;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float gv = g[j];
-            if (!(a * z[j] + s > 0.0f)) gv *= WUNET_SLOPE;
+            float gv = wunet_lrelu_bwd(a, s, z[j], g[j]);
             const bool pad = l + j >= A.Lt;                       // row padding: no gradient, no part in the sums or bounds
             if (pad) gv = 0.0f;
             const float zc = pad ? 0.0f : z[j] - mu;
@@ -872,21 +850,18 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
     }
     block_reduce_pass_a(s1, s2, s3, MODE == A_HEAD, mg, mz, red);
     if (FUSE) {
-        // bn_finalize_bwd_kernel's arithmetic on the (float-rounded, as if through part[]) sums, then gz_materialize_kernel's
-        const double t1 = (double)(float)s1, t2 = (double)(float)s2;
-        const double m1 = A.frozen ? 0.0 : t1 / A.count, m2 = A.frozen ? 0.0 : t2 / A.count;
-        const double ar = (double)gam * (double)rstd;
-        const float k1 = (float)ar, k2 = (float)(-ar * m2 * (double)rstd), k3 = (float)(ar * m2 * (double)rstd * (double)mu - ar * m1);
+        // bn_finalize_bwd_kernel's fold on the sums rounded to float (as if through part[]), then gz_materialize_kernel's g_z
+        const BnBwdFold f = bn_bwd_fold(gam, rstd, mu, (double)(float)s1, (double)(float)s2, A.count, A.frozen, 0.0f, 0.0f);
         if (threadIdx.x == 0) {
-            A.dgamma[c] = (float)t2;
-            A.dbeta[c] = (float)t1;
-            A.dbias[c] = A.frozen ? (float)(ar * t1) : 0.0f;
-            A.k1[c] = k1; A.k2[c] = k2; A.k3[c] = k3;
+            A.dgamma[c] = f.dgamma;
+            A.dbeta[c] = f.dbeta;
+            A.dbias[c] = f.dbias;
+            A.k1[c] = f.k1; A.k2[c] = f.k2; A.k3[c] = f.k3;
         }
         if (have) {
             wunet_f4 o;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j] = keep_l + j < A.Lt ? k1 * keep_g[j] + k2 * keep_z[j] + k3 : 0.0f;
+            for (int j = 0; j < 4; ++j) o[j] = keep_l + j < A.Lt ? wunet_gz(f.k1, f.k2, f.k3, keep_g[j], keep_z[j]) : 0.0f;
             wunet_st4(A.gpre + keep_i, o);
         }
         return;
@@ -904,25 +879,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_kernel(PassAArgs A)
     }
 }
 
-// ---------------------------------------------------------------------------- BN backward finalize
-// grid = C.  dgamma = sum g*xhat, dbeta = sum g, and the folded coefficients of
-// g_z = gamma*rstd*(g - mean(g) - xhat*mean(g*xhat)) = k1*g + k2*z + k3.
-// A frozen layer (BatchNorm on the running statistics, wunet_set_bn_frozen; mean / rstd hold running_mean / 1/sqrt(running_var + eps)):
-// y = a z + const, so g_z = a g - k1 = a, k2 = k3 = 0 - and the conv bias gets a sum g (batch statistics cancel it).
-struct BnBwdArgs {
-    const float* part; int rows;
-    const float* gamma; const float* mean; const float* rstd;
-    float* dgamma; float* dbeta;
-    float* dbias;        // conv bias feeding batch-statistics BN: exact zero gradient; frozen: a sum g
-    float* k1; float* k2; float* k3;
-    int C; double count;
-    const float* pmax;   // nullptr or pass A's [rows][C][2] maxima
-    float* bound;        // [C]: |k1| max|g| + |a m2 rstd| max|z - mean| + |a m1|  >=  max |g_z| of the channel
-    const float* e0rows; // nullptr, or the first layer's [rows][C][48] partial sums (pass_a_kernel<.., E0>): its weight gradient is finished here
-    float* dw0;          // [C][15]: dW[c][k] = k1 sum g x + k2 sum z x + k3 sum x
-    int frozen;          // the layer's BatchNorm ran on the running statistics
-};
-
+// BatchNorm-backward finalize of one channel per block from pass A's partial rows (BnBwdArgs, bn_bwd_fold: above pass A)
 static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_kernel(BnBwdArgs A)
 {
     __shared__ double red[5 * WUNET_WAVES];
@@ -943,16 +900,15 @@ static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_kernel(B
         mz = fmaxf(mz, pm.y);
     }
     block_reduce_pass_a(s1, s2, s3, false, mg, mz, red);
+    const BnBwdFold f = bn_bwd_fold(gam, rs, mu, s1, s2, A.count, A.frozen, mg, mz);      // (the sums are valid in every thread)
     if (tid == 0) {
-        const double m1 = A.frozen ? 0.0 : s1 / A.count, m2 = A.frozen ? 0.0 : s2 / A.count;
-        const double a = (double)gam * (double)rs;
-        A.dgamma[c] = (float)s2;
-        A.dbeta[c] = (float)s1;
-        A.dbias[c] = A.frozen ? (float)(a * s1) : 0.0f;
-        A.k1[c] = (float)a;
-        A.k2[c] = (float)(-a * m2 * (double)rs);
-        A.k3[c] = (float)(a * m2 * (double)rs * (double)mu - a * m1);
-        if (A.pmax) A.bound[c] = (float)(fabs(a) * (double)mg + fabs(a * m2 * (double)rs) * (double)mz + fabs(a * m1));
+        A.dgamma[c] = f.dgamma;
+        A.dbeta[c] = f.dbeta;
+        A.dbias[c] = f.dbias;
+        A.k1[c] = f.k1;
+        A.k2[c] = f.k2;
+        A.k3[c] = f.k3;
+        if (A.pmax) A.bound[c] = f.bound;
     }
     if (A.e0rows) {
         // the first layer's weight gradient from the three sums per tap: the rows in order, in double; the coefficients as g_z would have had them
@@ -970,12 +926,7 @@ static __global__ __launch_bounds__(WUNET_THREADS) void bn_finalize_bwd_kernel(B
             e0s[tid] = t;
         }
         __syncthreads();
-        if (tid < 15) {
-            const double m1 = A.frozen ? 0.0 : s1 / A.count, m2 = A.frozen ? 0.0 : s2 / A.count;
-            const double a = (double)gam * (double)rs;
-            const float k1 = (float)a, k2 = (float)(-a * m2 * (double)rs), k3 = (float)(a * m2 * (double)rs * (double)mu - a * m1);
-            A.dw0[c * 15 + tid] = (float)((double)k1 * e0s[tid] + (double)k2 * e0s[15 + tid] + (double)k3 * e0s[30 + tid]);      // (e0s[30 ..]: channel 0's rows)
-        }
+        if (tid < 15) A.dw0[c * 15 + tid] = (float)((double)f.k1 * e0s[tid] + (double)f.k2 * e0s[15 + tid] + (double)f.k3 * e0s[30 + tid]);      // (e0s[30 ..]: channel 0's rows)
     }
 }
 
@@ -1199,8 +1150,8 @@ static __global__ __launch_bounds__(WUNET_THREADS) void gz_materialize_kernel(co
         const float a = k1[c], b = k2[c], d = k3[c];
         const float4 gv = reinterpret_cast<const float4*>(g)[i], zv = reinterpret_cast<const float4*>(z)[i];
         float4 o;
-        o.x = a * gv.x + b * zv.x + d; o.y = a * gv.y + b * zv.y + d;
-        o.z = a * gv.z + b * zv.z + d; o.w = a * gv.w + b * zv.w + d;
+        o.x = wunet_gz(a, b, d, gv.x, zv.x); o.y = wunet_gz(a, b, d, gv.y, zv.y);
+        o.z = wunet_gz(a, b, d, gv.z, zv.z); o.w = wunet_gz(a, b, d, gv.w, zv.w);
         const int l = (int)((i << 2) & (((size_t)1 << logL) - 1));
         if (l + 3 >= Lt) {                                       // row padding: no gradient
             if (l >= Lt) o.x = 0.0f;

@@ -283,14 +283,14 @@ static __global__ __launch_bounds__(WUNET_THREADS) void wgrad_h3_reduce_kernel(W
 // latency + a kernel boundary on the backward's critical path.  Block 0 publishes the results.  The sums run over the rows in order,
 // in double: the same numbers as the tree of the separate kernel to the last bit of the float results.
 // HEAD (the last decoder layer, whose only consumer is the 1x1 head): its g = wh[c] * gh * LeakyReLU'(a z + s) is a function of the
-// one-channel head gradient gh [B][L] (pass_a_kernel<A_HEAD>'s arithmetic, bit for bit) - recomputed here from gh (1 / C of the
+// one-channel head gradient gh [B][L] (pass_a_kernel<A_HEAD>'s arithmetic, WRITTEN OUT A SECOND TIME in phase 2 below) - recomputed here from gh (1 / C of the
 // bytes) instead of written by pass A and read back: the largest layer's g (100 MB at batch 64) never exists.
 // ENC (an encoder layer whose data gradients are whole tensors): its g = (dXdec[b, coff+c, l] + (l even ? dXenc[b, c, l/2] : 0)) * LeakyReLU'
-// (pass_a_kernel<A_ENC>'s arithmetic, bit for bit) is recomputed here from the two data gradients (6 bytes per value read instead of
+// (pass_a_kernel<A_ENC>'s arithmetic - wunet_enc_combine, wunet_lrelu_bwd - written out a second time in phase 2 below; the loads are the shared ones) is recomputed here from the two data gradients (6 bytes per value read instead of
 // the 4 of g) so that pass A does not WRITE g (4 bytes per value; a written byte costs 1.4 x a read one on this part).
 struct GzHeadArgs {
     const float* gh; const float* wh; const float* a; const float* s;      // HEAD (gh != nullptr); a, s also ENC and UPH
-    const float* gd; const float* ge; int Cg0, coff;                        // ENC (gd != nullptr): dXdec [B][Cg0][L], dXenc [B][C][L/2]
+    WunetEncSrc enc;                                                        // ENC: dXdec's skip rows, dXenc
     const float* gq;                                                        // UPH (gq != nullptr): dXh [B][C][L], completed by pass_a_kernel<A_UPH>
 };
 #define WUNET_GZ_FIN_LOADS 1536   // (sweep 1152 / 2048 / 3100 / all: 5.41 / 5.42 / 5.46 / 5.50 ms per step - beyond the 512-sample level the prologue costs more than the launch)
@@ -331,16 +331,12 @@ __global__ __launch_bounds__(WUNET_THREADS) void gz_split_h3_kernel(const float*
                     }
                 }
             }
-            const double m1 = F.frozen ? 0.0 : s1 / F.count, m2 = F.frozen ? 0.0 : s2 / F.count;
-            const double a = (double)gam_ * (double)rs_;
-            const float k1c = (float)a, k2c = (float)(-a * m2 * (double)rs_);
-            const float k3c = (float)(a * m2 * (double)rs_ * (double)mu_ - a * m1);
-            const float bc = (float)(fabs(a) * (double)mg + fabs(a * m2 * (double)rs_) * (double)mz + fabs(a * m1));
-            ks[c] = k1c; ks[WUNET_GZ_FIN_C + c] = k2c; ks[2 * WUNET_GZ_FIN_C + c] = k3c;
-            m = fmaxf(m, bc);
+            const BnBwdFold f = bn_bwd_fold(gam_, rs_, mu_, s1, s2, F.count, F.frozen, mg, mz);
+            ks[c] = f.k1; ks[WUNET_GZ_FIN_C + c] = f.k2; ks[2 * WUNET_GZ_FIN_C + c] = f.k3;
+            m = fmaxf(m, f.bound);
             if (blockIdx.x == 0) {
-                F.dgamma[c] = (float)s2; F.dbeta[c] = (float)s1; F.dbias[c] = F.frozen ? (float)(a * s1) : 0.0f;
-                F.k1[c] = k1c; F.k2[c] = k2c; F.k3[c] = k3c; F.bound[c] = bc;
+                F.dgamma[c] = f.dgamma; F.dbeta[c] = f.dbeta; F.dbias[c] = f.dbias;
+                F.k1[c] = f.k1; F.k2[c] = f.k2; F.k3[c] = f.k3; F.bound[c] = f.bound;
             }
         }
 #pragma unroll
@@ -398,8 +394,8 @@ __global__ __launch_bounds__(WUNET_THREADS) void gz_split_h3_kernel(const float*
                 if (GM == GZ_G) gv[e] = wunet_ld4(g + o);
                 else if (GM == GZ_UPH) gv[e] = wunet_ld4(H.gq + o);        // (tile-edge values completed in place by pass_a_kernel<A_UPH>)
                 else if (GM == GZ_ENC) {
-                    gv[e] = wunet_ld4(H.gd + ((size_t)b * H.Cg0 + H.coff + cc) * L + 4 * l4);
-                    e2[e] = *reinterpret_cast<const float2*>(H.ge + ((size_t)b * C + cc) * (L >> 1) + 2 * l4);
+                    gv[e] = wunet_enc_skip4(H.enc, b, cc, L, 4 * l4);
+                    e2[e] = wunet_enc_half2(H.enc, b, C, cc, L, 4 * l4);
                 } else if (GM == GZ_HEAD) whv[e] = H.wh[cc];
             }
             // the eight channels' constants as 16-byte loads (k1 .. k3 and the BatchNorm scale / shift of the recompute modes: five arrays whose
@@ -422,7 +418,12 @@ __global__ __launch_bounds__(WUNET_THREADS) void gz_split_h3_kernel(const float*
 #pragma unroll
                 for (int e = 0; e < 8; ++e) hA[e] = hS[e] = 0.0f;
             }
-            // ---- phase 2: g (the recompute modes: pass_a_kernel's arithmetic in its order), g_z, the split
+            // ---- phase 2: g (the recompute modes: pass_a_kernel's arithmetic in its order), g_z, the split.  Written out, not through
+            // wunet_enc_combine / wunet_lrelu_bwd / wunet_gz, and the kernel keeps its loose parameters: hipcc vectorises and contracts this
+            // loop by its exact shape - through the helpers, or with the arguments in one struct, packed multiply-adds came apart and formed
+            // elsewhere and the gradients moved in the last bit on the hardware.  This is a SECOND, hand-written copy of the helpers' arithmetic:
+            // the recompute modes rely on it giving pass A's g and the other kernels' g_z bit for bit, so an edit to wunet_enc_combine,
+            // wunet_lrelu_bwd or wunet_gz (wunet_dev.h) has to be made here too (guard: test_backward_elementwise_switches_change_no_bit).
             wunet_f4 v[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {

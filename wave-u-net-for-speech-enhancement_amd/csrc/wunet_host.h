@@ -77,12 +77,14 @@ enum { LK_RAW = 0, LK_DECIM = 1, LK_UPCAT = 2 };
 //   WUNET_NO_SKIP_FUSE     the decoder-side operand pass reads the skip itself (eval mode's path)             test hook
 //   WUNET_NO_EVOP          no conv writes the next encoder layer's operand                                    A/B switch
 //   WUNET_NO_E0            the first layer's weight gradient as a GEMM of its own                             A/B switch
+//   WUNET_NO_ENC_GZ        the encoder layers' g written by pass A and read back, not recomputed by gz_split_h3_kernel  A/B switch
+//   WUNET_PA_SWAP=0        pass A on the (channels, pieces) grid of rounds 1 - 3                              A/B switch
 //   WUNET_UPT=0            no data gradient stores its upsampled half at the producer's resolution            A/B switch
 //   WUNET_WGRAD_XCD=0      wgrad_h3d_kernel keeps its 3-D grid                                                A/B switch
 //   WUNET_A_CAP=<n>        most pieces of a channel in the gradient-assembly pass (1 .. 256, default 128)     measurement hook
 struct PlanSwitches {
     const char *order_f, *order_d, *order_w;      // nullptr: the planner's own order (the text lives in the environment: use it within the call)
-    bool no_split, old_split, ktail_off, no_skip_fuse, no_evop, no_e0, upt_off, wgrad_xcd_off;
+    bool no_split, old_split, ktail_off, no_skip_fuse, no_evop, no_e0, no_enc_gz, pa_swap_off, upt_off, wgrad_xcd_off;
     int sps, h3u_eval, h3u_train, a_cap;          // sps < 1: the planner's rule
 };
 PlanSwitches read_plan_switches();
@@ -153,6 +155,8 @@ struct wunet_ctx {
     size_t bmax_off, bound_off;   // pass A maxima / per-channel |g_z| bounds (fp16-split scale)
     size_t bpart_off, wgpart_off, wpkb_off, gh_off, hpart_off, hpart2_off, e0part_off, total_floats;
     int e0 = 1;                   // the first layer's weight gradient from pass A's sums (pass_a_kernel<.., E0>); WUNET_NO_E0=1, read when the context is planned: off
+    int enc_gz = 1;               // gz_split_h3_kernel recomputes the encoder layers' g (GZ_ENC) instead of reading it back; WUNET_NO_ENC_GZ=1, likewise: off
+    int pa_swap = 1;              // pass A on the (pieces, channels) grid; WUNET_PA_SWAP=0, likewise: off
     int head_blocks;
     int h3 = 0;                   // fp16-split GEMMs: 0 off, 1 where the planner wants them, 2 wherever they can run
     int bf = 0;                   // the split kernels run their bf16 mode (one bf16 word per operand value, one MFMA pass)

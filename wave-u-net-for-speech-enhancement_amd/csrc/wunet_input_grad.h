@@ -4,7 +4,7 @@
 // g_z0 = k1 g + k2 z + k3 is encoder.0's gradient at its conv output.  The first layer's backward leaves it in one of three forms
 // (wunet_backward.cpp: first_layer_gz_source), a compile-time mode here like gz_split_h3_kernel's GZ_* modes:
 //   IG_ENC  nothing stored (pass_a_kernel<.., E0>): g is rebuilt from the consumers' data gradients - the skip rows of the last decoder
-//           layer plus encoder.1's, zero-stuffed onto the even positions, times LeakyReLU' (pass_a_kernel<A_ENC>'s arithmetic) - then k1..k3
+//           layer plus encoder.1's, zero-stuffed onto the even positions, times LeakyReLU' (WunetEncSrc, wunet_lrelu_bwd: what pass_a_kernel<A_ENC> calls) - then k1..k3
 //   IG_G    g stored (the weight gradient forms g_z while it stages its chunks): k1..k3 applied here
 //   IG_GZ   g_z stored (gz_materialize_kernel in place, or pass A's fused finalize)
 // One block: WUNET_IG_TP positions of one row, four per thread.  WUNET_IG_CC channels at a time are formed into LDS with the 7-sample
@@ -24,8 +24,7 @@ struct InputGradArgs {
     const float* k1; const float* k2; const float* k3;     // its BatchNorm-backward coefficients (frozen: k2 = k3 = 0)
     const float* g;                  // IG_G: g [B][C][L];  IG_GZ: g_z [B][C][L]
     const float* a; const float* s;  // IG_ENC: the layer's BatchNorm scale / shift (LeakyReLU' from a z + s)
-    const float* gd; int Cg0, coff;  // IG_ENC: the last decoder layer's data gradient [B][Cg0][L], the skip rows from channel coff
-    const float* ge;                 // IG_ENC: encoder.1's data gradient [B][C][L/2]
+    WunetEncSrc enc;                 // IG_ENC: the skip rows of the last decoder layer's data gradient, encoder.1's data gradient
     const float* w0;                 // encoder.0's conv weight [C][1][15]
     const float* wh;                 // head weight [1][C+1][1]: wh[C] multiplies the input
     const float* gh;                 // [B][L] head gradient before its 1x1 conv
@@ -53,22 +52,14 @@ __global__ __launch_bounds__(WUNET_THREADS) void input_grad_kernel(InputGradArgs
             gz = wunet_ld4(A.g + i);
         } else {
             const wunet_f4 z = wunet_ld4(A.z + i);
-            float g[4];
-            if (MODE == IG_G) {
-                const wunet_f4 gv = wunet_ld4(A.g + i);
-                g[0] = gv[0]; g[1] = gv[1]; g[2] = gv[2]; g[3] = gv[3];
-            } else {
-                const wunet_f4 d = wunet_ld4(A.gd + ((size_t)b * A.Cg0 + A.coff + c) * A.L + pc);
-                const float2 e = *reinterpret_cast<const float2*>(A.ge + ((size_t)b * A.C + c) * (A.L >> 1) + (pc >> 1));
-                g[0] = d[0] + e.x; g[1] = d[1]; g[2] = d[2] + e.y; g[3] = d[3];
-                const float a = A.a[c], s = A.s[c];
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (!(a * z[j] + s > 0.0f)) g[j] *= WUNET_SLOPE;
+            wunet_f4 g;
+            if (MODE == IG_G) g = wunet_ld4(A.g + i);
+            else {
+                const wunet_f4 d = wunet_enc_skip4(A.enc, b, c, A.L, pc);
+                const float2 e = wunet_enc_half2(A.enc, b, A.C, c, A.L, pc);
+                g = wunet_lrelu_bwd(A.a[c], A.s[c], z, wunet_enc_combine(d, e));
             }
-            const float k1 = A.k1[c], k2 = A.k2[c], k3 = A.k3[c];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) gz[j] = k1 * g[j] + k2 * z[j] + k3;
+            gz = wunet_gz(A.k1[c], A.k2[c], A.k3[c], g, z);
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) gz[j] = (ok && p + j < A.Lt) ? gz[j] : 0.0f;      // (zero padding of the conv; no gradient in the row padding)

@@ -322,7 +322,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void wgrad_mfma_kernel(WgradArgs A)
                         const wunet_f4 zv = wunet_sel4(b_ < A.B && co0 + (tid >> 4) + 16 * it < A.Cout, zreg[it]);
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            const float v = k1v[it] * gv[j] + k2v[it] * zv[j] + k3v[it];
+                            const float v = wunet_gz(k1v[it], k2v[it], k3v[it], gv[j], zv[j]);
                             gv[j] = l_ + j < A.Lt ? v : 0.0f;
                         }
                     }

@@ -223,6 +223,7 @@ PlanSwitches read_plan_switches()
         else if (got == 1) sw.h3u_eval = sw.h3u_train = a;      // one number: both thresholds (WUNET_H3U=0 turns the kernel off everywhere)
     }
     sw.no_skip_fuse = getenv("WUNET_NO_SKIP_FUSE") != nullptr; sw.no_evop = getenv("WUNET_NO_EVOP") != nullptr; sw.no_e0 = getenv("WUNET_NO_E0") != nullptr;
+    sw.no_enc_gz = getenv("WUNET_NO_ENC_GZ") != nullptr; sw.pa_swap_off = is_zero("WUNET_PA_SWAP");
     sw.upt_off = is_zero("WUNET_UPT"); sw.wgrad_xcd_off = is_zero("WUNET_WGRAD_XCD");
     sw.a_cap = getenv("WUNET_A_CAP") ? atoi(getenv("WUNET_A_CAP")) : 128;
     return sw;
@@ -477,6 +478,8 @@ static void decide_layers(wunet_ctx* c, const PlanSwitches& sw)
     const long long hb = ((long long)B * c->T) / 2048;
     c->head_blocks = (int)(hb < 1 ? 1 : (hb > 1024 ? 1024 : hb));
     c->e0 = sw.no_e0 ? 0 : 1;
+    c->enc_gz = sw.no_enc_gz ? 0 : 1;
+    c->pa_swap = sw.pa_swap_off ? 0 : 1;
 }
 
 // The hand-offs between layers, one predicate over the two layers involved each.

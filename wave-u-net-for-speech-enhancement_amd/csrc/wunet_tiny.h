@@ -50,8 +50,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_scalar_kernel(PassAArgs 
         if (MODE == A_HEAD) {
             g = A.g1[c] * A.g0[(size_t)b * A.L + l];
         } else if (MODE == A_ENC) {
-            g = A.g0[((size_t)b * A.Cg0 + A.coff + c) * A.L + l];
-            if ((l & 1) == 0) g += A.g1[((size_t)b * A.C + c) * (A.L >> 1) + (l >> 1)];
+            g = wunet_enc_g1(A.enc, b, A.C, c, A.L, l);
         } else {
             const int Lo = 2 * A.L;
             const float* row = A.g0 + ((size_t)b * A.Cg0 + c) * Lo;
@@ -64,7 +63,7 @@ __global__ __launch_bounds__(WUNET_THREADS) void pass_a_scalar_kernel(PassAArgs 
                 }
             }
         }
-        if (!(a * z + s > 0.0f)) g *= WUNET_SLOPE;
+        g = wunet_lrelu_bwd(a, s, z, g);
         A.gpre[zi] = g;
         s1 += (double)g;
         s2 += (double)(g * ((z - mu) * rstd));
@@ -82,7 +81,7 @@ static __global__ __launch_bounds__(WUNET_THREADS) void gz_scalar_kernel(const f
 {
     for (size_t i = (size_t)blockIdx.x * WUNET_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * WUNET_THREADS) {
         const int c = (int)((i >> logL) % (size_t)C);
-        gz[i] = k1[c] * g[i] + k2[c] * z[i] + k3[c];
+        gz[i] = wunet_gz(k1[c], k2[c], k3[c], g[i], z[i]);
     }
 }
 
