@@ -397,6 +397,17 @@ int wunet_op_conv1d_dgrad_split(const float* gz, const float* w, float* dx,
 int wunet_op_conv1d_wgrad_split(const float* gz, const float* x, float* dw,
                                 int B, int Cin, int Cout, int L, int K, void* stream);
 
+/* (tests / tools) The same three ops on the bf16 instantiations of those kernels - the arithmetic of wunet_set_h3(ctx, 3 | 4): one bf16 word per
+ * operand value (round to nearest even of the scaled value), one MFMA pass, the planner's bf16 tiling and split-K plan for the geometry.  The
+ * argument lists and shape conditions of the _split entry points.  The result is the conv of the bf16-rounded operands up to fp32
+ * accumulation (power-of-two scales, exact products). */
+int wunet_op_conv1d_bf16(const float* x, const float* w, const float* bias, float* z,
+                         int B, int Cin, int Cout, int L, int K, void* stream);
+int wunet_op_conv1d_dgrad_bf16(const float* gz, const float* w, float* dx,
+                               int B, int Cin, int Cout, int L, int K, void* stream);
+int wunet_op_conv1d_wgrad_bf16(const float* gz, const float* x, float* dw,
+                               int B, int Cin, int Cout, int L, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ EXPORTS = [
     "wunet_loss_backward", "wunet_layer_info", "wunet_num_conv_layers", "wunet_op_conv1d",
     "wunet_op_conv1d_dgrad", "wunet_op_conv1d_wgrad", "wunet_profile_enable", "wunet_profile_collect",
     "wunet_adam_step", "wunet_set_h3", "wunet_op_conv1d_split", "wunet_op_conv1d_dgrad_split", "wunet_op_conv1d_wgrad_split",
+    "wunet_op_conv1d_bf16", "wunet_op_conv1d_dgrad_bf16", "wunet_op_conv1d_wgrad_bf16",
     "wunet_backward_range_async", "wunet_backward_join", "wunet_debug_set_conv_trace", "wunet_crop_windows",
     "wunet_comm_unique_id", "wunet_comm_create", "wunet_comm_allreduce_sum", "wunet_comm_world", "wunet_comm_destroy",
     "wunet_debug_stamps", "wunet_set_bn_frozen", "wunet_backward_input", "wunet_adam_scratch_bytes", "wunet_adam_step_ex",
@@ -84,9 +85,10 @@ def declare(lib):
         lib.wunet_stoi_loss_backward.argtypes = [_vp, _vp, _sz, _sz, _i, _vp, _vp, _vp, _vp]
     lib.wunet_layer_info.argtypes = [_vp, _i, ctypes.POINTER(_sz), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     lib.wunet_num_conv_layers.argtypes = [_vp]
-    for name in ("wunet_op_conv1d", "wunet_op_conv1d_split"):
+    for name in ("wunet_op_conv1d", "wunet_op_conv1d_split", "wunet_op_conv1d_bf16"):
         getattr(lib, name).argtypes = [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
-    for name in ("wunet_op_conv1d_dgrad", "wunet_op_conv1d_wgrad", "wunet_op_conv1d_dgrad_split", "wunet_op_conv1d_wgrad_split"):
+    for name in ("wunet_op_conv1d_dgrad", "wunet_op_conv1d_wgrad", "wunet_op_conv1d_dgrad_split", "wunet_op_conv1d_wgrad_split",
+                 "wunet_op_conv1d_dgrad_bf16", "wunet_op_conv1d_wgrad_bf16"):
         getattr(lib, name).argtypes = [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]
     lib.wunet_adam_step.argtypes = [_i, _vp, _vp, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                     ctypes.c_double, ctypes.c_longlong, ctypes.c_double, _vp, _vp, _vp]

@@ -814,7 +814,8 @@ int wunet_op_conv1d_wgrad(const float* gz, const float* x, float* dw, int B, int
 }
 
 // ---- single-op entry points of the fp16-split kernels: the same planner, operand passes and GEMM kernels the network
-//      uses for that geometry (scales from the measured maxima, as in eval mode)
+//      uses for that geometry (scales from the measured maxima, as in eval mode).  bf: their bf16 mode (wunet_set_h3(ctx, 3 | 4):
+//      one bf16 word per operand value in the hi plane, the lo plane unused, one MFMA pass), the wunet_op_*_bf16 entry points
 namespace {
 struct DevBuf {
     void* p = nullptr;
@@ -835,7 +836,8 @@ int op_split_check(int B, int Cin, int Cout, int L, int K, bool backward)
 }
 
 // fp32 [B][C][L] -> scaled hi / lo in the split layout; slot: 8 floats, [0..1] receive {scale, 1/scale}, [4] the measured max
-// (one allocation: hi plane | lo plane | 64 zero bytes - the layout conv_h3d_kernel's DMA addressing wants, launch_conv_h3)
+// (one allocation: hi plane | lo plane | 64 zero bytes - the layout conv_h3d_kernel's DMA addressing wants, launch_conv_h3; the
+// bf16 mode writes the hi plane only)
 struct SplitBuf {
     DevBuf buf;
     size_t plane = 0;
@@ -843,7 +845,7 @@ struct SplitBuf {
     wunet_half* l() const { return reinterpret_cast<wunet_half*>(static_cast<char*>(buf.p) + plane); }
     const void* zpad() const { return static_cast<char*>(buf.p) + 2 * plane; }
 };
-int op_split_operand(const float* x, int B, int C, int L, SplitBuf& sb, float* slot, const float* ones, const float* zeros, hipStream_t st)
+int op_split_operand(const float* x, int B, int C, int L, SplitBuf& sb, float* slot, const float* ones, const float* zeros, int bf, hipStream_t st)
 {
     const int c8 = (C + 7) / 8;
     sb.plane = (size_t)B * c8 * L * 16;
@@ -852,13 +854,13 @@ int op_split_operand(const float* x, int B, int C, int L, SplitBuf& sb, float* s
     hipMemsetAsync(slot, 0, WUNET_SLOT_FLOATS * sizeof(float), st);
     const size_t n4 = (size_t)B * C * L / 4;
     WUNET_LAUNCH(act_max_kernel, dim3(capped_blocks(n4, WUNET_THREADS * 4, 2048)), dim3(WUNET_THREADS), 0, st, x, ones, zeros, C, ilog2(L), n4, slot + 4);
-    return launch_split(x, sb.h(), sb.l(), nullptr, slot + 4, nullptr, slot, B, C, L, st);
+    return launch_split(x, sb.h(), sb.l(), nullptr, slot + 4, nullptr, slot, B, C, L, st, bf);
 }
 
 int op_conv_split_common(const float* x, const float* w, const float* bias, float* out, int B, int kch, int rows, int Cout, int Cin,
-                         int L, int K, int transposed, hipStream_t st)
+                         int L, int K, int transposed, int bf, hipStream_t st)
 {
-    const H3ConvPlan p = plan_h3_conv(B, L, rows, kch, K, transposed != 0, 0, read_plan_switches());
+    const H3ConvPlan p = plan_h3_conv(B, L, rows, kch, K, transposed != 0, bf, read_plan_switches());
     SplitBuf xs;
     DevBuf wpk, misc, part;
     const size_t wh_halfs = (size_t)p.mtp * p.nch * K * 512, nout = (size_t)B * rows * L;
@@ -871,7 +873,7 @@ int op_conv_split_common(const float* x, const float* w, const float* bias, floa
     WUNET_LAUNCH(fill_kernel, dim3(4), dim3(WUNET_THREADS), 0, st, oz + kch, (size_t)kch, 0.0f);
     wunet_half* const whp = wpk.h();
     wunet_half* const wlp = wpk.h() + wh_halfs;
-    int rc = op_split_operand(x, B, kch, L, xs, xslot, oz, oz + kch, st);
+    int rc = op_split_operand(x, B, kch, L, xs, xslot, oz, oz + kch, bf, st);
     if (rc) return rc;
     {
         ScaleTable T{};
@@ -882,13 +884,13 @@ int op_conv_split_common(const float* x, const float* w, const float* bias, floa
         PackH3Desc& d = tab.d[0];
         d.w = w; d.hi = whp; d.lo = wlp; d.Cout = Cout; d.Cin = Cin; d.taps = K; d.rows = rows; d.kch = kch; d.mtiles = p.mtp; d.nch = p.nch;
         d.ntt = p.ntt; d.nfull = ((kch + 7) / 8) / 4; d.ns = h3_stage_count(kch, K, p.ntt);
-        d.transposed = transposed; d.wmax = wmax; d.wsc = wslot + 2;
+        d.transposed = transposed; d.wmax = wmax; d.wsc = wslot + 2; d.bf = bf;
         WUNET_LAUNCH(pack_h3_kernel, dim3(64, 1), dim3(WUNET_THREADS), 0, st, tab);
     }
     const bool split = p.ksplit > 1;
     ConvH3Launch h{};
     h.taps = K; h.mrep = p.mrep; h.mtiles_p = p.mtp; h.sps = p.sps; h.nch = p.nch; h.ntt = p.ntt;
-    h.B = B; h.rows = rows; h.kch = kch; h.L = L;
+    h.B = B; h.rows = rows; h.kch = kch; h.L = L; h.bf = bf;
     h.xh = xs.h(); h.xl = xs.l(); h.zpad = xs.zpad(); h.wh = whp; h.wl = wlp;
     h.bias = split ? nullptr : bias; h.sc = xslot; h.sc2 = wslot + 2; h.out = split ? part.f() : out;
     rc = launch_conv_h3(h, st);
@@ -896,34 +898,23 @@ int op_conv_split_common(const float* x, const float* w, const float* bias, floa
         const unsigned blocks = capped_blocks(nout, WUNET_THREADS, 2048);
         const float* partp = part.f();
         const int ks = p.ksplit;
+        char pname[48];
+        snprintf(pname, sizeof pname, "split_sum_kernel<%d>", ks);          // (profiler: the tests read the split count off the name)
+        prof_begin(st, pname, 0.0, 4.0 * (ks + 1.0) * nout);
         WUNET_LAUNCH(split_sum_kernel, dim3(blocks), dim3(WUNET_THREADS), 0, st, partp, ks, nout, out, bias, rows, ilog2(L));
+        prof_end(st);
     }
     hipStreamSynchronize(st);
     if (rc) return rc;
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
 }
-}  // namespace
 
-int wunet_op_conv1d_split(const float* x, const float* w, const float* bias, float* z, int B, int Cin, int Cout, int L, int K, void* stream)
+int op_wgrad_split_common(const float* gz, const float* x, float* dw, int B, int Cin, int Cout, int L, int K, int bf, hipStream_t st)
 {
-    if (op_split_check(B, Cin, Cout, L, K, false)) return WUNET_E_ARG;
-    return op_conv_split_common(x, w, bias, z, B, Cin, Cout, Cout, Cin, L, K, 0, (hipStream_t)stream);
-}
-
-int wunet_op_conv1d_dgrad_split(const float* gz, const float* w, float* dx, int B, int Cin, int Cout, int L, int K, void* stream)
-{
-    if (op_split_check(B, Cin, Cout, L, K, true)) return WUNET_E_ARG;
-    return op_conv_split_common(gz, w, nullptr, dx, B, Cout, Cin, Cout, Cin, L, K, 1, (hipStream_t)stream);
-}
-
-int wunet_op_conv1d_wgrad_split(const float* gz, const float* x, float* dw, int B, int Cin, int Cout, int L, int K, void* stream)
-{
-    if (op_split_check(B, Cin, Cout, L, K, true)) return WUNET_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
     LayerGeom l{};
     l.cin = Cin; l.cout = Cout; l.taps = K; l.L = L; l.logL = ilog2(L);
-    const H3WgradPlan w = plan_h3_wgrad(B, L, Cin, Cout, K, 0, read_plan_switches());
+    const H3WgradPlan w = plan_h3_wgrad(B, L, Cin, Cout, K, bf, read_plan_switches());
     SplitBuf xs, gs;
     DevBuf misc, part;
     const int cmax = Cin > Cout ? Cin : Cout;
@@ -933,9 +924,9 @@ int wunet_op_conv1d_wgrad_split(const float* gz, const float* x, float* dw, int 
     float* gslot = misc.f(), *xslot = misc.f() + 8, *oz = misc.f() + 16;
     WUNET_LAUNCH(fill_kernel, dim3(4), dim3(WUNET_THREADS), 0, st, oz, (size_t)cmax, 1.0f);
     WUNET_LAUNCH(fill_kernel, dim3(4), dim3(WUNET_THREADS), 0, st, oz + cmax, (size_t)cmax, 0.0f);
-    int rc = op_split_operand(gz, B, Cout, L, gs, gslot, oz, oz + cmax, st);
-    if (!rc) rc = op_split_operand(x, B, Cin, L, xs, xslot, oz, oz + cmax, st);
-    if (!rc) rc = launch_wgrad_h3(l, w, xs.h(), xs.l(), gs.h(), gs.l(), gslot, xslot, part.f(), B, st);
+    int rc = op_split_operand(gz, B, Cout, L, gs, gslot, oz, oz + cmax, bf, st);
+    if (!rc) rc = op_split_operand(x, B, Cin, L, xs, xslot, oz, oz + cmax, bf, st);
+    if (!rc) rc = launch_wgrad_h3(l, w, xs.h(), xs.l(), gs.h(), gs.l(), gslot, xslot, part.f(), B, st, bf);
     if (!rc) {
         WgradH3ReduceArgs ra{};
         ra.part = part.f(); ra.part_stride = h3w_part_stride(l, w); ra.splits = w.ksplit; ra.dw = dw;
@@ -947,6 +938,43 @@ int wunet_op_conv1d_wgrad_split(const float* gz, const float* x, float* dw, int 
     if (rc) return rc;
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
+}
+}  // namespace
+
+int wunet_op_conv1d_split(const float* x, const float* w, const float* bias, float* z, int B, int Cin, int Cout, int L, int K, void* stream)
+{
+    if (op_split_check(B, Cin, Cout, L, K, false)) return WUNET_E_ARG;
+    return op_conv_split_common(x, w, bias, z, B, Cin, Cout, Cout, Cin, L, K, 0, 0, (hipStream_t)stream);
+}
+
+int wunet_op_conv1d_dgrad_split(const float* gz, const float* w, float* dx, int B, int Cin, int Cout, int L, int K, void* stream)
+{
+    if (op_split_check(B, Cin, Cout, L, K, true)) return WUNET_E_ARG;
+    return op_conv_split_common(gz, w, nullptr, dx, B, Cout, Cin, Cout, Cin, L, K, 1, 0, (hipStream_t)stream);
+}
+
+int wunet_op_conv1d_wgrad_split(const float* gz, const float* x, float* dw, int B, int Cin, int Cout, int L, int K, void* stream)
+{
+    if (op_split_check(B, Cin, Cout, L, K, true)) return WUNET_E_ARG;
+    return op_wgrad_split_common(gz, x, dw, B, Cin, Cout, L, K, 0, (hipStream_t)stream);
+}
+
+int wunet_op_conv1d_bf16(const float* x, const float* w, const float* bias, float* z, int B, int Cin, int Cout, int L, int K, void* stream)
+{
+    if (op_split_check(B, Cin, Cout, L, K, false)) return WUNET_E_ARG;
+    return op_conv_split_common(x, w, bias, z, B, Cin, Cout, Cout, Cin, L, K, 0, 1, (hipStream_t)stream);
+}
+
+int wunet_op_conv1d_dgrad_bf16(const float* gz, const float* w, float* dx, int B, int Cin, int Cout, int L, int K, void* stream)
+{
+    if (op_split_check(B, Cin, Cout, L, K, true)) return WUNET_E_ARG;
+    return op_conv_split_common(gz, w, nullptr, dx, B, Cout, Cin, Cout, Cin, L, K, 1, 1, (hipStream_t)stream);
+}
+
+int wunet_op_conv1d_wgrad_bf16(const float* gz, const float* x, float* dw, int B, int Cin, int Cout, int L, int K, void* stream)
+{
+    if (op_split_check(B, Cin, Cout, L, K, true)) return WUNET_E_ARG;
+    return op_wgrad_split_common(gz, x, dw, B, Cin, Cout, L, K, 1, (hipStream_t)stream);
 }
 
 }  // extern "C"
