@@ -113,12 +113,12 @@ BwdLayerPlan bwd_layer_plan(const wunet_ctx* c, int i)
         q.pa_mode = A_UPH; q.pa_name = "pass_a_kernel<UPH>"; q.g_src_bytes = 4.0; q.gz_mode = GZ_UPH;
         q.stores_g = false;
     } else if (i >= n) {
-        q.pa_mode = A_UP; q.pa_name = "pass_a_kernel<UP>"; q.g_src_bytes = 8.0; q.gz_mode = GZ_G;
+        q.pa_mode = A_UP; q.pa_name = q.tiny ? "pass_a_scalar_kernel<UP>" : "pass_a_kernel<UP>"; q.g_src_bytes = 8.0; q.gz_mode = GZ_G;
     } else {
         // an encoder layer on the split kernels whose two data gradients are whole tensors: g is recomputed by gz_split_h3_kernel (ENC
         // mode) from them instead of written here and read back (WUNET_NO_ENC_GZ=1: A/B switch)
         q.g1_split = dx_stays_split(c, i + 1);
-        q.pa_mode = A_ENC; q.pa_name = q.e0 ? "pass_a_kernel<ENC, e0>" : "pass_a_kernel<ENC>"; q.g_src_bytes = 6.0; q.gz_mode = GZ_ENC;
+        q.pa_mode = A_ENC; q.pa_name = q.e0 ? "pass_a_kernel<ENC, e0>" : q.tiny ? "pass_a_scalar_kernel<ENC>" : "pass_a_kernel<ENC>"; q.g_src_bytes = 6.0; q.gz_mode = GZ_ENC;
         q.stores_g = !(c->enc_gz && recompute && !q.g1_split) && !q.e0;
     }
     if (q.stores_g) q.gz_mode = GZ_G;
@@ -279,9 +279,11 @@ int finalize_and_gz(const BwdCall& k, int i, const BwdLayerPlan& q, int fz)
 #undef WUNET_GZ_LAUNCH
         prof_end(st);
     } else if (q.tiny) {
+        prof_begin(st, "gz_scalar_kernel", 0.0, 12.0 * c->B * l.cout * l.L);
         WUNET_LAUNCH(gz_scalar_kernel, dim3((unsigned)((n4 * 4 + WUNET_THREADS - 1) / WUNET_THREADS) + 1), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g),
                      (const float*)(ws + l.z), (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), l.cout, l.logL,
                      (size_t)c->B * l.cout * l.L, ws + l.g);
+        prof_end(st);
     } else if (!q.gz_in_wgrad) {
         WUNET_LAUNCH(gz_materialize_kernel, dim3(capped_blocks(n4, WUNET_THREADS, 8192)), dim3(WUNET_THREADS), 0, st, (const float*)(ws + l.g), (const float*)(ws + l.z),
                      (const float*)(ws + l.k1), (const float*)(ws + l.k2), (const float*)(ws + l.k3), l.cout, l.logL, n4, ws + l.g, l.Lt);   // in place
@@ -360,8 +362,10 @@ int weight_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
     const float* xin = i == 0 ? k.noisy : ws + l.xin;
     const size_t nw = (size_t)l.cout * l.cin * l.taps;
     if (q.tiny) {
+        prof_begin(sd, "tiny_wgrad_kernel", 2.0 * c->B * l.L * nw, 4.0 * c->B * l.L * (l.cout + l.cin));
         WUNET_LAUNCH(tiny_wgrad_kernel, dim3((unsigned)((nw + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, sd,
                      (const float*)(ws + l.g), xin, k.grads[4 * i], c->B, l.cin, l.cout, l.L, l.taps);
+        prof_end(sd);
         WUNET_CHECK_LAUNCH();
         return WUNET_OK;
     }
@@ -392,11 +396,14 @@ int weight_gradient(const BwdCall& k, int i, const BwdLayerPlan& q)
         if (const char* e = getenv("WUNET_REDUCE_SERIAL")) sscanf(e, "%d,%lld", &serial_max, &serial_min_n4);
 #endif
         const size_t n4 = ra.part_stride / 4;
-        if (ra.splits <= serial_max && (long long)n4 >= serial_min_n4) {
+        const bool serial = ra.splits <= serial_max && (long long)n4 >= serial_min_n4;
+        prof_begin(sd, serial ? "wgrad_h3_reduce_serial_kernel" : "wgrad_h3_reduce_kernel", 0.0, 4.0 * ra.part_stride * (ra.splits + 1.0));
+        if (serial) {
             WUNET_LAUNCH(wgrad_h3_reduce_serial_kernel, dim3(capped_blocks(n4, WUNET_THREADS, 4096)), dim3(WUNET_THREADS), 0, sd, ra);
         } else {
             WUNET_LAUNCH(wgrad_h3_reduce_kernel, dim3(capped_blocks(n4, 16, 4096)), dim3(WUNET_THREADS), 0, sd, ra);
         }
+        prof_end(sd);
     } else {
         const unsigned blocks = capped_blocks(nw / 4, 16, 4096);                   // 16 float4 groups of outputs per block
         WUNET_LAUNCH(wgrad_reduce_kernel, dim3(blocks < 1 ? 1 : blocks), dim3(WUNET_THREADS), 0, sd,
