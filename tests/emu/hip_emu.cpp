@@ -1,6 +1,9 @@
 // TEST INFRASTRUCTURE ONLY: fiber scheduler behind hip_emu.h (x86-64 SysV).
 #include "hip_emu.h"
 
+#include <atomic>
+#include <cstdio>
+#include <cstring>
 #include <vector>
 
 namespace emu {
@@ -129,22 +132,38 @@ static void run_block(Worker& w)
     }
 }
 
+// A block's dynamic LDS is exactly the smem_bytes its launch asked for, with kGuard bytes of a fixed pattern right behind them: a kernel
+// whose layout needs more than the host requested damages the pattern, and the launch that did it ends the process with its size
+constexpr size_t kGuard = 256;
+constexpr unsigned char kGuardByte = 0xA5;
+
+static std::atomic<long> g_launches{0};
+long launch_count() { return g_launches; }
+
 void launch(dim3 grid, dim3 block, size_t smem_bytes, const std::function<void()>& body)
 {
     const long nblocks = (long)grid.x * grid.y * grid.z;
+    ++g_launches;
 #pragma omp parallel for schedule(dynamic)
     for (long bi = 0; bi < nblocks; ++bi) {
         Worker& w = worker();
         w.nthreads = (int)block.x;
         w.body = &body;
-        if (w.smem.size() * sizeof(float) < smem_bytes + 64) w.smem.resize(smem_bytes / sizeof(float) + 16);
+        if (w.smem.size() * sizeof(float) < smem_bytes + kGuard + 16) w.smem.resize((smem_bytes + kGuard) / sizeof(float) + 8);
         // 16-byte aligned dynamic LDS base
         uintptr_t base = ((uintptr_t)w.smem.data() + 15) & ~(uintptr_t)15;
         w.blk.dyn_smem = (float*)base;
+        unsigned char* const guard = (unsigned char*)base + smem_bytes;
+        memset(guard, kGuardByte, kGuard);
         w.blk.bdim = block;
         w.blk.gdim = grid;
         w.blk.bidx = dim3((unsigned)(bi % grid.x), (unsigned)((bi / grid.x) % grid.y), (unsigned)(bi / ((long)grid.x * grid.y)));
         run_block(w);
+        for (size_t k = 0; k < kGuard; ++k)
+            if (guard[k] != kGuardByte) {
+                fprintf(stderr, "hip_emu: a block wrote %zu bytes behind the %zu bytes of dynamic LDS its launch requested\n", k, smem_bytes);
+                std::abort();
+            }
     }
 }
 

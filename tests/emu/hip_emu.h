@@ -42,6 +42,7 @@ BlockState& cur_block();
 void block_barrier();
 void wave_barrier();
 void launch(dim3 grid, dim3 block, size_t smem_bytes, const std::function<void()>& body);
+long launch_count();      // launches of this process so far
 }  // namespace emu
 
 #define threadIdx (emu::cur_fiber().tidx)

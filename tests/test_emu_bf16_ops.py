@@ -14,7 +14,7 @@ Plan divergence (the planner does not depend on the device; every case prints th
 of the same geometry side by side, the split-K reduce named by its split count).  The tilings - rows per wave, items per tile, the
 weight-gradient kernel - are the same in all 26 cases; ONE case gets other split counts, B16-288x312-L16-k15 of the 16-level
 geometries: 27 splits forward and 15 in the data gradient against 15 and 14, because one operand plane of the 16-segment tile is
-48 KB of LDS instead of 96 and a CU then holds two blocks of it (h3d_blocks_per_cu), so one round of resident blocks takes twice the
+48 KB of LDS instead of 96 and a CU then holds two blocks of it (wunet_lds.h: ConvH3d::blocks_per_cu), so one round of resident blocks takes twice the
 splits.  The table of tests/split_op_cases.py has no such case (its 16-sample cases have too few K stages to split further).
 bf16_ref.PLAN_DIVERGENCE names the cases; each test holds it to what the planner does."""
 import importlib
@@ -142,7 +142,7 @@ def test_bf16_ops_at_16_level_geometries(case):
 
 
 def test_some_case_plans_differently_in_bf16():
-    """h3d_blocks_per_cu gives the bf16 mode other split-K plans: at least one geometry of this module must run one."""
+    """ConvH3d::blocks_per_cu (wunet_lds.h) gives the bf16 mode other split-K plans: at least one geometry of this module must run one."""
     assert R.PLAN_DIVERGENCE and R.PLAN_DIVERGENCE <= {C.case_id(c) for c in C.CASES + R.DEEP16_CASES}
 
 

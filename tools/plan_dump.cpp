@@ -11,7 +11,8 @@
 // --check prints nothing and asserts per context: the forward segment inside the workspace; every offset, in allotment order,
 // non-decreasing, 64-aligned and below its segment's end; a replanned context equal to a fresh one; skip_from, evop, upt, h3u,
 // h3u_train and h3w only on layers that meet what their readers rely on (fwd_handoffs_sound / upt_handoff_sound, restated from
-// plan fields).  Exit status 1 on a violation.
+// plan fields); for every kernel a layer may run, the bytes of dynamic LDS its launch requests (csrc/wunet_lds.h) times the resident
+// blocks per CU its planner counted on within the CU's LDS.  Exit status 1 on a violation.
 #include "wunet_host.h"
 
 using namespace wunet_host;
@@ -135,8 +136,51 @@ static std::string dump(const wunet_ctx* c, int length, int h3, const char* set)
     return out;
 }
 
-static long g_bad = 0;
+static long g_bad = 0, g_overcounted = 0;
 #define EXPECT(cond, ...) do { if (!(cond)) { ++g_bad; fprintf(stderr, "plan_dump: " __VA_ARGS__); fprintf(stderr, "  [%s]\n", #cond); } } while (0)
+
+// the LDS budget of layer i: per kernel it may run, bytes of one block x blocks per CU the planner assumed <= WUNET_LDS_PER_CU
+static void check_lds(const wunet_ctx* c, int i, const char* what)
+{
+    const LayerPlan& l = c->ly[i];
+    const auto fits = [&](const char* kernel, size_t bytes, int blocks) {
+        EXPECT(bytes * blocks <= WUNET_LDS_PER_CU, "%s: layer %d %s: %d block(s) of %zu bytes of LDS per CU\n", what, i, kernel, blocks, bytes);
+    };
+    const bool bf = c->bf != 0;
+    if (l.L >= 4) {         // the fp32 GEMMs (a level of 1-2 samples runs the scalar kernels)
+        if (!l.h3f && !l.first) fits("conv_mfma_kernel, forward", wunet_lds::conv_mfma(l.taps, l.f.mrep).bytes(wunet_lds::conv_mfma_rowp(l.L, l.f.nrep)), 1);
+        if (!l.h3d && i > 0) fits("conv_mfma_kernel, data gradient", wunet_lds::conv_mfma(l.taps, l.d.mrep).bytes(wunet_lds::conv_mfma_rowp(l.L, l.d.nrep)), 1);
+        if (!l.h3w) fits("wgrad_mfma_kernel", wunet_lds::wgrad_mfma(l.taps, l.w.mrep, l.w.nw, l.w.wsplit != 0).bytes(wunet_lds::wgrad_mfma_rowp(l.taps, l.L)),
+                         wgrad_blocks_per_cu(l.w, l.L, l.taps));
+    }
+    const int nseg = l.L >= 256 ? 1 : 256 / l.L;
+    if (l.h3f) {            // training, and eval with the table of constants where launch_conv_h3 keeps it (EVOP: the same layout)
+        const wunet_lds::ConvH3d y = wunet_lds::conv_h3d(HF(l).mrep, nseg, bf, false);
+        const int er = HF(l).mtp * 16;
+        fits("conv_h3d_kernel, forward", y.bytes(er, 0), y.blocks_per_cu());
+        fits("conv_h3d_kernel, eval forward", y.bytes(er, y.eval_table_fits(er) ? 1 : 0), y.blocks_per_cu());
+        if (l.h3u || l.h3u_train) fits("conv_h3u_kernel", wunet_lds::conv_h3u(HF(l).mrep).bytes((l.cin + 7) / 8, er), 1);
+    }
+    if (l.h3d) {
+        const wunet_lds::ConvH3d y = wunet_lds::conv_h3d(HD(l).mrep, nseg, bf, l.upt != 0);
+        fits("conv_h3d_kernel, data gradient", y.bytes(HD(l).mtp * 16, 0), wunet_lds::conv_h3d(HD(l).mrep, nseg, bf, false).blocks_per_cu());
+    }
+    if (l.h3w) {
+        const H3WgradPlan w = HW(c, l);
+        const int blocks = h3w_blocks_per_cu(l.taps, w.mrep, l.L);
+        if (w.dma) fits(w.db ? "wgrad_h3d_kernel, double buffered" : "wgrad_h3d_kernel", wunet_lds::wgrad_h3d(l.taps, w.mrep, w.db != 0, bf, w.tp).bytes(), blocks);
+        else {
+            // KNOWN over-count, reported and not a violation while plans must stay as they are: plan_h3_wgrad's slots rule counts two
+            // resident blocks of wgrad_h3_kernel with 2 m-tiles (its launch bounds) at every length, but at 5 taps and 16 samples the
+            // halo rows of the chunk's 8 items make the block 83584 bytes, so one fits a CU and the split-K sized for 512 slots takes two
+            // rounds.  Each block is held to the CU's LDS; every other plan is held to the blocks its planner counted on
+            const size_t bytes = wunet_lds::wgrad_h3(l.taps, w.mrep, l.L >= w.tp ? 1 : w.tp / l.L, w.tp, bf).bytes();
+            const bool known = l.taps == 5 && l.L == 16 && w.mrep == 2 && !bf && blocks == 2 && bytes * 2 > WUNET_LDS_PER_CU;
+            if (known) ++g_overcounted;
+            fits("wgrad_h3_kernel", bytes, known ? 1 : blocks);
+        }
+    }
+}
 
 static void check(const wunet_ctx* c, const char* what)
 {
@@ -180,6 +224,7 @@ static void check(const wunet_ctx* c, const char* what)
                    (long long)(w.ksplit - 1) * w.cps < chunks && (!w.dma || l.L >= w.tp), "%s: layer %d split weight gradient unsound\n", what, i);
         }
         if (l.h3d) EXPECT(l.h3f && i > 0, "%s: layer %d data gradient on the split kernels without the forward\n", what, i);
+        check_lds(c, i, what);
     }
 }
 
@@ -229,6 +274,8 @@ int main(int argc, char** argv)
         }
         apply_switches(set, false);
     }
-    fprintf(stderr, "plan_dump: %ld contexts, %ld lines, %ld violations\n", contexts, lines, g_bad);
+    fprintf(stderr, "plan_dump: %ld contexts, %ld lines, %ld violations", contexts, lines, g_bad);
+    if (g_overcounted) fprintf(stderr, " (%ld plans of wgrad_h3_kernel at 5 taps, 16 samples count two blocks per CU where the LDS holds one: known)", g_overcounted);
+    fprintf(stderr, "\n");
     return g_bad ? 1 : 0;
 }

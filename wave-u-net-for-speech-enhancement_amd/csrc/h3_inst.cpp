@@ -4,6 +4,7 @@
 
 #define WUNET_WCASE(T, M, S, P)                                                                            \
     if (taps == T && mrep == M && nseg == S && tp == P) {                                                  \
+        WUNET_LDS_CHECK(wunet_lds::wgrad_h3(T, M, S, P, bf).bytes())                                       \
         if (bf) {                                                                                          \
             if (WUNET_ALLOW_BIG_LDS((wgrad_h3_kernel<T, M, S, P, true>), smem) != 0) return -2;            \
             WUNET_LAUNCH((wgrad_h3_kernel<T, M, S, P, true>), grid, dim3(WUNET_THREADS), smem, st, a);     \
@@ -24,6 +25,7 @@ int wunet_launch_wgrad_h3(const WgradH3Args& a, int taps, int mrep, int nseg, in
 
 #define WUNET_DCASE(T, M, D)                                                                               \
     if (taps == T && mrep == M && db == D) {                                                               \
+        WUNET_LDS_CHECK(wunet_lds::wgrad_h3d(T, M, D, bf, 128).bytes())                                    \
         if (bf) {                                                                                          \
             if (WUNET_ALLOW_BIG_LDS((wgrad_h3d_kernel<T, M, D, true>), smem) != 0) return -2;              \
             WUNET_LAUNCH((wgrad_h3d_kernel<T, M, D, true>), grid, dim3(WUNET_THREADS), smem, st, a);       \

@@ -5,6 +5,7 @@
 #define WUNET_XCASE(T, M, S)                                                                               \
     if (taps == T && mrep == M && nseg == S) {                                                             \
         if (!WUNET_H3D_HAS_TAIL(M, S) && a.NFS != a.NS) return -3;      /* pack with a K tail, kernel without */ \
+        WUNET_LDS_CHECK(wunet_lds::conv_h3d(M, S, bf, false).bytes(a.mblocks * M * 16, a.epi_eval))        \
         if (bf) {                                                                                          \
             if (WUNET_ALLOW_BIG_LDS((conv_h3d_kernel<T, M, S, true>), smem) != 0) return -2;               \
             WUNET_LAUNCH((conv_h3d_kernel<T, M, S, true>), grid, dim3(WUNET_THREADS), smem, st, a);        \
@@ -19,6 +20,7 @@
 #define WUNET_XCASE_EVOP(M)                                                                                \
     if (evop && taps == 15 && mrep == M && nseg == 1 && !bf) {                                             \
         if (!WUNET_H3D_HAS_TAIL(M, 1) && a.NFS != a.NS) return -3;                                         \
+        WUNET_LDS_CHECK(wunet_lds::conv_h3d(M, 1, false, false).bytes(a.mblocks * M * 16, a.epi_eval))     \
         if (WUNET_ALLOW_BIG_LDS((conv_h3d_kernel<15, M, 1, false, true>), smem) != 0) return -2;           \
         WUNET_LAUNCH((conv_h3d_kernel<15, M, 1, false, true>), grid, dim3(WUNET_THREADS), smem, st, a);    \
         return 0;                                                                                          \
@@ -28,6 +30,7 @@
 #define WUNET_XCASE_UPT(M)                                                                                 \
     if (upt && taps == 5 && mrep == M && nseg == 1 && !bf && !evop) {                                      \
         if (!WUNET_H3D_HAS_TAIL(M, 1) && a.NFS != a.NS) return -3;                                         \
+        WUNET_LDS_CHECK(wunet_lds::conv_h3d(M, 1, false, true).bytes(a.mblocks * M * 16, a.epi_eval))      \
         if (WUNET_ALLOW_BIG_LDS((conv_h3d_kernel<5, M, 1, false, false, true>), smem) != 0) return -2;     \
         WUNET_LAUNCH((conv_h3d_kernel<5, M, 1, false, false, true>), grid, dim3(WUNET_THREADS), smem, st, a); \
         return 0;                                                                                          \

@@ -4,6 +4,7 @@
 
 // (the training launches - ConvH3uArgs::oxh set: the loaders copy the operand to HBM - run the COPY instantiation)
 #define WUNET_UCASE(M)                                                                                     \
+    if (mrep == M) WUNET_LDS_CHECK(wunet_lds::conv_h3u(M).bytes(a.C8, a.mblocks * M * 16))                 \
     if (mrep == M && a.oxh != nullptr) {                                                                   \
         if (WUNET_ALLOW_BIG_LDS((conv_h3u_kernel<M, true>), smem) != 0) return -2;                         \
         WUNET_LAUNCH((conv_h3u_kernel<M, true>), grid, dim3(2 * WUNET_THREADS), smem, st, a);              \

@@ -6,6 +6,7 @@
 #define WUNET_CAT(a) WUNET_CAT2(a, )
 #define WUNET_CASE(M, NW_, XIT_, WS_)                                                                             \
     if (mrep == M && nw == NW_ && xit == XIT_ && wsplit == (WS_ ? 1 : 0)) {                                        \
+        WUNET_LDS_CHECK(wunet_lds::wgrad_mfma(WUNET_INST_TAPS, M, NW_, WS_).bytes(a.rowp))                         \
         WUNET_LAUNCH((wgrad_mfma_kernel<WUNET_INST_TAPS, M, NW_, XIT_, WS_>), grid, dim3(WUNET_THREADS), smem, st, a); \
         return 0;                                                                                                  \
     }

@@ -12,6 +12,7 @@
 //   weights      hi / lo arrays  [m-tile][chunk of 32 ch][tap][4 quarters][16 rows][8 ch] halfs.
 #pragma once
 #include "wunet_dev.h"
+#include "wunet_lds.h"
 
 // 16-byte zero page the LDS-DMA pieces that lie outside a tensor are fetched from (halo beyond an item, channel groups beyond C8):
 // one copy per translation unit, in the code object - nothing to allocate or clear per step
@@ -117,23 +118,20 @@ struct WgradH3Args {
 template <int TAPS, int M_REP, int NSEG, int TP, bool BF = false>
 __global__ __launch_bounds__(WUNET_THREADS, (M_REP <= 2 ? 2 : 1)) void wgrad_h3_kernel(WgradH3Args A)
 {
-    constexpr int GP = TP + 4;                      // TP positions per chunk; plane stride (pieces) of the g_z image, 4 mod 16
-    constexpr int LSEG = TP / NSEG, SWX = LSEG + 16;        // NSEG > 1: L < TP, a chunk is NSEG items, each with its own halo rows
-    constexpr int XROWS = NSEG == 1 ? TP + 20 : NSEG * SWX; // x rows staged per plane (8 halo + samples + halo)
-    constexpr int XPOS = ((XROWS + 11) / 16) * 16 + 4;      // plane stride of the x image (4 mod 16)
-    constexpr int WG = TAPS == 15 ? 2 : 4;          // ci groups of 16 per block
+    constexpr wunet_lds::WgradH3 Y = wunet_lds::wgrad_h3(TAPS, M_REP, NSEG, TP, BF);
+    constexpr int GP = Y.gp, LSEG = Y.lseg, SWX = Y.swx, XROWS = Y.xrows, XPOS = Y.xpos, XG = Y.xg, GG = Y.gg, NPL = Y.npl;
     constexpr int TW = TAPS == 15 ? 8 : 5;          // taps per wave
     constexpr int OB = TAPS == 15 ? 1 : 8 - TAPS / 2;    // funnel offset of the wave's first tap
-    constexpr int CIB = WG * 16, XG = CIB / 8, GG = M_REP * 2;
-    constexpr int NPL = BF ? 1 : 2;                 // operand planes: hi (+ lo); BF: one bf16 word per value
+    constexpr int CIB = XG * 8;                     // input channels per block: 2 (15 taps) or 4 groups of 16
     constexpr int GPC = NPL * GG * TP;              // pieces staged per chunk: g_z, x
     constexpr int XPC = NPL * XG * XROWS;
     constexpr int GIT = (GPC + WUNET_THREADS - 1) / WUNET_THREADS;
     constexpr int XIT = (XPC + WUNET_THREADS - 1) / WUNET_THREADS;
     WUNET_DYN_SMEM(smem);
-    wunet_half* gs = reinterpret_cast<wunet_half*>(smem);                      // [hi|lo][GG][GP][8]
-    wunet_half* xs = gs + NPL * GG * GP * 8;                                     // [hi|lo][XG][XPOS][8] (+ slack behind it)
+    wunet_half* gs = reinterpret_cast<wunet_half*>(smem);
+    wunet_half* xs = gs + Y.xs() * 8;
     static_assert(XROWS <= XPOS, "x image");
+    static_assert((size_t)(Y.xs() + NPL * XG * XPOS + 8) * 16 == Y.bytes(), "the x image and its slack end the layout");
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, i16 = lane & 15;
     const int grp = TAPS == 15 ? wave >> 1 : wave;
@@ -270,20 +268,18 @@ struct WgradH3dArgs {
 template <int TAPS, int M_REP, bool DB, bool BF = false, int TP = 128>
 __global__ __launch_bounds__(WUNET_THREADS, ((DB && TP == 128) ? 1 : 2)) void wgrad_h3d_kernel(WgradH3dArgs A)
 {
-    constexpr int GP = TP + 4, XPOS = TP + 20;                    // plane strides (pieces), both 4 mod 16
+    constexpr wunet_lds::WgradH3d Y = wunet_lds::wgrad_h3d(TAPS, M_REP, DB, BF, TP);
+    constexpr int GP = Y.gp, XPOS = Y.xpos, XG = Y.xg, GG = Y.gg, NPL = Y.npl, GPCS = Y.gpcs, XPCS = Y.xpcs;
     static_assert(TP == 128 || TP == 64, "chunk");
-    constexpr int WG = TAPS == 15 ? 2 : 4;
     constexpr int TW = TAPS == 15 ? 8 : 5;
     constexpr int OB = TAPS == 15 ? 1 : 8 - TAPS / 2;
-    constexpr int CIB = WG * 16, XG = CIB / 8, GG = M_REP * 2;
-    constexpr int NPL = BF ? 1 : 2;                 // operand planes: hi (+ lo); BF: one bf16 word per value
-    constexpr int GPCS = NPL * GG * GP;             // pieces of the g_z image (rows 128..131 of a plane are never read or written)
-    constexpr int XPCS = NPL * XG * XPOS;           // pieces of the x image
+    constexpr int CIB = XG * 8;
     constexpr int GIT = (GPCS + WUNET_THREADS - 1) / WUNET_THREADS;
     constexpr int XIT = (XPCS + WUNET_THREADS - 1) / WUNET_THREADS;
-    constexpr int BUF = (GPCS + XPCS + 8) * 8;      // halfs per buffer (+ slack behind the x image)
+    constexpr int BUF = Y.buf() * 8;                // halfs per buffer
+    static_assert((size_t)(DB ? 2 : 1) * BUF * sizeof(wunet_half) == Y.bytes(), "the buffers are the layout");
     WUNET_DYN_SMEM(smem);
-    wunet_half* lds = reinterpret_cast<wunet_half*>(smem);            // [2][ g_z image | x image | slack ]
+    wunet_half* lds = reinterpret_cast<wunet_half*>(smem);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, i16 = lane & 15;
     const int grp = TAPS == 15 ? wave >> 1 : wave;

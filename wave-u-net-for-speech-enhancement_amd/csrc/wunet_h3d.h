@@ -37,25 +37,21 @@ __global__ __launch_bounds__(WUNET_THREADS, 2) void conv_h3d_kernel(ConvH3Args A
     constexpr int PAD = TAPS / 2;
     constexpr int TG = 5;                         // taps per stage
     constexpr int NTG = TAPS / TG;
-    constexpr int LSEG = 256 / NSEG, SW = LSEG + 16;
-    constexpr int COLS = NSEG * SW, Q4 = COLS / 4;
-    constexpr int NPL = BF ? 1 : 2;
-    constexpr int XP = NPL * 4 * COLS;            // 16-byte pieces of the x tile
-    constexpr int WPM = TG * 64;
-    constexpr int WP = NPL * M_REP * WPM;         // pieces of the W sub-tile of a stage
+    constexpr wunet_lds::ConvH3d Y = wunet_lds::conv_h3d(M_REP, NSEG, BF, UPT);
+    constexpr int LSEG = Y.lseg, SW = Y.sw, COLS = Y.cols, Q4 = COLS / 4, NPL = Y.npl, XP = Y.xp, WPM = Y.wpm, WP = Y.wp;
+    static_assert(WPM == TG * 64, "W run of an m-tile");
     constexpr int WIT = (WP + WUNET_THREADS - 1) / WUNET_THREADS;
     static_assert(XP % 64 == 0 && WP % 64 == 0, "whole DMA instructions per wave");
     WUNET_DYN_SMEM(smem);
-    wunet_half* xs = reinterpret_cast<wunet_half*>(smem);             // [hi|lo][4][COLS, de-interleaved][8]
-    wunet_half* ws = xs + XP * 8;                                      // [hi|lo][M_REP][TG][4][16][8]
-    float* red = reinterpret_cast<float*>(ws + WP * 8);                // [4 waves][M_REP * 16][2] statistics hand-over (UPT: room for [4] per row), + 4 maxima
-    // un-segmented tiles (the levels of 256 samples and more): [bias | eval a | eval s][ER], the epilogue's per-row constants, once per block
-    // instead of one global round trip per work item (the eval parts only where A.epi_eval says they fit).  (UPT: a data gradient has
-    // no bias - no table.)
-    constexpr bool EPI_LDS = NSEG == 1 && !UPT;
-    constexpr int RW = UPT ? 64 : 32;                                  // hand-over floats per 16 rows
-    float* const epi = red + WUNET_WAVES * M_REP * RW + 4;
+    wunet_half* xs = reinterpret_cast<wunet_half*>(smem);
+    wunet_half* ws = xs + Y.ws() * 8;
+    float* red = reinterpret_cast<float*>(xs + Y.red() * 8);
+    // (the table of per-row constants: once per block instead of one global round trip per work item)
+    constexpr bool EPI_LDS = Y.epi_lds;
+    float* const epi = red + Y.red_floats;
     const int ER = A.mblocks * M_REP * 16;
+    static_assert((size_t)(XP + WP) * 16 + (size_t)(WUNET_WAVES * M_REP * (UPT ? 64 : 32) + 4) * sizeof(float) == Y.bytes(0, 0) &&
+                  Y.bytes(16, 1) - Y.bytes(0, 0) == (EPI_LDS ? 3 * 16 * sizeof(float) : 0), "red, then the table, end the layout");
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, i16 = lane & 15;
     const int L = A.L;

@@ -413,18 +413,18 @@ template <int M_REP, bool COPY = false>
 __global__ __launch_bounds__(2 * WUNET_THREADS, 1) void conv_h3u_kernel(ConvH3uArgs A)
 {
     constexpr int PAD = 2, TG = 5;
-    constexpr int COLS = 272, Q4 = COLS / 4;
-    constexpr int XP = 2 * 4 * COLS;              // 16-byte pieces of one x tile (hi + lo)
-    constexpr int WPM = TG * 64;
-    constexpr int WP = 2 * M_REP * WPM;           // pieces of one W sub-tile
-    static_assert(WPM == 320, "W run = 256 + 64 pieces");
+    constexpr wunet_lds::ConvH3u Y = wunet_lds::conv_h3u(M_REP);
+    constexpr int COLS = Y.cols, Q4 = COLS / 4, XP = Y.xp, WPM = Y.wpm, WP = Y.wp;
+    static_assert(WPM == TG * 64 && WPM == 320, "W run = 256 + 64 pieces");
+    static_assert((size_t)(2 * XP + 2 * WP) * 16 + (size_t)(WUNET_WAVES * M_REP * 32 + 4) * sizeof(float) == Y.bytes(0, 0) &&
+                  Y.bytes(1, 16) - Y.bytes(0, 0) == (2 * 8 + 3 * 16) * sizeof(float), "red, coef and the table end the layout");
     WUNET_DYN_SMEM(smem);
-    wunet_half* const xs0 = reinterpret_cast<wunet_half*>(smem);          // [2][hi|lo][4][COLS, de-interleaved][8]
-    wunet_half* const ws0 = xs0 + 2 * XP * 8;                              // [2][hi|lo][M_REP][TG][4][16][8]
-    float* const red = reinterpret_cast<float*>(ws0 + 2 * WP * 8);        // [4 waves][M_REP * 16][2] statistics hand-over
-    float* const coef = red + WUNET_WAVES * M_REP * 32 + 4;                // [a | s][C8 * 8]: BatchNorm scale / shift of the operand's channels (x the operand scale)
+    wunet_half* const xs0 = reinterpret_cast<wunet_half*>(smem);
+    wunet_half* const ws0 = xs0 + Y.ws0() * 8;
+    float* const red = reinterpret_cast<float*>(xs0 + Y.red() * 8);
+    float* const coef = red + Y.coef;
     const int ER = A.mblocks * M_REP * 16;
-    float* const epi = coef + 2 * A.C8 * 8;                          // [bias | eval a | eval s][ER]: the epilogue's per-row constants
+    float* const epi = coef + Y.epi(A.C8);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = wunet_uniform(tid >> 6);
     const int cw = wave & 3;                      // MFMA wave / loader wave index

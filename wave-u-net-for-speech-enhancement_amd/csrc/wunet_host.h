@@ -47,7 +47,7 @@ inline size_t align64(size_t v) { return (v + 63) & ~(size_t)63; }
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 // blocks of a grid-stride launch: one per per_block elements of n, at most cap
 inline unsigned capped_blocks(size_t n, size_t per_block, size_t cap) { const size_t b = (n + per_block - 1) / per_block; return (unsigned)(b < cap ? b : cap); }
-inline int kc_of(int taps) { return taps == 15 ? 4 : 12; }
+inline int kc_of(int taps) { return wunet_lds::conv_mfma(taps, 1).kc; }      // input channels per K chunk of conv_mfma_kernel
 
 // Tiling of one implicit-GEMM conv: rows = output channels of the GEMM, kch = its K channels.
 struct ConvCfg { int mrep, nrep, mtiles_p, mblocks, cp, grid_x, ksplit, kcps; };
@@ -135,11 +135,11 @@ struct LayerDecisions {
 };
 struct LayerPlan : LayerGeom, LayerDecisions {};
 
-size_t h3d_smem(int nseg, int mrep, int bf, int mtp, int eval, int upt = 0);           // dynamic LDS of a conv_h3d_kernel block
-int h3d_blocks_per_cu(int nseg, int mrep, int bf);   // resident blocks per CU at that size
 int h3_stage_count(int kch, int taps, int ntt);
 size_t h3w_part_stride(const LayerGeom& g, const H3WgradPlan& w);
-size_t h3w_dma_smem(const LayerGeom& g, const H3WgradPlan& w, int bf);     // dynamic LDS of a double-buffered wgrad_h3d_kernel block
+// resident blocks per CU the split-K rules of the two weight-gradient planners count on (tools/plan_dump.cpp --check holds the layouts' bytes against them)
+int wgrad_blocks_per_cu(const WgradCfg& w, int L, int taps);
+int h3w_blocks_per_cu(int taps, int mrep, int L);
 bool up_pairs_regular(int Lin);       // the x2 upsample reads the source pairs ((j-1) >> 1, +1) at this length (fp32 coordinates, host check)
 unsigned pack_gx();
 

@@ -22,6 +22,8 @@
 //                   sides so every global load / LDS store is an aligned float4.
 #pragma once
 #include "wunet_dev.h"
+#include "wunet_lds.h"
+static_assert(WUNET_WAVES == wunet_lds::kWaves, "the layouts' waves per block");
 
 // A position tile of TN flattened (b,l) positions = nseg segments of seg = min(L, TN) positions; every
 // segment lies inside one batch item and is staged as seg+16 floats (halo of 8 left and right).
@@ -44,13 +46,14 @@ template <int TAPS, int M_REP, int N_REP>
 __global__ __launch_bounds__(WUNET_THREADS) void conv_mfma_kernel(ConvArgs A)
 {
     constexpr int PAD = TAPS / 2;
-    constexpr int KC = (TAPS == 15) ? 4 : 12;
+    constexpr wunet_lds::ConvMfma Y = wunet_lds::conv_mfma(TAPS, M_REP);
+    constexpr int KC = Y.kc, WCHUNK = Y.wchunk;
     constexpr int XIT = (TAPS == 15) ? 2 : 4;       // float4 x slots per thread: KC * r4 <= 256 * XIT
     constexpr int TN = 64 * N_REP;
-    constexpr int WCHUNK = KC * TAPS * 16;          // floats of one m-tile's K-chunk (240 float4)
+    static_assert((size_t)(KC * 16 + M_REP * WCHUNK) * sizeof(float) == Y.bytes(16), "ws [M_REP][WCHUNK] ends the layout (at a row stride of 16)");
     WUNET_DYN_SMEM(smem);
-    float* xs = smem;                               // [KC][rowp]
-    float* ws = smem + KC * A.rowp;                 // [M_REP][KC][TAPS][16]
+    float* xs = smem;
+    float* ws = smem + Y.ws(A.rowp);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, i16 = lane & 15;
     const int n0 = blockIdx.x * TN;
@@ -218,13 +221,14 @@ template <int TAPS, int M_REP, int NW, int XIT, bool WSPLIT>
 __global__ __launch_bounds__(WUNET_THREADS) void wgrad_mfma_kernel(WgradArgs A)
 {
     constexpr int PAD = TAPS / 2;
-    constexpr int TP = 64;
-    constexpr int GROW = TP + 2;                                // == 2 (mod 32): A fragments conflict free
+    constexpr wunet_lds::WgradMfma Y = wunet_lds::wgrad_mfma(TAPS, M_REP, NW, WSPLIT);
+    constexpr int TP = Y.tp, GROW = Y.grow, CIB = Y.cib;
     constexpr int CI_PER_NT = (TAPS == 15) ? 1 : 3;
-    constexpr int CIB = WSPLIT ? 1 : WUNET_WAVES * NW * CI_PER_NT;   // input channels per block
+    static_assert(CIB == (WSPLIT ? 1 : WUNET_WAVES * NW * CI_PER_NT), "a wave's n-tiles");
+    static_assert((size_t)(M_REP * 16 * GROW + CIB * 8) * sizeof(float) == Y.bytes(8), "xs [CIB][rowp] ends the layout (at a row stride of 8)");
     WUNET_DYN_SMEM(smem);
-    float* gs = smem;                          // [M_REP*16][GROW]
-    float* xs = smem + M_REP * 16 * GROW;      // [CIB][rowp]  (16-byte aligned: M_REP*16*66*4 is a multiple of 16)
+    float* gs = smem;
+    float* xs = smem + Y.xs();
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, i16 = lane & 15;
     const int split = blockIdx.x;

@@ -7,12 +7,12 @@
 #define WUNET_ALLOW_BIG_LDS(kern, smem) 0
 #else
 #define WUNET_LAUNCH(kern, grid, block, smem, stream, ...) hipLaunchKernelGGL(kern, grid, block, smem, stream, __VA_ARGS__)
-// gfx950 has 160 KiB of LDS per CU; more than 64 KiB of dynamic LDS must be requested per kernel
+// gfx950 has WUNET_LDS_PER_CU of LDS per CU; more than WUNET_LDS_OPT_IN of dynamic LDS must be requested per kernel
 // (granted once per kernel and device, remembered: hipFuncSetAttribute on every launch costs host time)
 #define WUNET_ALLOW_BIG_LDS(kern, smem)                                                                    \
     ([&]() -> int {                                                                                        \
         static size_t granted[64];                                                                         \
-        if ((size_t)(smem) <= 64 * 1024) return 0;                                                         \
+        if ((size_t)(smem) <= WUNET_LDS_OPT_IN) return 0;                                                  \
         int dev = 0;                                                                                       \
         if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0, granted[0] = 0;             \
         if ((size_t)(smem) <= granted[dev]) return 0;                                                      \
@@ -22,6 +22,16 @@
         return e;                                                                                          \
     }())
 #endif
+
+// Every dispatcher compares the dynamic LDS it is handed with what the layout of the chosen instantiation needs (wunet_lds.h) and
+// refuses a smaller request with a code of its own - nothing is launched; the bytes it needed are left in wunet_lds_needed
+#define WUNET_LAUNCH_E_LDS (-6)
+inline thread_local size_t wunet_lds_needed = 0;
+#define WUNET_LDS_CHECK(need)                                                      \
+    {                                                                              \
+        const size_t need_ = (need);                                               \
+        if (smem < need_) { wunet_lds_needed = need_; return WUNET_LAUNCH_E_LDS; } \
+    }
 
 // One translation unit per tap count keeps hipcc builds parallel.  Return 0 when a kernel
 // for (mrep, nrep) exists and was enqueued, -1 otherwise.

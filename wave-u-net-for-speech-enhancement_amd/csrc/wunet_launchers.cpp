@@ -5,6 +5,12 @@
 
 namespace wunet_host {
 
+// a dispatcher's refusal (WUNET_LAUNCH_E_LDS) as error text: the kernel and both byte counts
+static int lds_refused(const char* kernel, size_t smem)
+{
+    return fail(WUNET_E_ARG, "%s: %zu bytes of dynamic LDS requested, its layout needs %zu", kernel, smem, wunet_lds_needed);
+}
+
 ConvArgs make_conv_args(const float* x, int kch, const float* wpk, const float* bias, float* out, float* stats,
                         int B, int rows, int L, int taps, const ConvCfg& c, size_t split_stride)
 {
@@ -15,10 +21,8 @@ ConvArgs make_conv_args(const float* x, int kch, const float* wpk, const float* 
     a.seg = L < tn ? L : tn;
     a.seg_shift = ilog2(a.seg);
     a.segw = a.seg + 16;
-    const int rowlen = (tn / a.seg) * a.segw;
-    int rp = rowlen;
-    while (rp % 32 != 16) rp += 4;
-    a.rowp = rp;
+    const int rowlen = wunet_lds::staged_row(L, tn);
+    a.rowp = wunet_lds::conv_mfma_rowp(L, c.nrep);
     a.r4 = rowlen / 4;
     a.sw4 = a.segw / 4;
     a.r4_magic = (unsigned)(((1u << 20) + a.r4 - 1) / a.r4);
@@ -30,17 +34,17 @@ ConvArgs make_conv_args(const float* x, int kch, const float* wpk, const float* 
 
 int launch_conv(int taps, const ConvArgs& a, const ConvCfg& c, hipStream_t st)
 {
-    const int kc = kc_of(taps);
     char pname[96];
     snprintf(pname, sizeof pname, "conv_mfma_kernel<%d, %d, %d>", taps, c.mrep, c.nrep);
     // algorithmic work: 2*B*L*rows*kch*taps flops; input read once + output written once
     const double posn = (double)a.B * a.L;
     prof_begin(st, pname, 2.0 * posn * a.Cout * a.Cin * taps, 4.0 * posn * (a.Cout + a.Cin));
-    const size_t smem = ((size_t)kc * a.rowp + (size_t)c.mrep * kc * taps * 16) * sizeof(float);
+    const size_t smem = wunet_lds::conv_mfma(taps, c.mrep).bytes(a.rowp);
     const dim3 grid(c.grid_x, c.mblocks, c.ksplit);
     const int rc = taps == 15 ? wunet_launch_conv_15(a, c.mrep, c.nrep, grid, smem, st)
                               : wunet_launch_conv_5(a, c.mrep, c.nrep, grid, smem, st);
     prof_end(st);
+    if (rc == WUNET_LAUNCH_E_LDS) return lds_refused(pname, smem);
     if (rc != 0) return fail(WUNET_E_ARG, "no conv kernel for taps=%d mrep=%d nrep=%d", taps, c.mrep, c.nrep);
     return 0;
 }
@@ -52,12 +56,9 @@ WgradArgs make_wgrad_args(const float* x, const float* g, float* part, int B, in
     a.seg = L < 64 ? L : 64;
     a.seg_shift = ilog2(a.seg);
     a.segw = a.seg + 16;
-    const int nseg = 64 / a.seg;
-    a.r4 = nseg * a.segw / 4;
+    a.r4 = wunet_lds::staged_row(L, 64) / 4;
     a.sw4 = a.segw / 4;
-    int rp = a.r4 * 4;
-    if (taps == 5) while (rp % 32 != 8) rp += 4;     // 3 ci rows per n-tile land on disjoint banks
-    a.rowp = rp;
+    a.rowp = wunet_lds::wgrad_mfma_rowp(taps, L);
     a.r4_magic = (unsigned)(((1u << 20) + a.r4 - 1) / a.r4);
     a.sw4_magic = (unsigned)(((1u << 20) + a.sw4 - 1) / a.sw4);
     return a;
@@ -65,8 +66,7 @@ WgradArgs make_wgrad_args(const float* x, const float* g, float* part, int B, in
 
 int launch_wgrad_any(int taps, const WgradArgs& a, const WgradCfg& w, hipStream_t st)
 {
-    const int cib = w.wsplit ? 1 : 4 * w.nw * (taps == 15 ? 1 : 3);
-    const size_t smem = ((size_t)w.mrep * 16 * 66 + (size_t)cib * a.rowp) * sizeof(float);
+    const size_t smem = wunet_lds::wgrad_mfma(taps, w.mrep, w.nw, w.wsplit != 0).bytes(a.rowp);
     char pname[96];
     snprintf(pname, sizeof pname, "wgrad_mfma_kernel<%d, %d, %d, %d, %s>", taps, w.mrep, w.nw, w.xit, w.wsplit ? "true" : "false");
     const double posn = (double)a.B * a.L;
@@ -75,6 +75,7 @@ int launch_wgrad_any(int taps, const WgradArgs& a, const WgradCfg& w, hipStream_
     int rc = taps == 15 ? wunet_launch_wgrad_15(a, w.mrep, w.nw, w.xit, w.wsplit, grid, smem, st)
                         : wunet_launch_wgrad_5(a, w.mrep, w.nw, w.xit, w.wsplit, grid, smem, st);
     prof_end(st);
+    if (rc == WUNET_LAUNCH_E_LDS) return lds_refused(pname, smem);
     if (rc != 0) return fail(WUNET_E_ARG, "no wgrad kernel for taps=%d mrep=%d nw=%d xit=%d wsplit=%d", taps, w.mrep, w.nw, w.xit, w.wsplit);
     return 0;
 }
@@ -149,17 +150,20 @@ int launch_conv_h3(const ConvH3Launch& k, hipStream_t st)
     const double upt_bytes = upt ? -2.0 * posn * upt->c0 : 0.0;          // (UPT: the upsampled rows leave at half the length)
     prof_begin(st, pname, 2.0 * posn * rows * kch * taps, (bf ? 2.0 * posn * kch + 4.0 * posn * rows : 4.0 * posn * (rows + kch)) + (op ? 2.0 * posn * rows : 0.0) + upt_bytes);
     // (eval: BatchNorm scale / shift beside the bias in the block's table of per-row constants unless that costs the second block of a CU)
-    a.epi_eval = (k.xrows && nseg == 1 && 2 * h3d_smem(nseg, mrep, bf, k.mtiles_p, 1) <= 160u * 1024u) ? 1 : 0;
-    const size_t smem = h3d_smem(nseg, mrep, bf, k.mtiles_p, a.epi_eval, upt ? 1 : 0);
+    const int er = k.mtiles_p * 16;
+    a.epi_eval = (k.xrows && wunet_lds::conv_h3d(mrep, nseg, bf != 0, false).eval_table_fits(er)) ? 1 : 0;
+    const wunet_lds::ConvH3d lay = wunet_lds::conv_h3d(mrep, nseg, bf != 0, upt != nullptr);
+    const size_t smem = lay.bytes(er, a.epi_eval);
     const int nitems = a.ntiles * a.mblocks;
     // resident blocks: two per CU, one for the 16-segment tile (96 KB); a K-split layer whose items x splits fit them runs one item per block
-    int gx = h3_grid_cap() / 2 * h3d_blocks_per_cu(nseg, mrep, bf) / ksplit;
+    int gx = h3_grid_cap() / 2 * wunet_lds::conv_h3d(mrep, nseg, bf != 0, false).blocks_per_cu() / ksplit;
     if (gx < nitems) gx &= ~7;
     if (gx < 8) gx = 8;
     if (gx > nitems) gx = nitems;
     const dim3 grid((unsigned)gx, (unsigned)ksplit);
     const int rc = wunet_launch_conv_h3d(a, taps, mrep, nseg, grid, smem, st, bf != 0, op != nullptr, upt != nullptr);
     prof_end(st);
+    if (rc == WUNET_LAUNCH_E_LDS) return lds_refused(pname, smem);
     if (rc != 0) return fail(WUNET_E_ARG, "no conv_h3 kernel for taps=%d mrep=%d nseg=%d (rc %d)", taps, mrep, nseg, rc);
     return 0;
 }
@@ -174,7 +178,7 @@ int launch_conv_h3u(const ConvH3uArgs& a0, int mrep, int mtiles_p, int kch, hipS
     a.NS = (a.C8 + 3) / 4;
     a.ntiles = (int)((posn + 255) / 256); a.mblocks = mtiles_p / mrep;
     a.trace = g_h3_trace ? g_h3_trace + (1 << 20) : nullptr;      // (behind conv_h3d_kernel's region of the caller's trace buffer; written by -DWUNET_H3U_TRACE builds only)
-    const size_t smem = (size_t)(2 * 2 * 4 * 272 + 2 * 2 * mrep * 5 * 64) * 16 + (size_t)(WUNET_WAVES * mrep * 32 + 4 + 2 * a.C8 * 8 + 3 * mtiles_p * 16) * sizeof(float);   // (red, the coefficient table, the epilogue constants)
+    const size_t smem = wunet_lds::conv_h3u(mrep).bytes(a.C8, mtiles_p * 16);
     const int nitems = a.ntiles * a.mblocks;
     int gx = h3_grid_cap() / 2;                  // one block per CU
     if (gx > nitems) gx = nitems;
@@ -184,6 +188,7 @@ int launch_conv_h3u(const ConvH3uArgs& a0, int mrep, int mtiles_p, int kch, hipS
     prof_begin(st, pname, 2.0 * posn * a.Cout * kch * 5.0, 4.0 * posn * (a.Cout + a.C0 * 0.5 + a.C1));
     const int rc = wunet_launch_conv_h3u(a, mrep, dim3((unsigned)gx), smem, st);
     prof_end(st);
+    if (rc == WUNET_LAUNCH_E_LDS) return lds_refused(pname, smem);
     if (rc != 0) return fail(WUNET_E_ARG, "no conv_h3u kernel for mrep=%d (rc %d)", mrep, rc);
     return 0;
 }
@@ -195,9 +200,10 @@ int launch_wgrad_h3(const LayerGeom& l, const H3WgradPlan& w, const wunet_half* 
 {
     char pname[96];
     const double posn = (double)B * l.L;
-    const int xg = l.taps == 15 ? 4 : 8, tp = w.tp, nseg = l.L >= tp ? 1 : tp / l.L;
+    const int tp = w.tp, nseg = l.L >= tp ? 1 : tp / l.L;
     const dim3 grid(w.ksplit, w.nblocks, w.mblocks);
-    const int npl = bf ? 1 : 2;
+    const size_t smem = w.dma ? wunet_lds::wgrad_h3d(l.taps, w.mrep, w.db != 0, bf != 0, tp).bytes()
+                              : wunet_lds::wgrad_h3(l.taps, w.mrep, nseg, tp, bf != 0).bytes();
     int rc;
     const auto fill = [&](auto& a) {          // what the two kernels' argument blocks share
         a.xh = xh; a.xl = xl; a.gh = gh; a.gl = gl; a.sc = sc; a.sc2 = sc2; a.part = part; a.B = B; a.Cin = l.cin; a.Cout = l.cout;
@@ -213,18 +219,16 @@ int launch_wgrad_h3(const LayerGeom& l, const H3WgradPlan& w, const wunet_half* 
         a.ksplit = w.ksplit; a.nblocks = w.nblocks; a.mblocks = w.mblocks;
         // the blocks of one K split on one XCD where the planner found room (WgradH3dArgs::xcd_walk)
         a.xcd_walk = w.xcd;
-        const size_t smem_d = h3w_dma_smem(l, w, bf);
         const int nyz = w.nblocks * w.mblocks;
         const dim3 grid_x((unsigned)(((w.ksplit + 7) / 8) * 8 * nyz));
-        rc = wunet_launch_wgrad_h3d(a, l.taps, w.mrep, w.db != 0, a.xcd_walk ? grid_x : grid, w.db ? smem_d : smem_d / 2, st, bf != 0, tp);
+        rc = wunet_launch_wgrad_h3d(a, l.taps, w.mrep, w.db != 0, a.xcd_walk ? grid_x : grid, smem, st, bf != 0, tp);
     } else {
         WgradH3Args a{};
         fill(a);
-        const int xrows = nseg == 1 ? tp + 20 : nseg * (tp / nseg + 16), xpos = ((xrows + 11) / 16) * 16 + 4;
-        const size_t smem = ((size_t)npl * (w.mrep * 2) * (tp + 4) + (size_t)npl * xg * xpos + 8) * 16;
         rc = wunet_launch_wgrad_h3(a, l.taps, w.mrep, nseg, tp, grid, smem, st, bf != 0);
     }
     prof_end(st);
+    if (rc == WUNET_LAUNCH_E_LDS) return lds_refused(pname, smem);
     if (rc != 0) return fail(WUNET_E_ARG, "no wgrad_h3 kernel for taps=%d mrep=%d (rc %d)", l.taps, w.mrep, rc);
     return 0;
 }

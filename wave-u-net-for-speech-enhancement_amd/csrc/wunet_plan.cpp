@@ -147,6 +147,21 @@ ConvCfg plan_conv(int B, int L, int rows, int kch, int taps)
     }
     return c;
 }
+// Residency ESTIMATE of wgrad_mfma_kernel: accumulators + staging registers against the 512-entry register file per SIMD lane, and
+// an LDS footprint against the CU's.  The footprint is the kernel's layout at an estimated row stride, not the launch's: 5 taps count
+// the staged row + 24 floats, which is the launch's padding (wgrad_mfma_rowp: to 8 mod 32) from 64 samples on (80 -> 104) and more
+// than it below (32 samples: 96 -> 104, estimated 120; 2 samples: 576 -> 584, estimated 600).  Never less than the launch requests, so
+// the blocks counted here always fit; at a 2-sample level with 5 taps it counts one block where two fit, and the split-K of those
+// plans rests on it - the true size would change them, so the estimate stays
+int wgrad_blocks_per_cu(const WgradCfg& w, int L, int taps)
+{
+    const int regs = 4 * w.mrep * w.nw + 72 + 4 * (w.mrep + w.xit);
+    const int occ = regs <= 168 ? 3 : (regs <= 256 ? 2 : 1);
+    const int rowp_estimate = wunet_lds::staged_row(L, 64) + (taps == 5 ? 24 : 0);
+    const size_t lds = wunet_lds::wgrad_mfma(taps, w.mrep, w.nw, w.wsplit != 0).bytes(rowp_estimate);
+    const int occ_lds = (int)(WUNET_LDS_PER_CU / lds);
+    return occ_lds < occ ? (occ_lds < 1 ? 1 : occ_lds) : occ;
+}
 WgradCfg plan_wgrad(int B, int L, int cin, int cout, int taps)
 {
     WgradCfg w{};
@@ -179,18 +194,9 @@ WgradCfg plan_wgrad(int B, int L, int cin, int cout, int taps)
         w.nblocks = round_up(nt, 4 * w.nw) / (4 * w.nw);
         w.xit = big ? (w.nw == 6 && taps == 5 ? 6 : 2) : 8;
     }
-    // split-K: one resident wave of equal-work blocks.  Residency estimate: accumulators + staging registers
-    // against the 512-entry register file per SIMD lane, and the LDS footprint against 160 KiB.
+    // split-K: one resident wave of equal-work blocks
     {
-        const int regs = 4 * w.mrep * w.nw + 72 + 4 * (w.mrep + w.xit);
-        int occ = regs <= 168 ? 3 : (regs <= 256 ? 2 : 1);
-        const int segw = (L < 64 ? L : 64) + 16;
-        const int rowp = (64 / (L < 64 ? L : 64)) * segw + (taps == 5 ? 24 : 0);
-        const int cib = w.wsplit ? 1 : 4 * w.nw * (taps == 15 ? 1 : 3);
-        const long long lds = ((long long)w.mrep * 16 * 66 + (long long)cib * rowp) * 4;
-        const int occ_lds = (int)(160 * 1024 / lds);
-        if (occ_lds < occ) occ = occ_lds < 1 ? 1 : occ_lds;
-        const long long slots = 256LL * occ;
+        const long long slots = 256LL * wgrad_blocks_per_cu(w, L, taps);
         const long long mn = (long long)w.mblocks * w.nblocks;
         long long ks = slots / mn;
         if (ks < 1) ks = 1;
@@ -256,28 +262,10 @@ size_t h3w_part_stride(const LayerGeom& g, const H3WgradPlan& w)
     const int tw = g.taps == 15 ? 8 : 5;
     return (size_t)w.mblocks * w.nblocks * WUNET_WAVES * w.mrep * tw * 256;
 }
-// both LDS buffers of a wgrad_h3d_kernel block
-size_t h3w_dma_smem(const LayerGeom& g, const H3WgradPlan& w, int bf)
-{
-    const int xg = g.taps == 15 ? 4 : 8, tp = w.tp, npl = bf ? 1 : 2;
-    return (size_t)2 * (npl * (w.mrep * 2) * (tp + 4) + npl * xg * (tp + 20) + 8) * 16;
-}
 // wgrad_h3d_kernel<.., false> (single LDS buffer, two blocks per CU) where its registers allow: k5 up to 4 m-tiles, k15 up to 3
 static bool h3w_regs_allow_two_blocks(int taps, int mrep) { return (taps == 5 && mrep <= 4) || (taps == 15 && mrep <= 3); }
-
-// dynamic LDS of one conv_h3d_kernel block: x tile [planes][4][NSEG * (256 / NSEG + 16)] + W sub-tile [planes][M_REP][5][64] pieces of 16 bytes
-// + the statistics hand-over
-// (un-segmented tiles: + the epilogue's per-row constants - bias, in eval mode also the BatchNorm scale / shift - of the mtp * 16 padded rows)
-size_t h3d_smem(int nseg, int mrep, int bf, int mtp, int eval, int upt)
-{
-    const int npl = bf ? 1 : 2;
-    // (UPT: 64 hand-over floats per 16 rows instead of 32, no table of constants)
-    return (size_t)(npl * 4 * nseg * (256 / nseg + 16) + npl * mrep * 5 * 64) * 16
-         + (size_t)(WUNET_WAVES * mrep * (upt ? 64 : 32) + 4 + ((nseg == 1 && !upt) ? (eval ? 3 : 1) * mtp * 16 : 0)) * sizeof(float);
-}
-// blocks of that size a CU holds (launch bounds: two; the 16-segment tile's 96 KB: one) - the table of constants never costs the second block
-// (launch_conv_h3 leaves the eval part in global memory where it would)
-int h3d_blocks_per_cu(int nseg, int mrep, int bf) { return 2 * h3d_smem(nseg, mrep, bf, 0, 0) <= 160u * 1024u ? 2 : 1; }
+// resident blocks per CU of the split weight gradient: launch bounds of the wgrad kernels
+int h3w_blocks_per_cu(int taps, int mrep, int L) { return (mrep <= 2 || (L >= 128 && h3w_regs_allow_two_blocks(taps, mrep))) ? 2 : 1; }
 
 // conv_h3d_kernel split-K of the levels with fewer work items than resident blocks: the K stages are split so that ONE round of
 // resident blocks covers the layer, every block with (nearly) the same number of stages.  Round 4's block start / end times
@@ -339,7 +327,7 @@ H3ConvPlan plan_h3_conv(int B, int L, int rows, int kch, int taps, bool transpos
     p.ntt = (p.mrep < 4 && L >= 32) ? h3_tail_steps(kch, taps, sw) : 0;      // (WUNET_H3D_HAS_TAIL: the shapes at the register limit go without)
     const int ns = h3_stage_count(kch, taps, p.ntt);
     const int nseg = L >= 256 ? 1 : 256 / L;
-    p.sps = h3_stages_per_split(p.ntiles * (p.mtp / p.mrep), ns, 256 * h3d_blocks_per_cu(nseg, p.mrep, bf), sw);
+    p.sps = h3_stages_per_split(p.ntiles * (p.mtp / p.mrep), ns, 256 * wunet_lds::conv_h3d(p.mrep, nseg, bf != 0, false).blocks_per_cu(), sw);
     p.ksplit = (ns + p.sps - 1) / p.sps;
     return p;
 }
@@ -366,12 +354,10 @@ H3WgradPlan plan_h3_wgrad(int B, int L, int cin, int cout, int taps, int bf, con
     // wgrad_h3d_kernel (DMA-staged): whole chunks inside one item (L >= 128), both buffers within the 160 KB.  Two blocks per CU with
     // a single buffer where the registers allow it (two independent blocks hide each other's waits: +18-28 % on those kernels), else
     // one block with double-buffered tiles
-    const LayerGeom g{cin, cout, taps, L};
     const int nseg = L >= w.tp ? 1 : w.tp / L;
-    w.dma = (nseg == 1 && w.tp == 128 && h3w_dma_smem(g, w, bf) <= 160 * 1024 && w.mrep <= (taps == 15 ? 6 : 5)) ? 1 : 0;
+    w.dma = (nseg == 1 && w.tp == 128 && wunet_lds::wgrad_h3d(taps, w.mrep, true, bf != 0, w.tp).bytes() <= WUNET_LDS_PER_CU && w.mrep <= (taps == 15 ? 6 : 5)) ? 1 : 0;
     w.db = h3w_regs_allow_two_blocks(taps, w.mrep) ? 0 : 1;
-    const bool sb2 = L >= 128 && h3w_regs_allow_two_blocks(taps, w.mrep);
-    const long long slots = 256LL * ((w.mrep <= 2 || sb2) ? 2 : 1);      // resident blocks: launch bounds of the wgrad kernels
+    const long long slots = 256LL * h3w_blocks_per_cu(taps, w.mrep, L);
     long long ks = slots / ((long long)w.mblocks * w.nblocks);
     if (ks < 1) ks = 1;
     const long long chunks = ((long long)B * L + w.tp - 1) / w.tp;
