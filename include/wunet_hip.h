@@ -249,6 +249,42 @@ int wunet_stoi_loss_forward(const float* clean, const float* estimate, size_t ro
 int wunet_stoi_loss_backward(const void* saved, const float* grad_loss, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
                              float* grad_estimate, void* stream);
 
+/* ESTOI per row and as a training loss: the other branch of the same pystoi call, stoi(clean, estimate, fs, extended=True) (Jensen &
+ * Taal 2016; as a loss: Kolbaek et al. 2018).  Everything up to the band magnitudes is wunet_stoi_forward's - the same tables
+ * (wunet_stoi_tables_build), the same kept-frame rule and frame counts, the same 1e-5 for a row with fewer than 30 spectral frames -
+ * and every entry point takes the arguments of its wunet_stoi_* counterpart, in the same order, with the same argument errors.  With
+ * X[f][j], Y[f][j] the band magnitudes of the clean row and of the estimate (frame f, band j < 15), every segment m (frames m .. m + 29)
+ * normalises its 30 x 15 block of X and, separately, of Y twice:
+ *   1. per band j, over the 30 frames: minus the mean, divided by (the 2-norm + EPS);
+ *   2. per frame n, over the 15 bands of the result of 1: minus the mean, divided by (the 2-norm + EPS);
+ * EPS = 2^-52.  d_m = (1 / 30) sum_n sum_j x~[n][j] y~[n][j]; the row's score is the mean of d_m over its segments; the loss is
+ * -(1 / rows) sum_row score_row, the mean taken in double and rounded once, as for wunet_stoi_loss_forward.
+ * ONE departure from pystoi: before each normalisation pystoi adds EPS * randn dither to the block, only to avoid 0 / 0.  Nothing is
+ * added here; EPS stands in the two denominators instead.  The difference is at the 1e-15 level on any non-degenerate input.
+ *   wunet_estoi_forward / wunet_estoi_scratch_bytes: as wunet_stoi_forward / wunet_stoi_scratch_bytes.
+ *   wunet_estoi_loss_forward / _saved_bytes: as wunet_stoi_loss_forward; `saved` holds the same things.
+ *   wunet_estoi_loss_backward: grad_estimate = grad_loss[0] * d loss / d estimate, written for EVERY sample of every row.  The segment
+ *     stage is two launches - every segment's 30 x 15 block d d_m / d Y into scratch, then per (frame, band) the blocks of its at most 30
+ *     segments added in segment order - and the adjoint DFT GEMM, the frame gather and the transposed resampler of
+ *     wunet_stoi_loss_backward run behind it.  scratch: >= wunet_estoi_loss_scratch_bytes(..) (larger than STOI's by those blocks:
+ *     rows * (frames - 29) * 450 doubles).  Conventions of the derivative:
+ *       - the silent-frame mask depends on `clean` only and is a constant; there is no gradient with respect to `clean`;
+ *       - a band row or a frame column whose centred norm is exactly 0 normalises to zeros and passes no gradient (autograd: NaN);
+ *       - a (frame, band) whose Y is exactly 0 passes no gradient, as for wunet_stoi_loss_backward;
+ *       - a row with fewer than 30 spectral frames contributes the constant 1e-5 and an all-zero gradient;
+ *       - an all-zero estimate scores exactly 0.0 with an all-zero gradient.
+ * All segment arithmetic in double and in one fixed order, no atomics: bit-identical run to run.  Alignment, capture and limits as for
+ * the wunet_stoi_* calls. */
+size_t wunet_estoi_scratch_bytes(size_t rows, size_t row_len, int fs);
+int wunet_estoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                        float* out, int* frames_out, void* stream);
+size_t wunet_estoi_loss_scratch_bytes(size_t rows, size_t row_len, int fs);
+size_t wunet_estoi_loss_saved_bytes(size_t rows, size_t row_len, int fs);
+int wunet_estoi_loss_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                             void* saved, float* loss_out, float* per_row_out, int* frames_out, void* stream);
+int wunet_estoi_loss_backward(const void* saved, const float* grad_loss, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                              float* grad_estimate, void* stream);
+
 /* replaces optimizer.step() of torch.optim.Adam(params, lr, betas) as the reference builds it
  * (train.py:31-35; eps, weight_decay=0, amsgrad=False fixed by the reference's call) for n_tensors tensors in one
  * or two launches.  step is the 1-based step count AFTER the increment (torch's state["step"]).  numels: host array.

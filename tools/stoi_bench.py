@@ -5,7 +5,8 @@ included), at
 and, on the same host, the wall time of the float64 CPU yardstick (tests/stoi_ref.py: oracle64 - numpy / scipy, one row at a time,
 the way the reference's validation epoch calls pystoi) on the same inputs, with the distance between the two.  Also printed: the
 per-kernel times of (a) and (b) from the library's profiler.  There is no pass / fail time: the file records the first measurement.
-    python tools/stoi_bench.py [--out profiles/stoi_bench.txt] [--reps 30] [--commit <hash>]"""
+--extended measures metrics.stoi(extended=True) (ESTOI) against tests/estoi_ref.py instead.
+    python tools/stoi_bench.py [--out profiles/stoi_bench.txt] [--reps 30] [--commit <hash>] [--extended]"""
 import argparse
 import ctypes
 import importlib
@@ -26,10 +27,12 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stoi_bench.txt"))
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--commit", default="unknown")
+ap.add_argument("--extended", action="store_true")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "needs an MI355X"
 assert args.reps >= 20
 import stoi_ref as R  # noqa: E402
+import estoi_ref as E  # noqa: E402
 metrics = importlib.import_module(PKG + ".metrics")
 engine = importlib.import_module(PKG + ".engine").default_engine()
 dev = torch.device("cuda:0")
@@ -46,19 +49,20 @@ def timed(call):
     return e0.elapsed_time(e1)                # ms
 
 
-lines = [f"metrics.stoi at {FS} Hz on {torch.cuda.get_device_name(0)} (host {socket.gethostname()}, commit {args.commit}, torch {torch.__version__}), "
+NAME = "metrics.stoi(extended=True)" if args.extended else "metrics.stoi"
+lines = [f"{NAME} at {FS} Hz on {torch.cuda.get_device_name(0)} (host {socket.gethostname()}, commit {args.commit}, torch {torch.__version__}), "
          f"median of {args.reps} eager calls after 3 warm-up calls, HIP events, ms per call"]
 for label, (rows, T) in SHAPES.items():
     c, e = R.pair(rows if rows < 4 else 4, T, FS)
     c, e = c.repeat(rows // c.shape[0], 1), e.repeat(rows // e.shape[0], 1)     # (64 rows: the four generated ones, 16 times)
     cd, ed = c.to(dev), e.to(dev)
-    call = lambda: metrics.stoi(cd, ed, sample_rate=FS, return_frames=True)     # noqa: E731
+    call = lambda: metrics.stoi(cd, ed, sample_rate=FS, return_frames=True, extended=args.extended)     # noqa: E731
     for _ in range(3):
         score, frames = call()
     torch.cuda.synchronize()
     times = [timed(call) for _ in range(args.reps)]
     t0 = time.perf_counter()
-    s64, f64 = R.oracle64(c, e, FS)
+    s64, f64 = (E if args.extended else R).oracle64(c, e, FS)
     cpu_ms = (time.perf_counter() - t0) * 1e3
     d = float(np.abs(score.double().cpu().numpy() - s64).max())
     same = list(frames.cpu().numpy()) == list(f64)

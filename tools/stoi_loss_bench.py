@@ -5,8 +5,9 @@ time included), at 64 x 16384 at 16 kHz - the product's training chunk, one batc
   (b) torch ops  the same loss and gradient from torch ops and autograd on the device, batched over the rows (conv1d resampling, unfold /
                  fold framing, torch.fft, unfold segments) in float32: what a user can write today.  Its loss and gradient are printed
                  against the kernels' so that the two are seen to compute the same thing.
-There is no pass / fail time: the file records the first measurement.
-    python tools/stoi_loss_bench.py [--out profiles/stoi_loss_bench.txt] [--reps 30] [--commit <hash>]"""
+There is no pass / fail time: the file records the first measurement.  --extended measures loss.stoi_loss(extended=True) (ESTOI): the
+same torch graph with the segment step replaced by the two normalisations.
+    python tools/stoi_loss_bench.py [--out profiles/stoi_loss_bench.txt] [--reps 30] [--commit <hash>] [--extended]"""
 import argparse
 import ctypes
 import importlib
@@ -27,6 +28,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stoi_loss_bench.txt"))
 ap.add_argument("--reps", type=int, default=30)
 ap.add_argument("--commit", default="unknown")
+ap.add_argument("--extended", action="store_true")
 args = ap.parse_args()
 assert torch.cuda.is_available(), "needs an MI355X"
 assert args.reps >= 20
@@ -41,7 +43,8 @@ FS, ROWS, T = 16000, 64, 16384
 class TorchStoiLoss:
     """-mean STOI of [rows, T] float32 device tensors from torch ops, batched over the rows; autograd gives the gradient."""
 
-    def __init__(self, fs, device):
+    def __init__(self, fs, device, extended=False):
+        self.extended = extended
         p, q, L, h = R.taps(fs)
         self.p, self.q, self.L = p, q, L
         self.h = torch.from_numpy(h[::-1].copy()).float().to(device)[None, None, :]
@@ -80,12 +83,19 @@ class TorchStoiLoss:
         X, Y = (torch.sqrt(torch.where(fl, P, torch.ones_like(P)) @ self.bands) for P in spec)   # (dead frames: 1, no sqrt(0) in the backward)
         xs, ys = X.unfold(1, R.SEG, 1), Y.unfold(1, R.SEG, 1)                                   # [rows, segments, 15, 30]
         nseg = (nfr - R.SEG + 1).clamp(min=0)
+        sl = torch.arange(xs.shape[1], device=x.device)[None, :] < nseg[:, None]
+        if self.extended:                                                                       # ESTOI: per band over the frames, then per frame over the bands
+            def normalise(a, dim):
+                a = a - a.mean(dim=dim, keepdim=True)
+                return a / (a.norm(dim=dim, keepdim=True) + R.EPS)
+            d = (normalise(normalise(xs, 3), 2) * normalise(normalise(ys, 3), 2)).sum(dim=(2, 3)) / R.SEG
+            score = torch.where(sl, d, torch.zeros_like(d)).sum(dim=1) / nseg.clamp(min=1)
+            return -torch.where(nseg > 0, score, torch.full_like(score, R.SHORT)).mean()
         alpha = xs.norm(dim=3, keepdim=True) / (ys.norm(dim=3, keepdim=True) + R.EPS)
         yp = torch.minimum(alpha * ys, R.CLIP * xs)
         xs = xs - xs.mean(dim=3, keepdim=True)
         yp = yp - yp.mean(dim=3, keepdim=True)
         d = (xs * yp).sum(dim=3) / ((xs.norm(dim=3) + R.EPS) * (yp.norm(dim=3) + R.EPS))
-        sl = torch.arange(d.shape[1], device=x.device)[None, :] < nseg[:, None]
         d = torch.where(sl[:, :, None], d, torch.zeros_like(d))
         score = d.sum(dim=(1, 2)) / (nseg.clamp(min=1) * R.BANDS)
         return -torch.where(nseg > 0, score, torch.full_like(score, R.SHORT)).mean()
@@ -110,8 +120,10 @@ def measure(call):
 
 c, e = R.pair(4, T, FS)
 cd, ed = c.repeat(ROWS // 4, 1).to(dev), e.repeat(ROWS // 4, 1).to(dev)      # (64 rows: the four generated ones, 16 times)
-crit = loss_mod.stoi_loss(sample_rate=FS)
-ref = TorchStoiLoss(FS, dev)
+EXT = {"extended": True} if args.extended else {}
+NAME = "stoi_loss(extended=True)" if args.extended else "stoi_loss"
+crit = loss_mod.stoi_loss(sample_rate=FS, **EXT)
+ref = TorchStoiLoss(FS, dev, args.extended)
 x = ed.clone().requires_grad_(True)
 
 
@@ -134,11 +146,11 @@ gh = x.grad.clone()
 lt = torch_step()
 gt = x.grad.clone()
 torch.cuda.synchronize()
-lines = [f"loss.stoi_loss at {FS} Hz, {ROWS} x {T}, on {torch.cuda.get_device_name(0)} (host {socket.gethostname()}, commit {args.commit}, torch {torch.__version__}), "
+lines = [f"loss.{NAME} at {FS} Hz, {ROWS} x {T}, on {torch.cuda.get_device_name(0)} (host {socket.gethostname()}, commit {args.commit}, torch {torch.__version__}), "
          f"median of {args.reps} eager calls after 3 warm-up calls, HIP events, ms per call",
-         f"  stoi_loss forward + backward (HIP kernels): {measure(hip_step)}",
-         f"  stoi_loss forward alone (no_grad):          {measure(lambda: engine.stoi_loss_forward(cd, ed, FS))}",
-         f"  (a) metrics.stoi alone:                     {measure(lambda: metrics.stoi(cd, ed, sample_rate=FS))}",
+         f"  {NAME} forward + backward (HIP kernels): {measure(hip_step)}",
+         f"  {NAME} forward alone (no_grad):          {measure(lambda: engine.stoi_loss_forward(cd, ed, FS, **EXT))}",
+         f"  (a) metrics.stoi alone, same mode:          {measure(lambda: metrics.stoi(cd, ed, sample_rate=FS, **EXT))}",
          f"  (b) torch ops + autograd, float32, batched: {measure(torch_step)}",
          f"  the two compute the same thing: loss {lh.item():.8f} (HIP) / {lt.item():.8f} (torch ops); max |g_hip - g_torch| / max |g_hip| "
          f"{float((gh - gt).abs().max() / gh.abs().max()):.2e}; max |g_hip| {float(gh.abs().max()):.3e}",

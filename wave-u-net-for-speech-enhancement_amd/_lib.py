@@ -25,6 +25,8 @@ EXPORTS = [
     "wunet_stft_finalize", "wunet_stft_backward",
     "wunet_stoi_tables_bytes", "wunet_stoi_tables_build", "wunet_stoi_scratch_bytes", "wunet_stoi_forward",
     "wunet_stoi_loss_scratch_bytes", "wunet_stoi_loss_saved_bytes", "wunet_stoi_loss_forward", "wunet_stoi_loss_backward",
+    "wunet_estoi_scratch_bytes", "wunet_estoi_forward",
+    "wunet_estoi_loss_scratch_bytes", "wunet_estoi_loss_saved_bytes", "wunet_estoi_loss_forward", "wunet_estoi_loss_backward",
     "wunet_mix_scratch_bytes", "wunet_mix_windows", "wunet_apply_level", "wunet_reverb_windows",
 ]
 
@@ -83,6 +85,10 @@ def declare(lib):
         lib.wunet_stoi_loss_saved_bytes.restype = _sz
         lib.wunet_stoi_loss_forward.argtypes = [_vp, _vp, _sz, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
         lib.wunet_stoi_loss_backward.argtypes = [_vp, _vp, _sz, _sz, _i, _vp, _vp, _vp, _vp]
+    if hasattr(lib, "wunet_estoi_forward"):      # (the same; every call has the signature of its wunet_stoi_* counterpart)
+        for name in ("scratch_bytes", "forward", "loss_scratch_bytes", "loss_saved_bytes", "loss_forward", "loss_backward"):
+            stoi, estoi = getattr(lib, "wunet_stoi_" + name), getattr(lib, "wunet_estoi_" + name)
+            estoi.argtypes, estoi.restype = stoi.argtypes, stoi.restype
     lib.wunet_layer_info.argtypes = [_vp, _i, ctypes.POINTER(_sz), ctypes.POINTER(_i), ctypes.POINTER(_i)]
     lib.wunet_num_conv_layers.argtypes = [_vp]
     for name in ("wunet_op_conv1d", "wunet_op_conv1d_split", "wunet_op_conv1d_bf16"):

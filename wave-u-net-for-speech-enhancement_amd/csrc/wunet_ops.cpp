@@ -6,6 +6,7 @@
 #include "wunet_loss_rows.h"
 #include "wunet_stft.h"
 #include "wunet_stoi.h"
+#include "wunet_estoi.h"
 #include "wunet_mix.h"
 #include "wunet_reverb.h"
 
@@ -250,7 +251,9 @@ int wunet_stft_backward(const float* saved, const double* coefs, const float* gr
     return WUNET_OK;
 }
 
-// ---------------------------------------------------------------------------- STOI per row (wunet_stoi.h)
+// ---------------------------------------------------------------------------- STOI and ESTOI per row (wunet_stoi.h, wunet_estoi.h)
+// One host path for both: `extended` picks the segment stage (estoi_segment_kernel; in the backward estoi_segment_bwd_kernel +
+// estoi_gather_kernel) and the backward's scratch for the segments' gradient blocks - nothing else forks.
 namespace {
 struct StoiShape {
     int p, q, L;            // 10 kHz = fs p / q; L = 0 without resampling
@@ -341,7 +344,7 @@ struct StoiBuffers {
 
 // resampling, mask, spectra and segment sums of both entry points: everything but the final kernel
 int stoi_enqueue(const float* clean, const float* estimate, size_t rows, size_t row_len, const StoiShape& s, const float* tables, const StoiBuffers& B,
-                 hipStream_t st)
+                 bool extended, hipStream_t st)
 {
     const float* w = tables + WUNET_STOI_TAB_W;
     const float* x[2] = {clean, estimate};
@@ -380,8 +383,11 @@ int stoi_enqueue(const float* clean, const float* estimate, size_t rows, size_t 
         WUNET_CHECK_LAUNCH();
         StoiSegArgs G{};
         G.pw = P.pw; G.nk = B.nk; G.M = s.M; G.Fmax = s.Fmax; G.nblk = s.nblk; G.clip = 1.0 + std::pow(10.0, 15.0 / 20.0); G.part = B.part;
-        prof_begin(st, "stoi_segment_kernel", 0.0, 4.0 * 2.0 * s.M * WUNET_STOI_BP);
-        WUNET_LAUNCH(stoi_segment_kernel, dim3(s.nblk, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
+        prof_begin(st, extended ? "estoi_segment_kernel" : "stoi_segment_kernel", 0.0, 4.0 * 2.0 * s.M * WUNET_STOI_BP);
+        if (extended)
+            WUNET_LAUNCH(estoi_segment_kernel, dim3(s.nblk, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
+        else
+            WUNET_LAUNCH(stoi_segment_kernel, dim3(s.nblk, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
         prof_end(st);
         WUNET_CHECK_LAUNCH();
     }
@@ -393,11 +399,11 @@ struct StoiLossShape {
     StoiShape s;
     size_t v_nk, v_kept, v_inv, v_pw, v_reim, saved_bytes;
     size_t f_energy, f_res, f_part, f_score;            // forward
-    size_t b_gr, b_fg, b_g10k;                          // backward
+    size_t b_gr, b_fg, b_g10k, b_blk;                   // backward; b_blk: the segments' gradient blocks (ESTOI)
     size_t scratch_bytes;
 };
 
-int stoi_loss_shape(size_t rows, size_t T, int fs, StoiLossShape& l)
+int stoi_loss_shape(size_t rows, size_t T, int fs, bool extended, StoiLossShape& l)
 {
     if (stoi_shape(rows, T, fs, l.s)) return WUNET_E_ARG;
     const StoiShape& s = l.s;
@@ -420,13 +426,14 @@ int stoi_loss_shape(size_t rows, size_t T, int fs, StoiLossShape& l)
     l.b_gr = take(s.nblk ? (size_t)s.M * WUNET_STOI_BANDS * sizeof(double) : 0);
     l.b_fg = take(s.nblk ? (size_t)s.M * WUNET_STOI_N * sizeof(float) : 0);
     l.b_g10k = take(s.L ? rows * s.Tr * sizeof(float) : 0);
+    l.b_blk = take(extended && s.nblk ? rows * (size_t)(s.Fmax - WUNET_STOI_SEG + 1) * WUNET_ESTOI_BLK * sizeof(double) : 0);
     l.scratch_bytes = o > fwd ? o : fwd;
     return 0;
 }
-}  // namespace
 
-int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
-                       float* out, int* frames_out, void* stream)
+// the bodies of the wunet_stoi_* / wunet_estoi_* entry points below
+int stoi_forward(bool extended, const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                 float* out, int* frames_out, void* stream)
 {
     StoiShape s{};
     if (stoi_shape(rows, row_len, fs, s)) return WUNET_E_ARG;
@@ -437,32 +444,25 @@ int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, s
     StoiBuffers B{};
     B.nk = (int*)(sc + s.o_nk); B.kept = (int*)(sc + s.o_kept); B.energy = (double*)(sc + s.o_energy); B.res = (float*)(sc + s.o_res);
     B.pw = (float*)(sc + s.o_pw); B.part = (double*)(sc + s.o_part);
-    if (const int rc = stoi_enqueue(clean, estimate, rows, row_len, s, tables, B, st)) return rc;
+    if (const int rc = stoi_enqueue(clean, estimate, rows, row_len, s, tables, B, extended, st)) return rc;
     WUNET_LAUNCH(stoi_final_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), 0, st, (const double*)B.part, (const int*)(s.F0 > 0 ? B.nk : nullptr), s.nblk,
                  out, frames_out, (double*)nullptr);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
 }
 
-size_t wunet_stoi_loss_scratch_bytes(size_t rows, size_t row_len, int fs)
+size_t stoi_loss_bytes(bool extended, bool saved, size_t rows, size_t row_len, int fs)
 {
     StoiLossShape l{};
-    if (stoi_loss_shape(rows, row_len, fs, l)) return 0;
-    return l.scratch_bytes;
+    if (stoi_loss_shape(rows, row_len, fs, extended, l)) return 0;
+    return saved ? l.saved_bytes : l.scratch_bytes;
 }
 
-size_t wunet_stoi_loss_saved_bytes(size_t rows, size_t row_len, int fs)
+int stoi_loss_forward(bool extended, const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                      void* saved, float* loss_out, float* per_row_out, int* frames_out, void* stream)
 {
     StoiLossShape l{};
-    if (stoi_loss_shape(rows, row_len, fs, l)) return 0;
-    return l.saved_bytes;
-}
-
-int wunet_stoi_loss_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
-                            void* saved, float* loss_out, float* per_row_out, int* frames_out, void* stream)
-{
-    StoiLossShape l{};
-    if (stoi_loss_shape(rows, row_len, fs, l)) return WUNET_E_ARG;
+    if (stoi_loss_shape(rows, row_len, fs, extended, l)) return WUNET_E_ARG;
     if (!clean || !estimate || !tables || !scratch || !saved || !loss_out || ((size_t)tables & 15) || ((size_t)scratch & 15) || ((size_t)saved & 15))
         return fail(WUNET_E_ARG, "stoi loss: null argument (or tables / scratch / saved that are not 16-byte aligned)");
     const StoiShape& s = l.s;
@@ -472,7 +472,7 @@ int wunet_stoi_loss_forward(const float* clean, const float* estimate, size_t ro
     B.nk = (int*)(sv + l.v_nk); B.kept = (int*)(sv + l.v_kept); B.inv = (int*)(sv + l.v_inv); B.pw = (float*)(sv + l.v_pw); B.reim = (float*)(sv + l.v_reim);
     B.energy = (double*)(sc + l.f_energy); B.res = (float*)(sc + l.f_res); B.part = (double*)(sc + l.f_part);
     double* score = (double*)(sc + l.f_score);
-    if (const int rc = stoi_enqueue(clean, estimate, rows, row_len, s, tables, B, st)) return rc;
+    if (const int rc = stoi_enqueue(clean, estimate, rows, row_len, s, tables, B, extended, st)) return rc;
     WUNET_LAUNCH(stoi_final_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), 0, st, (const double*)B.part, (const int*)(s.F0 > 0 ? B.nk : nullptr), s.nblk,
                  per_row_out, frames_out, score);
     WUNET_CHECK_LAUNCH();
@@ -481,11 +481,11 @@ int wunet_stoi_loss_forward(const float* clean, const float* estimate, size_t ro
     return WUNET_OK;
 }
 
-int wunet_stoi_loss_backward(const void* saved, const float* grad_loss, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
-                             float* grad_estimate, void* stream)
+int stoi_loss_backward(bool extended, const void* saved, const float* grad_loss, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                       float* grad_estimate, void* stream)
 {
     StoiLossShape l{};
-    if (stoi_loss_shape(rows, row_len, fs, l)) return WUNET_E_ARG;
+    if (stoi_loss_shape(rows, row_len, fs, extended, l)) return WUNET_E_ARG;
     if (!saved || !grad_loss || !tables || !scratch || !grad_estimate || ((size_t)tables & 15) || ((size_t)scratch & 15) || ((size_t)saved & 15))
         return fail(WUNET_E_ARG, "stoi loss: null argument (or tables / scratch / saved that are not 16-byte aligned)");
     const StoiShape& s = l.s;
@@ -496,15 +496,31 @@ int wunet_stoi_loss_backward(const void* saved, const float* grad_loss, size_t r
     float* fg = (float*)(sc + l.b_fg);
     float* g10k = s.L ? (float*)(sc + l.b_g10k) : grad_estimate;
     if (s.nblk > 0) {
-        StoiSegBwdArgs G{};
-        G.pw = (const float*)(sv + l.v_pw); G.nk = nk; G.gl = grad_loss; G.M = s.M; G.Fmax = s.Fmax; G.clip = 1.0 + std::pow(10.0, 15.0 / 20.0);
-        G.inv_rows = 1.0 / (double)rows; G.gr = (double*)(sc + l.b_gr);
-        prof_begin(st, "stoi_segment_bwd_kernel", 0.0, 4.0 * 2.0 * s.M * WUNET_STOI_BP + 8.0 * s.M * WUNET_STOI_BANDS);
-        WUNET_LAUNCH(stoi_segment_bwd_kernel, dim3((s.Fmax + WUNET_STOI_FB - 1) / WUNET_STOI_FB, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
-        prof_end(st);
-        WUNET_CHECK_LAUNCH();
+        double* gr = (double*)(sc + l.b_gr);
+        if (extended) {
+            EstoiBwdArgs G{};
+            G.pw = (const float*)(sv + l.v_pw); G.nk = nk; G.gl = grad_loss; G.M = s.M; G.Fmax = s.Fmax; G.nsmax = s.Fmax - WUNET_STOI_SEG + 1;
+            G.inv_rows = 1.0 / (double)rows; G.blk = (double*)(sc + l.b_blk); G.gr = gr;
+            const double blocks = 8.0 * rows * G.nsmax * WUNET_ESTOI_BLK;
+            prof_begin(st, "estoi_segment_bwd_kernel", 0.0, 4.0 * 2.0 * s.M * WUNET_STOI_BP + blocks);
+            WUNET_LAUNCH(estoi_segment_bwd_kernel, dim3((G.nsmax + WUNET_ESTOI_SGB - 1) / WUNET_ESTOI_SGB, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
+            prof_end(st);
+            WUNET_CHECK_LAUNCH();
+            prof_begin(st, "estoi_gather_kernel", 0.0, blocks + 4.0 * s.M * WUNET_STOI_BP + 8.0 * s.M * WUNET_STOI_BANDS);
+            WUNET_LAUNCH(estoi_gather_kernel, dim3((s.Fmax * WUNET_STOI_BANDS + WUNET_THREADS - 1) / WUNET_THREADS, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
+            prof_end(st);
+            WUNET_CHECK_LAUNCH();
+        } else {
+            StoiSegBwdArgs G{};
+            G.pw = (const float*)(sv + l.v_pw); G.nk = nk; G.gl = grad_loss; G.M = s.M; G.Fmax = s.Fmax; G.clip = 1.0 + std::pow(10.0, 15.0 / 20.0);
+            G.inv_rows = 1.0 / (double)rows; G.gr = gr;
+            prof_begin(st, "stoi_segment_bwd_kernel", 0.0, 4.0 * 2.0 * s.M * WUNET_STOI_BP + 8.0 * s.M * WUNET_STOI_BANDS);
+            WUNET_LAUNCH(stoi_segment_bwd_kernel, dim3((s.Fmax + WUNET_STOI_FB - 1) / WUNET_STOI_FB, (unsigned)rows), dim3(WUNET_THREADS), 0, st, G);
+            prof_end(st);
+            WUNET_CHECK_LAUNCH();
+        }
         StoiSpecBwdArgs P{};
-        P.reim = (const float*)(sv + l.v_reim); P.gr = G.gr; P.basis = tables; P.nk = nk; P.M = s.M; P.Fmax = s.Fmax; P.fg = fg;
+        P.reim = (const float*)(sv + l.v_reim); P.gr = gr; P.basis = tables; P.nk = nk; P.M = s.M; P.Fmax = s.Fmax; P.fg = fg;
         const unsigned mtiles = (s.M + WUNET_STFT_FM - 1) / WUNET_STFT_FM;
         prof_begin(st, "stoi_spec_bwd_kernel", 2.0 * s.M * WUNET_STOI_N * 2.0 * WUNET_STOI_BP, 4.0 * (2.0 * s.M * WUNET_STOI_BP + (double)s.M * WUNET_STOI_N));
         WUNET_LAUNCH(stoi_spec_bwd_kernel, dim3(2 * mtiles), dim3(WUNET_THREADS), 0, st, P);
@@ -530,6 +546,51 @@ int wunet_stoi_loss_backward(const void* saved, const float* grad_loss, size_t r
         WUNET_CHECK_LAUNCH();
     }
     return WUNET_OK;
+}
+}  // namespace
+
+int wunet_stoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                       float* out, int* frames_out, void* stream)
+{
+    return stoi_forward(false, clean, estimate, rows, row_len, fs, tables, scratch, out, frames_out, stream);
+}
+
+size_t wunet_stoi_loss_scratch_bytes(size_t rows, size_t row_len, int fs) { return stoi_loss_bytes(false, false, rows, row_len, fs); }
+size_t wunet_stoi_loss_saved_bytes(size_t rows, size_t row_len, int fs) { return stoi_loss_bytes(false, true, rows, row_len, fs); }
+
+int wunet_stoi_loss_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                            void* saved, float* loss_out, float* per_row_out, int* frames_out, void* stream)
+{
+    return stoi_loss_forward(false, clean, estimate, rows, row_len, fs, tables, scratch, saved, loss_out, per_row_out, frames_out, stream);
+}
+
+int wunet_stoi_loss_backward(const void* saved, const float* grad_loss, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                             float* grad_estimate, void* stream)
+{
+    return stoi_loss_backward(false, saved, grad_loss, rows, row_len, fs, tables, scratch, grad_estimate, stream);
+}
+
+size_t wunet_estoi_scratch_bytes(size_t rows, size_t row_len, int fs) { return wunet_stoi_scratch_bytes(rows, row_len, fs); }
+
+int wunet_estoi_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                        float* out, int* frames_out, void* stream)
+{
+    return stoi_forward(true, clean, estimate, rows, row_len, fs, tables, scratch, out, frames_out, stream);
+}
+
+size_t wunet_estoi_loss_scratch_bytes(size_t rows, size_t row_len, int fs) { return stoi_loss_bytes(true, false, rows, row_len, fs); }
+size_t wunet_estoi_loss_saved_bytes(size_t rows, size_t row_len, int fs) { return stoi_loss_bytes(true, true, rows, row_len, fs); }
+
+int wunet_estoi_loss_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                             void* saved, float* loss_out, float* per_row_out, int* frames_out, void* stream)
+{
+    return stoi_loss_forward(true, clean, estimate, rows, row_len, fs, tables, scratch, saved, loss_out, per_row_out, frames_out, stream);
+}
+
+int wunet_estoi_loss_backward(const void* saved, const float* grad_loss, size_t rows, size_t row_len, int fs, const float* tables, void* scratch,
+                              float* grad_estimate, void* stream)
+{
+    return stoi_loss_backward(true, saved, grad_loss, rows, row_len, fs, tables, scratch, grad_estimate, stream);
 }
 
 // ---------------------------------------------------------------------------- fused Adam

@@ -25,6 +25,7 @@
 //   stoi_unframe_kernel       one thread per 10 kHz sample: its at most two kept frames x the at most two spectral frames over them
 //   stoi_resample_bwd_kernel  the transposed polyphase filter, one thread per input sample, double accumulation
 // fp32 operands and MFMA accumulation, every reduction in double and in one fixed order, no atomics: bit-identical run to run.
+// ESTOI (extended=True) is this sequence with another segment stage, forward and backward: wunet_estoi.h.
 #pragma once
 #include "wunet_stft.h"
 

@@ -564,55 +564,59 @@ class Engine:
             self._stoi_tables_cache[key] = tables
         return tables
 
-    def stoi(self, clean, estimate, sample_rate=16000, return_frames=False):
-        """include/wunet_hip.h: wunet_stoi_forward.  The last dimension is the utterance, all leading ones are flattened.  Returns float32
-        [rows] (and int32 [rows], the spectral frame count of every row, with return_frames).  Nothing is read back to the host."""
+    def _stoi_call(self, extended, name):
+        """wunet_stoi_<name>, or wunet_estoi_<name> with `extended` (ESTOI: the same arguments, the same tables)."""
+        return getattr(self.lib, ("wunet_estoi_" if extended else "wunet_stoi_") + name)
+
+    def stoi(self, clean, estimate, sample_rate=16000, return_frames=False, extended=False):
+        """include/wunet_hip.h: wunet_stoi_forward (extended: wunet_estoi_forward).  The last dimension is the utterance, all leading ones
+        are flattened.  Returns float32 [rows] (and int32 [rows], the spectral frame count of every row, with return_frames).  Nothing is
+        read back to the host."""
         R, T, dev = self._wave_pair("stoi", clean, estimate, "estimate")
         fs = int(sample_rate)
         tables = self.stoi_tables(fs, dev)
-        scratch = torch.empty(self._sized(self.lib.wunet_stoi_scratch_bytes(R, T, fs)) // 8, dtype=torch.float64, device=dev)
+        scratch = torch.empty(self._sized(self._stoi_call(extended, "scratch_bytes")(R, T, fs)) // 8, dtype=torch.float64, device=dev)
         out = torch.empty(R, dtype=torch.float32, device=dev)
         frames = torch.empty(R, dtype=torch.int32, device=dev) if return_frames else None
         with self._device_guard(dev):
-            self._check(self.lib.wunet_stoi_forward(clean.data_ptr(), estimate.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
-                                                    out.data_ptr(), frames.data_ptr() if frames is not None else None, self._stream(dev)))
+            self._check(self._stoi_call(extended, "forward")(clean.data_ptr(), estimate.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
+                                                             out.data_ptr(), frames.data_ptr() if frames is not None else None, self._stream(dev)))
         return (out, frames) if return_frames else out
 
-    def stoi_loss_forward(self, clean, enhanced, sample_rate=16000, per_row=False, with_backward=True):
-        """include/wunet_hip.h: wunet_stoi_loss_forward.  The last dimension is the utterance, all leading ones are flattened.  Returns
-        (loss, saved, per_row): loss - device scalar, -mean of the rows' STOI; saved - the buffer `stoi_loss_backward` needs (kept even
-        with with_backward=False: the forward writes its spectra there); per_row - float32 [rows] with per_row=True, else None."""
+    def stoi_loss_forward(self, clean, enhanced, sample_rate=16000, per_row=False, with_backward=True, extended=False):
+        """include/wunet_hip.h: wunet_stoi_loss_forward (extended: wunet_estoi_loss_forward).  The last dimension is the utterance, all
+        leading ones are flattened.  Returns (loss, saved, per_row): loss - device scalar, -mean of the rows' STOI; saved - the buffer
+        `stoi_loss_backward` needs (kept even with with_backward=False: the forward writes its spectra there); per_row - float32 [rows]
+        with per_row=True, else None."""
         R, T, dev = self._wave_pair("stoi loss", clean, enhanced)
         fs = int(sample_rate)
         tables = self.stoi_tables(fs, dev)
-        lib = self.lib
-        scratch = torch.empty(self._sized(lib.wunet_stoi_loss_scratch_bytes(R, T, fs)) // 8, dtype=torch.float64, device=dev)
-        saved = torch.empty(self._sized(lib.wunet_stoi_loss_saved_bytes(R, T, fs)) // 4, dtype=torch.float32, device=dev)
+        scratch = torch.empty(self._sized(self._stoi_call(extended, "loss_scratch_bytes")(R, T, fs)) // 8, dtype=torch.float64, device=dev)
+        saved = torch.empty(self._sized(self._stoi_call(extended, "loss_saved_bytes")(R, T, fs)) // 4, dtype=torch.float32, device=dev)
         out = torch.empty((), dtype=torch.float32, device=dev)
         rows = torch.empty(R, dtype=torch.float32, device=dev) if per_row else None
         with self._device_guard(dev):
-            self._check(lib.wunet_stoi_loss_forward(clean.data_ptr(), enhanced.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
-                                                    saved.data_ptr(), out.data_ptr(), rows.data_ptr() if rows is not None else None, None,
-                                                    self._stream(dev)))
+            self._check(self._stoi_call(extended, "loss_forward")(clean.data_ptr(), enhanced.data_ptr(), R, T, fs, tables.data_ptr(),
+                                                                  scratch.data_ptr(), saved.data_ptr(), out.data_ptr(),
+                                                                  rows.data_ptr() if rows is not None else None, None, self._stream(dev)))
         return out, (saved if with_backward else None), rows
 
-    def stoi_loss_backward(self, shape, saved, grad_loss, sample_rate=16000):
-        """d loss / d enhanced (a tensor of `shape`, every sample written) of the `stoi_loss_forward` that produced `saved`, times
-        grad_loss (a scalar tensor)."""
+    def stoi_loss_backward(self, shape, saved, grad_loss, sample_rate=16000, extended=False):
+        """d loss / d enhanced (a tensor of `shape`, every sample written) of the `stoi_loss_forward` that produced `saved` (with the
+        same `extended`), times grad_loss (a scalar tensor)."""
         fs = int(sample_rate)
         T = shape[-1]
         dev = saved.device
         g = torch.empty(shape, dtype=torch.float32, device=dev)
         R = g.numel() // T
-        lib = self.lib
-        if saved.dtype != torch.float32 or not saved.is_contiguous() or saved.numel() * 4 != lib.wunet_stoi_loss_saved_bytes(R, T, fs):
+        if saved.dtype != torch.float32 or not saved.is_contiguous() or saved.numel() * 4 != self._stoi_call(extended, "loss_saved_bytes")(R, T, fs):
             raise WunetError(f"stoi loss: saved is not the buffer of stoi_loss_forward on {tuple(shape)} at {fs} Hz")
         tables = self.stoi_tables(fs, dev)
-        scratch = torch.empty(self._sized(lib.wunet_stoi_loss_scratch_bytes(R, T, fs)) // 8, dtype=torch.float64, device=dev)
+        scratch = torch.empty(self._sized(self._stoi_call(extended, "loss_scratch_bytes")(R, T, fs)) // 8, dtype=torch.float64, device=dev)
         gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
         with self._device_guard(dev):
-            self._check(lib.wunet_stoi_loss_backward(saved.data_ptr(), gl.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
-                                                     g.data_ptr(), self._stream(dev)))
+            self._check(self._stoi_call(extended, "loss_backward")(saved.data_ptr(), gl.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
+                                                                   g.data_ptr(), self._stream(dev)))
         return g
 
     # ------------------------------------------------------------------ fused Adam, data input

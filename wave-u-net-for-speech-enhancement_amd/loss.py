@@ -26,6 +26,12 @@ ignores level, and phase below its 26 ms frames, so it is usually one term besid
 
     "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "weighted_loss",
                       "args": {"terms": [["l1_loss", 1.0], ["stoi_loss", 0.25, {"sample_rate": 16000}]]}}
+
+`stoi_loss(extended=True)`: minus the mean ESTOI (Jensen & Taal 2016; as a loss: Kolbaek et al. 2018), exactly as
+`metrics.stoi(extended=True)` computes it (include/wunet_hip.h: wunet_estoi_loss_*).  No min(alpha Y, clip X): no kink and no clipped
+items that pass nothing; a band row or a frame column of a segment whose centred norm is exactly 0 passes no gradient (autograd: NaN):
+
+    ["stoi_loss", 0.25, {"sample_rate": 16000, "extended": true}]
 """
 import torch
 import torch.nn as nn
@@ -165,40 +171,43 @@ def stft_loss(fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths
 
 class _StoiLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, sample_rate, engine, clean, enhanced):
+    def forward(ctx, sample_rate, extended, engine, clean, enhanced):
         if clean.requires_grad:                 # (before anything runs)
             raise NotImplementedError("stoi_loss: no gradient with respect to `clean` (the target also sets the silent-frame mask and "
                                       "the clipping level, so it is not minus the gradient of `enhanced`): detach it")
         clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
-        loss, saved, _ = engine.stoi_loss_forward(clean_c, enh_c, sample_rate)
-        ctx.sample_rate, ctx.engine, ctx.shape = sample_rate, engine, tuple(enh_c.shape)
+        loss, saved, _ = engine.stoi_loss_forward(clean_c, enh_c, sample_rate, extended=extended)
+        ctx.sample_rate, ctx.extended, ctx.engine, ctx.shape = sample_rate, extended, engine, tuple(enh_c.shape)
         ctx.save_for_backward(saved)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
         saved, = ctx.saved_tensors
-        g = ctx.engine.stoi_loss_backward(ctx.shape, saved, grad_loss, ctx.sample_rate) if ctx.needs_input_grad[3] else None
-        return None, None, None, g
+        g = None
+        if ctx.needs_input_grad[4]:
+            g = ctx.engine.stoi_loss_backward(ctx.shape, saved, grad_loss, ctx.sample_rate, extended=ctx.extended)
+        return None, None, None, None, g
 
 
 class HipStoiLoss(nn.Module):
-    """loss(clean, enhanced) -> -mean over rows of STOI (pystoi, extended=False) at `sample_rate`; the last dimension is the utterance.
-    Gradient with respect to `enhanced` only.  The first call on a device builds the rate's tables: capture a step graph after one
-    eager call, as for stft_loss."""
+    """loss(clean, enhanced) -> -mean over rows of STOI (pystoi, extended=False; ESTOI with extended=True) at `sample_rate`; the last
+    dimension is the utterance.  Gradient with respect to `enhanced` only.  The first call on a device builds the rate's tables (shared
+    by both modes): capture a step graph after one eager call, as for stft_loss."""
 
-    def __init__(self, sample_rate=16000):
+    def __init__(self, sample_rate=16000, extended=False):
         super().__init__()
         self.sample_rate = check_stoi_rate(sample_rate)
+        self.extended = bool(extended)
         self._engine_override = None
 
     def forward(self, clean, enhanced):
         engine = self._engine_override if self._engine_override is not None else default_engine()
-        return _StoiLossFn.apply(self.sample_rate, engine, clean, enhanced)
+        return _StoiLossFn.apply(self.sample_rate, self.extended, engine, clean, enhanced)
 
 
-def stoi_loss(sample_rate=16000):
-    return HipStoiLoss(sample_rate)
+def stoi_loss(sample_rate=16000, extended=False):
+    return HipStoiLoss(sample_rate, extended)
 
 
 class WeightedLoss(nn.Module):

@@ -43,12 +43,16 @@ def stft_magnitude(x, n_fft=320, hop=160, win_length=320, engine=None):
 
 
 @torch.no_grad()
-def stoi(clean, estimate, sample_rate=16000, return_frames=False, engine=None):
+def stoi(clean, estimate, sample_rate=16000, return_frames=False, engine=None, extended=False):
     """Short-time objective intelligibility of `estimate` against `clean`, per row: Taal et al. 2011 as pystoi computes it for
     stoi(clean, estimate, sample_rate, extended=False) - what the reference's validation epoch calls on the host at 16 kHz
     (util/utils.py:116-117) - on the device (include/wunet_hip.h: wunet_stoi_forward), without a host read: a row with fewer than 30
     spectral frames after the removal of its silent frames scores 1e-5 (pystoi's value; its warning is not reproduced).
     Returns float32 [rows]; with return_frames also int32 [rows], the spectral frame count of every row.  The tables of a
-    (device, sample_rate) are built on the first call; later calls allocate from torch's caching allocator only and can be captured."""
+    (device, sample_rate) are built on the first call; later calls allocate from torch's caching allocator only and can be captured.
+    extended=True: ESTOI (Jensen & Taal 2016), the other branch of the same pystoi call (include/wunet_hip.h: wunet_estoi_forward) - the
+    same resampler, silent-frame removal, spectra, frame counts and tables; every segment's 30 x 15 block of band magnitudes is
+    normalised per band and then per frame instead of clipped.  pystoi's EPS * randn dither before each normalisation is not added:
+    EPS stands in the denominators, a difference at the 1e-15 level."""
     engine = engine if engine is not None else default_engine()
-    return engine.stoi(clean.detach().contiguous(), estimate.detach().contiguous(), sample_rate, return_frames)
+    return engine.stoi(clean.detach().contiguous(), estimate.detach().contiguous(), sample_rate, return_frames, extended=bool(extended))

@@ -32,7 +32,8 @@ Differences from the reference loop, all on the f2 list:
     "si_sdr" the optional key `"stoi": "report"` also appends (mean STOI of the noisy recordings, mean STOI of the enhanced ones) to
     `validation_stoi` every validation epoch and leaves the score alone; `"stoi": "score"` makes the mean STOI of the enhanced
     recordings the epoch's score (`validation_scores` holds it, "find_max" applies as in the reference).  metrics.stoi at
-    `"custom": {"sample_rate": 16000}` (the reference hard-codes 16 kHz); still one device->host read per validation epoch;
+    `"custom": {"sample_rate": 16000}` (the reference hard-codes 16 kHz); still one device->host read per validation epoch.
+    `"stoi_extended": true` beside "stoi" makes both calls ESTOI (metrics.stoi(extended=True)); it needs the "stoi" key and a bool;
   * checkpoints keep the reference's names and keys (base_trainer.py:83-124) so either side can resume; only rank 0 writes.
 """
 import os
@@ -110,6 +111,11 @@ class Trainer:
             raise ValueError(f'trainer config "validation.stoi" must be "report" or "score" (got {self.validation_stoi_mode!r})')
         if self.validation_stoi_mode is not None and self.validation_metric != "si_sdr":
             raise ValueError('trainer config "validation.stoi" needs "validation.metric": "si_sdr" beside it')
+        self.validation_stoi_extended = vcfg.get("stoi_extended", False)
+        if not isinstance(self.validation_stoi_extended, bool):
+            raise ValueError(f'trainer config "validation.stoi_extended" must be true or false (got {self.validation_stoi_extended!r})')
+        if "stoi_extended" in vcfg and self.validation_stoi_mode is None:
+            raise ValueError('trainer config "validation.stoi_extended" needs "validation.stoi": "report" or "score" beside it')
         self.validation_sample_rate = int((vcfg.get("custom") or {}).get("sample_rate", 16000))
         self.validation_stoi = []     # with "validation.stoi": (mean STOI noisy, mean STOI enhanced) per validation epoch
         self.epochs = tcfg["epochs"]
@@ -216,8 +222,9 @@ class Trainer:
                 enhanced = enhance(model, mixture, self.validation_sample_length)
                 gains.append(metrics.si_sdr_improvement(clean, mixture, enhanced, engine=engine))
                 if self.validation_stoi_mode is not None:
-                    stois.append(torch.cat([metrics.stoi(clean, mixture, sample_rate=fs, engine=engine).reshape(-1),
-                                            metrics.stoi(clean, enhanced, sample_rate=fs, engine=engine).reshape(-1)]))
+                    ext = self.validation_stoi_extended
+                    stois.append(torch.cat([metrics.stoi(clean, mixture, sample_rate=fs, engine=engine, extended=ext).reshape(-1),
+                                            metrics.stoi(clean, enhanced, sample_rate=fs, engine=engine, extended=ext).reshape(-1)]))
         finally:
             for m, was in modes:                         # exactly the flags of before: a frozen BatchNorm layer stays frozen
                 m.training = was
