@@ -197,6 +197,46 @@ int wunet_stft_backward(const float* saved, const double* coefs, const float* gr
                         int win_length, double clamp, const float* basis, void* scratch, float* grad_enhanced, int accumulate,
                         void* stream);
 
+/* Power-law compressed spectral loss with a complex (phase-aware) term (Braun & Tashev 2021, "A consolidated view of loss functions
+ * for supervised deep learning-based speech enhancement"; the DNS-challenge baseline loss).  No reference counterpart.  One
+ * resolution (N, H, W) frames and transforms clean = c and enhanced = e exactly as the STFT loss above does (same window, centring,
+ * reflect padding, frames f = 0 .. T / H, bins b = 0 .. N/2, N/2 <= T - 1, and the basis of wunet_stft_basis).  Per bin of either signal:
+ *   P = re^2 + im^2,  Pc = max(P, clamp),  A = Pc^(compress / 2),  Z = (re + i im) Pc^((compress - 1) / 2);
+ *   L_i = mean over rows, frames and bins of (1 - complex_weight) (A_c - A_e)^2 + complex_weight |Z_c - Z_e|^2;
+ *   loss = (1 / n_res) sum_i L_i.
+ * Gradient with respect to `enhanced` only.  It follows torch.clamp: where P_e < clamp the factors Pc^.. are constants - A_e passes no
+ * gradient and Z_e is linear in (re, im), so an all-zero enhanced row gets a finite, non-zero gradient.  Equal signals give exactly 0
+ * and an all-zero gradient.
+ * Supported: the STFT loss's N / H / W, 1 .. WUNET_STFT_MAX_RESOLUTIONS resolutions, 0 < compress <= 1, 0 <= complex_weight <= 1, clamp
+ * finite and > 0; anything else is WUNET_E_ARG with a message.
+ * Arithmetic: fp32 operands and fp32 MFMA accumulation against the STFT loss's basis; the per-bin powers in double, A and Z rounded to
+ * float32 once (the backward recomputes the enhanced side to the same bits); every reduction and coefficient in double; no atomics,
+ * every sum has one fixed order: bit-identical run to run.
+ * The calls of one loss (the buffers' byte sizes are passed and checked: a buffer sized for another resolution is refused):
+ *   per resolution:  wunet_cspec_forward writes its partial sums to `scratch` (scratch_bytes >= wunet_cspec_scratch_bytes(..)) and, when
+ *                    `saved` is given (saved_bytes == wunet_cspec_saved_bytes(..); else NULL and 0), five planes [rows * F][BP] for the
+ *                    backward: re_e, im_e, A_c, Re Z_c, Im Z_c;
+ *   once:            wunet_cspec_finalize over the TABLE of the resolutions' scratch buffers (host arrays of n_res entries, read during
+ *                    the call): the loss, accumulated over the resolutions in double and rounded once, and (coefs != NULL)
+ *                    coefs[n_res][WUNET_CSPEC_COEFS] = (1 - complex_weight) / (n_res count), complex_weight / (n_res count), the mean
+ *                    of (A_c - A_e)^2, the mean of |Z_c - Z_e|^2, with count = rows F bins;
+ *   per resolution:  wunet_cspec_backward(saved, .., coefs + i * WUNET_CSPEC_COEFS, grad_loss, ..): the adjoint GEMM into `scratch`
+ *                    (scratch_bytes >= wunet_cspec_scratch_bytes(.., with_backward = 1); the forward's buffer may be reused after the
+ *                    finalize), then the STFT loss's overlap-add; grad_enhanced = (accumulate ? grad_enhanced : 0) + grad_loss[0] *
+ *                    d loss_i / d e, so several resolutions sum in the order of the calls.  compress and clamp: the forward's.
+ * Caller-owned memory, no allocation, no synchronisation, no host read-back: every call can be captured. */
+#define WUNET_CSPEC_COEFS 4      /* two gradient scales, two term values per resolution, double */
+size_t wunet_cspec_scratch_bytes(size_t rows, size_t row_len, int n_fft, int hop, int with_backward);
+size_t wunet_cspec_saved_bytes(size_t rows, size_t row_len, int n_fft, int hop);
+int wunet_cspec_forward(const float* clean, const float* enhanced, size_t rows, size_t row_len, int n_fft, int hop, int win_length,
+                        double compress, double clamp, const float* basis, void* scratch, size_t scratch_bytes, float* saved,
+                        size_t saved_bytes, void* stream);
+int wunet_cspec_finalize(int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop,
+                         double complex_weight, float* loss_out, double* coefs, void* stream);
+int wunet_cspec_backward(const float* saved, size_t saved_bytes, const double* coefs, const float* grad_loss, size_t rows, size_t row_len,
+                         int n_fft, int hop, int win_length, double compress, double clamp, const float* basis, void* scratch,
+                         size_t scratch_bytes, float* grad_enhanced, int accumulate, void* stream);
+
 /* STOI per row (no reference counterpart on the device: the reference's validation epoch calls pystoi on the host per recording,
  * trainer/trainer.py:128-143, util/utils.py:116-117): Taal et al. 2011 with pystoi's choices for stoi(clean, estimate, fs,
  * extended=False) - resample_poly to 10 kHz with pystoi's Kaiser filter, removal of the frames (256 / hop 128, hanning(258)[1:-1])

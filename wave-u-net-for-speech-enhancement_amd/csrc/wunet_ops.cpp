@@ -5,6 +5,7 @@
 #include "wunet_h3_elem.h"
 #include "wunet_loss_rows.h"
 #include "wunet_stft.h"
+#include "wunet_cspec.h"
 #include "wunet_stoi.h"
 #include "wunet_estoi.h"
 #include "wunet_mix.h"
@@ -239,6 +240,118 @@ int wunet_stft_backward(const float* saved, const double* coefs, const float* gr
     B.ktiles = (unsigned)((s.k1 - s.k0 + WUNET_STFT_BWN - 1) / WUNET_STFT_BWN);           // (at most 32; mtiles < 2^25)
     prof_begin(st, "stft_bwd_kernel", 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP, 4.0 * (3.0 * s.M * s.BP + (double)(s.k1 - s.k0) * (2.0 * s.BP + s.M)));
     WUNET_LAUNCH(stft_bwd_kernel, dim3(B.ktiles * s.mtiles), dim3(WUNET_THREADS), 0, st, B);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    StftOlaArgs O{};
+    O.scratch = (const float*)scratch; O.gl = grad_loss; O.g = grad_enhanced; O.T = row_len; O.total = rows * row_len; O.F = s.F;
+    O.N = n_fft; O.H = hop; O.k0 = s.k0; O.k1 = s.k1; O.accumulate = accumulate != 0;
+    prof_begin(st, "stft_ola_kernel", 0.0, 4.0 * ((double)s.M * (s.k1 - s.k0) + (accumulate ? 2.0 : 1.0) * rows * row_len));
+    WUNET_LAUNCH(stft_ola_kernel, dim3((unsigned)((O.total + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st, O);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- compressed spectral loss (wunet_cspec.h)
+// The resolutions, the basis, the frame tiling and the overlap-add are the STFT loss's (stft_shape above); only the partials (two
+// doubles per block) and the saved planes (five) differ.
+namespace {
+inline size_t cspec_fwd_bytes(const StftShape& s) { return stft_nparts(s) * 2 * sizeof(double); }
+inline size_t cspec_bwd_bytes(const StftShape& s, int n_fft) { return (size_t)s.M * n_fft * sizeof(float); }
+inline size_t cspec_saved(const StftShape& s) { return (size_t)WUNET_CSPEC_PLANES * s.M * s.BP * sizeof(float); }
+int cspec_knobs(double compress, double clamp)
+{
+    if (!(compress > 0.0) || compress > 1.0) return fail(WUNET_E_ARG, "cspec: compress must be in (0, 1] (got %g)", compress);
+    if (!(clamp > 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "cspec: clamp must be finite and > 0 (got %g)", clamp);
+    return 0;
+}
+}  // namespace
+
+size_t wunet_cspec_scratch_bytes(size_t rows, size_t row_len, int n_fft, int hop, int with_backward)
+{
+    StftShape s{};
+    if (row_len == 0 || stft_shape(rows, row_len, n_fft, hop, 1, s)) return 0;
+    const size_t fwd = cspec_fwd_bytes(s), bwd = cspec_bwd_bytes(s, n_fft);
+    return with_backward && bwd > fwd ? bwd : fwd;
+}
+
+size_t wunet_cspec_saved_bytes(size_t rows, size_t row_len, int n_fft, int hop)
+{
+    StftShape s{};
+    if (row_len == 0 || stft_shape(rows, row_len, n_fft, hop, 1, s)) return 0;
+    return cspec_saved(s);
+}
+
+int wunet_cspec_forward(const float* clean, const float* enhanced, size_t rows, size_t row_len, int n_fft, int hop, int win_length,
+                        double compress, double clamp, const float* basis, void* scratch, size_t scratch_bytes, float* saved,
+                        size_t saved_bytes, void* stream)
+{
+    StftShape s{};
+    if (row_len == 0) return fail(WUNET_E_ARG, "cspec: row_len must be > 0");
+    if (stft_shape(rows, row_len, n_fft, hop, win_length, s) || cspec_knobs(compress, clamp)) return WUNET_E_ARG;
+    if (!clean || !enhanced || !basis || ((size_t)basis & 15)) return fail(WUNET_E_ARG, "cspec: null argument (or a basis that is not 16-byte aligned)");
+    if (!scratch || scratch_bytes < cspec_fwd_bytes(s))
+        return fail(WUNET_E_ARG, "cspec: the forward needs %zu bytes of scratch for this resolution (got %zu)", cspec_fwd_bytes(s), scratch_bytes);
+    if (saved ? saved_bytes != cspec_saved(s) : saved_bytes != 0)
+        return fail(WUNET_E_ARG, "cspec: saved must be the %zu bytes of wunet_cspec_saved_bytes for this resolution, or NULL and 0 (got %zu)",
+                    cspec_saved(s), saved_bytes);
+    CspecFwdArgs C{};
+    StftFwdArgs& A = C.S;
+    A.c = clean; A.e = enhanced; A.basis = basis; A.T = row_len; A.M = s.M; A.F = s.F; A.N = n_fft; A.H = hop; A.BP = s.BP; A.bins = s.bins;
+    A.k0 = s.k0; A.k1 = s.k1; A.clamp = (float)clamp; A.part = (double*)scratch; A.saved = saved;
+    C.hs = 0.5 * (compress - 1.0);
+    const dim3 grid(s.mtiles, (unsigned)(s.BP / WUNET_STFT_BN));
+    prof_begin((hipStream_t)stream, "cspec_fwd_kernel", 2.0 * 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP,
+               4.0 * (2.0 * rows * row_len + (double)(s.k1 - s.k0) * 2.0 * s.BP + (saved ? (double)WUNET_CSPEC_PLANES * s.M * s.BP : 0.0)));
+    WUNET_LAUNCH(cspec_fwd_kernel, grid, dim3(WUNET_THREADS), 0, (hipStream_t)stream, C);
+    prof_end((hipStream_t)stream);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_cspec_finalize(int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop,
+                         double complex_weight, float* loss_out, double* coefs, void* stream)
+{
+    if (n_res < 1 || n_res > WUNET_STFT_MAX_RES) return fail(WUNET_E_ARG, "cspec: 1 .. %d resolutions per call (got %d)", WUNET_STFT_MAX_RES, n_res);
+    if (!scratch || !n_fft || !hop || !loss_out) return fail(WUNET_E_ARG, "cspec: null argument");
+    if (!(complex_weight >= 0.0) || complex_weight > 1.0) return fail(WUNET_E_ARG, "cspec: complex_weight must be in [0, 1] (got %g)", complex_weight);
+    if (row_len == 0) return fail(WUNET_E_ARG, "cspec: row_len must be > 0");
+    CspecFinalArgs A{};
+    for (int i = 0; i < n_res; ++i) {
+        StftShape s{};
+        if (stft_shape(rows, row_len, n_fft[i], hop[i], 1, s)) return WUNET_E_ARG;
+        if (!scratch[i]) return fail(WUNET_E_ARG, "cspec: null scratch of resolution %d", i);
+        A.part[i] = (const double*)scratch[i];
+        A.nparts[i] = (unsigned)stft_nparts(s);
+        A.count[i] = (double)s.M * (double)s.bins;
+    }
+    A.n_res = n_res; A.lambda = complex_weight; A.loss = loss_out; A.coefs = coefs;
+    WUNET_LAUNCH(cspec_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, (hipStream_t)stream, A);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_cspec_backward(const float* saved, size_t saved_bytes, const double* coefs, const float* grad_loss, size_t rows, size_t row_len,
+                         int n_fft, int hop, int win_length, double compress, double clamp, const float* basis, void* scratch,
+                         size_t scratch_bytes, float* grad_enhanced, int accumulate, void* stream)
+{
+    StftShape s{};
+    if (row_len == 0) return fail(WUNET_E_ARG, "cspec: row_len must be > 0");
+    if (stft_shape(rows, row_len, n_fft, hop, win_length, s) || cspec_knobs(compress, clamp)) return WUNET_E_ARG;
+    if (!saved || !coefs || !grad_loss || !basis || !grad_enhanced || ((size_t)basis & 15))
+        return fail(WUNET_E_ARG, "cspec: null argument (or a basis that is not 16-byte aligned)");
+    if (saved_bytes != cspec_saved(s))
+        return fail(WUNET_E_ARG, "cspec: saved must be the %zu bytes of wunet_cspec_saved_bytes for this resolution (got %zu)", cspec_saved(s), saved_bytes);
+    if (!scratch || scratch_bytes < cspec_bwd_bytes(s, n_fft))
+        return fail(WUNET_E_ARG, "cspec: the backward needs %zu bytes of scratch for this resolution (got %zu)", cspec_bwd_bytes(s, n_fft), scratch_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    CspecBwdArgs B{};
+    B.saved = saved; B.coefs = coefs; B.basis = basis; B.M = s.M; B.N = n_fft; B.BP = s.BP; B.bins = s.bins; B.k0 = s.k0; B.k1 = s.k1;
+    B.clamp = (float)clamp; B.compress = compress; B.hs = 0.5 * (compress - 1.0); B.scratch = (float*)scratch;
+    B.ktiles = (unsigned)((s.k1 - s.k0 + WUNET_STFT_BWN - 1) / WUNET_STFT_BWN);           // (at most 32; mtiles < 2^25)
+    prof_begin(st, "cspec_bwd_kernel", 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP,
+               4.0 * ((double)WUNET_CSPEC_PLANES * s.M * s.BP + (double)(s.k1 - s.k0) * (2.0 * s.BP + s.M)));
+    WUNET_LAUNCH(cspec_bwd_kernel, dim3(B.ktiles * s.mtiles), dim3(WUNET_THREADS), 0, st, B);
     prof_end(st);
     WUNET_CHECK_LAUNCH();
     StftOlaArgs O{};

@@ -7,6 +7,7 @@
 //                       the epilogue forms the magnitudes and one partial (three doubles) of the block's sums
 //   stft_final_kernel   ONE block: the partials of every resolution in block order -> sc, mag, the loss, the gradient coefficients
 //   stft_bwd_kernel     adjoint GEMM [rows F][2 bins] x basis^T -> scratch [rows F][N]; A is formed in the loader from the saved spectra
+//                       (dft_adjoint_gemm: the loop is shared with wunet_cspec.h, which brings its own bins)
 //   stft_ola_kernel     overlap-add as a gather: every sample sums its frames' contributions in frame order, the reflected ones too
 // fp32 operands and accumulation, every reduction and coefficient in double, no atomics: bit-identical run to run.
 #pragma once
@@ -274,34 +275,43 @@ __device__ __forceinline__ void stft_bin_grad(float re, float im, float sc, floa
     }
 }
 
-// grid ktiles * (M / 64 rounded up), the k tiles of one frame tile next to each other (they read the same saved spectra): out[m][k] = sum_b dRe[m][b] cos[k][b] + dIm[m][b] (-sin)[k][b].  K tile = 8 bins:
-// Gs[64 frames][8 dRe | 8 dIm], Bt[8 cos | 8 -sin][128 k] (the basis tile transposed on its way into LDS).
-static __global__ __launch_bounds__(WUNET_THREADS) void stft_bwd_kernel(StftBwdArgs A)
+// What stft_bwd_kernel's loader forms its A from: PLANES saved planes [M][BP] per bin, pad(q) what a row beyond M loads of plane q,
+// grad() the bin's (dRe, dIm) from its PLANES values.
+struct StftBinGrad {
+    static constexpr int PLANES = 3;             // re_e, im_e, S_c
+    float clamp;
+    double ca, cb;
+    __device__ __forceinline__ static float pad(int q) { return q == 2 ? 1.0f : 0.0f; }
+    __device__ __forceinline__ void grad(const float (&r)[PLANES], float& dre, float& dim) const { stft_bin_grad(r[0], r[1], r[2], clamp, ca, cb, dre, dim); }
+};
+
+// One block of the adjoint GEMM of every loss on this basis (stft_bwd_kernel, cspec_bwd_kernel).  grid ktiles * (M / 64 rounded up), the
+// k tiles of one frame tile next to each other (they read the same saved spectra): out[m][k] = sum_b dRe[m][b] cos[k][b] + dIm[m][b] (-sin)[k][b].  K tile = 8 bins:
+// Gs[64 frames][8 dRe | 8 dIm] (WUNET_STFT_FM * WUNET_STFT_AS floats), Bt[8 cos | 8 -sin][128 k] (the basis tile transposed on its way
+// into LDS; WUNET_STFT_KT * WUNET_STFT_BWS floats).  Bin: see StftBinGrad.
+template <class Bin>
+__device__ __forceinline__ void dft_adjoint_gemm(const Bin& bin, const float* saved, const float* basis, unsigned M, unsigned ktiles, int N, int BP, int bins,
+                                                 int k0, int k1, float* scratch, float* Gs, float* Bt)
 {
-    __shared__ __attribute__((aligned(16))) float Gs[WUNET_STFT_FM * WUNET_STFT_AS];
-    __shared__ __attribute__((aligned(16))) float Bt[WUNET_STFT_KT * WUNET_STFT_BWS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lq = lane >> 4;
-    const int kout0 = A.k0 + (int)(blockIdx.x % A.ktiles) * WUNET_STFT_BWN;
-    const unsigned m0 = (blockIdx.x / A.ktiles) * WUNET_STFT_FM;
-    const double ca = A.coefs[0], cb = A.coefs[1];
-    const size_t plane = (size_t)A.M * A.BP;
+    const int kout0 = k0 + (int)(blockIdx.x % ktiles) * WUNET_STFT_BWN;
+    const unsigned m0 = (blockIdx.x / ktiles) * WUNET_STFT_FM;
+    const size_t plane = (size_t)M * BP;
     // loader roles.  G: bin tid & 7, frames (tid >> 3) + 32 j.  B: piece = tid + 256 j: window position piece >> 2, quarter piece & 3
     // (cos | -sin, first | second four bins)
     const int gb = tid & 7;
-    float rg[2][3];
+    float rg[2][Bin::PLANES];
     wunet_f4 rb[2];
-    const int nb = (A.bins + 7) & ~7;
+    const int nb = (bins + 7) & ~7;
 #define WUNET_STFT_BLOAD(B0_)                                                                                     \
     do {                                                                                                          \
         _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                                           \
             const unsigned m = m0 + (unsigned)(tid >> 3) + 32u * j;                                               \
-            const size_t o = (size_t)m * A.BP + (B0_) + gb;                                                       \
-            const bool ok = m < A.M;                                                                              \
-            rg[j][0] = ok ? A.saved[o] : 0.0f;                                                                    \
-            rg[j][1] = ok ? A.saved[plane + o] : 0.0f;                                                            \
-            rg[j][2] = ok ? A.saved[2 * plane + o] : 1.0f;                                                        \
+            const size_t o = (size_t)m * BP + (B0_) + gb;                                                         \
+            const bool ok = m < M;                                                                                \
+            _Pragma("unroll") for (int q = 0; q < Bin::PLANES; ++q) rg[j][q] = ok ? saved[q * plane + o] : Bin::pad(q); \
             const int piece = tid + WUNET_THREADS * j, k = kout0 + (piece >> 2), qu = piece & 3;                  \
-            rb[j] = wunet_sel4(k < A.k1, wunet_ld4(A.basis + (size_t)(k < A.k1 ? k : A.k0) * 2 * A.BP + (qu >> 1) * A.BP + (B0_) + (qu & 1) * 4)); \
+            rb[j] = wunet_sel4(k < k1, wunet_ld4(basis + (size_t)(k < k1 ? k : k0) * 2 * BP + (qu >> 1) * BP + (B0_) + (qu & 1) * 4)); \
         }                                                                                                         \
     } while (0)
     wunet_f4 acc[8];
@@ -314,7 +324,7 @@ static __global__ __launch_bounds__(WUNET_THREADS) void stft_bwd_kernel(StftBwdA
         for (int j = 0; j < 2; ++j) {
             const int ml = (tid >> 3) + 32 * j;
             float dre, dim;
-            stft_bin_grad(rg[j][0], rg[j][1], rg[j][2], A.clamp, ca, cb, dre, dim);
+            bin.grad(rg[j], dre, dim);
             Gs[ml * WUNET_STFT_AS + gb] = dre;
             Gs[ml * WUNET_STFT_AS + 8 + gb] = dim;
             const int piece = tid + WUNET_THREADS * j, kk = piece >> 2, qu = piece & 3, c = (qu >> 1) * 8 + (qu & 1) * 4;
@@ -338,9 +348,16 @@ static __global__ __launch_bounds__(WUNET_THREADS) void stft_bwd_kernel(StftBwdA
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const unsigned m = m0 + (unsigned)(wave * 16 + lq * 4 + r);
-            if (m < A.M && k < A.k1) A.scratch[(size_t)m * A.N + k] = acc[nt][r];
+            if (m < M && k < k1) scratch[(size_t)m * N + k] = acc[nt][r];
         }
     }
+}
+
+static __global__ __launch_bounds__(WUNET_THREADS) void stft_bwd_kernel(StftBwdArgs A)
+{
+    __shared__ __attribute__((aligned(16))) float Gs[WUNET_STFT_FM * WUNET_STFT_AS];
+    __shared__ __attribute__((aligned(16))) float Bt[WUNET_STFT_KT * WUNET_STFT_BWS];
+    dft_adjoint_gemm(StftBinGrad{A.clamp, A.coefs[0], A.coefs[1]}, A.saved, A.basis, A.M, A.ktiles, A.N, A.BP, A.bins, A.k0, A.k1, A.scratch, Gs, Bt);
 }
 
 struct StftOlaArgs {

@@ -85,6 +85,7 @@ def _load_torch_ext():
 # ---------------------------------------------------------------------- multi-resolution STFT loss (include/wunet_hip.h: wunet_stft_*)
 STFT_COEFS = 4                       # WUNET_STFT_COEFS of include/wunet_hip.h: a, b, sc, mag per resolution
 STFT_MAX_RESOLUTIONS = 8             # WUNET_STFT_MAX_RESOLUTIONS
+CSPEC_COEFS = 4                      # WUNET_CSPEC_COEFS: the two gradient scales, the two term values per resolution (wunet_cspec_*)
 
 
 def check_stft_resolution(n_fft, hop, win_length):
@@ -525,6 +526,59 @@ class Engine:
                 self._check(lib.wunet_stft_backward(saved[i].data_ptr(), coefs.data_ptr() + 8 * STFT_COEFS * i, gl.data_ptr(), R, T, N, H, W,
                                                     float(clamp), self.stft_basis(N, W, dev).data_ptr(), scr.data_ptr(), g.data_ptr(),
                                                     1 if i else 0, st))
+        return g
+
+    # ------------------------------------------------------------------ compressed spectral loss (wunet_cspec_*)
+    def cspec_loss_forward(self, clean, enhanced, resolutions, compress=0.3, complex_weight=0.3, clamp=1e-7, with_backward=True):
+        """resolutions: a sequence of (n_fft, hop, win_length).  The last dimension is the utterance, all leading ones are flattened.
+        Returns (loss, coefs, saved): loss - device scalar; coefs - float64 [n_res, CSPEC_COEFS] (the two gradient scales, the two term
+        values per resolution); saved - one float32 buffer per resolution for `cspec_loss_backward` (None with with_backward=False)."""
+        R, T, dev = self._wave_pair("compressed spectral loss", clean, enhanced)
+        n = len(resolutions)
+        if n < 1 or n > STFT_MAX_RESOLUTIONS:
+            raise WunetError(f"compressed spectral loss: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {n})")
+        lib = self.lib
+        out = torch.empty((), dtype=torch.float32, device=dev)
+        coefs = torch.empty(n, CSPEC_COEFS, dtype=torch.float64, device=dev)
+        scratch, saved = [], []
+        with self._device_guard(dev):
+            st = self._stream(dev)
+            for N, H, W in resolutions:
+                basis = self.stft_basis(N, W, dev)
+                scr = torch.empty(self._sized(lib.wunet_cspec_scratch_bytes(R, T, N, H, 0)) // 8, dtype=torch.float64, device=dev)
+                sv = torch.empty(lib.wunet_cspec_saved_bytes(R, T, N, H) // 4, dtype=torch.float32, device=dev) if with_backward else None
+                self._check(lib.wunet_cspec_forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(compress), float(clamp),
+                                                    basis.data_ptr(), scr.data_ptr(), scr.numel() * 8,
+                                                    sv.data_ptr() if sv is not None else None, sv.numel() * 4 if sv is not None else 0, st))
+                scratch.append(scr)
+                saved.append(sv)
+            self._check(lib.wunet_cspec_finalize(n, self._ptrs(scratch), R, T, (ctypes.c_int * n)(*[r[0] for r in resolutions]),
+                                                 (ctypes.c_int * n)(*[r[1] for r in resolutions]), float(complex_weight),
+                                                 out.data_ptr(), coefs.data_ptr(), st))
+        return out, coefs, (saved if with_backward else None)
+
+    def cspec_loss_backward(self, shape, resolutions, coefs, saved, grad_loss, compress=0.3, clamp=1e-7):
+        """d loss / d enhanced (a tensor of `shape`) of the `cspec_loss_forward` that produced `coefs` and `saved`, times grad_loss (a
+        scalar tensor).  The resolutions are added in their order: one fixed order of sums."""
+        n = len(resolutions)
+        if coefs.dtype != torch.float64 or coefs.numel() != n * CSPEC_COEFS or not coefs.is_contiguous() or saved is None or len(saved) != n:
+            raise WunetError(f"compressed spectral loss: coefs / saved must be those of cspec_loss_forward over the same {n} resolutions")
+        dev = coefs.device
+        T = shape[-1]
+        g = torch.empty(shape, dtype=torch.float32, device=dev)
+        R = g.numel() // T
+        gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
+        lib = self.lib
+        with self._device_guard(dev):
+            st = self._stream(dev)
+            for i, (N, H, W) in enumerate(resolutions):
+                if saved[i].dtype != torch.float32 or saved[i].device != dev:
+                    raise WunetError(f"compressed spectral loss: saved[{i}] is not the buffer of resolution {(N, H, W)} on {tuple(shape)}")
+                scr = torch.empty(lib.wunet_cspec_scratch_bytes(R, T, N, H, 1) // 4, dtype=torch.float32, device=dev)
+                self._check(lib.wunet_cspec_backward(saved[i].data_ptr(), saved[i].numel() * 4, coefs.data_ptr() + 8 * CSPEC_COEFS * i,
+                                                     gl.data_ptr(), R, T, N, H, W, float(compress), float(clamp),
+                                                     self.stft_basis(N, W, dev).data_ptr(), scr.data_ptr(), scr.numel() * 4, g.data_ptr(),
+                                                     1 if i else 0, st))
         return g
 
     def stft_magnitude(self, x, n_fft=320, hop=160, win_length=320):

@@ -32,6 +32,14 @@ ignores level, and phase below its 26 ms frames, so it is usually one term besid
 items that pass nothing; a band row or a frame column of a segment whose centred norm is exactly 0 passes no gradient (autograd: NaN):
 
     ["stoi_loss", 0.25, {"sample_rate": 16000, "extended": true}]
+
+`compressed_spectral_loss` (no reference counterpart): the power-law compressed spectral loss with a complex, phase-aware term (Braun &
+Tashev 2021; the DNS-challenge baseline loss; include/wunet_hip.h: wunet_cspec_*) - per STFT bin (1 - complex_weight) (A_c - A_e)^2 +
+complex_weight |Z_c - Z_e|^2 with A = |S|^compress and Z = S |S|^(compress - 1), averaged; gradient with respect to `enhanced` only;
+below `clamp` (on the power) the compression factors are constants, so silence still gets a gradient through the complex term:
+
+    "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "weighted_loss",
+                      "args": {"terms": [["l1_loss", 1.0], ["compressed_spectral_loss", 0.5, {"compress": 0.3, "complex_weight": 0.3}]]}}
 """
 import torch
 import torch.nn as nn
@@ -169,6 +177,59 @@ def stft_loss(fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths
     return HipStftLoss(fft_sizes, hop_sizes, win_lengths, sc_weight, mag_weight, clamp)
 
 
+class _CspecLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mod, engine, clean, enhanced):
+        if clean.requires_grad:                 # (before anything runs)
+            raise NotImplementedError("compressed_spectral_loss: no gradient with respect to `clean`: detach it")
+        clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
+        loss, coefs, saved = engine.cspec_loss_forward(clean_c, enh_c, mod.resolutions, mod.compress, mod.complex_weight, mod.clamp)
+        ctx.mod, ctx.engine, ctx.shape = mod, engine, tuple(enh_c.shape)
+        ctx.save_for_backward(coefs, *saved)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        coefs, *saved = ctx.saved_tensors
+        g = None
+        if ctx.needs_input_grad[3]:
+            g = ctx.engine.cspec_loss_backward(ctx.shape, ctx.mod.resolutions, coefs, saved, grad_loss, ctx.mod.compress, ctx.mod.clamp)
+        return None, None, None, g
+
+
+class HipCompressedSpectralLoss(nn.Module):
+    """loss(clean, enhanced) -> mean over the resolutions of mean [(1 - complex_weight) (A_c - A_e)^2 + complex_weight |Z_c - Z_e|^2]
+    with A = max(P, clamp)^(compress / 2), Z = (re + i im) max(P, clamp)^((compress - 1) / 2), P = re^2 + im^2 of the STFT (stft_loss's
+    conventions); the last dimension is the utterance.  Gradient with respect to `enhanced` only."""
+
+    def __init__(self, fft_sizes=(512,), hop_sizes=(128,), win_lengths=(512,), compress=0.3, complex_weight=0.3, clamp=1e-7):
+        super().__init__()
+        name = "compressed_spectral_loss"
+        fft_sizes, hop_sizes, win_lengths = list(fft_sizes), list(hop_sizes), list(win_lengths)
+        if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
+            raise ValueError(f"{name}: fft_sizes, hop_sizes and win_lengths must have equal lengths (got {len(fft_sizes)}, "
+                             f"{len(hop_sizes)}, {len(win_lengths)})")
+        if not 1 <= len(fft_sizes) <= STFT_MAX_RESOLUTIONS:
+            raise ValueError(f"{name}: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {len(fft_sizes)})")
+        if not (compress > 0.0 and compress <= 1.0):
+            raise ValueError(f"{name}: compress must be in (0, 1] (got {compress})")
+        if not (complex_weight >= 0.0 and complex_weight <= 1.0):
+            raise ValueError(f"{name}: complex_weight must be in [0, 1] (got {complex_weight})")
+        if not (clamp > 0.0 and clamp < float("inf")):
+            raise ValueError(f"{name}: clamp must be finite and > 0 (got {clamp})")
+        self.resolutions = tuple(check_stft_resolution(n, h, w) for n, h, w in zip(fft_sizes, hop_sizes, win_lengths))
+        self.compress, self.complex_weight, self.clamp = float(compress), float(complex_weight), float(clamp)
+        self._engine_override = None
+
+    def forward(self, clean, enhanced):
+        engine = self._engine_override if self._engine_override is not None else default_engine()
+        return _CspecLossFn.apply(self, engine, clean, enhanced)
+
+
+def compressed_spectral_loss(fft_sizes=(512,), hop_sizes=(128,), win_lengths=(512,), compress=0.3, complex_weight=0.3, clamp=1e-7):
+    return HipCompressedSpectralLoss(fft_sizes, hop_sizes, win_lengths, compress, complex_weight, clamp)
+
+
 class _StoiLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, sample_rate, extended, engine, clean, enhanced):
@@ -224,8 +285,8 @@ class WeightedLoss(nn.Module):
                 raise ValueError(f"weighted_loss: a term is [factory_name, weight] or [factory_name, weight, args] (got {term!r})")
             name, weight = term[0], float(term[1])
             factory = globals().get(name)
-            if name not in _FACTORIES or factory is None:
-                raise ValueError(f"weighted_loss: unknown loss {name!r} (one of {sorted(_FACTORIES)})")
+            if name not in _FACTORIES + _SPECTRAL_FACTORIES or factory is None:
+                raise ValueError(f"weighted_loss: unknown loss {name!r} (one of {sorted(_FACTORIES + _SPECTRAL_FACTORIES)})")
             mods.append(factory(**(dict(term[2]) if len(term) == 3 else {})))
             weights.append(weight)
         self.terms = nn.ModuleList(mods)
@@ -240,6 +301,7 @@ class WeightedLoss(nn.Module):
 
 
 _FACTORIES = ("mse_loss", "l1_loss", "smooth_l1_loss", "si_sdr_loss", "snr_loss", "stft_loss", "stoi_loss")
+_SPECTRAL_FACTORIES = ("compressed_spectral_loss",)       # the factories added since: WeightedLoss consults both tuples
 
 
 def weighted_loss(terms):
