@@ -449,6 +449,30 @@ int wunet_reverb_windows(const float* clean_flat, long long clean_total, const f
                          int early_taps, int batch, int length,
                          float* reverberant, float* direct /* [batch][1][length] or NULL */, void* stream);
 
+/* Chunked enhancement with overlap (the reference cuts a recording into disjoint chunks, enhancement.py:57-69; this is the same with
+ * a margin dropped at every chunk edge and a cross-fade between neighbours; csrc/wunet_chunks.h).  L = length, m = margin, f = fade,
+ * hop H = L - 2 m - f with H >= 1 and f <= H, so at most two chunks cover a sample.  A recording of T samples has
+ * n = max(1, ceil((T - f) / H)) chunks; chunk k reads samples [k H - m, k H - m + L) of it, zeros outside [0, T), and is trusted on
+ * [k H, k H + H + f).  For the output sample t < T, with k = min(t / H, n - 1), j = t - k H and y_k the model's output for chunk k:
+ *   k >= 1 and j < f:  out[t] = ramp[j] y_k[m + j] + (1 - ramp[j]) y_(k-1)[m + H + j]   (1 - ramp[j] in float32, then one fma)
+ *   otherwise:         out[t] = y_k[m + j], the same bits.
+ * The recordings of a call lie in one flat float32 array of `total` samples, each at its own start; the output array has the same layout.
+ *
+ * wunet_chunk_gather: chunks[i][0][j] = flat[start + s + j] where 0 <= s + j < T and 0 <= start + s + j < total, else 0, for rows[i] =
+ *   (flat start of the recording, T, chunk start s = k H - m).  Loads are masked, nothing outside `flat` is addressed.
+ * wunet_chunk_overlap_add: the formula above for every recording recs[r] = (flat start, T, first chunk row, chunk count), written to
+ *   out_flat[start + t].  ramp: device float32 [fade] (the window's shape is data), NULL exactly when fade == 0.  max_len: the largest
+ *   T, it sizes the grid (samples beyond it are not written).  A chunk row outside [0, n), an offset outside a chunk and an output
+ *   index outside [0, total) are skipped, never addressed.
+ * rows / recs: device int64.  n, n_recs < 2^31, length <= 2^30.  One launch each; everything ragged is read from device memory, so a
+ * captured call follows its tables.  No atomics: bit-identical run to run.  Caller-owned memory, no allocation, no synchronisation.
+ * 16-byte accesses are used wherever the addresses involved are aligned, dwords elsewhere: no alignment is required. */
+int wunet_chunk_gather(const float* flat, long long total, const long long* rows /* [n][3]: flat start, T, chunk start */,
+                       long long n, int length, float* chunks /* [n][1][length] */, void* stream);
+int wunet_chunk_overlap_add(const float* chunks /* [n][1][length] */, long long n, int length, int margin, int fade,
+                            const float* ramp /* [fade] or NULL */, const long long* recs /* [n_recs][4]: flat start, T, first row, count */,
+                            long long n_recs, long long max_len, float* out_flat, long long total, void* stream);
+
 /* Measurement aid (tools/conv_trace.py; no reference counterpart): a device buffer of gridDim.x * 64 uint64 that the DMA-staged
  * conv / data-gradient kernel (conv_h3d_kernel) fills with shader-clock stamps of each block's phases (entry; per K stage: tile
  * landed, W buffer released, MFMAs issued; epilogue done), or NULL (default) to turn the stamps off.  Process-wide. */

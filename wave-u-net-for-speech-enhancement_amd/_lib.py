@@ -29,6 +29,7 @@ EXPORTS = [
     "wunet_estoi_scratch_bytes", "wunet_estoi_forward",
     "wunet_estoi_loss_scratch_bytes", "wunet_estoi_loss_saved_bytes", "wunet_estoi_loss_forward", "wunet_estoi_loss_backward",
     "wunet_mix_scratch_bytes", "wunet_mix_windows", "wunet_apply_level", "wunet_reverb_windows",
+    "wunet_chunk_gather", "wunet_chunk_overlap_add",
 ]
 
 _vp = ctypes.c_void_p
@@ -130,6 +131,10 @@ def declare(lib):
     if hasattr(lib, "wunet_reverb_windows"):     # (the same)
         lib.wunet_apply_level.argtypes = [_vp, _vp, _i, _i, _vp, _vp]
         lib.wunet_reverb_windows.argtypes = [_vp, ctypes.c_longlong, _vp, ctypes.c_longlong, _vp, _i, _i, _i, _vp, _vp, _vp]
+    if hasattr(lib, "wunet_chunk_gather"):       # (the same)
+        _ll = ctypes.c_longlong
+        lib.wunet_chunk_gather.argtypes = [_vp, _ll, _vp, _ll, _i, _vp, _vp]
+        lib.wunet_chunk_overlap_add.argtypes = [_vp, _ll, _i, _i, _i, _vp, _vp, _ll, _ll, _vp, _ll, _vp]
     lib.wunet_comm_unique_id.argtypes = [_vp]
     lib.wunet_comm_create.argtypes = [_vp, _i, _i, ctypes.POINTER(_vp)]
     lib.wunet_comm_allreduce_sum.argtypes = [_vp, _vp, _sz, _vp]

@@ -10,6 +10,7 @@
 #include "wunet_estoi.h"
 #include "wunet_mix.h"
 #include "wunet_reverb.h"
+#include "wunet_chunks.h"
 
 using namespace wunet_host;
 
@@ -915,6 +916,50 @@ int wunet_reverb_windows(const float* clean_flat, long long clean_total, const f
     // (the taps are the tables': the profiler's FLOP column counts one tap per sample, the bytes the two outputs)
     prof_begin(st, "reverb_kernel", 2.0 * n, 4.0 * 3.0 * n);
     WUNET_LAUNCH(reverb_kernel, dim3((unsigned)((length + WUNET_REVERB_CH - 1) / WUNET_REVERB_CH), (unsigned)batch), dim3(WUNET_THREADS), 0, st, A);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- chunked enhancement with overlap (wunet_chunks.h)
+static unsigned chunk_pieces_y(long long pieces) { return (unsigned)(pieces < (long long)WUNET_CHUNK_MAX_Y ? pieces : (long long)WUNET_CHUNK_MAX_Y); }
+
+int wunet_chunk_gather(const float* flat, long long total, const long long* rows, long long n, int length, float* chunks, void* stream)
+{
+    if (n < 1 || length < 1) return fail(WUNET_E_ARG, "chunk_gather: n and length must be >= 1 (got %lld x %d)", n, length);
+    if (n > 0x7fffffffLL || length > (1 << 30)) return fail(WUNET_E_ARG, "chunk_gather: at most 2^31 - 1 chunks of 2^30 samples per call (got %lld x %d)", n, length);
+    if (total < 1 || total >= WUNET_CHUNK_LIMIT) return fail(WUNET_E_ARG, "chunk_gather: bad size of the flat array (total=%lld)", total);
+    if (!flat || !rows || !chunks) return fail(WUNET_E_ARG, "chunk_gather: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const long long pieces = ((long long)length + WUNET_CHUNK_PIECE - 1) / WUNET_CHUNK_PIECE;
+    const double cnt = (double)n * length;
+    prof_begin(st, "chunk_gather_kernel", 0.0, 4.0 * 2.0 * cnt);
+    WUNET_LAUNCH(chunk_gather_kernel, dim3((unsigned)n, chunk_pieces_y(pieces)), dim3(WUNET_THREADS), 0, st, flat, total, rows, length, chunks);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_chunk_overlap_add(const float* chunks, long long n, int length, int margin, int fade, const float* ramp, const long long* recs,
+                            long long n_recs, long long max_len, float* out_flat, long long total, void* stream)
+{
+    if (n < 1 || length < 1) return fail(WUNET_E_ARG, "chunk_overlap_add: n and length must be >= 1 (got %lld x %d)", n, length);
+    if (n > 0x7fffffffLL || length > (1 << 30)) return fail(WUNET_E_ARG, "chunk_overlap_add: at most 2^31 - 1 chunks of 2^30 samples per call (got %lld x %d)", n, length);
+    if (margin < 0 || fade < 0) return fail(WUNET_E_ARG, "chunk_overlap_add: margin and fade must be >= 0 (got %d, %d)", margin, fade);
+    const long long hop = (long long)length - 2LL * margin - fade;
+    if (hop < 1 || fade > hop)
+        return fail(WUNET_E_ARG, "chunk_overlap_add: the hop length - 2 margin - fade must be >= 1 and >= fade (length=%d margin=%d fade=%d)", length, margin, fade);
+    if ((fade > 0) != (ramp != nullptr)) return fail(WUNET_E_ARG, "chunk_overlap_add: ramp must be given exactly when fade > 0 (fade=%d)", fade);
+    if (n_recs < 1 || n_recs > 0x7fffffffLL) return fail(WUNET_E_ARG, "chunk_overlap_add: n_recs must be in [1, 2^31) (got %lld)", n_recs);
+    if (max_len < 1 || max_len >= WUNET_CHUNK_LIMIT) return fail(WUNET_E_ARG, "chunk_overlap_add: bad max_len (%lld)", max_len);
+    if (total < 1 || total >= WUNET_CHUNK_LIMIT) return fail(WUNET_E_ARG, "chunk_overlap_add: bad size of the flat output (total=%lld)", total);
+    if (!chunks || !recs || !out_flat) return fail(WUNET_E_ARG, "chunk_overlap_add: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    ChunkOlaArgs A{};
+    A.chunks = chunks; A.n = n; A.length = length; A.margin = margin; A.fade = fade; A.hop = (int)hop; A.ramp = ramp; A.recs = recs;
+    A.pieces = (max_len + WUNET_CHUNK_PIECE - 1) / WUNET_CHUNK_PIECE; A.out_flat = out_flat; A.total = total;
+    prof_begin(st, "chunk_overlap_add_kernel", 0.0, 4.0 * 2.0 * (double)total);
+    WUNET_LAUNCH(chunk_overlap_add_kernel, dim3((unsigned)n_recs, chunk_pieces_y(A.pieces)), dim3(WUNET_THREADS), 0, st, A);
     prof_end(st);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;

@@ -814,6 +814,48 @@ class Engine:
             self._check(self.lib.wunet_apply_level(src.data_ptr(), gains.data_ptr(), B, L, dst.data_ptr(), self._stream(src.device)))
         return dst
 
+    def chunk_gather(self, flat, rows, chunks):
+        """include/wunet_hip.h: wunet_chunk_gather.  chunks[i, 0, j] = flat[start + s + j] inside the recording that rows[i] = (flat start,
+        T, chunk start s) names, 0 outside it.  One launch, nothing read back, no scratch."""
+        if rows.dtype != torch.int64 or flat.dtype != torch.float32 or chunks.dtype != torch.float32:
+            raise WunetError("chunk_gather: a float32 array and chunks and int64 rows expected")
+        for t in (flat, rows, chunks):
+            self._require(t, "chunk_gather tensor")
+        if flat.dim() != 1 or chunks.dim() < 2:
+            raise WunetError("chunk_gather: the array must be flat and the chunks [n, ..., L]")
+        n, L = chunks.shape[0], chunks.shape[-1]
+        if chunks.numel() != n * L or tuple(rows.shape) != (n, 3):
+            raise WunetError("chunk_gather: shape mismatch (rows [n, 3], chunks [n, 1, L])")
+        dev = chunks.device
+        if flat.device != dev or rows.device != dev:
+            raise WunetError("chunk_gather: every tensor must live on the chunks' device")
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_chunk_gather(flat.data_ptr(), flat.numel(), rows.data_ptr(), n, L, chunks.data_ptr(), self._stream(dev)))
+
+    def chunk_overlap_add(self, chunks, recs, out_flat, margin, fade, ramp, max_len):
+        """include/wunet_hip.h: wunet_chunk_overlap_add.  out_flat[start + t], t < T, for every recording recs[r] = (flat start, T, first
+        chunk row, chunk count): chunk k's sample m + j outside the cross-fades, ramp[j] y_k + (1 - ramp[j]) y_(k-1) inside them.  ramp:
+        float32 [fade], None exactly when fade == 0; max_len: the largest T.  One launch, nothing read back, no scratch."""
+        f32 = torch.float32
+        if recs.dtype != torch.int64 or chunks.dtype != f32 or out_flat.dtype != f32 or (ramp is not None and ramp.dtype != f32):
+            raise WunetError("chunk_overlap_add: float32 chunks, ramp and output and int64 recs expected")
+        for t in (chunks, recs, out_flat) + ((ramp,) if ramp is not None else ()):
+            self._require(t, "chunk_overlap_add tensor")
+        if out_flat.dim() != 1 or chunks.dim() < 2:
+            raise WunetError("chunk_overlap_add: the output must be flat and the chunks [n, ..., L]")
+        n, L = chunks.shape[0], chunks.shape[-1]
+        margin, fade = int(margin), int(fade)
+        if chunks.numel() != n * L or recs.dim() != 2 or recs.shape[1] != 4 or (ramp is not None and tuple(ramp.shape) != (fade,)) or \
+                (ramp is None) != (fade == 0):
+            raise WunetError("chunk_overlap_add: shape mismatch (chunks [n, 1, L], recs [R, 4], ramp [fade] or None when fade == 0)")
+        dev = chunks.device
+        if recs.device != dev or out_flat.device != dev or (ramp is not None and ramp.device != dev):
+            raise WunetError("chunk_overlap_add: every tensor must live on the chunks' device")
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_chunk_overlap_add(chunks.data_ptr(), n, L, margin, fade, ramp.data_ptr() if ramp is not None else None,
+                                                         recs.data_ptr(), recs.shape[0], int(max_len), out_flat.data_ptr(), out_flat.numel(),
+                                                         self._stream(dev)))
+
 
 class _CtxHold:
     """`with engine._using(shape...) as handle`: the context cannot be evicted while the block runs."""

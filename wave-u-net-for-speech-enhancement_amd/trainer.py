@@ -28,6 +28,9 @@ Differences from the reference loop, all on the f2 list:
     to `validation_scores`, compared with `best_score` as base_trainer.py:149-157 does, and a best one writes best_model.tar
     (base_trainer.py:118-120).  Every module's training flag (a frozen BatchNorm layer included) is restored afterwards, so a captured
     step graph stays valid.  Without the "metric" key the loader stays unused, as in earlier versions of this trainer;
+  * `"validation": {"custom": {"margin": m, "fade": f, "window": "hann"}}` enhances with overlapped, cross-faded chunks and
+    `"validation": {"recordings_per_pass": N}` enhances N recordings per pass in shared slabs (inference.py: enhance / enhance_many);
+    the score, the one device->host read and the restored flags are the same.  Without these keys nothing changes;
   * STOI, the first half of the reference's score (STOI + PESQ') / 2 (trainer/trainer.py:128-143), on the device: beside "metric":
     "si_sdr" the optional key `"stoi": "report"` also appends (mean STOI of the noisy recordings, mean STOI of the enhanced ones) to
     `validation_stoi` every validation epoch and leaves the score alone; `"stoi": "score"` makes the mean STOI of the enhanced
@@ -105,6 +108,20 @@ class Trainer:
         self.validation_interval = int(vcfg.get("interval", 0)) if self.validation_metric and validation_dataloader is not None else 0
         self.validation_find_max = bool(vcfg.get("find_max", True))
         self.validation_sample_length = int((vcfg.get("custom") or {}).get("sample_length", 16384))
+        # overlapped chunks (inference.py: margin / fade / window) and several recordings per pass (inference.enhance_many), both opt-in
+        custom = vcfg.get("custom") or {}
+        self.validation_overlap = {key: custom[key] for key in ("margin", "fade", "window") if key in custom}
+        if self.validation_overlap:
+            from .inference import chunk_hop
+            try:
+                chunk_hop(self.validation_sample_length, **self.validation_overlap)
+            except (ValueError, TypeError) as e:
+                raise ValueError(f'trainer config "validation.custom": {e}') from None
+        self.validation_recordings_per_pass = vcfg.get("recordings_per_pass")
+        n_pass = self.validation_recordings_per_pass
+        if n_pass is not None and (isinstance(n_pass, bool) or not isinstance(n_pass, int) or n_pass < 1):
+            raise ValueError(f'trainer config "validation.recordings_per_pass" must be an integer >= 1 (got {n_pass!r}); leave it out to '
+                             "enhance one recording at a time")
         self.validation_scores = []   # one mean SI-SDR improvement [dB] per validation epoch (the mean enhanced STOI with "stoi": "score")
         self.validation_stoi_mode = vcfg.get("stoi")
         if self.validation_stoi_mode not in (None, "report", "score"):
@@ -206,20 +223,40 @@ class Trainer:
     @torch.no_grad()
     def _validation_epoch(self, epoch):
         from . import metrics
-        from .inference import enhance
+        from .inference import enhance, enhance_many
         model = getattr(self.model, "module", self.model)
         engine = getattr(model, "_engine_override", None)
         modes = [(m, m.training) for m in self.model.modules()]
         self.model.eval()
         gains, stois = [], []
         fs = self.validation_sample_rate
-        try:
+        per_pass = self.validation_recordings_per_pass
+
+        def flush(held):
+            outs = enhance_many(model, [mix for mix, _ in held], self.validation_sample_length, **self.validation_overlap)
+            return [(mix, cl, out) for (mix, cl), out in zip(held, outs)]
+
+        def passes():
+            """(mixture, clean, enhanced) per recording, in the loader's order; with "recordings_per_pass" the recordings of a pass share
+            the slabs of one enhance_many call."""
+            held = []
             for mixture, clean, _name in self.validation_data_loader:
                 if mixture.dim() != 3 or mixture.shape[0] != 1:
                     raise ValueError("Only support batch size is 1 in enhancement stage.")       # reference wording, trainer/trainer.py:64
                 mixture = mixture.to(self.device, non_blocking=True)
                 clean = clean.to(self.device, non_blocking=True)
-                enhanced = enhance(model, mixture, self.validation_sample_length)
+                if per_pass is None:
+                    yield mixture, clean, enhance(model, mixture, self.validation_sample_length, **self.validation_overlap)
+                    continue
+                held.append((mixture, clean))
+                if len(held) == per_pass:
+                    yield from flush(held)
+                    held = []
+            if held:
+                yield from flush(held)
+
+        try:
+            for mixture, clean, enhanced in passes():
                 gains.append(metrics.si_sdr_improvement(clean, mixture, enhanced, engine=engine))
                 if self.validation_stoi_mode is not None:
                     ext = self.validation_stoi_extended
