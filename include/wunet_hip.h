@@ -473,6 +473,30 @@ int wunet_chunk_overlap_add(const float* chunks /* [n][1][length] */, long long 
                             const float* ramp /* [fade] or NULL */, const long long* recs /* [n_recs][4]: flat start, T, first row, count */,
                             long long n_recs, long long max_len, float* out_flat, long long total, void* stream);
 
+/* Rational resampling of ragged rows (no reference counterpart in code: a reference user resamples with librosa on the host;
+ * csrc/wunet_resample.h): a polyphase FIR filter over many rows of different lengths that share one rate pair, one launch.
+ * up / down in lowest terms; taps: device float32 h'[0 .. n_taps), n_taps = 2 L + 1, the gain `up` already folded in - the filter's
+ * shape and gain are data.  For the row rows[i] = (in start, T_in, out start, T_out) and the output sample m < T_out:
+ *   c = m down + L,  phase = c mod up,  i_hi = c / up
+ *   out[out start + m] = sum_j h'[phase + up j] in[in start + i_hi - j]   over the j with phase + up j < n_taps and 0 <= i_hi - j < T_in
+ * (zeros outside the row).  With T_out = ceil(T_in up / down) this is scipy.signal.resample_poly(x, up, down, window = h) for h' = up h;
+ * a smaller T_out truncates, a larger one reads zeros behind the row.  float32 operands, products exact in double, the sum in double
+ * in increasing j, one rounding to float32.  No atomics: bit-identical run to run.
+ * max_out: the largest T_out, it sizes the grid (outputs beyond it are not computed).  A row whose start, length or extent lies
+ * outside [0, in_total] / [0, out_total], or with a negative value, is skipped, never addressed.  rows: device int64; everything ragged
+ * is read from device memory, so a captured call follows its table.  Caller-owned memory, no allocation, no synchronisation, no
+ * alignment required.  -1 with wunet_last_error() text for: a null pointer; n, max_out, up or down < 1; up and down not coprime;
+ * n_taps even or above WUNET_RESAMPLE_MAX_TAPS (max(up, down) above WUNET_RESAMPLE_MAX_RATIO); n >= 2^31; an array of 2^50 samples.
+ * wunet_resample_tile: the outputs a block of the kernel owns per trip for that filter (what the tests put row lengths next to), 0
+ *   for a filter the entry refuses. */
+#define WUNET_RESAMPLE_MAX_TAPS 12801
+#define WUNET_RESAMPLE_MAX_RATIO 640
+int wunet_resample_rows(const float* in, long long in_total,
+                        const long long* rows /* [n][4]: in start, T_in, out start, T_out */, long long n,
+                        long long max_out, int up, int down, const float* taps, int n_taps,
+                        float* out, long long out_total, void* stream);
+long long wunet_resample_tile(int up, int down, int n_taps);
+
 /* Measurement aid (tools/conv_trace.py; no reference counterpart): a device buffer of gridDim.x * 64 uint64 that the DMA-staged
  * conv / data-gradient kernel (conv_h3d_kernel) fills with shader-clock stamps of each block's phases (entry; per K stage: tile
  * landed, W buffer released, MFMAs issued; epilogue done), or NULL (default) to turn the stamps off.  Process-wide. */

@@ -1,4 +1,4 @@
-// Dynamic-LDS layouts of the six kernels that carve their allocation by hand: one description per kernel, read by the kernel (with
+// Dynamic-LDS layouts of the seven kernels that carve their allocation by hand: one description per kernel, read by the kernel (with
 // its template arguments: region pointers and the addressing constants), by the planner (occupancy), by the launcher (the bytes it
 // requests) and by the dispatcher of every instantiation (which refuses a request smaller than its layout).  Plain constexpr C++:
 // no HIP types, so host-only programs (tools/plan_dump.cpp) and the emulator build read it too.
@@ -115,5 +115,28 @@ struct ConvH3u {
     constexpr size_t bytes(int c8, int er) const { return (size_t)red() * 16 + (size_t)(coef + epi(c8) + 3 * er) * sizeof(float); }
 };
 constexpr ConvH3u conv_h3u(int mrep) { return {272, 2 * 4 * 272, 5 * 64, 2 * mrep * 5 * 64, kWaves * mrep * 32 + 4}; }
+
+// ---- resample_rows_kernel, floats:  hs [ntaps] the filter as it lies in memory | xs [span] the input under one tile of outputs
+// A tile is `tile` consecutive outputs of one row, 4 g ng of them with g a multiple of `up`: a thread owns the 4 outputs o, o + g,
+// o + 2 g, o + 3 g, which share one phase and so one set of taps (wunet_resample.h).  g ng is about 512, two trips of the block's
+// threads, and is taken smaller where `down / up` is so large that the input under the tile would not fit kResampleSpanMax floats.
+constexpr int kResampleOut = 4;                      // outputs per thread and trip
+constexpr int kResampleSpanMax = 16384;              // floats of xs at the most (64 KiB; with the largest filter 114 KiB of the CU's 160)
+struct Resample {
+    int g, ng, tile, span, ntaps;
+    constexpr int xs() const { return ntaps; }
+    constexpr int end() const { return ntaps + span; }
+    constexpr size_t bytes() const { return (size_t)end() * sizeof(float); }
+};
+// floats of input under `tile` outputs: the last output's i_hi minus the first one's, plus the taps of a phase, rounded up
+constexpr long long resample_span(long long tile, int up, int down, int ntaps) { return ((tile - 1) * down + (ntaps - 1)) / up + 3; }
+constexpr Resample resample(int up, int down, int ntaps)
+{
+    int k = up < 64 ? 64 / up : 1, ng = 512 / (up * k) > 1 ? 512 / (up * k) : 1;
+    while (ng > 1 && resample_span((long long)kResampleOut * up * k * ng, up, down, ntaps) > kResampleSpanMax) --ng;
+    while (k > 1 && resample_span((long long)kResampleOut * up * k * ng, up, down, ntaps) > kResampleSpanMax) --k;
+    const int g = up * k, tile = kResampleOut * g * ng;
+    return {g, ng, tile, (int)resample_span(tile, up, down, ntaps), ntaps};
+}
 
 }  // namespace wunet_lds

@@ -11,6 +11,7 @@
 #include "wunet_mix.h"
 #include "wunet_reverb.h"
 #include "wunet_chunks.h"
+#include "wunet_resample.h"
 
 using namespace wunet_host;
 
@@ -960,6 +961,56 @@ int wunet_chunk_overlap_add(const float* chunks, long long n, int length, int ma
     A.pieces = (max_len + WUNET_CHUNK_PIECE - 1) / WUNET_CHUNK_PIECE; A.out_flat = out_flat; A.total = total;
     prof_begin(st, "chunk_overlap_add_kernel", 0.0, 4.0 * 2.0 * (double)total);
     WUNET_LAUNCH(chunk_overlap_add_kernel, dim3((unsigned)n_recs, chunk_pieces_y(A.pieces)), dim3(WUNET_THREADS), 0, st, A);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- rational resampling of ragged rows (wunet_resample.h)
+static long long gcd_ll(long long a, long long b) { while (b) { const long long t = a % b; a = b; b = t; } return a; }
+
+// the argument checks shared by the two entries: 0, or -1 with the message set
+static int resample_filter_check(int up, int down, int n_taps)
+{
+    if (up < 1 || down < 1) return fail(WUNET_E_ARG, "resample: up and down must be >= 1 (got %d / %d)", up, down);
+    if (gcd_ll(up, down) != 1) return fail(WUNET_E_ARG, "resample: up / down must be in lowest terms, coprime (got %d / %d)", up, down);
+    if (up > WUNET_RESAMPLE_MAX_RATIO || down > WUNET_RESAMPLE_MAX_RATIO)
+        return fail(WUNET_E_ARG, "resample: max(up, down) is above the cap of %d (got %d / %d)", WUNET_RESAMPLE_MAX_RATIO, up, down);
+    if (n_taps < 1 || (n_taps & 1) == 0) return fail(WUNET_E_ARG, "resample: n_taps = 2 L + 1 must be odd (got %d)", n_taps);
+    if (n_taps > WUNET_RESAMPLE_MAX_TAPS) return fail(WUNET_E_ARG, "resample: n_taps is above the cap of %d taps (got %d)", WUNET_RESAMPLE_MAX_TAPS, n_taps);
+    return 0;
+}
+
+long long wunet_resample_tile(int up, int down, int n_taps)
+{
+    if (resample_filter_check(up, down, n_taps)) return 0;
+    return wunet_lds::resample(up, down, n_taps).tile;
+}
+
+int wunet_resample_rows(const float* in, long long in_total, const long long* rows, long long n, long long max_out, int up, int down,
+                        const float* taps, int n_taps, float* out, long long out_total, void* stream)
+{
+    if (n < 1 || max_out < 1) return fail(WUNET_E_ARG, "resample: n and max_out must be >= 1 (got %lld, %lld)", n, max_out);
+    if (n > 0x7fffffffLL) return fail(WUNET_E_ARG, "resample: at most 2^31 - 1 rows per call (got %lld)", n);
+    if (resample_filter_check(up, down, n_taps)) return WUNET_E_ARG;
+    if (in_total < 1 || in_total >= WUNET_RESAMPLE_LIMIT || out_total < 1 || out_total >= WUNET_RESAMPLE_LIMIT)
+        return fail(WUNET_E_ARG, "resample: bad size of an array (in_total=%lld out_total=%lld)", in_total, out_total);
+    if (!in || !rows || !taps || !out) return fail(WUNET_E_ARG, "resample: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    const wunet_lds::Resample lay = wunet_lds::resample(up, down, n_taps);
+    if (max_out > out_total) max_out = out_total;
+    ResampleArgs A{};
+    A.in = in; A.in_total = in_total; A.rows = rows; A.max_out = max_out; A.tiles = (max_out + lay.tile - 1) / lay.tile;
+    A.up = up; A.down = down; A.half = (n_taps - 1) / 2; A.taps = taps;
+    A.g = lay.g; A.ng = lay.ng; A.tile = lay.tile; A.span = lay.span; A.ntaps = n_taps; A.out = out; A.out_total = out_total;
+    long long y = (WUNET_RESAMPLE_BLOCKS + n - 1) / n;
+    if (y > A.tiles) y = A.tiles;
+    if (y > (long long)WUNET_CHUNK_MAX_Y) y = WUNET_CHUNK_MAX_Y;
+    if (WUNET_ALLOW_BIG_LDS(resample_rows_kernel, lay.bytes())) return fail(WUNET_E_RUNTIME, "resample: %zu bytes of LDS were not granted", lay.bytes());
+    // (the profiler's columns for rows of max_out outputs: the terms of an output, the samples in and out)
+    const double outs = (double)n * (double)max_out;
+    prof_begin(st, "resample_rows_kernel", 2.0 * outs * ((n_taps - 1) / up + 1), 4.0 * outs * (1.0 + (double)down / up));
+    WUNET_LAUNCH(resample_rows_kernel, dim3((unsigned)n, (unsigned)y), dim3(WUNET_THREADS), lay.bytes(), st, A);
     prof_end(st);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;

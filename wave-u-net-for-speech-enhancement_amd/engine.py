@@ -166,6 +166,7 @@ class Engine:
         self.weights_generation = 0
         self._stft_bases = {}                         # (n_fft, win_length, device) -> windowed DFT basis (stft_basis)
         self._stoi_tables_cache = {}                  # (sample rate, device) -> basis | window | resampler taps (stoi_tables)
+        self._resample_taps_cache = {}                # (up, down, device) -> the resampling filter on the device (resample_taps)
         # per-step calls marshalled in C++ when the extension is built and this engine drives the HIP library it is linked to
         self._fast = _load_torch_ext() if (lib is None and not host_memory) else None
 
@@ -855,6 +856,37 @@ class Engine:
             self._check(self.lib.wunet_chunk_overlap_add(chunks.data_ptr(), n, L, margin, fade, ramp.data_ptr() if ramp is not None else None,
                                                          recs.data_ptr(), recs.shape[0], int(max_len), out_flat.data_ptr(), out_flat.numel(),
                                                          self._stream(dev)))
+
+    # ------------------------------------------------------------------ sample-rate conversion (wunet_resample_rows)
+    def resample_taps(self, rate_in, rate_out, device):
+        """(up, down, the device copy of resample.resample_taps' filter) of one (rate pair, device), made once: on the first (eager)
+        call, so that a later graph capture sees no allocation (the rule of stft_basis and stoi_tables)."""
+        from .resample import resample_taps
+        up, down, h = resample_taps(rate_in, rate_out)
+        key = (up, down, str(device))
+        taps = self._resample_taps_cache.get(key)
+        if taps is None:
+            taps = self._resample_taps_cache[key] = torch.from_numpy(h.copy()).to(device)
+        return up, down, taps
+
+    def resample_rows(self, flat, rows, out, rate_in, rate_out, max_out):
+        """include/wunet_hip.h: wunet_resample_rows.  For every row rows[i] = (in start, T_in, out start, T_out) of the flat float32
+        array `flat`, out[out start + m], m < T_out, is the polyphase filter of resample.resample_taps(rate_in, rate_out) over the
+        row's T_in samples.  max_out: the largest T_out.  One launch, nothing read back, no scratch."""
+        if rows.dtype != torch.int64 or flat.dtype != torch.float32 or out.dtype != torch.float32:
+            raise WunetError("resample_rows: float32 arrays and int64 rows expected")
+        for t in (flat, rows, out):
+            self._require(t, "resample_rows tensor")
+        if flat.dim() != 1 or out.dim() != 1 or rows.dim() != 2 or rows.shape[1] != 4 or rows.shape[0] < 1:
+            raise WunetError("resample_rows: shape mismatch (flat arrays in and out, rows [n, 4] with n >= 1)")
+        dev = out.device
+        if flat.device != dev or rows.device != dev:
+            raise WunetError("resample_rows: every tensor must live on one device")
+        up, down, taps = self.resample_taps(rate_in, rate_out, dev)
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_resample_rows(flat.data_ptr(), flat.numel(), rows.data_ptr(), rows.shape[0], int(max_out), up, down,
+                                                     taps.data_ptr(), taps.numel(), out.data_ptr(), out.numel(), self._stream(dev)))
+        return out
 
 
 class _CtxHold:

@@ -20,6 +20,10 @@ Two things beyond the reference, both opt-in (include/wunet_hip.h: wunet_chunk_g
     (Wave-U-Net's "context", Demucs' apply_model); it has not been measured on this project.
   * `enhance_many(model, recordings, ...)`: the chunks of many recordings of any lengths share the slabs of one pass - one flat array,
     one table of chunks, one table of recordings, one gather and one overlap-add - instead of one small forward per recording.
+  * recordings at another sample rate than the model's, `enhance(..., sample_rate=48000)` / `enhance_many(..., sample_rates=[...])`:
+    resampled to `model_rate` on the device (resample.py, wunet_resample_rows), enhanced by the paths above, unchanged, and resampled
+    back to the rate and the length they came with.  The way back is never short: ceil(ceil(T u / d) d / u) >= T.  What lay above
+    model_rate / 2 in the input is removed by the first filter and is not restored.
 """
 import functools
 
@@ -125,6 +129,19 @@ def _result_to_host(out_flat):
     return host
 
 
+def _other_rate(sample_rate, model_rate, what="sample_rate"):
+    """None when the recording is at the model's rate (or no rate is given), else the checked pair (rate, model rate); ValueError for a
+    rate that is not a positive integer and for a pair whose filter is above the resampler's cap."""
+    if sample_rate is None:
+        return None
+    from .resample import rate_ratio
+    try:
+        up, down = rate_ratio(sample_rate, model_rate)
+    except ValueError as e:
+        raise ValueError(f"enhance: {what} / model_rate: {e}") from None
+    return None if up == down else (int(sample_rate), int(model_rate))
+
+
 def _check_call(model, max_batch):
     if model.training:
         raise RuntimeError("enhance() needs model.eval(): chunks are only independent with running BatchNorm statistics")
@@ -133,18 +150,33 @@ def _check_call(model, max_batch):
 
 
 @torch.no_grad()
-def enhance(model, mixture, sample_length=16384, max_batch=256, to_host=False, margin=0, fade=0, window="hann", engine=None):
+def enhance(model, mixture, sample_length=16384, max_batch=256, to_host=False, margin=0, fade=0, window="hann", engine=None,
+            sample_rate=None, model_rate=16000):
     """mixture: float32 [1, 1, T] (any T, the reference's batch-1 contract, enhancement.py:50) on the model's device.
     Returns the enhanced waveform [1, 1, T] - on the model's device, or with to_host=True as a host tensor (what the reference
     hands to the file writer, enhancement.py:66-71): every slab goes into one pinned buffer with an asynchronous copy,
     one synchronisation at the end instead of one per chunk.
     margin / fade / window: the overlapped chunks of this file's header (margin = fade = 0, the default: the reference's disjoint
-    chunks, by the code path of before).  engine: the engine of the two chunk kernels; default the model's own."""
+    chunks, by the code path of before).  engine: the engine of the chunk and resampling kernels; default the model's own.
+    sample_rate: the rate of `mixture` in Hz when it is not the model's (default None: the samples are run as they are).  With a rate
+    other than `model_rate` the mixture is resampled to model_rate on the device, enhanced as above (sample_length, margin and fade
+    count samples at model_rate) and resampled back to its own rate and its own T.  Content above model_rate / 2 is not restored:
+    the output is band-limited to the model's band.  to_host=True is then one pinned copy of the result at the input's rate."""
     if mixture.dim() != 3 or mixture.shape[0] != 1 or mixture.shape[1] != 1:
         raise ValueError("Only support batch size is 1 in enhancement stage.")       # reference wording, enhancement.py:50
     _check_call(model, max_batch)
     chunk_hop(sample_length, margin, fade, window)
     T = mixture.shape[-1]
+    rates = _other_rate(sample_rate, model_rate)
+    if rates is not None:
+        from .resample import resample
+        if T < 1:
+            raise ValueError("enhance: a recording needs at least one sample (got 0)")
+        eng = _engine_of(model, engine)
+        at_model = resample(mixture.to(torch.float32), rates[0], rates[1], engine=eng)
+        enhanced = enhance(model, at_model, sample_length, max_batch, False, margin, fade, window, engine)
+        back = resample(enhanced.to(torch.float32), rates[1], rates[0], engine=eng, length=T).view(-1)
+        return (_result_to_host(back) if to_host else back).view(1, 1, T)
     if margin or fade:
         if T < 1:
             raise ValueError("enhance: a recording needs at least one sample (got 0)")
@@ -170,14 +202,19 @@ def enhance(model, mixture, sample_length=16384, max_batch=256, to_host=False, m
 
 
 @torch.no_grad()
-def enhance_many(model, recordings, sample_length=16384, max_batch=256, to_host=False, margin=0, fade=0, window="hann", engine=None):
+def enhance_many(model, recordings, sample_length=16384, max_batch=256, to_host=False, margin=0, fade=0, window="hann", engine=None,
+                 sample_rates=None, model_rate=16000):
     """recordings: a list of float32 [1, 1, T_r] (or [T_r]) tensors of any lengths on the model's device.  Returns the list of enhanced
     waveforms in the same shapes (views of one buffer; with to_host=True of one pinned host buffer).  The chunks of all recordings are
     cut by one gather, run in slabs of `max_batch` chunks that recordings share, and put back by one overlap-add.  The gather and the
     overlap-add give a recording the bits enhance() gives it alone (at margin = fade = 0 too, where enhance() itself runs the code
     path of before), so the results are equal bit for bit whenever the model gives a row the same bits in a slab of another size.  In
     eval mode no row reads another, but the network's planner picks its GEMM tiling and reduction split by batch size (csrc/wunet_plan.cpp),
-    so at other slab sizes a row may differ by the rounding of those sums."""
+    so at other slab sizes a row may differ by the rounding of those sums.
+    sample_rates: None (default: the samples are run as they are), one rate in Hz for all recordings or a list with one rate per
+    recording.  Recordings at another rate than `model_rate` are resampled to it - one launch per distinct rate, written straight into
+    the flat array of the pass - share the slabs with all the others at model_rate, and are resampled back to their own rate and
+    length, again one launch per distinct rate (what enhance(..., sample_rate=) does for one recording, bit for bit)."""
     _check_call(model, max_batch)
     chunk_hop(sample_length, margin, fade, window)
     recordings = list(recordings)
@@ -192,6 +229,17 @@ def enhance_many(model, recordings, sample_length=16384, max_batch=256, to_host=
         if x.shape[-1] < 1:
             raise ValueError("enhance: a recording needs at least one sample (got 0)")
     lengths = [int(x.shape[-1]) for x in recordings]
+    if sample_rates is not None:
+        if isinstance(sample_rates, (list, tuple)):
+            if len(sample_rates) != len(recordings):
+                raise ValueError(f"enhance_many: sample_rates needs one rate per recording (got {len(sample_rates)} for {len(recordings)})")
+            pairs = [_other_rate(r, model_rate, "sample_rates") for r in sample_rates]
+            if any(r is None for r in sample_rates):
+                raise ValueError("enhance_many: sample_rates must not contain None")
+        else:
+            pairs = [_other_rate(sample_rates, model_rate, "sample_rates")] * len(recordings)
+        if any(p is not None for p in pairs):
+            return _enhance_many_rates(model, recordings, lengths, pairs, sample_length, max_batch, to_host, margin, fade, window, engine)
     _, recs, total = chunk_tables(lengths, sample_length, margin, fade)
     flat = torch.empty(total, dtype=torch.float32, device=dev)   # (the gaps between recordings are never read: the gather masks by T)
     for x, (start, T, _, _) in zip(recordings, recs.tolist()):
@@ -200,3 +248,40 @@ def enhance_many(model, recordings, sample_length=16384, max_batch=256, to_host=
     if to_host:
         out_flat = _result_to_host(out_flat)
     return [out_flat[s:s + T].view(x.shape) for x, s, T in zip(recordings, starts.tolist(), lengths)]
+
+
+def _enhance_many_rates(model, recordings, lengths, pairs, sample_length, max_batch, to_host, margin, fade, window, engine):
+    """enhance_many where some recording is not at the model's rate.  pairs[r]: None or (rate, model rate) of recording r."""
+    from .resample import resampled_length
+    eng = _engine_of(model, engine)
+    dev = recordings[0].device
+    at_model = [T if p is None else resampled_length(T, p[0], p[1]) for T, p in zip(lengths, pairs)]
+    _, recs, total = chunk_tables(at_model, sample_length, margin, fade)
+    starts = recs[:, 0].tolist()
+    groups = {}                                                   # rate -> the recordings at it, in their order
+    for r, p in enumerate(pairs):
+        groups.setdefault(None if p is None else p[0], []).append(r)
+    model_rate = next(p[1] for p in pairs if p is not None)
+    flat = torch.empty(total, dtype=torch.float32, device=dev)
+    for rate, members in groups.items():
+        if rate is None:
+            for r in members:
+                flat[starts[r]:starts[r] + lengths[r]].copy_(recordings[r].reshape(-1))
+            continue
+        src = torch.cat([recordings[r].reshape(-1) for r in members]) if len(members) > 1 else recordings[members[0]].contiguous().view(-1)
+        offs = np.concatenate([[0], np.cumsum([lengths[r] for r in members])])
+        table = np.asarray([(offs[k], lengths[r], starts[r], at_model[r]) for k, r in enumerate(members)], np.int64).reshape(-1, 4)
+        eng.resample_rows(src, torch.from_numpy(table).to(dev, non_blocking=True), flat, rate, model_rate, max(at_model[r] for r in members))
+    out_flat, _ = _table_driven(model, flat, at_model, sample_length, max_batch, margin, fade, window, engine)
+    own = np.concatenate([[0], np.cumsum(lengths)])               # the results at their own rates, back to back
+    final = torch.empty(int(own[-1]), dtype=torch.float32, device=dev)
+    for rate, members in groups.items():
+        if rate is None:
+            for r in members:
+                final[own[r]:own[r] + lengths[r]].copy_(out_flat[starts[r]:starts[r] + lengths[r]])
+            continue
+        table = np.asarray([(starts[r], at_model[r], own[r], lengths[r]) for r in members], np.int64).reshape(-1, 4)
+        eng.resample_rows(out_flat, torch.from_numpy(table).to(dev, non_blocking=True), final, model_rate, rate, max(lengths[r] for r in members))
+    if to_host:
+        final = _result_to_host(final)
+    return [final[int(own[r]):int(own[r]) + T].view(x.shape) for r, (x, T) in enumerate(zip(recordings, lengths))]

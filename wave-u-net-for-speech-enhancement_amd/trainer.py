@@ -31,6 +31,10 @@ Differences from the reference loop, all on the f2 list:
   * `"validation": {"custom": {"margin": m, "fade": f, "window": "hann"}}` enhances with overlapped, cross-faded chunks and
     `"validation": {"recordings_per_pass": N}` enhances N recordings per pass in shared slabs (inference.py: enhance / enhance_many);
     the score, the one device->host read and the restored flags are the same.  Without these keys nothing changes;
+  * `"validation": {"custom": {"sample_rate": 48000, "model_rate": 16000}}`: validation files at another rate than the network's.
+    Every recording is resampled to "model_rate" on the device, enhanced, and resampled back to its own rate and length
+    (inference.py: enhance(sample_rate=, model_rate=)); SI-SDR and STOI score at the files' rate, "sample_rate".  Without "model_rate",
+    or with the two equal, nothing changes;
   * STOI, the first half of the reference's score (STOI + PESQ') / 2 (trainer/trainer.py:128-143), on the device: beside "metric":
     "si_sdr" the optional key `"stoi": "report"` also appends (mean STOI of the noisy recordings, mean STOI of the enhanced ones) to
     `validation_stoi` every validation epoch and leaves the score alone; `"stoi": "score"` makes the mean STOI of the enhanced
@@ -134,6 +138,17 @@ class Trainer:
         if "stoi_extended" in vcfg and self.validation_stoi_mode is None:
             raise ValueError('trainer config "validation.stoi_extended" needs "validation.stoi": "report" or "score" beside it')
         self.validation_sample_rate = int((vcfg.get("custom") or {}).get("sample_rate", 16000))
+        # "custom.model_rate": the rate the network runs at when the validation files ("custom.sample_rate") are at another one - the
+        # recordings are resampled to it, enhanced and resampled back on the device (inference.py); the scores stay at the files' rate
+        self.validation_rates = {}
+        if "model_rate" in custom:
+            from .inference import _other_rate
+            try:
+                _other_rate(custom.get("sample_rate", 16000), custom["model_rate"])
+            except ValueError as e:
+                raise ValueError(f'trainer config "validation.custom": {e}') from None
+            if custom["model_rate"] != self.validation_sample_rate:
+                self.validation_rates = {"sample_rate": self.validation_sample_rate, "model_rate": int(custom["model_rate"])}
         self.validation_stoi = []     # with "validation.stoi": (mean STOI noisy, mean STOI enhanced) per validation epoch
         self.epochs = tcfg["epochs"]
         self.save_checkpoint_interval = tcfg.get("save_checkpoint_interval", 0)
@@ -233,7 +248,8 @@ class Trainer:
         per_pass = self.validation_recordings_per_pass
 
         def flush(held):
-            outs = enhance_many(model, [mix for mix, _ in held], self.validation_sample_length, **self.validation_overlap)
+            many = {"sample_rates": self.validation_rates["sample_rate"], "model_rate": self.validation_rates["model_rate"]} if self.validation_rates else {}
+            outs = enhance_many(model, [mix for mix, _ in held], self.validation_sample_length, **self.validation_overlap, **many)
             return [(mix, cl, out) for (mix, cl), out in zip(held, outs)]
 
         def passes():
@@ -246,7 +262,7 @@ class Trainer:
                 mixture = mixture.to(self.device, non_blocking=True)
                 clean = clean.to(self.device, non_blocking=True)
                 if per_pass is None:
-                    yield mixture, clean, enhance(model, mixture, self.validation_sample_length, **self.validation_overlap)
+                    yield mixture, clean, enhance(model, mixture, self.validation_sample_length, **self.validation_overlap, **self.validation_rates)
                     continue
                 held.append((mixture, clean))
                 if len(held) == per_pass:

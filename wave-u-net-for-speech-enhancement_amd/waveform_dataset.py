@@ -7,7 +7,8 @@ Two pieces, both float32 mono like the reference's items:
   aligned random crop as util/utils.py:101-113 including its use of `np.random.randint`, so a seeded run crops the
   same windows).  The reference decodes with librosa.load(sr=None); this image has no audio library, so RIFF/WAVE
   files are parsed here (PCM 8/16/24/32 bit and IEEE float 32/64, any channel count -> mono mean, no resampling -
-  what librosa.load(sr=None, mono=True) returns for such files).
+  what librosa.load(sr=None, mono=True) returns for such files).  The three pack_* functions below take `sample_rate=` to bring
+  files of other rates to the shard's rate on the device (resample.py) while they are packed.
 
       "train_dataset": {"module": "wave-u-net-for-speech-enhancement_amd.waveform_dataset", "main": "Dataset",
                         "args": {"dataset": "~/train.txt", "limit": null, "offset": 0, "sample_length": 16384, "mode": "train"}}
@@ -139,14 +140,43 @@ class Dataset(data.Dataset):
 
 
 # ---------------------------------------------------------------------------------------------- shards
-def pack_shard(dataset, prefix, limit=None, offset=0):
+def _target_rate(sample_rate):
+    if sample_rate is None:
+        return None
+    from .resample import rate_ratio
+    rate_ratio(sample_rate, sample_rate)                       # (ValueError for what is not a positive integer)
+    return int(sample_rate)
+
+
+def _at_rate(x, rate, target, engine):
+    """The decoded file x (float32, `rate` Hz) at `target` Hz: resampled on the device (resample.py) when the two differ."""
+    if rate == target:
+        return x
+    from .resample import resample
+    if engine is None:
+        from .engine import default_engine
+        engine = default_engine()
+    if len(x) == 0:
+        return x
+    dev = torch.device("cpu") if engine.host_memory else torch.device("cuda", torch.cuda.current_device())
+    return resample(torch.from_numpy(x).to(dev), rate, target, engine=engine).cpu().numpy()
+
+
+def pack_shard(dataset, prefix, limit=None, offset=0, sample_rate=None, engine=None):
     """Decode every pair of the list file once into `<prefix>.noisy.f32`, `<prefix>.clean.f32` (flat float32) and
-    `<prefix>.index.json` ({"names", "starts", "lengths", "sample_rate"}).  Returns the number of items."""
+    `<prefix>.index.json` ({"names", "starts", "lengths", "sample_rate"}).  Returns the number of items.
+    sample_rate: the rate of the shard in Hz.  A file at another rate is resampled to it on the device (`engine`: default the
+    process's) before it is written, so a list of mixed rates is legal and the index records `sample_rate`.  Default None: every file
+    must have one rate, which the index records - nothing is resampled."""
     pairs = PairList(dataset, limit, offset)
-    names, starts, lengths, rate, pos = [], [], [], None, 0
+    target = _target_rate(sample_rate)
+    names, starts, lengths, rate, pos = [], [], [], target, 0
     with open(prefix + ".noisy.f32", "wb") as fn, open(prefix + ".clean.f32", "wb") as fc:
         for k in range(len(pairs)):
             mixture, clean, r0, r1, name = pairs.decode(k)
+            if target is not None:
+                mixture, clean = _at_rate(mixture, r0, target, engine), _at_rate(clean, r1, target, engine)
+                r0 = r1 = target
             assert len(mixture) == len(clean), f"Inconsistent dataset length: {pairs.pair(k)[0]}"
             assert r0 == r1 and (rate is None or rate == r0), f"mixed sample rates: {pairs.pair(k)[0]}"
             rate = r0
@@ -237,17 +267,21 @@ class ShardLoader:
 
 
 # ---------------------------------------------------------------------------------------------- mixtures made on the device
-def pack_mono_shard(list_file, prefix, limit=None, offset=0):
+def pack_mono_shard(list_file, prefix, limit=None, offset=0, sample_rate=None, engine=None):
     """Decode every file of the list (one path per line; `offset` lines skipped, then at most `limit` kept) once into `<prefix>.f32`
     (flat float32) and `<prefix>.index.json` (pack_shard's keys: {"names", "starts", "lengths", "sample_rate"}; an item's name is its
-    file's stem).  The clean corpus and the noise corpus of a MixLoader are each one such shard.  Returns the number of items."""
+    file's stem).  The clean corpus and the noise corpus of a MixLoader are each one such shard.  Returns the number of items.
+    sample_rate / engine: pack_shard's - with a rate, files at other rates are resampled to it on the device."""
     with open(os.path.abspath(os.path.expanduser(list_file)), "r") as f:
         paths = [ln.strip() for ln in f][offset:]
     paths = [p for p in (paths[:limit] if limit else paths) if p]
-    names, starts, lengths, rate, pos = [], [], [], None, 0
+    target = _target_rate(sample_rate)
+    names, starts, lengths, rate, pos = [], [], [], target, 0
     with open(prefix + ".f32", "wb") as out:
         for path in paths:
             x, r = read_wav(path)
+            if target is not None:
+                x, r = _at_rate(x, r, target, engine), target
             assert rate is None or rate == r, f"mixed sample rates: {path}"
             rate = r
             out.write(x.tobytes())
@@ -263,20 +297,25 @@ def pack_mono_shard(list_file, prefix, limit=None, offset=0):
 RIR_MAX_TAPS = 16384          # include/wunet_hip.h: WUNET_REVERB_MAX_TAPS
 
 
-def pack_rir_shard(list_file, prefix, max_taps=8192, limit=None, offset=0):
+def pack_rir_shard(list_file, prefix, max_taps=8192, limit=None, offset=0, sample_rate=None, engine=None):
     """Room impulse responses for MixLoader(rir_prefix=...): pack_mono_shard's list handling (one path per line) and files (`<prefix>.f32`,
     `<prefix>.index.json` with the same keys), but every response is cut to start at its direct path and scaled to it: with
     p = argmax |h| the stored item is h[p : p + max_taps] / h[p], so h[0] == 1.0.  The propagation delay is gone - a dry target stays
-    time-aligned with the reverberant signal - and so is the response's own gain.  Returns the number of items."""
+    time-aligned with the reverberant signal - and so is the response's own gain.  Returns the number of items.
+    sample_rate / engine: pack_shard's - with a rate, a response at another rate is resampled to it on the device first, so the direct
+    path is found, and max_taps counted, at the shard's rate."""
     if not 1 <= max_taps <= RIR_MAX_TAPS:
         raise ValueError(f"max_taps must be in [1, {RIR_MAX_TAPS}], got {max_taps}")
     with open(os.path.abspath(os.path.expanduser(list_file)), "r") as f:
         paths = [ln.strip() for ln in f][offset:]
     paths = [p for p in (paths[:limit] if limit else paths) if p]
-    names, starts, lengths, rate, pos = [], [], [], None, 0
+    target = _target_rate(sample_rate)
+    names, starts, lengths, rate, pos = [], [], [], target, 0
     with open(prefix + ".f32", "wb") as out:
         for path in paths:
             h, r = read_wav(path)
+            if target is not None:
+                h, r = _at_rate(h, r, target, engine), target
             if rate is not None and rate != r:
                 raise ValueError(f"mixed sample rates: {path} ({r} vs {rate})")
             rate = r
