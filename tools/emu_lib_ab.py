@@ -10,8 +10,13 @@ emulator build reports no flops / bytes).  Planner switches are read when a cont
 (A base library from before PlanSwitches reads WUNET_WGRAD_XCD and WUNET_A_CAP once per process: set those outside, one run each.
 One from before WUNET_NO_ENC_GZ and WUNET_PA_SWAP joined them reads those two at its first backward and keeps them: its runs of their
 cases have them unset - the results are to be the same bits either way.)
+The auxiliary entry points (aux_cases: the losses forward and backward, the loader ops, the chunk ops, resampling, on the tests' case
+tables) are compared the same way, array by array plus the profiler's text, and their refusals (refusals: one bad argument per call)
+by return value and wunet_last_error().  The 12 hex digits printed per auxiliary case are a hash of the new library's arrays: two
+checkouts of the Python side can be held against each other by the tool's output.  EMU_LIB_AB_AUX_ONLY=1 skips the network cases.
 Exit status 0: nothing differs."""
 import ctypes
+import hashlib
 import importlib
 import os
 import sys
@@ -158,6 +163,228 @@ def run_case(lib, shape, h3, mode, mask_name, switches):
     return res
 
 
+# ------------------------------------------------------------------ the auxiliary entry points: losses, loader ops, chunks, resampling
+CPU = torch.device("cpu")
+
+
+def _loss_and_grad(crit, c, e):
+    x = e.detach().clone().requires_grad_(True)
+    loss = crit(c, x)
+    loss.backward()
+    return {"loss": loss.detach().numpy().copy(), "grad": x.grad.numpy().copy()}
+
+
+def aux_cases():
+    """(label, run(engine) -> {name: array}) over the case tables of the tests (tests/*_cases.py): their shapes are the smallest at
+    which these kernels can go wrong.  The losses run forward and backward; the spectral ones include a window shorter than n_fft
+    (a, d) and three resolutions in one call (d: the backward accumulates)."""
+    import chunks_cases as K
+    import cspec_loss_cases as CS
+    import estoi_cases as EC
+    import mix_cases as M
+    import resample_cases as RS
+    import reverb_cases as RV
+    import stft_loss_cases as S
+    import stft_loss_ref
+    import stoi_loss_cases as SL
+    import stoi_ref
+    out = []
+    for name in S.EMU_CASES:
+        rows, T, res = S.CASES[name]
+        c, e = stft_loss_ref.pair(rows, T)
+        out.append((f"stft_loss {name}", lambda eng, res=res, c=c, e=e: _loss_and_grad(S.criterion(eng, res), c, e)))
+        for compress, weight in [k[1:] for k in CS.params((name,))]:
+            out.append((f"cspec_loss {name} compress={compress} complex_weight={weight}", lambda eng, res=res, c=c, e=e, kw=dict(
+                compress=compress, complex_weight=weight): _loss_and_grad(CS.criterion(eng, res, **kw), c, e)))
+    rows, T, res = S.CASES["a"]
+    mags = importlib.import_module(PKG + ".metrics").stft_magnitude
+    out.append(("stft_magnitude a", lambda eng: {"mag": mags(stft_loss_ref.pair(rows, T)[1], *res[0], engine=eng).numpy().copy()}))
+    for name in SL.CASES:
+        c, e = stoi_ref.pair(*SL.CASES[name])
+        fs = SL.CASES[name][2]
+        out.append((f"stoi_loss {name}", lambda eng, fs=fs, c=c, e=e: _loss_and_grad(SL.make(eng, fs), c, e)))
+        out.append((f"estoi_loss {name}", lambda eng, fs=fs, c=c, e=e: _loss_and_grad(EC.make_loss(eng, fs), c, e)))
+
+    def mix(eng, name):
+        m, cl, gains = M.run(eng, CPU, name)
+        level = eng.apply_level(m.clone(), gains)                              # (in place on a copy: the multiply of clean_out)
+        return {"mixture": m.numpy().copy(), "clean": cl.numpy().copy(), "gains": gains.numpy().copy(), "level": level.numpy().copy()}
+
+    def reverb(eng, name):
+        rev, direct = RV.run(eng, CPU, name)
+        return {"reverberant": rev.numpy().copy(), "direct": direct.numpy().copy(), "alone": RV.run(eng, CPU, name, with_direct=False)[0].numpy().copy()}
+
+    def chunks(eng, name, window):
+        L, m, f, lengths = K.CASES[name]
+        return {f"T={T}": K.enhance_one(eng, CPU, K.recording(T), L, m, f, window, K.Stub(L)).numpy().copy() for T in lengths}
+
+    def resample(eng, name):
+        rate_in, rate_out, T = RS.CASES[name]
+        x = torch.from_numpy(np.stack([RS.signal(T), RS.signal(T, seed=1)]))
+        return {"out": RS.resample_mod().resample(x, rate_in, rate_out, engine=eng).numpy().copy()}
+
+    def resample_ragged(eng, rates):
+        """RS.run_table's layout (rows at odd offsets of guarded arrays) without its oracle."""
+        rs = RS.resample_mod()
+        rows = [(T, rs.resampled_length(T, *rates)) for T in RS.RAGGED]
+        ins, in_total = RS.odd_layout([r[0] for r in rows])
+        outs, out_total = RS.odd_layout([r[1] for r in rows], first=3)
+        src = np.full(in_total, K.SENTINEL, np.float32)
+        for k, ((T, _), s) in enumerate(zip(rows, ins)):
+            src[s:s + T] = RS.signal(T, seed=k % 3)
+        table = torch.from_numpy(np.asarray([(a, T, b, To) for (T, To), a, b in zip(rows, ins, outs)], np.int64))
+        out = torch.full((out_total,), K.SENTINEL)
+        eng.resample_rows(torch.from_numpy(src), table, out, *rates, max(r[1] for r in rows))
+        return {"out": out.numpy().copy()}
+
+    out += [(f"mix_windows + apply_level {name}", lambda eng, name=name: mix(eng, name)) for name in M.CASES]
+    out += [(f"reverb_windows {name}", lambda eng, name=name: reverb(eng, name)) for name in RV.CASES]
+    out += [(f"chunk_gather + chunk_overlap_add {name} {w}", lambda eng, name=name, w=w: chunks(eng, name, w)) for name in K.CASES for w in K.WINDOWS]
+    out += [(f"resample_rows {name}", lambda eng, name=name: resample(eng, name)) for name in RS.CASES]
+    out += [(f"resample_rows ragged {r[0]} -> {r[1]}", lambda eng, r=r: resample_ragged(eng, r)) for r in RS.RAGGED_RATES]
+    return out
+
+
+def run_aux(lib, fn):
+    eng = eng_mod.Engine(lib=lib, host_memory=True)
+    lib.wunet_profile_enable(1)
+    res = {}
+    try:
+        res = fn(eng)
+    finally:
+        res["profile"] = profile_text(lib)
+    return res
+
+
+def refusals():
+    """(entry point, arguments): one bad argument per refusal of the auxiliary entry points; every other argument is valid (P: a zeroed,
+    64-byte aligned MiB, large enough for the shapes here should a call go through).  Compared: the return value and wunet_last_error()."""
+    raw = ctypes.create_string_buffer((1 << 20) + 64)
+    P = (ctypes.addressof(raw) + 63) & ~63
+    refusals.keep = raw
+    nan, big = float("nan"), 1 << 62
+    ints = lambda *v: ctypes.cast((ctypes.c_int * len(v))(*v), ctypes.c_void_p)                     # noqa: E731
+    ptrs = lambda *v: ctypes.cast((ctypes.c_void_p * len(v))(*v), ctypes.c_void_p)                  # noqa: E731
+    out = []
+    # one resolution on 2 rows of 100 samples: n_fft 64, hop 16, window 48
+    shapes = [(2, 0, 64, 16, 48), (2, 100, 60, 16, 48), (2, 100, 8192, 16, 48), (2, 100, 64, 0, 48), (2, 100, 64, 65, 48), (0, 100, 64, 16, 48),
+              (2, 20, 64, 16, 48), (1 << 30, 100, 64, 16, 48), (2, 1 << 30, 64, 16, 48), (1 << 29, 256, 64, 1, 48)]
+    for fam in ("stft", "cspec"):
+        for R, T, N, H, W in shapes:                          # (the size queries and finalize do not take the window)
+            out.append((f"wunet_{fam}_scratch_bytes", (R, T, N, H, 1)))
+            out.append((f"wunet_{fam}_saved_bytes", (R, T, N, H)))
+            out.append((f"wunet_{fam}_finalize", (1, ptrs(P), R, T, ints(N), ints(H)) + ((1.0, 1.0) if fam == "stft" else (0.3,)) + (P, P, None)))
+    shapes += [(2, 100, 64, 16, 0), (2, 100, 64, 16, 65)]
+    fwd = lambda a, b, clamp, basis, scr, sv, mag, shape=(2, 100, 64, 16, 48): ("wunet_stft_forward", (a, b) + shape + (clamp, basis, scr, sv, mag, None))   # noqa: E731
+    out += [fwd(P, P, 1e-7, P, P, P, None, s) for s in shapes]
+    out += [fwd(P, None, 1e-7, P, P, P, None), fwd(P, P, 1e-7, None, P, P, None), fwd(P, P, 1e-7, P + 4, P, P, None), fwd(P, P, 0.0, P, P, P, None),
+            fwd(P, P, nan, P, P, P, None), fwd(P, P, 1e39, P, P, P, None), fwd(P, P, 1e-7, P, None, P, None), fwd(None, P, -1.0, P, None, None, P),
+            fwd(None, P, 0.0, P, None, None, None), fwd(None, P, 0.0, P, None, P, P)]
+    fin = lambda *a: ("wunet_stft_finalize", a + (None,))                      # noqa: E731
+    out += [fin(0, ptrs(P), 2, 100, ints(64), ints(16), 1.0, 1.0, P, P), fin(9, ptrs(*[P] * 9), 2, 100, ints(*[64] * 9), ints(*[16] * 9), 1.0, 1.0, P, P),
+            fin(1, None, 2, 100, ints(64), ints(16), 1.0, 1.0, P, P), fin(1, ptrs(P), 2, 100, None, ints(16), 1.0, 1.0, P, P),
+            fin(1, ptrs(P), 2, 100, ints(64), None, 1.0, 1.0, P, P), fin(1, ptrs(P), 2, 100, ints(64), ints(16), 1.0, 1.0, None, P),
+            fin(1, ptrs(P), 2, 100, ints(64), ints(16), nan, 1.0, P, P), fin(1, ptrs(P), 2, 100, ints(64), ints(16), 1.0, nan, P, P),
+            fin(2, ptrs(P, None), 2, 100, ints(64, 64), ints(16, 16), 1.0, 1.0, P, P), fin(2, ptrs(P, P), 2, 100, ints(64, 60), ints(16, 16), 1.0, 1.0, P, P)]
+    bwd = lambda sv, co, gl, clamp, basis, scr, g, shape=(2, 100, 64, 16, 48): ("wunet_stft_backward", (sv, co, gl) + shape + (clamp, basis, scr, g, 0, None))   # noqa: E731
+    out += [bwd(P, P, P, 1e-7, P, P, P, s) for s in shapes]
+    out += [bwd(None, P, P, 1e-7, P, P, P), bwd(P, None, P, 1e-7, P, P, P), bwd(P, P, None, 1e-7, P, P, P), bwd(P, P, P, 1e-7, None, P, P),
+            bwd(P, P, P, 1e-7, P + 4, P, P), bwd(P, P, P, 1e-7, P, None, P), bwd(P, P, P, 1e-7, P, P, None), bwd(P, P, P, 0.0, P, P, P),
+            bwd(P, P, P, nan, P, P, P)]
+    # the compressed spectral loss on the same shape: 14 frames, 64 padded bins, 2 partials per block
+    n_scr, n_bwd, n_sv = (1 << 20), (1 << 20), 5 * 14 * 64 * 4
+    cf = lambda a, b, compress, clamp, basis, scr, nscr, sv, nsv, shape=(2, 100, 64, 16, 48): (         # noqa: E731
+        "wunet_cspec_forward", (a, b) + shape + (compress, clamp, basis, scr, nscr, sv, nsv, None))
+    out += [cf(P, P, 0.3, 1e-7, P, P, n_scr, P, n_sv, s) for s in shapes]
+    out += [cf(P, P, 0.0, 1e-7, P, P, n_scr, P, n_sv), cf(P, P, 1.5, 1e-7, P, P, n_scr, P, n_sv), cf(P, P, nan, 1e-7, P, P, n_scr, P, n_sv),
+            cf(P, P, 0.3, 0.0, P, P, n_scr, P, n_sv), cf(P, P, 0.3, 1e39, P, P, n_scr, P, n_sv), cf(None, P, 0.3, 1e-7, P, P, n_scr, P, n_sv),
+            cf(P, None, 0.3, 1e-7, P, P, n_scr, P, n_sv), cf(P, P, 0.3, 1e-7, None, P, n_scr, P, n_sv), cf(P, P, 0.3, 1e-7, P + 4, P, n_scr, P, n_sv),
+            cf(P, P, 0.3, 1e-7, P, None, n_scr, P, n_sv), cf(P, P, 0.3, 1e-7, P, P, 8, P, n_sv), cf(P, P, 0.3, 1e-7, P, P, n_scr, P, n_sv - 4),
+            cf(P, P, 0.3, 1e-7, P, P, n_scr, None, n_sv)]
+    cfin = lambda *a: ("wunet_cspec_finalize", a + (None,))                   # noqa: E731
+    out += [cfin(0, ptrs(P), 2, 100, ints(64), ints(16), 0.3, P, P), cfin(9, ptrs(*[P] * 9), 2, 100, ints(*[64] * 9), ints(*[16] * 9), 0.3, P, P),
+            cfin(1, None, 2, 100, ints(64), ints(16), 0.3, P, P), cfin(1, ptrs(P), 2, 100, None, ints(16), 0.3, P, P),
+            cfin(1, ptrs(P), 2, 100, ints(64), None, 0.3, P, P), cfin(1, ptrs(P), 2, 100, ints(64), ints(16), 0.3, None, P),
+            cfin(1, ptrs(P), 2, 100, ints(64), ints(16), -0.1, P, P), cfin(1, ptrs(P), 2, 100, ints(64), ints(16), 1.5, P, P),
+            cfin(1, ptrs(P), 2, 100, ints(64), ints(16), nan, P, P), cfin(2, ptrs(P, None), 2, 100, ints(64, 64), ints(16, 16), 0.3, P, P),
+            cfin(2, ptrs(P, P), 2, 100, ints(64, 60), ints(16, 16), 0.3, P, P)]
+    cb = lambda sv, nsv, co, gl, compress, clamp, basis, scr, nscr, g, shape=(2, 100, 64, 16, 48): (    # noqa: E731
+        "wunet_cspec_backward", (sv, nsv, co, gl) + shape + (compress, clamp, basis, scr, nscr, g, 0, None))
+    out += [cb(P, n_sv, P, P, 0.3, 1e-7, P, P, n_bwd, P, s) for s in shapes]
+    out += [cb(P, n_sv, P, P, 0.0, 1e-7, P, P, n_bwd, P), cb(P, n_sv, P, P, 0.3, 0.0, P, P, n_bwd, P), cb(None, n_sv, P, P, 0.3, 1e-7, P, P, n_bwd, P),
+            cb(P, n_sv, None, P, 0.3, 1e-7, P, P, n_bwd, P), cb(P, n_sv, P, None, 0.3, 1e-7, P, P, n_bwd, P), cb(P, n_sv, P, P, 0.3, 1e-7, None, P, n_bwd, P),
+            cb(P, n_sv, P, P, 0.3, 1e-7, P + 4, P, n_bwd, P), cb(P, n_sv, P, P, 0.3, 1e-7, P, P, n_bwd, None), cb(P, n_sv + 4, P, P, 0.3, 1e-7, P, P, n_bwd, P),
+            cb(P, n_sv, P, P, 0.3, 1e-7, P, None, n_bwd, P), cb(P, n_sv, P, P, 0.3, 1e-7, P, P, 64, P)]
+    # row losses (kind 3: SI-SDR)
+    rf = lambda kind, eps, c, e, R, T, loss, scr: ("wunet_loss_rows_forward", (kind, 1, eps, c, e, R, T, loss, None, None, scr, None))   # noqa: E731
+    rb = lambda kind, c, e, co, gl, R, T, g: ("wunet_loss_rows_backward", (kind, c, e, co, gl, R, T, g, None))                           # noqa: E731
+    out += [rf(2, 1e-8, P, P, 2, 100, P, P), rf(3, 1e-8, P, P, 0, 100, P, P), rf(3, 1e-8, P, P, 2, 0, P, P), rf(3, 1e-8, P, P, 1 << 30, 100, P, P),
+            rf(3, 1e-8, P, P, 2, 1 << 40, P, P), rf(3, 1e-8, None, P, 2, 100, P, P), rf(3, 1e-8, P, P, 2, 100, P, None), rf(3, -1.0, P, P, 2, 100, P, P),
+            rf(3, nan, P, P, 2, 100, P, P), rb(5, P, P, P, P, 2, 100, P), rb(4, P, P, P, P, 0, 100, P), rb(4, P, P, P, P, 2, 1 << 40, P),
+            rb(4, P, P, None, P, 2, 100, P), rb(4, P, P, P, P, 2, 100, None)]
+    out += [("wunet_loss_rows_scratch_bytes", (0, 100)), ("wunet_loss_rows_scratch_bytes", (2, 0))]
+    # the loader ops: 2 windows of 8 samples out of arrays of 64
+    out += [("wunet_mix_scratch_bytes", s) for s in [(0, 8), (2, 0), (65536, 8), (2, (1 << 30) + 1)]]
+    mw = lambda cl, ct, no, nt, rows, par, peak, B, L, scr, m, c: ("wunet_mix_windows", (cl, ct, no, nt, rows, par, peak, B, L, scr, m, c, None, None))   # noqa: E731
+    out += [mw(P, 64, P, 64, P, P, 0.99, 0, 8, P, P, P), mw(P, 64, P, 64, P, P, 0.99, 2, 0, P, P, P), mw(P, 64, P, 64, P, P, 0.99, 65536, 8, P, P, P),
+            mw(P, 1 << 40, P, 64, P, P, 0.99, 2, (1 << 30) + 1, P, P, P), mw(P, 7, P, 64, P, P, 0.99, 2, 8, P, P, P), mw(P, 64, P, 0, P, P, 0.99, 2, 8, P, P, P),
+            mw(P, 1 << 60, P, 64, P, P, 0.99, 2, 8, P, P, P), mw(P, 64, P, 1 << 60, P, P, 0.99, 2, 8, P, P, P), mw(None, 64, P, 64, P, P, 0.99, 2, 8, P, P, P),
+            mw(P, 64, P, 64, None, P, 0.99, 2, 8, P, P, P), mw(P, 64, P, 64, P, P, 0.99, 2, 8, None, P, P), mw(P, 64, P, 64, P, P, 0.99, 2, 8, P, P, None),
+            mw(P, 64, P, 64, P, P, nan, 2, 8, P, P, P), mw(P, 64, P, 64, P, P, 0.99, 2, 8, P + 4, P, P), mw(P, 64, P, 64, P, P, 0.99, 2, 8, P, P + 4, P),
+            mw(P, 64, P, 64, P, P, 0.99, 2, 8, P, P, P + 8)]
+    al = lambda src, gains, B, L, dst: ("wunet_apply_level", (src, gains, B, L, dst, None))       # noqa: E731
+    out += [al(P, P, 0, 8, P), al(P, P, 2, 0, P), al(P, P, 65536, 8, P), al(P, P, 2, (1 << 30) + 1, P), al(None, P, 2, 8, P), al(P, None, 2, 8, P),
+            al(P, P, 2, 8, None), al(P + 4, P, 2, 8, P), al(P, P, 2, 8, P + 4)]
+    rv = lambda cl, ct, rir, rt, rows, early, B, L, rev, direct: ("wunet_reverb_windows", (cl, ct, rir, rt, rows, early, B, L, rev, direct, None))   # noqa: E731
+    out += [rv(P, 64, P, 64, P, 1, 0, 8, P, P), rv(P, 64, P, 64, P, 1, 2, 0, P, P), rv(P, 64, P, 64, P, 1, 65536, 8, P, P),
+            rv(P, 1 << 40, P, 64, P, 1, 2, (1 << 30) + 1, P, P), rv(P, 7, P, 64, P, 1, 2, 8, P, P), rv(P, 64, P, 0, P, 1, 2, 8, P, P),
+            rv(P, 1 << 60, P, 64, P, 1, 2, 8, P, P), rv(P, 64, P, 1 << 60, P, 1, 2, 8, P, P), rv(None, 64, P, 64, P, 1, 2, 8, P, P),
+            rv(P, 64, None, 64, P, 1, 2, 8, P, P), rv(P, 64, P, 64, None, 1, 2, 8, P, P), rv(P, 64, P, 64, P, 1, 2, 8, None, P),
+            rv(P, 64, P, 64, P, 0, 2, 8, P, P), rv(P, 64, P, 64, P, 1, 2, 8, P + 4, P), rv(P, 64, P, 64, P, 1, 2, 8, P, P + 4)]
+    # the chunk ops: 2 chunks of 16 samples, margin 2, fade 4 (hop 8)
+    cg = lambda flat, total, rows, n, L, chunks: ("wunet_chunk_gather", (flat, total, rows, n, L, chunks, None))          # noqa: E731
+    out += [cg(P, 64, P, 0, 16, P), cg(P, 64, P, 2, 0, P), cg(P, 64, P, 1 << 31, 16, P), cg(P, 64, P, 2, (1 << 30) + 1, P), cg(P, 0, P, 2, 16, P),
+            cg(P, big, P, 2, 16, P), cg(None, 64, P, 2, 16, P), cg(P, 64, None, 2, 16, P), cg(P, 64, P, 2, 16, None)]
+    co = lambda ch, n, L, m, f, ramp, recs, nrec, maxlen, out_, total: ("wunet_chunk_overlap_add", (ch, n, L, m, f, ramp, recs, nrec, maxlen, out_, total, None))   # noqa: E731
+    out += [co(P, 0, 16, 2, 4, P, P, 1, 24, P, 64), co(P, 2, 0, 2, 4, P, P, 1, 24, P, 64), co(P, 1 << 31, 16, 2, 4, P, P, 1, 24, P, 64),
+            co(P, 2, (1 << 30) + 1, 2, 4, P, P, 1, 24, P, 64), co(P, 2, 16, -1, 4, P, P, 1, 24, P, 64), co(P, 2, 16, 2, -1, P, P, 1, 24, P, 64),
+            co(P, 2, 16, 8, 0, None, P, 1, 24, P, 64), co(P, 2, 16, 2, 7, P, P, 1, 24, P, 64), co(P, 2, 16, 2, 4, None, P, 1, 24, P, 64),
+            co(P, 2, 16, 2, 0, P, P, 1, 24, P, 64), co(P, 2, 16, 2, 4, P, P, 0, 24, P, 64), co(P, 2, 16, 2, 4, P, P, 1 << 31, 24, P, 64),
+            co(P, 2, 16, 2, 4, P, P, 1, 0, P, 64), co(P, 2, 16, 2, 4, P, P, 1, big, P, 64), co(P, 2, 16, 2, 4, P, P, 1, 24, P, 0),
+            co(P, 2, 16, 2, 4, P, P, 1, 24, P, big), co(None, 2, 16, 2, 4, P, P, 1, 24, P, 64), co(P, 2, 16, 2, 4, P, None, 1, 24, P, 64),
+            co(P, 2, 16, 2, 4, P, P, 1, 24, None, 64)]
+    # resampling: 2 rows, 1 / 3 with 21 taps
+    rr = lambda i, it, rows, n, mo, up, down, taps, nt, o, ot: ("wunet_resample_rows", (i, it, rows, n, mo, up, down, taps, nt, o, ot, None))   # noqa: E731
+    out += [rr(P, 64, P, 0, 8, 1, 3, P, 21, P, 64), rr(P, 64, P, 2, 0, 1, 3, P, 21, P, 64), rr(P, 64, P, 1 << 31, 8, 1, 3, P, 21, P, 64),
+            rr(P, 64, P, 2, 8, 0, 3, P, 21, P, 64), rr(P, 64, P, 2, 8, 1, 0, P, 21, P, 64), rr(P, 64, P, 2, 8, 2, 4, P, 21, P, 64),
+            rr(P, 64, P, 2, 8, 1, 100000, P, 21, P, 64), rr(P, 64, P, 2, 8, 1, 3, P, 20, P, 64), rr(P, 64, P, 2, 8, 1, 3, P, 0, P, 64),
+            rr(P, 64, P, 2, 8, 1, 3, P, (1 << 24) + 1, P, 64), rr(P, 0, P, 2, 8, 1, 3, P, 21, P, 64), rr(P, big, P, 2, 8, 1, 3, P, 21, P, 64),
+            rr(P, 64, P, 2, 8, 1, 3, P, 21, P, 0), rr(P, 64, P, 2, 8, 1, 3, P, 21, P, big), rr(None, 64, P, 2, 8, 1, 3, P, 21, P, 64),
+            rr(P, 64, None, 2, 8, 1, 3, P, 21, P, 64), rr(P, 64, P, 2, 8, 1, 3, None, 21, P, 64), rr(P, 64, P, 2, 8, 1, 3, P, 21, None, 64)]
+    out += [("wunet_resample_tile", (0, 3, 21)), ("wunet_resample_tile", (2, 4, 21)), ("wunet_resample_tile", (1, 3, 20))]
+    return out
+
+
+def compare_refusals(libs):
+    """Every call of refusals() on both libraries, in one order: (return value, wunet_last_error()) must agree and the call be refused."""
+    differing, table, seen = 0, refusals(), set()
+    for name, args in table:
+        got = []
+        for L in libs:
+            rc = getattr(L, name)(*args)
+            got.append((rc, L.wunet_last_error().decode()))
+        seen.add(got[1])
+        refused = all((rc == 0) if name.endswith(("_bytes", "_tile")) else (rc != 0) for rc, _ in got)
+        if got[0] != got[1] or not refused:
+            differing += 1
+            print(f"DIFF  {name}{args}: base {got[0]}  new {got[1]}{'' if refused else '  (not refused)'}")
+    print(f"{len(table)} refused calls, {len(seen)} distinct (return value, message) pairs, {differing} differing")
+    if os.environ.get("EMU_LIB_AB_VERBOSE"):
+        for rc, msg in sorted(seen, key=str):
+            print(f"      {rc}: {msg}")
+    return differing
+
+
 def main():
     if len(sys.argv) < 2:
         sys.exit(__doc__)
@@ -175,7 +402,18 @@ def main():
         L.wunet_last_error.restype = ctypes.c_char_p
         L.wunet_workspace_bytes.restype = ctypes.c_size_t
     differing, kernels = 0, set()
-    table = cases()
+    table = [] if os.environ.get("EMU_LIB_AB_AUX_ONLY") else cases()
+    aux = aux_cases()
+    for label, fn in aux:
+        a, b = (run_aux(L, fn) for L in libs)
+        bad = [k for k in a if k not in b or not np.array_equal(a[k], b[k])] + [k for k in b if k not in a]
+        kernels.update(ln.split("\t")[0] for ln in b["profile"].splitlines())
+        digest = hashlib.sha1(b"".join(np.ascontiguousarray(b[k]).tobytes() for k in sorted(b) if k != "profile")).hexdigest()[:12]
+        print(f"{'DIFF' if bad else 'same'}  {label}  [{len(a) - 1} arrays {digest}, {len(a['profile'].splitlines())} kernel names]", flush=True)
+        for k in bad:
+            print("      differs:", k)
+        differing += bool(bad)
+    differing += compare_refusals(libs)
     for shape, h3, mode, mask_name, switches in table:
         a, b = (run_case(L, shape, h3, mode, mask_name, switches) for L in libs)
         bad = [k for k in a if k not in b or not np.array_equal(a[k], b[k])] + [k for k in b if k not in a]
@@ -190,7 +428,7 @@ def main():
                 print("      new: ", b[k].replace("\n", " | "))
         differing += bool(bad)
     print("kernel names seen:", ", ".join(sorted(kernels)))
-    print(f"{len(table)} cases, {differing} differing")
+    print(f"{len(table)} network cases, {len(aux)} auxiliary cases and the refusals: {differing} differing")
     return 1 if differing else 0
 
 

@@ -113,12 +113,12 @@ int wunet_loss_rows_backward(int kind, const float* clean, const float* enhanced
 
 // ---------------------------------------------------------------------------- multi-resolution STFT loss (wunet_stft.h)
 namespace {
-struct StftShape { unsigned M, F; int BP, bins, k0, k1; unsigned mtiles; };
+struct StftShape { size_t rows, T; int N, H; unsigned M, F; int BP, bins, k0, k1; unsigned mtiles; };      // (rows, T, N, H: the call's own)
 
-// every constraint of one resolution on (rows, T); fills the derived sizes.  T == 0: the checks that need the waveform are skipped
-// (the basis calls).
+// every constraint of one resolution on (rows, T); fills the derived sizes.  T == 0 (the basis calls): the checks that need the waveform are skipped.
 int stft_shape(size_t rows, size_t T, int N, int H, int W, StftShape& s)
 {
+    s.rows = rows; s.T = T; s.N = N; s.H = H;
     if (N < 16 || N > 4096 || N % 16) return fail(WUNET_E_ARG, "stft: n_fft must be a multiple of 16 in 16 .. 4096 (got %d)", N);
     if (W < 1 || W > N) return fail(WUNET_E_ARG, "stft: win_length must be in 1 .. n_fft (got %d, n_fft %d)", W, N);
     s.bins = N / 2 + 1;
@@ -138,6 +138,67 @@ int stft_shape(size_t rows, size_t T, int N, int H, int W, StftShape& s)
     return 0;
 }
 inline size_t stft_nparts(const StftShape& s) { return (size_t)s.mtiles * (size_t)(s.BP / WUNET_STFT_BN); }
+
+// ---- one host path for the STFT loss and the compressed spectral loss (wunet_cspec.h); `what` ("stft" / "cspec") starts the messages
+// the resolution of one call (stft_shape's messages say "stft" for both); what == nullptr: a size query, an empty row is 0 without a message
+int spectral_shape(const char* what, size_t rows, size_t row_len, int n_fft, int hop, int win_length, StftShape& s)
+{
+    if (row_len == 0) return what ? fail(WUNET_E_ARG, "%s: row_len must be > 0", what) : WUNET_E_ARG;
+    return stft_shape(rows, row_len, n_fft, hop, win_length, s);
+}
+// the forward's partials (`fwd` bytes), or with `bwd` the adjoint GEMM's M x n_fft floats where those are more
+inline size_t spectral_scratch(const StftShape& s, size_t fwd, int bwd) { const size_t b = bwd ? (size_t)s.M * s.N * sizeof(float) : 0; return b > fwd ? b : fwd; }
+// StftFwdArgs of one resolution (CspecFwdArgs carries one as .S); returns the forward's grid.  (extern "C++", here and on the two templates
+// below: this whole file is one extern "C" block, which allows neither a template nor a C++ class as a result)
+extern "C++" dim3 fill_fwd_args(StftFwdArgs& A, const StftShape& s, const float* clean, const float* enhanced, double clamp, const float* basis,
+                                void* scratch, float* saved, float* mag_out)
+{
+    A.c = clean; A.e = enhanced; A.basis = basis; A.T = s.T; A.M = s.M; A.F = s.F; A.N = s.N; A.H = s.H; A.BP = s.BP; A.bins = s.bins;
+    A.k0 = s.k0; A.k1 = s.k1; A.clamp = (float)clamp; A.part = (double*)scratch; A.saved = saved; A.mag_out = mag_out;
+    return dim3(s.mtiles, (unsigned)(s.BP / WUNET_STFT_BN));
+}
+// part / nparts / count of StftFinalArgs or CspecFinalArgs: one entry per resolution
+extern "C++" template <class Args>
+int fill_final_args(Args& A, const char* what, int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop)
+{
+    for (int i = 0; i < n_res; ++i) {
+        StftShape s{};
+        if (spectral_shape(what, rows, row_len, n_fft[i], hop[i], 1, s)) return WUNET_E_ARG;
+        if (!scratch[i]) return fail(WUNET_E_ARG, "%s: null scratch of resolution %d", what, i);
+        A.part[i] = (const double*)scratch[i]; A.nparts[i] = (unsigned)stft_nparts(s); A.count[i] = (double)s.M * (double)s.bins;
+    }
+    return 0;
+}
+// the adjoint-GEMM fields of StftBwdArgs or CspecBwdArgs and the profiler's record of `kernel`, which reads `planes` saved planes
+extern "C++" template <class Args>
+void fill_adjoint_args(Args& B, const char* kernel, int planes, const StftShape& s, const float* saved, const double* coefs, const float* basis,
+                       double clamp, void* scratch, hipStream_t st)
+{
+    B.saved = saved; B.coefs = coefs; B.basis = basis; B.M = s.M; B.N = s.N; B.BP = s.BP; B.bins = s.bins; B.k0 = s.k0; B.k1 = s.k1;
+    B.clamp = (float)clamp; B.scratch = (float*)scratch;
+    B.ktiles = (unsigned)((s.k1 - s.k0 + WUNET_STFT_BWN - 1) / WUNET_STFT_BWN);           // (at most 32; mtiles < 2^25)
+    prof_begin(st, kernel, 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP, 4.0 * ((double)planes * s.M * s.BP + (double)(s.k1 - s.k0) * (2.0 * s.BP + s.M)));
+}
+// the overlap-add of the adjoint GEMM's frames into grad_enhanced: the tail of both backwards
+int launch_stft_ola(const StftShape& s, const void* scratch, const float* grad_loss, float* grad_enhanced, int accumulate, hipStream_t st)
+{
+    StftOlaArgs O{};
+    O.scratch = (const float*)scratch; O.gl = grad_loss; O.g = grad_enhanced; O.T = s.T; O.total = s.rows * s.T; O.F = s.F;
+    O.N = s.N; O.H = s.H; O.k0 = s.k0; O.k1 = s.k1; O.accumulate = accumulate != 0;
+    prof_begin(st, "stft_ola_kernel", 0.0, 4.0 * ((double)s.M * (s.k1 - s.k0) + (accumulate ? 2.0 : 1.0) * s.rows * s.T));
+    WUNET_LAUNCH(stft_ola_kernel, dim3((unsigned)((O.total + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st, O);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+inline size_t cspec_fwd_bytes(const StftShape& s) { return stft_nparts(s) * 2 * sizeof(double); }
+inline size_t cspec_saved(const StftShape& s) { return (size_t)WUNET_CSPEC_PLANES * s.M * s.BP * sizeof(float); }
+int cspec_knobs(double compress, double clamp)
+{
+    if (!(compress > 0.0) || compress > 1.0) return fail(WUNET_E_ARG, "cspec: compress must be in (0, 1] (got %g)", compress);
+    if (!(clamp > 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "cspec: clamp must be finite and > 0 (got %g)", clamp);
+    return 0;
+}
 }  // namespace
 
 size_t wunet_stft_basis_bytes(int n_fft)
@@ -161,24 +222,20 @@ int wunet_stft_basis(int n_fft, int win_length, float* basis, void* stream)
 size_t wunet_stft_scratch_bytes(size_t rows, size_t row_len, int n_fft, int hop, int with_backward)
 {
     StftShape s{};
-    if (row_len == 0 || stft_shape(rows, row_len, n_fft, hop, 1, s)) return 0;
-    const size_t fwd = stft_nparts(s) * 3 * sizeof(double), bwd = (size_t)s.M * n_fft * sizeof(float);
-    return with_backward && bwd > fwd ? bwd : fwd;
+    return spectral_shape(nullptr, rows, row_len, n_fft, hop, 1, s) ? 0 : spectral_scratch(s, stft_nparts(s) * 3 * sizeof(double), with_backward);
 }
 
 size_t wunet_stft_saved_bytes(size_t rows, size_t row_len, int n_fft, int hop)
 {
     StftShape s{};
-    if (row_len == 0 || stft_shape(rows, row_len, n_fft, hop, 1, s)) return 0;
-    return (size_t)3 * s.M * s.BP * sizeof(float);
+    return spectral_shape(nullptr, rows, row_len, n_fft, hop, 1, s) ? 0 : (size_t)3 * s.M * s.BP * sizeof(float);
 }
 
 int wunet_stft_forward(const float* clean, const float* enhanced, size_t rows, size_t row_len, int n_fft, int hop, int win_length,
                        double clamp, const float* basis, void* scratch, float* saved, float* mag_out, void* stream)
 {
     StftShape s{};
-    if (row_len == 0) return fail(WUNET_E_ARG, "stft: row_len must be > 0");
-    if (stft_shape(rows, row_len, n_fft, hop, win_length, s)) return WUNET_E_ARG;
+    if (spectral_shape("stft", rows, row_len, n_fft, hop, win_length, s)) return WUNET_E_ARG;
     if (!enhanced || !basis || ((size_t)basis & 15)) return fail(WUNET_E_ARG, "stft: null argument (or a basis that is not 16-byte aligned)");
     if (clean) {
         if (!(clamp > 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "stft: clamp must be finite and > 0 (got %g)", clamp);
@@ -188,9 +245,7 @@ int wunet_stft_forward(const float* clean, const float* enhanced, size_t rows, s
         if (!mag_out || saved) return fail(WUNET_E_ARG, "stft: without `clean` the call writes mag_out only");
     }
     StftFwdArgs A{};
-    A.c = clean; A.e = enhanced; A.basis = basis; A.T = row_len; A.M = s.M; A.F = s.F; A.N = n_fft; A.H = hop; A.BP = s.BP; A.bins = s.bins;
-    A.k0 = s.k0; A.k1 = s.k1; A.clamp = (float)clamp; A.part = (double*)scratch; A.saved = saved; A.mag_out = mag_out;
-    const dim3 grid(s.mtiles, (unsigned)(s.BP / WUNET_STFT_BN));
+    const dim3 grid = fill_fwd_args(A, s, clean, enhanced, clamp, basis, scratch, saved, mag_out);
     // (profiler: 2 flops x frames x window support x 2 BP columns per signal; the waveforms and the basis once, the saved spectra)
     prof_begin((hipStream_t)stream, clean ? "stft_fwd_kernel<pair>" : "stft_fwd_kernel<one>", (clean ? 2.0 : 1.0) * 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP,
                4.0 * ((clean ? 2.0 : 1.0) * rows * row_len + (double)(s.k1 - s.k0) * 2.0 * s.BP + (saved ? 3.0 * s.M * s.BP : 0.0)));
@@ -211,15 +266,7 @@ int wunet_stft_finalize(int n_res, const void* const* scratch, size_t rows, size
     if (!scratch || !n_fft || !hop || !loss_out) return fail(WUNET_E_ARG, "stft: null argument");
     if (!(sc_weight == sc_weight) || !(mag_weight == mag_weight)) return fail(WUNET_E_ARG, "stft: a weight is NaN");
     StftFinalArgs A{};
-    for (int i = 0; i < n_res; ++i) {
-        StftShape s{};
-        if (row_len == 0) return fail(WUNET_E_ARG, "stft: row_len must be > 0");
-        if (stft_shape(rows, row_len, n_fft[i], hop[i], 1, s)) return WUNET_E_ARG;
-        if (!scratch[i]) return fail(WUNET_E_ARG, "stft: null scratch of resolution %d", i);
-        A.part[i] = (const double*)scratch[i];
-        A.nparts[i] = (unsigned)stft_nparts(s);
-        A.count[i] = (double)s.M * (double)s.bins;
-    }
+    if (fill_final_args(A, "stft", n_res, scratch, rows, row_len, n_fft, hop)) return WUNET_E_ARG;
     A.n_res = n_res; A.w_sc = sc_weight; A.w_mag = mag_weight; A.loss = loss_out; A.coefs = coefs;
     WUNET_LAUNCH(stft_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, (hipStream_t)stream, A);
     WUNET_CHECK_LAUNCH();
@@ -230,58 +277,30 @@ int wunet_stft_backward(const float* saved, const double* coefs, const float* gr
                         int win_length, double clamp, const float* basis, void* scratch, float* grad_enhanced, int accumulate, void* stream)
 {
     StftShape s{};
-    if (row_len == 0) return fail(WUNET_E_ARG, "stft: row_len must be > 0");
-    if (stft_shape(rows, row_len, n_fft, hop, win_length, s)) return WUNET_E_ARG;
+    if (spectral_shape("stft", rows, row_len, n_fft, hop, win_length, s)) return WUNET_E_ARG;
     if (!saved || !coefs || !grad_loss || !basis || !scratch || !grad_enhanced || ((size_t)basis & 15))
         return fail(WUNET_E_ARG, "stft: null argument (or a basis that is not 16-byte aligned)");
     if (!(clamp > 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "stft: clamp must be finite and > 0 (got %g)", clamp);
     hipStream_t st = (hipStream_t)stream;
     StftBwdArgs B{};
-    B.saved = saved; B.coefs = coefs; B.basis = basis; B.M = s.M; B.N = n_fft; B.BP = s.BP; B.bins = s.bins; B.k0 = s.k0; B.k1 = s.k1;
-    B.clamp = (float)clamp; B.scratch = (float*)scratch;
-    B.ktiles = (unsigned)((s.k1 - s.k0 + WUNET_STFT_BWN - 1) / WUNET_STFT_BWN);           // (at most 32; mtiles < 2^25)
-    prof_begin(st, "stft_bwd_kernel", 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP, 4.0 * (3.0 * s.M * s.BP + (double)(s.k1 - s.k0) * (2.0 * s.BP + s.M)));
+    fill_adjoint_args(B, "stft_bwd_kernel", 3, s, saved, coefs, basis, clamp, scratch, st);
     WUNET_LAUNCH(stft_bwd_kernel, dim3(B.ktiles * s.mtiles), dim3(WUNET_THREADS), 0, st, B);
     prof_end(st);
     WUNET_CHECK_LAUNCH();
-    StftOlaArgs O{};
-    O.scratch = (const float*)scratch; O.gl = grad_loss; O.g = grad_enhanced; O.T = row_len; O.total = rows * row_len; O.F = s.F;
-    O.N = n_fft; O.H = hop; O.k0 = s.k0; O.k1 = s.k1; O.accumulate = accumulate != 0;
-    prof_begin(st, "stft_ola_kernel", 0.0, 4.0 * ((double)s.M * (s.k1 - s.k0) + (accumulate ? 2.0 : 1.0) * rows * row_len));
-    WUNET_LAUNCH(stft_ola_kernel, dim3((unsigned)((O.total + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st, O);
-    prof_end(st);
-    WUNET_CHECK_LAUNCH();
-    return WUNET_OK;
+    return launch_stft_ola(s, scratch, grad_loss, grad_enhanced, accumulate, st);
 }
 
 // ---------------------------------------------------------------------------- compressed spectral loss (wunet_cspec.h)
-// The resolutions, the basis, the frame tiling and the overlap-add are the STFT loss's (stft_shape above); only the partials (two
-// doubles per block) and the saved planes (five) differ.
-namespace {
-inline size_t cspec_fwd_bytes(const StftShape& s) { return stft_nparts(s) * 2 * sizeof(double); }
-inline size_t cspec_bwd_bytes(const StftShape& s, int n_fft) { return (size_t)s.M * n_fft * sizeof(float); }
-inline size_t cspec_saved(const StftShape& s) { return (size_t)WUNET_CSPEC_PLANES * s.M * s.BP * sizeof(float); }
-int cspec_knobs(double compress, double clamp)
-{
-    if (!(compress > 0.0) || compress > 1.0) return fail(WUNET_E_ARG, "cspec: compress must be in (0, 1] (got %g)", compress);
-    if (!(clamp > 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "cspec: clamp must be finite and > 0 (got %g)", clamp);
-    return 0;
-}
-}  // namespace
-
 size_t wunet_cspec_scratch_bytes(size_t rows, size_t row_len, int n_fft, int hop, int with_backward)
 {
     StftShape s{};
-    if (row_len == 0 || stft_shape(rows, row_len, n_fft, hop, 1, s)) return 0;
-    const size_t fwd = cspec_fwd_bytes(s), bwd = cspec_bwd_bytes(s, n_fft);
-    return with_backward && bwd > fwd ? bwd : fwd;
+    return spectral_shape(nullptr, rows, row_len, n_fft, hop, 1, s) ? 0 : spectral_scratch(s, cspec_fwd_bytes(s), with_backward);
 }
 
 size_t wunet_cspec_saved_bytes(size_t rows, size_t row_len, int n_fft, int hop)
 {
     StftShape s{};
-    if (row_len == 0 || stft_shape(rows, row_len, n_fft, hop, 1, s)) return 0;
-    return cspec_saved(s);
+    return spectral_shape(nullptr, rows, row_len, n_fft, hop, 1, s) ? 0 : cspec_saved(s);
 }
 
 int wunet_cspec_forward(const float* clean, const float* enhanced, size_t rows, size_t row_len, int n_fft, int hop, int win_length,
@@ -289,8 +308,7 @@ int wunet_cspec_forward(const float* clean, const float* enhanced, size_t rows, 
                         size_t saved_bytes, void* stream)
 {
     StftShape s{};
-    if (row_len == 0) return fail(WUNET_E_ARG, "cspec: row_len must be > 0");
-    if (stft_shape(rows, row_len, n_fft, hop, win_length, s) || cspec_knobs(compress, clamp)) return WUNET_E_ARG;
+    if (spectral_shape("cspec", rows, row_len, n_fft, hop, win_length, s) || cspec_knobs(compress, clamp)) return WUNET_E_ARG;
     if (!clean || !enhanced || !basis || ((size_t)basis & 15)) return fail(WUNET_E_ARG, "cspec: null argument (or a basis that is not 16-byte aligned)");
     if (!scratch || scratch_bytes < cspec_fwd_bytes(s))
         return fail(WUNET_E_ARG, "cspec: the forward needs %zu bytes of scratch for this resolution (got %zu)", cspec_fwd_bytes(s), scratch_bytes);
@@ -298,11 +316,8 @@ int wunet_cspec_forward(const float* clean, const float* enhanced, size_t rows, 
         return fail(WUNET_E_ARG, "cspec: saved must be the %zu bytes of wunet_cspec_saved_bytes for this resolution, or NULL and 0 (got %zu)",
                     cspec_saved(s), saved_bytes);
     CspecFwdArgs C{};
-    StftFwdArgs& A = C.S;
-    A.c = clean; A.e = enhanced; A.basis = basis; A.T = row_len; A.M = s.M; A.F = s.F; A.N = n_fft; A.H = hop; A.BP = s.BP; A.bins = s.bins;
-    A.k0 = s.k0; A.k1 = s.k1; A.clamp = (float)clamp; A.part = (double*)scratch; A.saved = saved;
+    const dim3 grid = fill_fwd_args(C.S, s, clean, enhanced, clamp, basis, scratch, saved, nullptr);
     C.hs = 0.5 * (compress - 1.0);
-    const dim3 grid(s.mtiles, (unsigned)(s.BP / WUNET_STFT_BN));
     prof_begin((hipStream_t)stream, "cspec_fwd_kernel", 2.0 * 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP,
                4.0 * (2.0 * rows * row_len + (double)(s.k1 - s.k0) * 2.0 * s.BP + (saved ? (double)WUNET_CSPEC_PLANES * s.M * s.BP : 0.0)));
     WUNET_LAUNCH(cspec_fwd_kernel, grid, dim3(WUNET_THREADS), 0, (hipStream_t)stream, C);
@@ -317,16 +332,8 @@ int wunet_cspec_finalize(int n_res, const void* const* scratch, size_t rows, siz
     if (n_res < 1 || n_res > WUNET_STFT_MAX_RES) return fail(WUNET_E_ARG, "cspec: 1 .. %d resolutions per call (got %d)", WUNET_STFT_MAX_RES, n_res);
     if (!scratch || !n_fft || !hop || !loss_out) return fail(WUNET_E_ARG, "cspec: null argument");
     if (!(complex_weight >= 0.0) || complex_weight > 1.0) return fail(WUNET_E_ARG, "cspec: complex_weight must be in [0, 1] (got %g)", complex_weight);
-    if (row_len == 0) return fail(WUNET_E_ARG, "cspec: row_len must be > 0");
     CspecFinalArgs A{};
-    for (int i = 0; i < n_res; ++i) {
-        StftShape s{};
-        if (stft_shape(rows, row_len, n_fft[i], hop[i], 1, s)) return WUNET_E_ARG;
-        if (!scratch[i]) return fail(WUNET_E_ARG, "cspec: null scratch of resolution %d", i);
-        A.part[i] = (const double*)scratch[i];
-        A.nparts[i] = (unsigned)stft_nparts(s);
-        A.count[i] = (double)s.M * (double)s.bins;
-    }
+    if (fill_final_args(A, "cspec", n_res, scratch, rows, row_len, n_fft, hop)) return WUNET_E_ARG;
     A.n_res = n_res; A.lambda = complex_weight; A.loss = loss_out; A.coefs = coefs;
     WUNET_LAUNCH(cspec_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, (hipStream_t)stream, A);
     WUNET_CHECK_LAUNCH();
@@ -338,32 +345,21 @@ int wunet_cspec_backward(const float* saved, size_t saved_bytes, const double* c
                          size_t scratch_bytes, float* grad_enhanced, int accumulate, void* stream)
 {
     StftShape s{};
-    if (row_len == 0) return fail(WUNET_E_ARG, "cspec: row_len must be > 0");
-    if (stft_shape(rows, row_len, n_fft, hop, win_length, s) || cspec_knobs(compress, clamp)) return WUNET_E_ARG;
+    if (spectral_shape("cspec", rows, row_len, n_fft, hop, win_length, s) || cspec_knobs(compress, clamp)) return WUNET_E_ARG;
     if (!saved || !coefs || !grad_loss || !basis || !grad_enhanced || ((size_t)basis & 15))
         return fail(WUNET_E_ARG, "cspec: null argument (or a basis that is not 16-byte aligned)");
     if (saved_bytes != cspec_saved(s))
         return fail(WUNET_E_ARG, "cspec: saved must be the %zu bytes of wunet_cspec_saved_bytes for this resolution (got %zu)", cspec_saved(s), saved_bytes);
-    if (!scratch || scratch_bytes < cspec_bwd_bytes(s, n_fft))
-        return fail(WUNET_E_ARG, "cspec: the backward needs %zu bytes of scratch for this resolution (got %zu)", cspec_bwd_bytes(s, n_fft), scratch_bytes);
+    if (!scratch || scratch_bytes < spectral_scratch(s, 0, 1))
+        return fail(WUNET_E_ARG, "cspec: the backward needs %zu bytes of scratch for this resolution (got %zu)", spectral_scratch(s, 0, 1), scratch_bytes);
     hipStream_t st = (hipStream_t)stream;
     CspecBwdArgs B{};
-    B.saved = saved; B.coefs = coefs; B.basis = basis; B.M = s.M; B.N = n_fft; B.BP = s.BP; B.bins = s.bins; B.k0 = s.k0; B.k1 = s.k1;
-    B.clamp = (float)clamp; B.compress = compress; B.hs = 0.5 * (compress - 1.0); B.scratch = (float*)scratch;
-    B.ktiles = (unsigned)((s.k1 - s.k0 + WUNET_STFT_BWN - 1) / WUNET_STFT_BWN);           // (at most 32; mtiles < 2^25)
-    prof_begin(st, "cspec_bwd_kernel", 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP,
-               4.0 * ((double)WUNET_CSPEC_PLANES * s.M * s.BP + (double)(s.k1 - s.k0) * (2.0 * s.BP + s.M)));
+    B.compress = compress; B.hs = 0.5 * (compress - 1.0);
+    fill_adjoint_args(B, "cspec_bwd_kernel", WUNET_CSPEC_PLANES, s, saved, coefs, basis, clamp, scratch, st);
     WUNET_LAUNCH(cspec_bwd_kernel, dim3(B.ktiles * s.mtiles), dim3(WUNET_THREADS), 0, st, B);
     prof_end(st);
     WUNET_CHECK_LAUNCH();
-    StftOlaArgs O{};
-    O.scratch = (const float*)scratch; O.gl = grad_loss; O.g = grad_enhanced; O.T = row_len; O.total = rows * row_len; O.F = s.F;
-    O.N = n_fft; O.H = hop; O.k0 = s.k0; O.k1 = s.k1; O.accumulate = accumulate != 0;
-    prof_begin(st, "stft_ola_kernel", 0.0, 4.0 * ((double)s.M * (s.k1 - s.k0) + (accumulate ? 2.0 : 1.0) * rows * row_len));
-    WUNET_LAUNCH(stft_ola_kernel, dim3((unsigned)((O.total + WUNET_THREADS - 1) / WUNET_THREADS)), dim3(WUNET_THREADS), 0, st, O);
-    prof_end(st);
-    WUNET_CHECK_LAUNCH();
-    return WUNET_OK;
+    return launch_stft_ola(s, scratch, grad_loss, grad_enhanced, accumulate, st);
 }
 
 // ---------------------------------------------------------------------------- STOI and ESTOI per row (wunet_stoi.h, wunet_estoi.h)
@@ -833,16 +829,22 @@ int wunet_crop_windows(const float* mixture_flat, const float* clean_flat, const
 #define WUNET_MIX_BLOCKS 1024
 #define WUNET_MIX_MIN_PIECE 1024         // one trip of 4 samples per thread
 
-static int mix_shape_check(int batch, int length)
+// ---- the checks that the row-table ops share.  n windows of `length` samples: the rows are a grid's y (the loader ops' batch), with
+// `chunks` its x (the chunk ops' n).  `op` starts the messages; nullptr: a size query, which answers 0 without a message.
+static int window_shape_check(const char* op, long long n, int length, bool chunks)
 {
-    if (batch < 1 || length < 1) return fail(WUNET_E_ARG, "mix: batch and length must be >= 1 (got %d x %d)", batch, length);
-    if (batch > 65535 || length > (1 << 30)) return fail(WUNET_E_ARG, "mix: at most 65535 rows of 2^30 samples per call (got %d x %d)", batch, length);
-    return 0;
+    if (n >= 1 && length >= 1 && n <= (chunks ? 0x7fffffffLL : 65535LL) && length <= (1 << 30)) return 0;
+    if (!op) return WUNET_E_ARG;
+    if (n < 1 || length < 1) return fail(WUNET_E_ARG, "%s: %s and length must be >= 1 (got %lld x %d)", op, chunks ? "n" : "batch", n, length);
+    return fail(WUNET_E_ARG, "%s: at most %s of 2^30 samples per call (got %lld x %d)", op, chunks ? "2^31 - 1 chunks" : "65535 rows", n, length);
 }
+// a flat array's total (or its longest row) in [lo, limit); rows of a multiple of 4 samples move 16 bytes at a time: a, b (or null) aligned so
+static bool total_in_range(long long total, long long lo, long long limit) { return total >= lo && total < limit; }
+static bool rows_misaligned(int length, const void* a, const void* b) { return (length & 3) == 0 && (((size_t)a | (size_t)b) & 15); }
 
 size_t wunet_mix_scratch_bytes(int batch, int length)
 {
-    if (batch < 1 || length < 1 || batch > 65535 || length > (1 << 30)) return 0;
+    if (window_shape_check(nullptr, batch, length, false)) return 0;
     size_t ppr, plen;
     row_pieces((size_t)batch, (size_t)length, WUNET_MIX_BLOCKS, WUNET_MIX_MIN_PIECE, ppr, plen);
     return (size_t)batch * ppr * WUNET_MIX_PART * sizeof(double);
@@ -852,13 +854,13 @@ int wunet_mix_windows(const float* clean_flat, long long clean_total, const floa
                       const float* params, float peak_limit, int batch, int length, void* scratch, float* mixture, float* clean_out,
                       float* gains, void* stream)
 {
-    if (mix_shape_check(batch, length)) return WUNET_E_ARG;
+    if (window_shape_check("mix", batch, length, false)) return WUNET_E_ARG;
     if (clean_total < length) return fail(WUNET_E_ARG, "mix: the clean array is shorter than one window (clean_total=%lld length=%d)", clean_total, length);
     if (noise_total < 1) return fail(WUNET_E_ARG, "mix: the noise array is empty (noise_total=%lld)", noise_total);
     if (clean_total >= (1LL << 60) || noise_total >= (1LL << 60)) return fail(WUNET_E_ARG, "mix: array too large");
     if (!clean_flat || !noise_flat || !rows || !params || !scratch || !mixture || !clean_out) return fail(WUNET_E_ARG, "mix: null argument");
     if (!(peak_limit == peak_limit)) return fail(WUNET_E_ARG, "mix: peak_limit is NaN");
-    if (((size_t)scratch & 7) || ((length & 3) == 0 && (((size_t)mixture | (size_t)clean_out) & 15)))
+    if (((size_t)scratch & 7) || rows_misaligned(length, mixture, clean_out))
         return fail(WUNET_E_ARG, "mix: scratch needs 8-byte alignment, the outputs 16-byte alignment when length %% 4 == 0");
     hipStream_t st = (hipStream_t)stream;
     MixArgs A{};
@@ -883,9 +885,9 @@ int wunet_mix_windows(const float* clean_flat, long long clean_total, const floa
 // dst = a src with the a that wunet_mix_windows wrote into `gains` (a target that is not the window the mix read, at the mixture's level)
 int wunet_apply_level(const float* src, const float* gains, int batch, int length, float* dst, void* stream)
 {
-    if (mix_shape_check(batch, length)) return WUNET_E_ARG;
+    if (window_shape_check("mix", batch, length, false)) return WUNET_E_ARG;
     if (!src || !gains || !dst) return fail(WUNET_E_ARG, "apply_level: null argument");
-    if ((length & 3) == 0 && (((size_t)src | (size_t)dst) & 15)) return fail(WUNET_E_ARG, "apply_level: src and dst need 16-byte alignment when length %% 4 == 0");
+    if (rows_misaligned(length, src, dst)) return fail(WUNET_E_ARG, "apply_level: src and dst need 16-byte alignment when length %% 4 == 0");
     hipStream_t st = (hipStream_t)stream;
     const double n = (double)batch * length;
     prof_begin(st, "apply_level_kernel", n, 4.0 * 2.0 * n);
@@ -900,14 +902,13 @@ int wunet_apply_level(const float* src, const float* gains, int batch, int lengt
 int wunet_reverb_windows(const float* clean_flat, long long clean_total, const float* rir_flat, long long rir_total, const long long* rows,
                          int early_taps, int batch, int length, float* reverberant, float* direct, void* stream)
 {
-    if (batch < 1 || length < 1) return fail(WUNET_E_ARG, "reverb: batch and length must be >= 1 (got %d x %d)", batch, length);
-    if (batch > 65535 || length > (1 << 30)) return fail(WUNET_E_ARG, "reverb: at most 65535 rows of 2^30 samples per call (got %d x %d)", batch, length);
+    if (window_shape_check("reverb", batch, length, false)) return WUNET_E_ARG;
     if (clean_total < length) return fail(WUNET_E_ARG, "reverb: the clean array is shorter than one window (clean_total=%lld length=%d)", clean_total, length);
     if (rir_total < 1) return fail(WUNET_E_ARG, "reverb: the rir array is empty (rir_total=%lld)", rir_total);
     if (clean_total >= (1LL << 60) || rir_total >= (1LL << 60)) return fail(WUNET_E_ARG, "reverb: array too large");
     if (!clean_flat || !rir_flat || !rows || !reverberant) return fail(WUNET_E_ARG, "reverb: null argument");
     if (direct && early_taps < 1) return fail(WUNET_E_ARG, "reverb: early_taps must be >= 1 when direct is given (got %d)", early_taps);
-    if ((length & 3) == 0 && (((size_t)reverberant | (size_t)direct) & 15))
+    if (rows_misaligned(length, reverberant, direct))
         return fail(WUNET_E_ARG, "reverb: the outputs need 16-byte alignment when length %% 4 == 0");
     hipStream_t st = (hipStream_t)stream;
     ReverbArgs A{};
@@ -927,9 +928,8 @@ static unsigned chunk_pieces_y(long long pieces) { return (unsigned)(pieces < (l
 
 int wunet_chunk_gather(const float* flat, long long total, const long long* rows, long long n, int length, float* chunks, void* stream)
 {
-    if (n < 1 || length < 1) return fail(WUNET_E_ARG, "chunk_gather: n and length must be >= 1 (got %lld x %d)", n, length);
-    if (n > 0x7fffffffLL || length > (1 << 30)) return fail(WUNET_E_ARG, "chunk_gather: at most 2^31 - 1 chunks of 2^30 samples per call (got %lld x %d)", n, length);
-    if (total < 1 || total >= WUNET_CHUNK_LIMIT) return fail(WUNET_E_ARG, "chunk_gather: bad size of the flat array (total=%lld)", total);
+    if (window_shape_check("chunk_gather", n, length, true)) return WUNET_E_ARG;
+    if (!total_in_range(total, 1, WUNET_CHUNK_LIMIT)) return fail(WUNET_E_ARG, "chunk_gather: bad size of the flat array (total=%lld)", total);
     if (!flat || !rows || !chunks) return fail(WUNET_E_ARG, "chunk_gather: null argument");
     hipStream_t st = (hipStream_t)stream;
     const long long pieces = ((long long)length + WUNET_CHUNK_PIECE - 1) / WUNET_CHUNK_PIECE;
@@ -944,16 +944,15 @@ int wunet_chunk_gather(const float* flat, long long total, const long long* rows
 int wunet_chunk_overlap_add(const float* chunks, long long n, int length, int margin, int fade, const float* ramp, const long long* recs,
                             long long n_recs, long long max_len, float* out_flat, long long total, void* stream)
 {
-    if (n < 1 || length < 1) return fail(WUNET_E_ARG, "chunk_overlap_add: n and length must be >= 1 (got %lld x %d)", n, length);
-    if (n > 0x7fffffffLL || length > (1 << 30)) return fail(WUNET_E_ARG, "chunk_overlap_add: at most 2^31 - 1 chunks of 2^30 samples per call (got %lld x %d)", n, length);
+    if (window_shape_check("chunk_overlap_add", n, length, true)) return WUNET_E_ARG;
     if (margin < 0 || fade < 0) return fail(WUNET_E_ARG, "chunk_overlap_add: margin and fade must be >= 0 (got %d, %d)", margin, fade);
     const long long hop = (long long)length - 2LL * margin - fade;
     if (hop < 1 || fade > hop)
         return fail(WUNET_E_ARG, "chunk_overlap_add: the hop length - 2 margin - fade must be >= 1 and >= fade (length=%d margin=%d fade=%d)", length, margin, fade);
     if ((fade > 0) != (ramp != nullptr)) return fail(WUNET_E_ARG, "chunk_overlap_add: ramp must be given exactly when fade > 0 (fade=%d)", fade);
     if (n_recs < 1 || n_recs > 0x7fffffffLL) return fail(WUNET_E_ARG, "chunk_overlap_add: n_recs must be in [1, 2^31) (got %lld)", n_recs);
-    if (max_len < 1 || max_len >= WUNET_CHUNK_LIMIT) return fail(WUNET_E_ARG, "chunk_overlap_add: bad max_len (%lld)", max_len);
-    if (total < 1 || total >= WUNET_CHUNK_LIMIT) return fail(WUNET_E_ARG, "chunk_overlap_add: bad size of the flat output (total=%lld)", total);
+    if (!total_in_range(max_len, 1, WUNET_CHUNK_LIMIT)) return fail(WUNET_E_ARG, "chunk_overlap_add: bad max_len (%lld)", max_len);
+    if (!total_in_range(total, 1, WUNET_CHUNK_LIMIT)) return fail(WUNET_E_ARG, "chunk_overlap_add: bad size of the flat output (total=%lld)", total);
     if (!chunks || !recs || !out_flat) return fail(WUNET_E_ARG, "chunk_overlap_add: null argument");
     hipStream_t st = (hipStream_t)stream;
     ChunkOlaArgs A{};
@@ -993,7 +992,7 @@ int wunet_resample_rows(const float* in, long long in_total, const long long* ro
     if (n < 1 || max_out < 1) return fail(WUNET_E_ARG, "resample: n and max_out must be >= 1 (got %lld, %lld)", n, max_out);
     if (n > 0x7fffffffLL) return fail(WUNET_E_ARG, "resample: at most 2^31 - 1 rows per call (got %lld)", n);
     if (resample_filter_check(up, down, n_taps)) return WUNET_E_ARG;
-    if (in_total < 1 || in_total >= WUNET_RESAMPLE_LIMIT || out_total < 1 || out_total >= WUNET_RESAMPLE_LIMIT)
+    if (!total_in_range(in_total, 1, WUNET_RESAMPLE_LIMIT) || !total_in_range(out_total, 1, WUNET_RESAMPLE_LIMIT))
         return fail(WUNET_E_ARG, "resample: bad size of an array (in_total=%lld out_total=%lld)", in_total, out_total);
     if (!in || !rows || !taps || !out) return fail(WUNET_E_ARG, "resample: null argument");
     hipStream_t st = (hipStream_t)stream;

@@ -88,6 +88,24 @@ STFT_MAX_RESOLUTIONS = 8             # WUNET_STFT_MAX_RESOLUTIONS
 CSPEC_COEFS = 4                      # WUNET_CSPEC_COEFS: the two gradient scales, the two term values per resolution (wunet_cspec_*)
 
 
+class _SpectralFamily:
+    """What tells the two spectral losses apart on their one host path (Engine._spectral_loss_*): c - the entry points are wunet_<c>_*;
+    what - starts the messages; coefs - float64 values per resolution; cspec - wunet_cspec_*'s call shape: scalars (compress, clamp) not
+    (clamp,), one finalize weight not two, byte counts behind the scratch and saved pointers (wunet_stft_forward: mag_out); saved_by_dtype
+    - the backward holds saved[i] to float32 and leaves its size to the C call, else it holds its bytes to wunet_<c>_saved_bytes."""
+
+    def __init__(self, c, what, coefs, cspec, saved_by_dtype):
+        self.c, self.what, self.coefs, self.cspec, self.saved_by_dtype = c, what, coefs, cspec, saved_by_dtype
+
+
+_STFT = _SpectralFamily("stft", "stft loss", STFT_COEFS, False, False)
+_CSPEC = _SpectralFamily("cspec", "compressed spectral loss", CSPEC_COEFS, True, True)
+
+
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 def check_stft_resolution(n_fft, hop, win_length):
     """The constraints of one resolution that do not depend on the waveform (what wunet_stft_* refuses with WUNET_E_ARG)."""
     n_fft, hop, win_length = int(n_fft), int(hop), int(win_length)
@@ -164,6 +182,7 @@ class Engine:
         # Bumped by everything that rewrites weights WITHOUT moving a Python version counter: the replay of a captured step graph
         # (FusedAdam.advance_host_step) - part of the eval cache's signature, so an eval forward after N replays re-packs.
         self.weights_generation = 0
+        self._spectral = {}                           # "stft" / "cspec" -> their five C calls in self.lib (_spectral_calls)
         self._stft_bases = {}                         # (n_fft, win_length, device) -> windowed DFT basis (stft_basis)
         self._stoi_tables_cache = {}                  # (sample rate, device) -> basis | window | resampler taps (stoi_tables)
         self._resample_taps_cache = {}                # (up, down, device) -> the resampling filter on the device (resample_taps)
@@ -224,9 +243,9 @@ class Engine:
         if not t.is_contiguous():
             raise WunetError(f"{name}: tensor must be contiguous")
         if self.host_memory:
-            if t.device.type != "cpu":
+            if not t.is_cpu:
                 raise WunetError(f"{name}: emulator engine takes CPU tensors")
-        elif t.device.type != "cuda":
+        elif not t.is_cuda:              # (device.type != "cuda", without making the device object)
             raise WunetError(f"{name}: the HIP path needs tensors on an MI355X (got device {t.device}); "
                              "there is no CPU fallback")
 
@@ -273,6 +292,24 @@ class Engine:
             raise WunetError(f"{what}: needs at least one row of at least one sample, got {tuple(other.shape)}")
         T = other.shape[-1]
         return other.numel() // T, T, other.device
+
+    def _table_op(self, op, label, expected, tensors, table):
+        """The checks every row-table op (mix_windows .. resample_rows) starts with; `op` starts the messages.  tensors: the op's, in
+        argument order (None: an optional one not given), float32 except the int64 `table`; `expected` words the dtype message; each then
+        goes through _require as `label`.  Returns the tensors given, for _same_device once the op has checked its own shapes."""
+        given = [t for t in tensors if t is not None]
+        for t in given:
+            if t.dtype is not (torch.int64 if t is table else torch.float32):
+                raise WunetError(f"{op}: {expected} expected")
+        for t in given:
+            self._require(t, label)
+        return given
+
+    @staticmethod
+    def _same_device(op, tensors, device, where):
+        for t in tensors:
+            if t.device != device:
+                raise WunetError(f"{op}: every tensor must live on {where}")
 
     def _sized(self, nbytes):
         """The answer of a size query of the C ABI: 0 is a refused shape, and wunet_last_error says why."""
@@ -445,10 +482,9 @@ class Engine:
         rows = torch.empty(R, dtype=torch.float32, device=dev) if per_row else None
         coefs = torch.empty(R, LOSS_ROW_COEFS, dtype=torch.float64, device=dev) if with_backward else None
         scratch = torch.empty(max(1, self.lib.wunet_loss_rows_scratch_bytes(R, T) // 8), dtype=torch.float64, device=dev)
-        ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
         with self._device_guard(dev):
             self._check(self.lib.wunet_loss_rows_forward(ROW_LOSS_KINDS[kind], 1 if zero_mean else 0, float(eps), clean.data_ptr(),
-                                                         enhanced.data_ptr(), R, T, out.data_ptr(), ptr(rows), ptr(coefs),
+                                                         enhanced.data_ptr(), R, T, out.data_ptr(), _ptr(rows), _ptr(coefs),
                                                          scratch.data_ptr(), self._stream(dev)))
         return out, coefs, rows
 
@@ -470,7 +506,10 @@ class Engine:
     def stft_basis(self, n_fft, win_length, device):
         """The windowed DFT basis of (n_fft, win_length) on `device`, built once: on the first (eager) call, so that a later graph capture
         sees neither its allocation nor its launch."""
-        key = (n_fft, win_length, str(device))
+        return self._basis(n_fft, win_length, device, str(device))
+
+    def _basis(self, n_fft, win_length, device, where):
+        key = (n_fft, win_length, where)                 # (where = str(device): a loop over resolutions makes the string once)
         basis = self._stft_bases.get(key)
         if basis is None:
             basis = torch.empty(self._sized(self.lib.wunet_stft_basis_bytes(n_fft)) // 4, dtype=torch.float32, device=device)
@@ -479,108 +518,97 @@ class Engine:
             self._stft_bases[key] = basis
         return basis
 
-    def stft_loss_forward(self, clean, enhanced, resolutions, sc_weight=1.0, mag_weight=1.0, clamp=1e-7, with_backward=True):
-        """resolutions: a sequence of (n_fft, hop, win_length).  The last dimension is the utterance, all leading ones are flattened.
-        Returns (loss, coefs, saved): loss - device scalar; coefs - float64 [n_res, STFT_COEFS] (a, b, sc, mag per resolution);
-        saved - one float32 buffer per resolution for `stft_loss_backward` (None with with_backward=False)."""
-        R, T, dev = self._wave_pair("stft loss", clean, enhanced)
+    def _spectral_calls(self, fam):
+        """(scratch_bytes, saved_bytes, forward, finalize, backward) of one spectral loss in this engine's library, looked up once."""
+        if fam.c not in self._spectral:
+            self._spectral[fam.c] = tuple(getattr(self.lib, f"wunet_{fam.c}_{n}") for n in ("scratch_bytes", "saved_bytes", "forward", "finalize", "backward"))
+        return self._spectral[fam.c]
+
+    def _spectral_loss_forward(self, fam, clean, enhanced, resolutions, knobs, weights, with_backward):
+        """Both spectral losses: per resolution wunet_<c>_forward with the scalars `knobs`, then one wunet_<c>_finalize with `weights`."""
+        R, T, dev = self._wave_pair(fam.what, clean, enhanced)
         n = len(resolutions)
         if n < 1 or n > STFT_MAX_RESOLUTIONS:
-            raise WunetError(f"stft loss: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {n})")
-        lib = self.lib
+            raise WunetError(f"{fam.what}: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {n})")
+        scratch_bytes, saved_bytes, forward, finalize, _ = self._spectral_calls(fam)
         out = torch.empty((), dtype=torch.float32, device=dev)
-        coefs = torch.empty(n, STFT_COEFS, dtype=torch.float64, device=dev)
+        coefs = torch.empty(n, fam.coefs, dtype=torch.float64, device=dev)
         scratch, saved = [], []
+        where = str(dev)
         with self._device_guard(dev):
             st = self._stream(dev)
             for N, H, W in resolutions:
-                basis = self.stft_basis(N, W, dev)
-                scr = torch.empty(self._sized(lib.wunet_stft_scratch_bytes(R, T, N, H, 0)) // 8, dtype=torch.float64, device=dev)
-                sv = torch.empty(lib.wunet_stft_saved_bytes(R, T, N, H) // 4, dtype=torch.float32, device=dev) if with_backward else None
-                self._check(lib.wunet_stft_forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(clamp), basis.data_ptr(),
-                                                   scr.data_ptr(), sv.data_ptr() if sv is not None else None, None, st))
+                basis = self._basis(N, W, dev, where)
+                scr = torch.empty(self._sized(scratch_bytes(R, T, N, H, 0)) // 8, dtype=torch.float64, device=dev)
+                sv = torch.empty(saved_bytes(R, T, N, H) // 4, dtype=torch.float32, device=dev) if with_backward else None
+                if fam.cspec:
+                    rc = forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(knobs[0]), float(knobs[1]), basis.data_ptr(),
+                                 scr.data_ptr(), scr.numel() * 8, _ptr(sv), sv.numel() * 4 if sv is not None else 0, st)
+                else:
+                    rc = forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(knobs[0]), basis.data_ptr(), scr.data_ptr(), _ptr(sv), None, st)
+                self._check(rc)
                 scratch.append(scr)
                 saved.append(sv)
-            self._check(lib.wunet_stft_finalize(n, self._ptrs(scratch), R, T, (ctypes.c_int * n)(*[r[0] for r in resolutions]),
-                                                (ctypes.c_int * n)(*[r[1] for r in resolutions]), float(sc_weight), float(mag_weight),
-                                                out.data_ptr(), coefs.data_ptr(), st))
+            ffts, hops = (ctypes.c_int * n)(*[r[0] for r in resolutions]), (ctypes.c_int * n)(*[r[1] for r in resolutions])
+            if fam.cspec:
+                rc = finalize(n, self._ptrs(scratch), R, T, ffts, hops, float(weights[0]), out.data_ptr(), coefs.data_ptr(), st)
+            else:
+                rc = finalize(n, self._ptrs(scratch), R, T, ffts, hops, float(weights[0]), float(weights[1]), out.data_ptr(), coefs.data_ptr(), st)
+            self._check(rc)
         return out, coefs, (saved if with_backward else None)
 
-    def stft_loss_backward(self, shape, resolutions, coefs, saved, grad_loss, clamp=1e-7):
-        """d loss / d enhanced (a tensor of `shape`) of the `stft_loss_forward` that produced `coefs` and `saved`, times grad_loss (a scalar
-        tensor).  The resolutions are added in their order: one fixed order of sums."""
+    def _spectral_loss_backward(self, fam, shape, resolutions, coefs, saved, grad_loss, knobs):
+        """Both spectral losses: per resolution wunet_<c>_backward with the scalars `knobs`; the first writes g, the others add to it."""
         n = len(resolutions)
-        if coefs.dtype != torch.float64 or coefs.numel() != n * STFT_COEFS or not coefs.is_contiguous() or saved is None or len(saved) != n:
-            raise WunetError(f"stft loss: coefs / saved must be those of stft_loss_forward over the same {n} resolutions")
+        if coefs.dtype != torch.float64 or coefs.numel() != n * fam.coefs or not coefs.is_contiguous() or saved is None or len(saved) != n:
+            raise WunetError(f"{fam.what}: coefs / saved must be those of {fam.c}_loss_forward over the same {n} resolutions")
         dev = coefs.device
         T = shape[-1]
         g = torch.empty(shape, dtype=torch.float32, device=dev)
         R = g.numel() // T
         gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
-        lib = self.lib
+        scratch_bytes, saved_bytes, _, _, backward = self._spectral_calls(fam)
+        where = str(dev)
         with self._device_guard(dev):
             st = self._stream(dev)
             for i, (N, H, W) in enumerate(resolutions):
-                if saved[i].numel() * 4 != lib.wunet_stft_saved_bytes(R, T, N, H) or saved[i].device != dev:
-                    raise WunetError(f"stft loss: saved[{i}] is not the buffer of resolution {(N, H, W)} on {tuple(shape)}")
-                scr = torch.empty(lib.wunet_stft_scratch_bytes(R, T, N, H, 1) // 4, dtype=torch.float32, device=dev)
-                self._check(lib.wunet_stft_backward(saved[i].data_ptr(), coefs.data_ptr() + 8 * STFT_COEFS * i, gl.data_ptr(), R, T, N, H, W,
-                                                    float(clamp), self.stft_basis(N, W, dev).data_ptr(), scr.data_ptr(), g.data_ptr(),
-                                                    1 if i else 0, st))
+                sv = saved[i]
+                wrong = sv.dtype != torch.float32 if fam.saved_by_dtype else sv.numel() * 4 != saved_bytes(R, T, N, H)
+                if wrong or sv.device != dev:
+                    raise WunetError(f"{fam.what}: saved[{i}] is not the buffer of resolution {(N, H, W)} on {tuple(shape)}")
+                scr = torch.empty(scratch_bytes(R, T, N, H, 1) // 4, dtype=torch.float32, device=dev)
+                basis = self._basis(N, W, dev, where)
+                if fam.cspec:
+                    rc = backward(sv.data_ptr(), sv.numel() * 4, coefs.data_ptr() + 8 * fam.coefs * i, gl.data_ptr(), R, T, N, H, W, float(knobs[0]),
+                                  float(knobs[1]), basis.data_ptr(), scr.data_ptr(), scr.numel() * 4, g.data_ptr(), 1 if i else 0, st)
+                else:
+                    rc = backward(sv.data_ptr(), coefs.data_ptr() + 8 * fam.coefs * i, gl.data_ptr(), R, T, N, H, W, float(knobs[0]),
+                                  basis.data_ptr(), scr.data_ptr(), g.data_ptr(), 1 if i else 0, st)
+                self._check(rc)
         return g
+
+    def stft_loss_forward(self, clean, enhanced, resolutions, sc_weight=1.0, mag_weight=1.0, clamp=1e-7, with_backward=True):
+        """resolutions: a sequence of (n_fft, hop, win_length).  The last dimension is the utterance, all leading ones are flattened.
+        Returns (loss, coefs, saved): loss - device scalar; coefs - float64 [n_res, STFT_COEFS] (a, b, sc, mag per resolution);
+        saved - one float32 buffer per resolution for `stft_loss_backward` (None with with_backward=False)."""
+        return self._spectral_loss_forward(_STFT, clean, enhanced, resolutions, (clamp,), (sc_weight, mag_weight), with_backward)
+
+    def stft_loss_backward(self, shape, resolutions, coefs, saved, grad_loss, clamp=1e-7):
+        """d loss / d enhanced (a tensor of `shape`) of the `stft_loss_forward` that produced `coefs` and `saved`, times grad_loss (a scalar
+        tensor).  The resolutions are added in their order: one fixed order of sums."""
+        return self._spectral_loss_backward(_STFT, shape, resolutions, coefs, saved, grad_loss, (clamp,))
 
     # ------------------------------------------------------------------ compressed spectral loss (wunet_cspec_*)
     def cspec_loss_forward(self, clean, enhanced, resolutions, compress=0.3, complex_weight=0.3, clamp=1e-7, with_backward=True):
         """resolutions: a sequence of (n_fft, hop, win_length).  The last dimension is the utterance, all leading ones are flattened.
         Returns (loss, coefs, saved): loss - device scalar; coefs - float64 [n_res, CSPEC_COEFS] (the two gradient scales, the two term
         values per resolution); saved - one float32 buffer per resolution for `cspec_loss_backward` (None with with_backward=False)."""
-        R, T, dev = self._wave_pair("compressed spectral loss", clean, enhanced)
-        n = len(resolutions)
-        if n < 1 or n > STFT_MAX_RESOLUTIONS:
-            raise WunetError(f"compressed spectral loss: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {n})")
-        lib = self.lib
-        out = torch.empty((), dtype=torch.float32, device=dev)
-        coefs = torch.empty(n, CSPEC_COEFS, dtype=torch.float64, device=dev)
-        scratch, saved = [], []
-        with self._device_guard(dev):
-            st = self._stream(dev)
-            for N, H, W in resolutions:
-                basis = self.stft_basis(N, W, dev)
-                scr = torch.empty(self._sized(lib.wunet_cspec_scratch_bytes(R, T, N, H, 0)) // 8, dtype=torch.float64, device=dev)
-                sv = torch.empty(lib.wunet_cspec_saved_bytes(R, T, N, H) // 4, dtype=torch.float32, device=dev) if with_backward else None
-                self._check(lib.wunet_cspec_forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(compress), float(clamp),
-                                                    basis.data_ptr(), scr.data_ptr(), scr.numel() * 8,
-                                                    sv.data_ptr() if sv is not None else None, sv.numel() * 4 if sv is not None else 0, st))
-                scratch.append(scr)
-                saved.append(sv)
-            self._check(lib.wunet_cspec_finalize(n, self._ptrs(scratch), R, T, (ctypes.c_int * n)(*[r[0] for r in resolutions]),
-                                                 (ctypes.c_int * n)(*[r[1] for r in resolutions]), float(complex_weight),
-                                                 out.data_ptr(), coefs.data_ptr(), st))
-        return out, coefs, (saved if with_backward else None)
+        return self._spectral_loss_forward(_CSPEC, clean, enhanced, resolutions, (compress, clamp), (complex_weight,), with_backward)
 
     def cspec_loss_backward(self, shape, resolutions, coefs, saved, grad_loss, compress=0.3, clamp=1e-7):
         """d loss / d enhanced (a tensor of `shape`) of the `cspec_loss_forward` that produced `coefs` and `saved`, times grad_loss (a
         scalar tensor).  The resolutions are added in their order: one fixed order of sums."""
-        n = len(resolutions)
-        if coefs.dtype != torch.float64 or coefs.numel() != n * CSPEC_COEFS or not coefs.is_contiguous() or saved is None or len(saved) != n:
-            raise WunetError(f"compressed spectral loss: coefs / saved must be those of cspec_loss_forward over the same {n} resolutions")
-        dev = coefs.device
-        T = shape[-1]
-        g = torch.empty(shape, dtype=torch.float32, device=dev)
-        R = g.numel() // T
-        gl = grad_loss.to(device=dev, dtype=torch.float32).contiguous()
-        lib = self.lib
-        with self._device_guard(dev):
-            st = self._stream(dev)
-            for i, (N, H, W) in enumerate(resolutions):
-                if saved[i].dtype != torch.float32 or saved[i].device != dev:
-                    raise WunetError(f"compressed spectral loss: saved[{i}] is not the buffer of resolution {(N, H, W)} on {tuple(shape)}")
-                scr = torch.empty(lib.wunet_cspec_scratch_bytes(R, T, N, H, 1) // 4, dtype=torch.float32, device=dev)
-                self._check(lib.wunet_cspec_backward(saved[i].data_ptr(), saved[i].numel() * 4, coefs.data_ptr() + 8 * CSPEC_COEFS * i,
-                                                     gl.data_ptr(), R, T, N, H, W, float(compress), float(clamp),
-                                                     self.stft_basis(N, W, dev).data_ptr(), scr.data_ptr(), scr.numel() * 4, g.data_ptr(),
-                                                     1 if i else 0, st))
-        return g
+        return self._spectral_loss_backward(_CSPEC, shape, resolutions, coefs, saved, grad_loss, (compress, clamp))
 
     def stft_magnitude(self, x, n_fft=320, hop=160, win_length=320):
         """|STFT| of every row of x (periodic Hann, center=True, reflect padding - torch.stft's conventions): float32 [rows, F, n_fft/2 + 1]."""
@@ -612,8 +640,8 @@ class Engine:
             tables = torch.empty(self._sized(self.lib.wunet_stoi_tables_bytes(key[0])) // 4, dtype=torch.float32, device=device)
             h = torch.from_numpy(taps[2]).to(device) if taps is not None else None
             with self._device_guard(device):
-                self._check(self.lib.wunet_stoi_tables_build(key[0], h.data_ptr() if h is not None else None, h.numel() if h is not None else 0,
-                                                             tables.data_ptr(), self._stream(device)))
+                self._check(self.lib.wunet_stoi_tables_build(key[0], _ptr(h), h.numel() if h is not None else 0, tables.data_ptr(),
+                                                             self._stream(device)))
                 if h is not None and not self.host_memory:
                     h.record_stream(torch.cuda.current_stream(device))       # (the copy kernel may still be reading it when h is freed)
             self._stoi_tables_cache[key] = tables
@@ -635,7 +663,7 @@ class Engine:
         frames = torch.empty(R, dtype=torch.int32, device=dev) if return_frames else None
         with self._device_guard(dev):
             self._check(self._stoi_call(extended, "forward")(clean.data_ptr(), estimate.data_ptr(), R, T, fs, tables.data_ptr(), scratch.data_ptr(),
-                                                             out.data_ptr(), frames.data_ptr() if frames is not None else None, self._stream(dev)))
+                                                             out.data_ptr(), _ptr(frames), self._stream(dev)))
         return (out, frames) if return_frames else out
 
     def stoi_loss_forward(self, clean, enhanced, sample_rate=16000, per_row=False, with_backward=True, extended=False):
@@ -653,7 +681,7 @@ class Engine:
         with self._device_guard(dev):
             self._check(self._stoi_call(extended, "loss_forward")(clean.data_ptr(), enhanced.data_ptr(), R, T, fs, tables.data_ptr(),
                                                                   scratch.data_ptr(), saved.data_ptr(), out.data_ptr(),
-                                                                  rows.data_ptr() if rows is not None else None, None, self._stream(dev)))
+                                                                  _ptr(rows), None, self._stream(dev)))
         return out, (saved if with_backward else None), rows
 
     def stoi_loss_backward(self, shape, saved, grad_loss, sample_rate=16000, extended=False):
@@ -713,17 +741,16 @@ class Engine:
         n = len(params)
         numels = (ctypes.c_size_t * n)(*[p.numel() for p in params])
         dev = params[0].device
-        ptr = lambda t: t.data_ptr() if t is not None else None          # noqa: E731
         with self._device_guard(dev):
             if ex:
                 self._check(self.lib.wunet_adam_step_ex(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg), self._ptrs(exp_avg_sq),
                                                         numels, float(lr), float(beta1), float(beta2), float(eps), int(step),
-                                                        float(grad_scale), float(weight_decay), clip, ptr(step_dev), ptr(hyper_dev),
-                                                        ptr(lr_dev), ptr(scratch), self._stream(dev)))
+                                                        float(grad_scale), float(weight_decay), clip, _ptr(step_dev), _ptr(hyper_dev),
+                                                        _ptr(lr_dev), _ptr(scratch), self._stream(dev)))
             else:
                 self._check(self.lib.wunet_adam_step(n, self._ptrs(params), self._ptrs(grads), self._ptrs(exp_avg),
                                                      self._ptrs(exp_avg_sq), numels, float(lr), float(beta1), float(beta2),
-                                                     float(eps), int(step), float(grad_scale), ptr(step_dev), ptr(hyper_dev), self._stream(dev)))
+                                                     float(eps), int(step), float(grad_scale), _ptr(step_dev), _ptr(hyper_dev), self._stream(dev)))
 
     def adam_scratch_bytes(self, n_tensors):
         """Device bytes of the partial sums of the gradient norm (adam_step(max_grad_norm=...)) over n_tensors tensors."""
@@ -747,12 +774,8 @@ class Engine:
         circular noise window that rows[b] = (clean start, noise item start, noise item length, noise phase) names, at params[b] =
         (snr_db, linear level); gains (optional float32 [B, 2]) receives (g, a).  Two launches, nothing read back; the scratch comes from
         torch's allocator."""
-        f32 = torch.float32
-        if rows.dtype != torch.int64 or any(t.dtype != f32 for t in (clean_flat, noise_flat, params, mixture, clean_out)) or \
-                (gains is not None and gains.dtype != f32):
-            raise WunetError("mix_windows: float32 arrays, params, outputs and gains and int64 rows expected")
-        for t in (clean_flat, noise_flat, rows, params, mixture, clean_out) + ((gains,) if gains is not None else ()):
-            self._require(t, "mix tensor")
+        given = self._table_op("mix_windows", "mix tensor", "float32 arrays, params, outputs and gains and int64 rows",
+                               (clean_flat, noise_flat, rows, params, mixture, clean_out, gains), rows)
         if clean_flat.dim() != 1 or noise_flat.dim() != 1 or mixture.dim() < 2:
             raise WunetError("mix_windows: the two arrays must be flat and the outputs [B, ..., L]")
         B, L = mixture.shape[0], mixture.shape[-1]
@@ -760,8 +783,7 @@ class Engine:
                 (gains is not None and tuple(gains.shape) != (B, 2)):
             raise WunetError("mix_windows: shape mismatch (rows [B, 4], params [B, 2], gains [B, 2], outputs [B, 1, L])")
         dev = mixture.device
-        if any(t.device != dev for t in (clean_flat, noise_flat, rows, params, clean_out)) or (gains is not None and gains.device != dev):
-            raise WunetError("mix_windows: every tensor must live on the outputs' device")
+        self._same_device("mix_windows", given, dev, "the outputs' device")
         nbytes = self.lib.wunet_mix_scratch_bytes(B, L)
         if nbytes == 0:
             raise WunetError(f"mix_windows: bad shape (batch={B} length={L})")
@@ -769,48 +791,38 @@ class Engine:
         with self._device_guard(dev):
             self._check(self.lib.wunet_mix_windows(clean_flat.data_ptr(), clean_flat.numel(), noise_flat.data_ptr(), noise_flat.numel(),
                                                    rows.data_ptr(), params.data_ptr(), float(peak_limit), B, L, scratch.data_ptr(),
-                                                   mixture.data_ptr(), clean_out.data_ptr(), gains.data_ptr() if gains is not None else None,
-                                                   self._stream(dev)))
+                                                   mixture.data_ptr(), clean_out.data_ptr(), _ptr(gains), self._stream(dev)))
 
     def reverb_windows(self, clean_flat, rir_flat, rows, reverberant, direct=None, early_taps=1):
         """include/wunet_hip.h: wunet_reverb_windows.  reverberant[b, 0, :] = the clean window that rows[b] = (window start, clean item
         start, RIR start, RIR taps) names, convolved with its room impulse response (the source is zero in front of the item start);
         direct (optional, the same shape) receives the first min(early_taps, taps) taps' share.  A row with no taps is passed through.
         One launch, nothing read back, no scratch."""
-        f32 = torch.float32
-        if rows.dtype != torch.int64 or any(t.dtype != f32 for t in (clean_flat, rir_flat, reverberant)) or \
-                (direct is not None and direct.dtype != f32):
-            raise WunetError("reverb_windows: float32 arrays and outputs and int64 rows expected")
-        for t in (clean_flat, rir_flat, rows, reverberant) + ((direct,) if direct is not None else ()):
-            self._require(t, "reverb tensor")
+        given = self._table_op("reverb_windows", "reverb tensor", "float32 arrays and outputs and int64 rows",
+                               (clean_flat, rir_flat, rows, reverberant, direct), rows)
         if clean_flat.dim() != 1 or rir_flat.dim() != 1 or reverberant.dim() < 2:
             raise WunetError("reverb_windows: the two arrays must be flat and the outputs [B, ..., L]")
         B, L = reverberant.shape[0], reverberant.shape[-1]
         if reverberant.numel() != B * L or tuple(rows.shape) != (B, 4) or (direct is not None and direct.shape != reverberant.shape):
             raise WunetError("reverb_windows: shape mismatch (rows [B, 4], outputs [B, 1, L])")
         dev = reverberant.device
-        if any(t.device != dev for t in (clean_flat, rir_flat, rows)) or (direct is not None and direct.device != dev):
-            raise WunetError("reverb_windows: every tensor must live on the outputs' device")
+        self._same_device("reverb_windows", given, dev, "the outputs' device")
         with self._device_guard(dev):
             self._check(self.lib.wunet_reverb_windows(clean_flat.data_ptr(), clean_flat.numel(), rir_flat.data_ptr(), rir_flat.numel(),
-                                                      rows.data_ptr(), int(early_taps), B, L, reverberant.data_ptr(),
-                                                      direct.data_ptr() if direct is not None else None, self._stream(dev)))
+                                                      rows.data_ptr(), int(early_taps), B, L, reverberant.data_ptr(), _ptr(direct),
+                                                      self._stream(dev)))
 
     def apply_level(self, src, gains, dst=None):
         """include/wunet_hip.h: wunet_apply_level.  dst[b] = gains[b, 1] * src[b] for the [B, 2] gains table that mix_windows wrote - the
         multiply that made its clean_out.  dst None: in place.  Returns dst."""
         dst = src if dst is None else dst
-        if any(t.dtype != torch.float32 for t in (src, gains, dst)):
-            raise WunetError("apply_level: float32 src, gains and dst expected")
-        for t in (src, gains, dst):
-            self._require(t, "apply_level tensor")
+        given = self._table_op("apply_level", "apply_level tensor", "float32 src, gains and dst", (src, gains, dst), None)
         if src.dim() < 2:
             raise WunetError("apply_level: shape mismatch (src and dst [B, ..., L], gains [B, 2])")
         B, L = src.shape[0], src.shape[-1]
         if src.numel() != B * L or dst.shape != src.shape or tuple(gains.shape) != (B, 2):
             raise WunetError("apply_level: shape mismatch (src and dst [B, ..., L], gains [B, 2])")
-        if gains.device != src.device or dst.device != src.device:
-            raise WunetError("apply_level: every tensor must live on one device")
+        self._same_device("apply_level", given, src.device, "one device")
         with self._device_guard(src.device):
             self._check(self.lib.wunet_apply_level(src.data_ptr(), gains.data_ptr(), B, L, dst.data_ptr(), self._stream(src.device)))
         return dst
@@ -818,18 +830,14 @@ class Engine:
     def chunk_gather(self, flat, rows, chunks):
         """include/wunet_hip.h: wunet_chunk_gather.  chunks[i, 0, j] = flat[start + s + j] inside the recording that rows[i] = (flat start,
         T, chunk start s) names, 0 outside it.  One launch, nothing read back, no scratch."""
-        if rows.dtype != torch.int64 or flat.dtype != torch.float32 or chunks.dtype != torch.float32:
-            raise WunetError("chunk_gather: a float32 array and chunks and int64 rows expected")
-        for t in (flat, rows, chunks):
-            self._require(t, "chunk_gather tensor")
+        given = self._table_op("chunk_gather", "chunk_gather tensor", "a float32 array and chunks and int64 rows", (flat, rows, chunks), rows)
         if flat.dim() != 1 or chunks.dim() < 2:
             raise WunetError("chunk_gather: the array must be flat and the chunks [n, ..., L]")
         n, L = chunks.shape[0], chunks.shape[-1]
         if chunks.numel() != n * L or tuple(rows.shape) != (n, 3):
             raise WunetError("chunk_gather: shape mismatch (rows [n, 3], chunks [n, 1, L])")
         dev = chunks.device
-        if flat.device != dev or rows.device != dev:
-            raise WunetError("chunk_gather: every tensor must live on the chunks' device")
+        self._same_device("chunk_gather", given, dev, "the chunks' device")
         with self._device_guard(dev):
             self._check(self.lib.wunet_chunk_gather(flat.data_ptr(), flat.numel(), rows.data_ptr(), n, L, chunks.data_ptr(), self._stream(dev)))
 
@@ -837,11 +845,8 @@ class Engine:
         """include/wunet_hip.h: wunet_chunk_overlap_add.  out_flat[start + t], t < T, for every recording recs[r] = (flat start, T, first
         chunk row, chunk count): chunk k's sample m + j outside the cross-fades, ramp[j] y_k + (1 - ramp[j]) y_(k-1) inside them.  ramp:
         float32 [fade], None exactly when fade == 0; max_len: the largest T.  One launch, nothing read back, no scratch."""
-        f32 = torch.float32
-        if recs.dtype != torch.int64 or chunks.dtype != f32 or out_flat.dtype != f32 or (ramp is not None and ramp.dtype != f32):
-            raise WunetError("chunk_overlap_add: float32 chunks, ramp and output and int64 recs expected")
-        for t in (chunks, recs, out_flat) + ((ramp,) if ramp is not None else ()):
-            self._require(t, "chunk_overlap_add tensor")
+        given = self._table_op("chunk_overlap_add", "chunk_overlap_add tensor", "float32 chunks, ramp and output and int64 recs",
+                               (chunks, recs, out_flat, ramp), recs)
         if out_flat.dim() != 1 or chunks.dim() < 2:
             raise WunetError("chunk_overlap_add: the output must be flat and the chunks [n, ..., L]")
         n, L = chunks.shape[0], chunks.shape[-1]
@@ -850,12 +855,10 @@ class Engine:
                 (ramp is None) != (fade == 0):
             raise WunetError("chunk_overlap_add: shape mismatch (chunks [n, 1, L], recs [R, 4], ramp [fade] or None when fade == 0)")
         dev = chunks.device
-        if recs.device != dev or out_flat.device != dev or (ramp is not None and ramp.device != dev):
-            raise WunetError("chunk_overlap_add: every tensor must live on the chunks' device")
+        self._same_device("chunk_overlap_add", given, dev, "the chunks' device")
         with self._device_guard(dev):
-            self._check(self.lib.wunet_chunk_overlap_add(chunks.data_ptr(), n, L, margin, fade, ramp.data_ptr() if ramp is not None else None,
-                                                         recs.data_ptr(), recs.shape[0], int(max_len), out_flat.data_ptr(), out_flat.numel(),
-                                                         self._stream(dev)))
+            self._check(self.lib.wunet_chunk_overlap_add(chunks.data_ptr(), n, L, margin, fade, _ptr(ramp), recs.data_ptr(), recs.shape[0],
+                                                         int(max_len), out_flat.data_ptr(), out_flat.numel(), self._stream(dev)))
 
     # ------------------------------------------------------------------ sample-rate conversion (wunet_resample_rows)
     def resample_taps(self, rate_in, rate_out, device):
@@ -873,15 +876,11 @@ class Engine:
         """include/wunet_hip.h: wunet_resample_rows.  For every row rows[i] = (in start, T_in, out start, T_out) of the flat float32
         array `flat`, out[out start + m], m < T_out, is the polyphase filter of resample.resample_taps(rate_in, rate_out) over the
         row's T_in samples.  max_out: the largest T_out.  One launch, nothing read back, no scratch."""
-        if rows.dtype != torch.int64 or flat.dtype != torch.float32 or out.dtype != torch.float32:
-            raise WunetError("resample_rows: float32 arrays and int64 rows expected")
-        for t in (flat, rows, out):
-            self._require(t, "resample_rows tensor")
+        given = self._table_op("resample_rows", "resample_rows tensor", "float32 arrays and int64 rows", (flat, rows, out), rows)
         if flat.dim() != 1 or out.dim() != 1 or rows.dim() != 2 or rows.shape[1] != 4 or rows.shape[0] < 1:
             raise WunetError("resample_rows: shape mismatch (flat arrays in and out, rows [n, 4] with n >= 1)")
         dev = out.device
-        if flat.device != dev or rows.device != dev:
-            raise WunetError("resample_rows: every tensor must live on one device")
+        self._same_device("resample_rows", given, dev, "one device")
         up, down, taps = self.resample_taps(rate_in, rate_out, dev)
         with self._device_guard(dev):
             self._check(self.lib.wunet_resample_rows(flat.data_ptr(), flat.numel(), rows.data_ptr(), rows.shape[0], int(max_out), up, down,

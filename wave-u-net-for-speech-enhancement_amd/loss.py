@@ -63,15 +63,21 @@ class _LossFn(torch.autograd.Function):
         return None, None, g_clean, (g if ctx.needs_input_grad[3] else None)
 
 
-class HipLoss(nn.Module):
+class _HipLossModule(nn.Module):
+    """What every loss module here shares: the engine it runs on (`_engine_override`, which tests and tools set, or the process's)."""
+    _engine_override = None
+
+    def _engine(self):
+        return self._engine_override if self._engine_override is not None else default_engine()
+
+
+class HipLoss(_HipLossModule):
     def __init__(self, kind):
         super().__init__()
         self.kind = kind
-        self._engine_override = None
 
     def forward(self, clean, enhanced):
-        engine = self._engine_override if self._engine_override is not None else default_engine()
-        return _LossFn.apply(self.kind, engine, clean, enhanced)
+        return _LossFn.apply(self.kind, self._engine(), clean, enhanced)
 
 
 def mse_loss():
@@ -86,26 +92,32 @@ def smooth_l1_loss():
     return HipLoss("smooth_l1")
 
 
-class _RowLossFn(torch.autograd.Function):
+class _EnhancedGradFn(torch.autograd.Function):
+    """The losses with a gradient with respect to `enhanced` only.  `mod` (an _EnhancedGradLoss) supplies the message of the refusal,
+    _loss_forward(engine, clean, enhanced) -> (loss, tensors to save) and _loss_backward(engine, shape, saved tensors, grad_loss)."""
+
     @staticmethod
-    def forward(ctx, kind, zero_mean, eps, engine, clean, enhanced):
+    def forward(ctx, mod, engine, clean, enhanced):
         if clean.requires_grad:                 # (before anything runs)
-            raise NotImplementedError(f"{kind}_loss: no gradient with respect to `clean` (the target also sets the signal energy, so it is "
-                                      "not minus the gradient of `enhanced` as for the element-wise losses): detach it")
+            raise NotImplementedError(mod._no_clean_grad)
         clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
-        loss, coefs, _ = engine.loss_rows_forward(kind, clean_c, enh_c, zero_mean, eps)
-        ctx.kind, ctx.engine = kind, engine
-        ctx.save_for_backward(clean_c, enh_c, coefs)
+        loss, saved = mod._loss_forward(engine, clean_c, enh_c)
+        ctx.mod, ctx.engine, ctx.shape = mod, engine, tuple(enh_c.shape)
+        ctx.save_for_backward(*saved)
         return loss
 
     @staticmethod
     def backward(ctx, grad_loss):
-        clean, enh, coefs = ctx.saved_tensors
-        g = ctx.engine.loss_rows_backward(ctx.kind, clean, enh, coefs, grad_loss) if ctx.needs_input_grad[5] else None
-        return None, None, None, None, None, g
+        g = ctx.mod._loss_backward(ctx.engine, ctx.shape, ctx.saved_tensors, grad_loss) if ctx.needs_input_grad[3] else None
+        return None, None, None, g
 
 
-class HipRowLoss(nn.Module):
+class _EnhancedGradLoss(_HipLossModule):
+    def forward(self, clean, enhanced):
+        return _EnhancedGradFn.apply(self, self._engine(), clean, enhanced)
+
+
+class HipRowLoss(_EnhancedGradLoss):
     """loss(clean, enhanced) -> -mean over rows of si_sdr / snr [dB]; the last dimension is the utterance."""
 
     def __init__(self, kind, zero_mean=True, eps=1e-8):
@@ -113,11 +125,15 @@ class HipRowLoss(nn.Module):
         if not (eps >= 0.0 and eps < float("inf")):
             raise ValueError(f"{kind}_loss: eps must be finite and >= 0 (got {eps})")
         self.kind, self.zero_mean, self.eps = kind, bool(zero_mean), float(eps)
-        self._engine_override = None
+        self._no_clean_grad = (f"{kind}_loss: no gradient with respect to `clean` (the target also sets the signal energy, so it is "
+                               "not minus the gradient of `enhanced` as for the element-wise losses): detach it")
 
-    def forward(self, clean, enhanced):
-        engine = self._engine_override if self._engine_override is not None else default_engine()
-        return _RowLossFn.apply(self.kind, self.zero_mean, self.eps, engine, clean, enhanced)
+    def _loss_forward(self, engine, clean, enhanced):
+        loss, coefs, _ = engine.loss_rows_forward(self.kind, clean, enhanced, self.zero_mean, self.eps)
+        return loss, (clean, enhanced, coefs)
+
+    def _loss_backward(self, engine, shape, saved, grad_loss):
+        return engine.loss_rows_backward(self.kind, *saved, grad_loss)
 
 
 def si_sdr_loss(zero_mean=True, eps=1e-8):
@@ -128,143 +144,93 @@ def snr_loss(zero_mean=True, eps=1e-8):
     return HipRowLoss("snr", zero_mean, eps)
 
 
-class _StftLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mod, engine, clean, enhanced):
-        if clean.requires_grad:                 # (before anything runs)
-            raise NotImplementedError("stft_loss: no gradient with respect to `clean` (the target also sets the spectral-convergence "
-                                      "norm, so it is not minus the gradient of `enhanced`): detach it")
-        clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
-        loss, coefs, saved = engine.stft_loss_forward(clean_c, enh_c, mod.resolutions, mod.sc_weight, mod.mag_weight, mod.clamp)
-        ctx.mod, ctx.engine, ctx.shape = mod, engine, tuple(enh_c.shape)
-        ctx.save_for_backward(coefs, *saved)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        coefs, *saved = ctx.saved_tensors
-        g = None
-        if ctx.needs_input_grad[3]:
-            g = ctx.engine.stft_loss_backward(ctx.shape, ctx.mod.resolutions, coefs, saved, grad_loss, ctx.mod.clamp)
-        return None, None, None, g
+def _check_resolutions(name, fft_sizes, hop_sizes, win_lengths):
+    """The three lists of a spectral loss, zipped into (n_fft, hop, win_length) triples for check_stft_resolution."""
+    fft_sizes, hop_sizes, win_lengths = list(fft_sizes), list(hop_sizes), list(win_lengths)
+    if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
+        raise ValueError(f"{name}: fft_sizes, hop_sizes and win_lengths must have equal lengths (got {len(fft_sizes)}, "
+                         f"{len(hop_sizes)}, {len(win_lengths)})")
+    if not 1 <= len(fft_sizes) <= STFT_MAX_RESOLUTIONS:
+        raise ValueError(f"{name}: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {len(fft_sizes)})")
+    return list(zip(fft_sizes, hop_sizes, win_lengths))
 
 
-class HipStftLoss(nn.Module):
+class HipStftLoss(_EnhancedGradLoss):
     """loss(clean, enhanced) -> mean over the resolutions of sc_weight * spectral convergence + mag_weight * log-magnitude L1; the last
     dimension is the utterance.  Gradient with respect to `enhanced` only."""
+    _no_clean_grad = ("stft_loss: no gradient with respect to `clean` (the target also sets the spectral-convergence "
+                      "norm, so it is not minus the gradient of `enhanced`): detach it")
 
     def __init__(self, fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), sc_weight=1.0, mag_weight=1.0,
                  clamp=1e-7):
         super().__init__()
-        fft_sizes, hop_sizes, win_lengths = list(fft_sizes), list(hop_sizes), list(win_lengths)
-        if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
-            raise ValueError(f"stft_loss: fft_sizes, hop_sizes and win_lengths must have equal lengths (got {len(fft_sizes)}, "
-                             f"{len(hop_sizes)}, {len(win_lengths)})")
-        if not 1 <= len(fft_sizes) <= STFT_MAX_RESOLUTIONS:
-            raise ValueError(f"stft_loss: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {len(fft_sizes)})")
+        triples = _check_resolutions("stft_loss", fft_sizes, hop_sizes, win_lengths)
         if not (clamp > 0.0 and clamp < float("inf")):
             raise ValueError(f"stft_loss: clamp must be finite and > 0 (got {clamp})")
-        self.resolutions = tuple(check_stft_resolution(n, h, w) for n, h, w in zip(fft_sizes, hop_sizes, win_lengths))
+        self.resolutions = tuple(check_stft_resolution(n, h, w) for n, h, w in triples)
         self.sc_weight, self.mag_weight, self.clamp = float(sc_weight), float(mag_weight), float(clamp)
-        self._engine_override = None
 
-    def forward(self, clean, enhanced):
-        engine = self._engine_override if self._engine_override is not None else default_engine()
-        return _StftLossFn.apply(self, engine, clean, enhanced)
+    def _loss_forward(self, engine, clean, enhanced):
+        loss, coefs, saved = engine.stft_loss_forward(clean, enhanced, self.resolutions, self.sc_weight, self.mag_weight, self.clamp)
+        return loss, (coefs, *saved)
+
+    def _loss_backward(self, engine, shape, saved, grad_loss):
+        return engine.stft_loss_backward(shape, self.resolutions, saved[0], list(saved[1:]), grad_loss, self.clamp)
 
 
 def stft_loss(fft_sizes=(1024, 2048, 512), hop_sizes=(120, 240, 50), win_lengths=(600, 1200, 240), sc_weight=1.0, mag_weight=1.0, clamp=1e-7):
     return HipStftLoss(fft_sizes, hop_sizes, win_lengths, sc_weight, mag_weight, clamp)
 
 
-class _CspecLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, mod, engine, clean, enhanced):
-        if clean.requires_grad:                 # (before anything runs)
-            raise NotImplementedError("compressed_spectral_loss: no gradient with respect to `clean`: detach it")
-        clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
-        loss, coefs, saved = engine.cspec_loss_forward(clean_c, enh_c, mod.resolutions, mod.compress, mod.complex_weight, mod.clamp)
-        ctx.mod, ctx.engine, ctx.shape = mod, engine, tuple(enh_c.shape)
-        ctx.save_for_backward(coefs, *saved)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        coefs, *saved = ctx.saved_tensors
-        g = None
-        if ctx.needs_input_grad[3]:
-            g = ctx.engine.cspec_loss_backward(ctx.shape, ctx.mod.resolutions, coefs, saved, grad_loss, ctx.mod.compress, ctx.mod.clamp)
-        return None, None, None, g
-
-
-class HipCompressedSpectralLoss(nn.Module):
+class HipCompressedSpectralLoss(_EnhancedGradLoss):
     """loss(clean, enhanced) -> mean over the resolutions of mean [(1 - complex_weight) (A_c - A_e)^2 + complex_weight |Z_c - Z_e|^2]
     with A = max(P, clamp)^(compress / 2), Z = (re + i im) max(P, clamp)^((compress - 1) / 2), P = re^2 + im^2 of the STFT (stft_loss's
     conventions); the last dimension is the utterance.  Gradient with respect to `enhanced` only."""
+    _no_clean_grad = "compressed_spectral_loss: no gradient with respect to `clean`: detach it"
 
     def __init__(self, fft_sizes=(512,), hop_sizes=(128,), win_lengths=(512,), compress=0.3, complex_weight=0.3, clamp=1e-7):
         super().__init__()
         name = "compressed_spectral_loss"
-        fft_sizes, hop_sizes, win_lengths = list(fft_sizes), list(hop_sizes), list(win_lengths)
-        if not (len(fft_sizes) == len(hop_sizes) == len(win_lengths)):
-            raise ValueError(f"{name}: fft_sizes, hop_sizes and win_lengths must have equal lengths (got {len(fft_sizes)}, "
-                             f"{len(hop_sizes)}, {len(win_lengths)})")
-        if not 1 <= len(fft_sizes) <= STFT_MAX_RESOLUTIONS:
-            raise ValueError(f"{name}: 1 .. {STFT_MAX_RESOLUTIONS} resolutions (got {len(fft_sizes)})")
+        triples = _check_resolutions(name, fft_sizes, hop_sizes, win_lengths)
         if not (compress > 0.0 and compress <= 1.0):
             raise ValueError(f"{name}: compress must be in (0, 1] (got {compress})")
         if not (complex_weight >= 0.0 and complex_weight <= 1.0):
             raise ValueError(f"{name}: complex_weight must be in [0, 1] (got {complex_weight})")
         if not (clamp > 0.0 and clamp < float("inf")):
             raise ValueError(f"{name}: clamp must be finite and > 0 (got {clamp})")
-        self.resolutions = tuple(check_stft_resolution(n, h, w) for n, h, w in zip(fft_sizes, hop_sizes, win_lengths))
+        self.resolutions = tuple(check_stft_resolution(n, h, w) for n, h, w in triples)
         self.compress, self.complex_weight, self.clamp = float(compress), float(complex_weight), float(clamp)
-        self._engine_override = None
 
-    def forward(self, clean, enhanced):
-        engine = self._engine_override if self._engine_override is not None else default_engine()
-        return _CspecLossFn.apply(self, engine, clean, enhanced)
+    def _loss_forward(self, engine, clean, enhanced):
+        loss, coefs, saved = engine.cspec_loss_forward(clean, enhanced, self.resolutions, self.compress, self.complex_weight, self.clamp)
+        return loss, (coefs, *saved)
+
+    def _loss_backward(self, engine, shape, saved, grad_loss):
+        return engine.cspec_loss_backward(shape, self.resolutions, saved[0], list(saved[1:]), grad_loss, self.compress, self.clamp)
 
 
 def compressed_spectral_loss(fft_sizes=(512,), hop_sizes=(128,), win_lengths=(512,), compress=0.3, complex_weight=0.3, clamp=1e-7):
     return HipCompressedSpectralLoss(fft_sizes, hop_sizes, win_lengths, compress, complex_weight, clamp)
 
 
-class _StoiLossFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, sample_rate, extended, engine, clean, enhanced):
-        if clean.requires_grad:                 # (before anything runs)
-            raise NotImplementedError("stoi_loss: no gradient with respect to `clean` (the target also sets the silent-frame mask and "
-                                      "the clipping level, so it is not minus the gradient of `enhanced`): detach it")
-        clean_c, enh_c = clean.detach().contiguous(), enhanced.detach().contiguous()
-        loss, saved, _ = engine.stoi_loss_forward(clean_c, enh_c, sample_rate, extended=extended)
-        ctx.sample_rate, ctx.extended, ctx.engine, ctx.shape = sample_rate, extended, engine, tuple(enh_c.shape)
-        ctx.save_for_backward(saved)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        saved, = ctx.saved_tensors
-        g = None
-        if ctx.needs_input_grad[4]:
-            g = ctx.engine.stoi_loss_backward(ctx.shape, saved, grad_loss, ctx.sample_rate, extended=ctx.extended)
-        return None, None, None, None, g
-
-
-class HipStoiLoss(nn.Module):
+class HipStoiLoss(_EnhancedGradLoss):
     """loss(clean, enhanced) -> -mean over rows of STOI (pystoi, extended=False; ESTOI with extended=True) at `sample_rate`; the last
     dimension is the utterance.  Gradient with respect to `enhanced` only.  The first call on a device builds the rate's tables (shared
     by both modes): capture a step graph after one eager call, as for stft_loss."""
+    _no_clean_grad = ("stoi_loss: no gradient with respect to `clean` (the target also sets the silent-frame mask and "
+                      "the clipping level, so it is not minus the gradient of `enhanced`): detach it")
 
     def __init__(self, sample_rate=16000, extended=False):
         super().__init__()
         self.sample_rate = check_stoi_rate(sample_rate)
         self.extended = bool(extended)
-        self._engine_override = None
 
-    def forward(self, clean, enhanced):
-        engine = self._engine_override if self._engine_override is not None else default_engine()
-        return _StoiLossFn.apply(self.sample_rate, self.extended, engine, clean, enhanced)
+    def _loss_forward(self, engine, clean, enhanced):
+        loss, saved, _ = engine.stoi_loss_forward(clean, enhanced, self.sample_rate, extended=self.extended)
+        return loss, (saved,)
+
+    def _loss_backward(self, engine, shape, saved, grad_loss):
+        return engine.stoi_loss_backward(shape, saved[0], grad_loss, self.sample_rate, extended=self.extended)
 
 
 def stoi_loss(sample_rate=16000, extended=False):
