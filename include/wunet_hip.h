@@ -348,7 +348,8 @@ int wunet_adam_step(int n_tensors, float* const* params, const float* const* gra
  * step_dev may be NULL (then `step` counts, as in wunet_adam_step).  hyper_dev is required, WUNET_ADAM_HYPER_FLOATS floats that
  * the call overwrites: [0] lr / (1 - beta1^t), [1] sqrt(1 - beta2^t), [2] clip (1 when off), [3] the norm before clipping
  * (0 when off), [4] 1 - lr * weight_decay, the rest reserved.  Capture-safe: no allocation, no synchronisation, no host read-back.
- * With all three parts off the result has the bits of wunet_adam_step. */
+ * Both entry points run the same kernels; with all three parts off the result has the bits of wunet_adam_step, which stays the
+ * entry for a 2-float hyper buffer (or none): nothing behind its slot 1 is read or written. */
 #define WUNET_ADAM_HYPER_FLOATS 8
 size_t wunet_adam_scratch_bytes(int n_tensors);
 int wunet_adam_step_ex(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,

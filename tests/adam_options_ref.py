@@ -113,6 +113,54 @@ def run_fused(optim_mod, case, *, decoupled=False, max_grad_norm=MAX_NORM, devic
     return out, opt
 
 
+SENTINEL = -123.0                                  # finite: slots compare with ==
+
+
+def check_hyper_buffer_bounds(lib, device="cpu", stream=None):
+    """The two C entry points share their kernels; their hyper buffers differ: wunet_adam_step documents 2 floats (or none), wunet_adam_step_ex
+    WUNET_ADAM_HYPER_FLOATS = 8 of which 5 are used.  One tensor of 7 elements, an 8-float buffer pre-filled with SENTINEL per call: the
+    plain entry with a device counter writes slots 0 and 1 only and increments the counter by one; without a counter it takes a NULL
+    hyper pointer; the _ex entry with everything off writes clip = 1, norm = 0 and decay = 1 to slots 2..4 and nothing behind them."""
+    import ctypes
+    g = torch.Generator().manual_seed(7)
+    arr = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())                 # noqa: E731
+    numels = (ctypes.c_size_t * 1)(7)
+
+    def fresh():
+        ts = [torch.randn(7, generator=g).to(device), torch.randn(7, generator=g).to(device), torch.zeros(7, device=device), torch.zeros(7, device=device)]
+        return ts, torch.full((8,), SENTINEL, device=device), torch.full((), 4, dtype=torch.int64, device=device)
+
+    def done(rc, p0, ts):
+        assert rc == 0, lib.wunet_last_error()
+        if torch.device(device).type == "cuda":
+            torch.cuda.synchronize()
+        assert torch.isfinite(ts[0]).all() and not torch.equal(ts[0], p0) and ts[2].any() and ts[3].any()      # the step ran
+
+    hp = (1e-3, 0.9, 0.999, 1e-8)
+    # wunet_adam_step, device counter
+    ts, hyper, counter = fresh()
+    p0 = ts[0].clone()
+    done(lib.wunet_adam_step(1, *(arr(t) for t in ts), numels, *hp, 1, 1.0, counter.data_ptr(), hyper.data_ptr(), stream), p0, ts)
+    h = hyper.cpu()
+    assert int(counter) == 5
+    assert (h[2:] == SENTINEL).all(), h
+    want = (1e-3 / (1.0 - 0.9 ** 5), math.sqrt(1.0 - 0.999 ** 5))      # (doubles rounded to float once: 2^-24, and an ulp of pow)
+    assert all(abs(float(h[k]) - want[k]) <= 1.2e-7 * want[k] for k in range(2)), h
+    # wunet_adam_step, host step: no hyper buffer at all
+    ts, hyper, counter = fresh()
+    p0 = ts[0].clone()
+    done(lib.wunet_adam_step(1, *(arr(t) for t in ts), numels, *hp, 5, 1.0, None, None, stream), p0, ts)
+    assert int(counter) == 4 and (hyper.cpu() == SENTINEL).all()
+    # wunet_adam_step_ex, every option off
+    ts, hyper, counter = fresh()
+    p0 = ts[0].clone()
+    done(lib.wunet_adam_step_ex(1, *(arr(t) for t in ts), numels, *hp, 1, 1.0, 0.0, 0.0, counter.data_ptr(), hyper.data_ptr(), None, None, stream), p0, ts)
+    h = hyper.cpu()
+    assert int(counter) == 5
+    assert (h[5:] == SENTINEL).all(), h
+    assert h[2] == 1.0 and h[3] == 0.0 and h[4] == 1.0 and h[0] != SENTINEL and h[1] != SENTINEL, h
+
+
 def distances(got, ref):
     """(norm: worst relative distance; exp_avg, exp_avg_sq: worst distance as a fraction of the tensor's largest reference value;
     params: worst absolute distance, and the bar STEPS * 2^-23 * max|p|)."""

@@ -1,8 +1,11 @@
 """-m "not gpu": the options of the fused Adam step on the CPU emulator - gradient clipping by the global norm
-(grad_sqnorm_partial_kernel + adam_hyper_ex_kernel), decoupled weight decay (FusedAdamW) and the lr read from device memory
-(adam_ex_kernel, csrc/wunet_elementwise.h behind wunet_adam_step_ex).  No reference counterpart (train.py:31-35 builds a plain
+(grad_sqnorm_partial_kernel + adam_hyper_kernel), decoupled weight decay (FusedAdamW) and the lr read from device memory
+(adam_kernel's optional slots, csrc/wunet_adam.h behind wunet_adam_step_ex).  No reference counterpart (train.py:31-35 builds a plain
 Adam): the yardstick is a float64 restatement of torch.nn.utils.clip_grad_norm_ + torch.optim.Adam / AdamW in torch's operation
-order (tests/adam_options_ref.py); torch's own fp32 pair is printed for information.
+order (tests/adam_options_ref.py); torch's own fp32 pair is printed for information.  wunet_adam_step and wunet_adam_step_ex run
+ONE pair of kernels: the "bits of the plain step" tests below hold the two entry points' paths through it against each other (host
+or one-thread hyper launch and a 2-float buffer against the one-block hyper launch and the optional slots); that the kernels kept
+the bits they had as two pairs is tools/emu_lib_ab.py's comparison with a library of the commit before (profiles/adam_unify_ab.txt).
 
 Measured on the emulator, 4 steps, max_grad_norm=5, lr changing every step (worst over FusedAdam and FusedAdamW; bar in brackets):
   mixed shapes (1 ... 256*1024+5 elements): norm 4.9e-8 [2.5e-7], exp_avg 1.0e-7 [1e-6], exp_avg_sq 2.3e-7 [2e-6],
@@ -71,7 +74,8 @@ def test_clipped_step_matches_the_float64_restatement(optim_mod, emu_engine, cas
 @pytest.mark.parametrize("device_step", [False, True], ids=["host_step", "device_step"])
 @pytest.mark.parametrize("case", ["mixed", "many"])
 def test_a_norm_that_never_clips_has_the_bits_of_the_plain_step(optim_mod, emu_engine, case, device_step):
-    """max_grad_norm=1e30: clip is exactly 1 and adam_ex_kernel must produce what adam_kernel produces - parameters and moments."""
+    """max_grad_norm=1e30: clip is exactly 1 and adam_kernel with its optional slots must produce what it produces without them -
+    parameters and moments."""
     plain = _run(optim_mod, emu_engine, case, max_grad_norm=None, device_step=device_step)
     never = _run(optim_mod, emu_engine, case, max_grad_norm=1e30, device_step=device_step)
     assert _equal(plain, never)
@@ -283,3 +287,9 @@ def test_adam_step_ex_refuses_bad_arguments(emu_engine):
     with pytest.raises(RuntimeError, match="hyper_dev"):
         emu_engine.adam_step([p], [g], [m], [v], 1e-3, 0.9, 0.999, 1e-8, 1, max_grad_norm=1.0)
     assert call(hyper.data_ptr()) == 0 and int(step) == 1               # all options off: the plain step through the _ex entry
+
+
+def test_each_entry_point_stays_inside_its_hyper_buffer(emu_engine):
+    """wunet_adam_step (2 floats, or no buffer at all) and wunet_adam_step_ex (8 floats) run the same two kernels: neither writes a
+    slot the other's buffer does not have (adam_options_ref.check_hyper_buffer_bounds)."""
+    R.check_hyper_buffer_bounds(emu_engine.lib)

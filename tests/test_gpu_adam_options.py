@@ -1,6 +1,6 @@
 """-m gpu: the options of the fused Adam step on the MI355X - gradient clipping by the global norm, decoupled weight decay
-(FusedAdamW) and the lr read from device memory (wunet_adam_step_ex: grad_sqnorm_partial_kernel, adam_hyper_ex_kernel,
-adam_ex_kernel).  No reference counterpart (train.py:31-35 builds a plain Adam, trainer/trainer.py:34-38 does not clip): the
+(FusedAdamW) and the lr read from device memory (wunet_adam_step_ex: grad_sqnorm_partial_kernel, then adam_hyper_kernel and
+adam_kernel with the optional slots of the hyper buffer - the kernels of wunet_adam_step).  No reference counterpart (train.py:31-35 builds a plain Adam, trainer/trainer.py:34-38 does not clip): the
 yardstick of the op tests is the float64 restatement of clip_grad_norm_ + Adam / AdamW of tests/adam_options_ref.py with the bars
 of the emulator tests (tests/test_adam_options_emu.py), the yardstick of the Trainer test is the written-out eager loop.
 """
@@ -51,6 +51,15 @@ def test_clipped_step_on_device_tensors(optim_mod, dev, case):
     R.check_against_reference(f"{case} grad_scale", scaled, case, False, grad_scale=0.25)
     R.check_against_reference(f"{case} prescaled", prescaled, case, False, grad_scale=0.25)
     assert scaled[3] == prescaled[3]
+
+
+def test_each_entry_point_stays_inside_its_hyper_buffer(pkg, dev):
+    """tests/test_adam_options_emu.py's test of the same name on the device: wunet_adam_step writes slots 0 and 1 of its hyper buffer
+    and nothing behind them, takes a NULL buffer without a device counter, and wunet_adam_step_ex with everything off writes the
+    neutral clip, norm and decay and nothing behind slot 4."""
+    eng = importlib.import_module(PKG_NAME + ".engine").default_engine()
+    with torch.cuda.device(dev):
+        R.check_hyper_buffer_bounds(eng.lib, dev, eng._stream(dev))
 
 
 def _make(pkg, dev, n, ci):

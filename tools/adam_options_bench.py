@@ -1,7 +1,8 @@
 """GPU box: what the options of the fused Adam step cost.  The captured training step at batch 64 x 16384 with
 FusedAdamW(max_grad_norm, device_lr, weight_decay) against the default FusedAdam, alternating three times, and the optimiser step
 alone (a graph of 10 steps, so launch gaps do not count): the difference is one read of the gradients by grad_sqnorm_partial_kernel
-plus the one-block adam_hyper_ex_kernel.   python tools/adam_options_bench.py"""
+plus adam_hyper_kernel as one block instead of one thread (the update kernel is the same one either way).
+python tools/adam_options_bench.py"""
 import importlib, sys, os, statistics
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -14,6 +14,7 @@ The auxiliary entry points (aux_cases: the losses forward and backward, the load
 tables) are compared the same way, array by array plus the profiler's text, and their refusals (refusals: one bad argument per call)
 by return value and wunet_last_error().  The 12 hex digits printed per auxiliary case are a hash of the new library's arrays: two
 checkouts of the Python side can be held against each other by the tool's output.  EMU_LIB_AB_AUX_ONLY=1 skips the network cases.
+The fused Adam step runs through both of its C entry points on the cases and refusals of tools/adam_lib_ab.py (compare_adam).
 Exit status 0: nothing differs."""
 import ctypes
 import hashlib
@@ -385,6 +386,27 @@ def compare_refusals(libs):
     return differing
 
 
+def compare_adam(libs):
+    """The fused Adam step through both C entry points (tools/adam_lib_ab.py: its cases, its refusals): parameters, both moments, the
+    hyper buffer and the step counter after 4 steps, array by array; the refusals by return value and message."""
+    import adam_lib_ab as AB
+    differing, table = 0, AB.adam_cases()
+    for label, *case in table:
+        a, b = (AB.run_adam(L, "cpu", *case) for L in libs)
+        bad = [k for k in a if not np.array_equal(a[k], b[k])]
+        print(f"{'DIFF' if bad else 'same'}  {label}  [{len(a)} arrays {AB.digest(b)}]", flush=True)
+        for k in bad:
+            print("      differs:", k)
+        differing += bool(bad)
+    ra, rb = (AB.adam_refusals(L) for L in libs)
+    bad = [(x, y) for x, y in zip(ra, rb) if x != y or y[2] == "NOT REFUSED"]
+    for x, y in bad:
+        print(f"DIFF  {x[0]}: base {x[1:]}  new {y[1:]}")
+    print(f"{len(table)} Adam cases, {len(rb)} refused Adam calls, {len(set(r[1:] for r in rb))} distinct (return value, message) pairs, "
+          f"{differing + len(bad)} differing")
+    return differing + len(bad)
+
+
 def main():
     if len(sys.argv) < 2:
         sys.exit(__doc__)
@@ -414,6 +436,7 @@ def main():
             print("      differs:", k)
         differing += bool(bad)
     differing += compare_refusals(libs)
+    differing += compare_adam(libs)
     for shape, h3, mode, mask_name, switches in table:
         a, b = (run_case(L, shape, h3, mode, mask_name, switches) for L in libs)
         bad = [k for k in a if k not in b or not np.array_equal(a[k], b[k])] + [k for k in b if k not in a]

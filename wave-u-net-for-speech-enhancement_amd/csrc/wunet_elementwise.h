@@ -1,9 +1,10 @@
 // Memory-bound kernels of the Wave-U-Net hot path: weight packing, BatchNorm statistics
 // finalisation (forward and backward), the output head, the gradient-assembly pass
 // ("pass A": upsample^T / zero-stuffed decimation^T / skip add + LeakyReLU' + BN-backward sums),
-// split-K reduction of weight gradients, and the losses.
+// split-K reduction of weight gradients, the first encoder conv and the conv input materialisation.
+// (The block reductions are wunet_reduce.h's; the optimiser, the losses and the loader's kernels have headers of their own.)
 #pragma once
-#include "wunet_dev.h"
+#include "wunet_reduce.h"
 
 // ---------------------------------------------------------------------------- weight packing
 // One descriptor per (layer, direction).  dst[mt][c][t][i] = W[o = mt*16+i][c][t] (forward) or the
@@ -40,67 +41,6 @@ static __global__ __launch_bounds__(WUNET_THREADS) void pack_weights_kernel(Pack
         }
         d.dst[idx] = v;
     }
-}
-
-// ---------------------------------------------------------------------------- block reduce helper
-// sums N doubles over the 256-thread block; result valid in every thread.  red = N * WUNET_WAVES doubles of LDS.
-// Butterfly inside each wave (no barrier), the four wave sums through LDS: two barriers instead of the nine of a 256-wide LDS tree -
-// these reductions end kernels that are a few microseconds of pure latency (BatchNorm finalizes, split-K sums).  Fixed order.
-template <int N>
-__device__ __forceinline__ void block_sum(double (&a)[N], double* red)
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) a[k] += wunet_shfl_xor_d(a[k], m);
-    }
-    __syncthreads();                           // (the previous user of red is done with it)
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) red[k * WUNET_WAVES + (tid >> 6)] = a[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k)
-        a[k] = (red[k * WUNET_WAVES] + red[k * WUNET_WAVES + 1]) + (red[k * WUNET_WAVES + 2] + red[k * WUNET_WAVES + 3]);
-}
-
-// the two sums of the network's own kernels (BatchNorm finalizes, split-K sums, the head's backward)
-__device__ __forceinline__ void block_sum2(double& a, double& b, double* red)
-{
-    double v[2] = {a, b};
-    block_sum<2>(v, red);
-    a = v[0]; b = v[1];
-}
-
-// Piece `piece` of row `row`, a row being `len` samples cut into pieces of `plen` (row_pieces in wunet_ops.cpp): samples [beg, end) of
-// the row, never empty.
-struct RowPiece { size_t row, piece, beg, end; };
-__device__ __forceinline__ RowPiece row_piece(size_t row, size_t piece, size_t plen, size_t len)
-{
-    const size_t beg = piece * plen;
-    return RowPiece{row, piece, beg, beg + plen < len ? beg + plen : len};
-}
-
-// max of two non-negative floats over the block (same LDS buffer, after a block_sum2); result valid in thread 0
-__device__ __forceinline__ void block_max2(float& a, float& b, double* red)
-{
-    float* fr = reinterpret_cast<float*>(red);
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        a = fmaxf(a, wunet_shfl_xor(a, m));
-        b = fmaxf(b, wunet_shfl_xor(b, m));
-    }
-    __syncthreads();
-    if ((tid & 63) == 0) {
-        fr[tid >> 6] = a;
-        fr[WUNET_WAVES + (tid >> 6)] = b;
-    }
-    __syncthreads();
-    a = fmaxf(fmaxf(fr[0], fr[1]), fmaxf(fr[2], fr[3]));
-    b = fmaxf(fmaxf(fr[WUNET_WAVES], fr[WUNET_WAVES + 1]), fmaxf(fr[WUNET_WAVES + 2], fr[WUNET_WAVES + 3]));
 }
 
 // ---------------------------------------------------------------------------- BN forward finalize
@@ -571,34 +511,6 @@ struct PassAArgs {
     const float* gamma; float* dgamma; float* dbeta; float* dbias; float* k1; float* k2; float* k3; double count;
     int frozen;          // FUSE: the layer's BatchNorm ran on the running statistics (BnBwdArgs::frozen)
 };
-
-// The pass's closing reduction: two sums (three in HEAD mode) and two maxima over the block behind ONE barrier - butterflies inside each wave, the four
-// waves' values through LDS, added in block_sum2's order (the same bits).  Rounds 1 - 6 ran block_sum2, block_max2 (and a second block_sum2
-// in HEAD mode) one after the other: four to seven barriers at the end of blocks that are only 4 - 8 loop trips long.  Sums valid in every thread,
-// maxima too.  red: 5 * WUNET_WAVES doubles.
-__device__ __forceinline__ void block_reduce_pass_a(double& s1, double& s2, double& s3, bool want3, float& mg, float& mz, double* red)
-{
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-        s1 += wunet_shfl_xor_d(s1, m);
-        s2 += wunet_shfl_xor_d(s2, m);
-        if (want3) s3 += wunet_shfl_xor_d(s3, m);
-        mg = fmaxf(mg, wunet_shfl_xor(mg, m));
-        mz = fmaxf(mz, wunet_shfl_xor(mz, m));
-    }
-    if ((tid & 63) == 0) {
-        const int w = tid >> 6;
-        red[w] = s1; red[WUNET_WAVES + w] = s2; red[2 * WUNET_WAVES + w] = s3;
-        red[3 * WUNET_WAVES + w] = (double)mg; red[4 * WUNET_WAVES + w] = (double)mz;        // (a float survives the round trip through a double)
-    }
-    __syncthreads();
-    s1 = (red[0] + red[1]) + (red[2] + red[3]);
-    s2 = (red[WUNET_WAVES] + red[WUNET_WAVES + 1]) + (red[WUNET_WAVES + 2] + red[WUNET_WAVES + 3]);
-    s3 = (red[2 * WUNET_WAVES] + red[2 * WUNET_WAVES + 1]) + (red[2 * WUNET_WAVES + 2] + red[2 * WUNET_WAVES + 3]);
-    mg = fmaxf(fmaxf((float)red[3 * WUNET_WAVES], (float)red[3 * WUNET_WAVES + 1]), fmaxf((float)red[3 * WUNET_WAVES + 2], (float)red[3 * WUNET_WAVES + 3]));
-    mz = fmaxf(fmaxf((float)red[4 * WUNET_WAVES], (float)red[4 * WUNET_WAVES + 1]), fmaxf((float)red[4 * WUNET_WAVES + 2], (float)red[4 * WUNET_WAVES + 3]));
-}
 
 // What one loop trip of pass A loads for its four samples (everything that comes from memory, nothing derived): two trips' loads are issued
 // before the first trip's values are used.
@@ -1160,277 +1072,5 @@ static __global__ __launch_bounds__(WUNET_THREADS) void gz_materialize_kernel(co
             o.w = 0.0f;
         }
         reinterpret_cast<float4*>(gz)[i] = o;
-    }
-}
-
-// ---------------------------------------------------------------------------- data input: aligned window crops (f4)
-// out[b][j] = flat[starts[b] + j] for the mixture and the clean array alike (the reference's sample_fixed_length_data_aligned,
-// util/utils.py:101-113, for a whole batch).  A window start is any sample, so the loads are dwords (64 consecutive per wave
-// instruction: coalesced, never 16-byte aligned in general); a thread gathers 4 consecutive samples and stores them as one
-// aligned float4 per array when the row length allows it.  HBM-bound: 16 B read + 16 B written per thread.
-static __global__ __launch_bounds__(WUNET_THREADS) void crop_windows_kernel(const float* mix_flat, const float* clean_flat, const long long* starts,
-                                                                            long long total, int length, float* mix, float* clean)
-{
-    const int b = blockIdx.y;
-    long long s0 = starts[b];
-    if (s0 < 0) s0 = 0;                                   // (a corrupt start must not read outside the shard)
-    if (s0 > total - length) s0 = total - length;
-    const int j0 = (blockIdx.x * WUNET_THREADS + threadIdx.x) * 4;
-    if (j0 >= length) return;
-    const float* ms = mix_flat + s0 + j0;
-    const float* cs = clean_flat + s0 + j0;
-    float* md = mix + (size_t)b * length + j0;
-    float* cd = clean + (size_t)b * length + j0;
-    if (j0 + 4 <= length && (length & 3) == 0) {
-        const wunet_f4 m = {ms[0], ms[1], ms[2], ms[3]};
-        const wunet_f4 c = {cs[0], cs[1], cs[2], cs[3]};
-        wunet_st4(md, m);
-        wunet_st4(cd, c);
-    } else {
-        for (int k = 0; k < 4 && j0 + k < length; ++k) { md[k] = ms[k]; cd[k] = cs[k]; }
-    }
-}
-
-static __global__ __launch_bounds__(WUNET_THREADS) void fill_kernel(float* p, size_t n, float v)
-{
-    for (size_t i = (size_t)blockIdx.x * WUNET_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * WUNET_THREADS) p[i] = v;
-}
-
-// ---------------------------------------------------------------------------- losses
-// loss(clean, enhanced) of trainer/trainer.py:36; kind 0 = MSELoss, 1 = L1Loss (model/loss.py:3-7),
-// 2 = SmoothL1Loss(beta=1).  mean reduction.
-__device__ __forceinline__ float loss_term(int kind, float d)
-{
-    if (kind == 0) return d * d;
-    const float ad = fabsf(d);
-    if (kind == 1) return ad;
-    return ad < 1.0f ? 0.5f * d * d : ad - 0.5f;
-}
-__device__ __forceinline__ float loss_dterm(int kind, float d)   // derivative w.r.t. d = enhanced - clean
-{
-    if (kind == 0) return 2.0f * d;
-    const float sg = (d > 0.0f ? 1.0f : 0.0f) - (d < 0.0f ? 1.0f : 0.0f);
-    if (kind == 1) return sg;
-    return fabsf(d) < 1.0f ? d : sg;
-}
-
-static __global__ __launch_bounds__(WUNET_THREADS) void loss_partial_kernel(int kind, const float* clean, const float* enh, size_t n, double* part)
-{
-    __shared__ double red[WUNET_WAVES];
-    double s[1] = {0.0};
-    // four trips' loads in flight (a thread's 16 trips at batch 64 x 16384 were 16 dependent memory round trips: 10.4 us for 8 MB); the terms are
-    // added in the one-trip loop's order - the same bits
-    const size_t stride = (size_t)gridDim.x * WUNET_THREADS;
-    size_t i = (size_t)blockIdx.x * WUNET_THREADS + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        float e[4], c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { e[u] = enh[i + u * stride]; c[u] = clean[i + u * stride]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) s[0] += (double)loss_term(kind, e[u] - c[u]);
-    }
-    for (; i < n; i += stride) s[0] += (double)loss_term(kind, enh[i] - clean[i]);
-    block_sum<1>(s, red);
-    if (threadIdx.x == 0) part[blockIdx.x] = s[0];
-}
-
-static __global__ __launch_bounds__(WUNET_THREADS) void loss_final_kernel(const double* part, int rows, size_t n, float* loss)
-{
-    __shared__ double red[WUNET_WAVES];
-    double s[1] = {0.0};
-    for (int r = threadIdx.x; r < rows; r += WUNET_THREADS) s[0] += part[r];
-    block_sum<1>(s, red);
-    if (threadIdx.x == 0) *loss = (float)(s[0] / (double)n);
-}
-
-// grad_enh[i] = gscale[0] * dterm(enh - clean) / n
-static __global__ __launch_bounds__(WUNET_THREADS) void loss_bwd_kernel(int kind, const float* clean, const float* enh, const float* gscale, size_t n, float* genh)
-{
-    const float sc = gscale[0] / (float)n;
-    const size_t stride = (size_t)gridDim.x * WUNET_THREADS;
-    size_t i = (size_t)blockIdx.x * WUNET_THREADS + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {             // (four trips' loads ahead of the first store)
-        float e[4], c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { e[u] = enh[i + u * stride]; c[u] = clean[i + u * stride]; }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) genh[i + u * stride] = sc * loss_dterm(kind, e[u] - c[u]);
-    }
-    for (; i < n; i += stride) genh[i] = sc * loss_dterm(kind, enh[i] - clean[i]);
-}
-
-// ---------------------------------------------------------------------------- fused Adam
-// torch.optim.Adam(lr, betas, eps=1e-8, weight_decay=0, amsgrad=False) as the reference builds it
-// (train.py:31-35), for up to WUNET_ADAM_MAX tensors per launch: blockIdx.y = tensor, blockIdx.x strides inside it.
-// Same operation order as torch's single-tensor path: m.lerp_(g, 1-b1); v = v*b2 + (1-b2)*g*g;
-// denom = sqrt(v)/sqrt(1-b2^t) + eps; p -= (lr/(1-b1^t)) * m/denom.
-#define WUNET_ADAM_MAX 64
-struct AdamTable {
-    float* p[WUNET_ADAM_MAX];
-    const float* g[WUNET_ADAM_MAX];
-    float* m[WUNET_ADAM_MAX];
-    float* v[WUNET_ADAM_MAX];
-    unsigned n[WUNET_ADAM_MAX];
-};
-
-// gscale: the gradient is multiplied by it first (1/world_size of the data-parallel average folded into the step: the same
-// rounding as a separate g.mul_(1/world) pass).  hyper != nullptr: {step_size, bc2_sqrt} come from device memory
-// (adam_hyper_kernel: the step counter lives on the device, so a captured graph replays the right bias corrections).
-static __global__ __launch_bounds__(WUNET_THREADS) void adam_kernel(AdamTable T, float one_minus_b1, float b2, float one_minus_b2,
-                                                              float bc2_sqrt, float eps, float step_size, float gscale,
-                                                              const float* hyper)
-{
-    if (hyper) { step_size = hyper[0]; bc2_sqrt = hyper[1]; }
-    const int t = blockIdx.y;
-    float* p = T.p[t];
-    const float* g = T.g[t];
-    float* m = T.m[t];
-    float* v = T.v[t];
-    const unsigned n = T.n[t];
-    for (unsigned i = blockIdx.x * WUNET_THREADS + threadIdx.x; i < n; i += gridDim.x * WUNET_THREADS) {
-        const float gi = gscale == 1.0f ? g[i] : g[i] * gscale;
-        float mi = m[i], vi = v[i];
-        mi = mi + one_minus_b1 * (gi - mi);
-        vi = vi * b2 + one_minus_b2 * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = p[i] - step_size * (mi / denom);
-    }
-}
-
-// step counter on the device: *step += 1, then the bias-corrected step size lr / (1 - b1^t) and sqrt(1 - b2^t) in double like
-// torch's host arithmetic (one thread)
-static __global__ void adam_hyper_kernel(long long* step, double lr, double beta1, double beta2, float* hyper)
-{
-    const long long t = *step + 1;
-    *step = t;
-    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
-    hyper[0] = (float)(lr / bc1);
-    hyper[1] = (float)sqrt(bc2);
-}
-
-// ---------------------------------------------------------------------------- fused Adam, the optional parts (wunet_adam_step_ex)
-// Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_), decoupled weight decay (torch.optim.AdamW) and an lr read from
-// device memory: per-step scalars that live in the hyper buffer next to {step_size, bc2_sqrt}, so a captured step replays unchanged
-// under an lr schedule.  Slots of the hyper buffer (WUNET_ADAM_HYPER_FLOATS of include/wunet_hip.h):
-#define WUNET_HYPER_STEP_SIZE 0
-#define WUNET_HYPER_BC2_SQRT 1
-#define WUNET_HYPER_CLIP 2        // min(1, max_norm / (norm + 1e-6)); 1 when clipping is off
-#define WUNET_HYPER_NORM 3        // the norm of the scaled gradient before clipping; 0 when clipping is off
-#define WUNET_HYPER_DECAY 4       // 1 - lr * weight_decay
-
-// Sum of (gscale * g)^2 per block, in double.  Grid as for adam_kernel (blockIdx.y = tensor, blockIdx.x strides inside it); block
-// (x, y) writes part[y * gridDim.x + x] - also when it had no element (0): the slots need no memset and adam_hyper_ex_kernel adds
-// every one of them.  Four trips' loads are in flight ahead of the first use (loss_partial_kernel); the terms are added in the
-// one-trip loop's order.
-static __global__ __launch_bounds__(WUNET_THREADS) void grad_sqnorm_partial_kernel(AdamTable T, float gscale, double* part)
-{
-    __shared__ double red[WUNET_WAVES];
-    const int t = blockIdx.y;
-    const float* g = T.g[t];
-    const unsigned n = T.n[t];
-    const double gs = (double)gscale;
-    double s[1] = {0.0};
-    const size_t stride = (size_t)gridDim.x * WUNET_THREADS;
-    size_t i = (size_t)blockIdx.x * WUNET_THREADS + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        float e[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) e[u] = g[i + u * stride];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { const double x = gs * (double)e[u]; s[0] += x * x; }
-    }
-    for (; i < n; i += stride) { const double x = gs * (double)g[i]; s[0] += x * x; }
-    block_sum<1>(s, red);
-    if (threadIdx.x == 0) part[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s[0];
-}
-
-// adam_hyper_kernel with the optional parts, one block.  n_part > 0: the n_part partial sums of grad_sqnorm_partial_kernel are
-// added in a fixed order in double (thread k takes k, k + 256, ...; then block_sum's tree), norm = sqrt(sum) and
-// clip = min(1, max_norm / (norm + 1e-6)) - clip_grad_norm_'s formula, in double, rounded to float once; a non-finite norm
-// propagates as in torch (error_if_nonfinite=False): inf gives clip 0, NaN gives NaN.  lr_dev != nullptr: the learning rate is
-// read from device memory (a double: lr / bc1 then has the bits of the host path).  step_dev != nullptr: the device counter is
-// incremented and used, otherwise `step` is the host's count.
-static __global__ __launch_bounds__(WUNET_THREADS) void adam_hyper_ex_kernel(long long* step_dev, long long step, double lr, const double* lr_dev,
-                                                                       double beta1, double beta2, double weight_decay, double max_norm,
-                                                                       const double* part, int n_part, float* hyper)
-{
-    __shared__ double red[WUNET_WAVES];
-    double s[1] = {0.0};
-    int r = threadIdx.x;
-    for (; r + 3 * WUNET_THREADS < n_part; r += 4 * WUNET_THREADS) {
-        double e[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) e[u] = part[r + u * WUNET_THREADS];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) s[0] += e[u];
-    }
-    for (; r < n_part; r += WUNET_THREADS) s[0] += part[r];
-    block_sum<1>(s, red);
-    if (threadIdx.x != 0) return;
-    long long t = step;
-    if (step_dev) {
-        t = *step_dev + 1;
-        *step_dev = t;
-    }
-    if (lr_dev) lr = *lr_dev;
-    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
-    double norm = 0.0, clip = 1.0;
-    if (n_part > 0) {
-        norm = sqrt(s[0]);
-        const double c = max_norm / (norm + 1e-6);
-        clip = c > 1.0 ? 1.0 : c;                   // (a NaN stays: torch.clamp(max=1) keeps it too)
-    }
-    hyper[WUNET_HYPER_STEP_SIZE] = (float)(lr / bc1);
-    hyper[WUNET_HYPER_BC2_SQRT] = (float)sqrt(bc2);
-    hyper[WUNET_HYPER_CLIP] = (float)clip;
-    hyper[WUNET_HYPER_NORM] = (float)norm;
-    hyper[WUNET_HYPER_DECAY] = (float)(1.0 - lr * weight_decay);
-}
-
-// The roundings of adam_kernel AS hipcc COMPILES IT for gfx950, written out so that adam_ex_kernel with neutral options (clip 1, decay 1)
-// gives adam_kernel's bits whatever the optimiser decides here: under the default -ffp-contract=fast adam_kernel's two moment lines come
-// out as separate multiplies and adds (v_pk_mul_f32 / v_pk_add_f32: every product rounded) and only its last line, p - step_size * q,
-// as ONE v_fma_f32.  adam_ex_kernel therefore pins contraction off and asks for that one fma by name; the emulator build
-// (-ffp-contract=off) rounds that product in adam_kernel too.  tests/test_gpu_adam_options.py compares the two kernels bit for bit.
-__device__ __forceinline__ float adam_update(float p, float step_size, float q)
-{
-#ifdef WUNET_EMU
-    return p - step_size * q;
-#else
-    return __builtin_fmaf(-step_size, q, p);
-#endif
-}
-
-// adam_kernel with the optional parts; everything per-step comes from the hyper buffer.  gi = g * (gscale * clip), no multiply when
-// the factor is exactly 1; p <- p * decay first when decay != 1 (torch.optim.AdamW's order: the decayed parameter is rounded to
-// float before the update is subtracted, never fused into it); then adam_kernel's moment and update lines.  The gradient itself is NOT modified
-// (clip_grad_norm_ scales it in place; the fused step does not pay that write).
-static __global__ __launch_bounds__(WUNET_THREADS) void adam_ex_kernel(AdamTable T, float one_minus_b1, float b2, float one_minus_b2,
-                                                                 float eps, float gscale, const float* hyper)
-{
-    const float step_size = hyper[WUNET_HYPER_STEP_SIZE], bc2_sqrt = hyper[WUNET_HYPER_BC2_SQRT];
-    const float factor = gscale * hyper[WUNET_HYPER_CLIP], decay = hyper[WUNET_HYPER_DECAY];
-    const int t = blockIdx.y;
-    float* p = T.p[t];
-    const float* g = T.g[t];
-    float* m = T.m[t];
-    float* v = T.v[t];
-    const unsigned n = T.n[t];
-    for (unsigned i = blockIdx.x * WUNET_THREADS + threadIdx.x; i < n; i += gridDim.x * WUNET_THREADS) {
-#ifdef __clang__
-#pragma clang fp contract(off)
-#endif
-        const float gi = factor == 1.0f ? g[i] : g[i] * factor;
-        float mi = m[i], vi = v[i];
-        mi = mi + one_minus_b1 * (gi - mi);
-        vi = vi * b2 + one_minus_b2 * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        float pi = p[i];
-        if (decay != 1.0f) pi = pi * decay;
-        p[i] = adam_update(pi, step_size, mi / denom);
     }
 }

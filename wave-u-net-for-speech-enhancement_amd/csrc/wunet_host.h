@@ -5,7 +5,12 @@
 //   wunet_launchers.cpp argument blocks + launches of the GEMM kernels, weight packs, side stream
 //   wunet_forward.cpp   wunet_forward
 //   wunet_backward.cpp  wunet_backward[_range[_async]], wunet_backward_join
-//   wunet_ops.cpp       loss, fused Adam, window crops, profiler read-out, single-op entry points (tests / tools)
+//   wunet_ops.cpp       every other entry point: the losses and metrics (wunet_loss_mean.h, wunet_loss_rows.h, wunet_stft.h, wunet_cspec.h,
+//                       wunet_stoi.h, wunet_estoi.h), fused Adam (wunet_adam.h: one kernel pair and one enqueue behind both entries), the
+//                       loader ops (wunet_mix.h with the window crops, wunet_reverb.h, wunet_chunks.h, wunet_resample.h), profiler read-out,
+//                       single-op entry points (tests / tools)
+// Device code the translation units share: wunet_dev.h (vocabulary), wunet_reduce.h (block reductions), wunet_elementwise.h /
+// wunet_h3_elem.h / wunet_tiny.h (the network's memory-bound kernels), wunet_kernels.h / wunet_h3*.h (the GEMMs), wunet_lds.h.
 #pragma once
 #include <cstdarg>
 #include <cmath>

@@ -1,5 +1,5 @@
 // Row-structured losses: scale-invariant SDR and SNR per utterance (include/wunet_hip.h: wunet_loss_rows_*).  The three element-wise
-// means of wunet_elementwise.h treat the batch as one flat array; these reduce every row (the last dimension, T samples) on its own.
+// means of wunet_loss_mean.h treat the batch as one flat array; these reduce every row (the last dimension, T samples) on its own.
 //   loss_rows_partial_kernel   one pass over the pair: a block reduces one piece of one row to five raw sums, in double
 //   loss_rows_final_kernel     the pieces of each row in piece order -> centred moments -> v [dB] and the gradient coefficients; the loss
 //   loss_rows_bwd_kernel       g[i] = -grad_loss / R * (A_r e[i] + C_r s[i] + D_r), applied in its centred form, streaming
@@ -7,7 +7,8 @@
 // of it, which fp32 sums do not survive ("Row losses").  A float x float product is exact in double, so the raw sums carry
 // only the rounding of their additions.  No atomics anywhere: every sum has one fixed order, results are bit-identical run to run.
 #pragma once
-#include "wunet_elementwise.h"
+#include "wunet_reduce.h"
+#include "wunet_row_piece.h"
 
 #define WUNET_ROWS_SUMS 5            // per piece: sum s, sum x, sum s^2, sum x^2, sum x s   (x = e for si_sdr, e - s for snr)
 #define WUNET_ROWS_KIND_SNR 4        // == WUNET_LOSS_SNR

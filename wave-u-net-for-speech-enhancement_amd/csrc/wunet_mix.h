@@ -1,4 +1,6 @@
-// Data input, on-the-fly mixing (include/wunet_hip.h: wunet_mix_windows): a batch of clean windows and a batch of noise windows gathered
+// Data input.  Aligned crops (include/wunet_hip.h: wunet_crop_windows):
+//   crop_windows_kernel  the (mixture, clean) windows of a batch out of two flat arrays, one launch
+// On-the-fly mixing (wunet_mix_windows): a batch of clean windows and a batch of noise windows gathered
 // from two flat float32 arrays resident in HBM, mixed at a per-row SNR and level that the host drew.
 //   mix_partial_kernel   one pass over both windows: a block reduces one piece of one row to sum c^2, sum n^2 (double), max|c|, max|n|
 //   mix_apply_kernel     every block folds its row's partials in piece order -> g, a (double, rounded once to float32), then
@@ -11,8 +13,38 @@
 // so the loads are dwords (crop_windows_kernel's reasoning); a thread owns 4 consecutive samples and stores one float4 per output when
 // the row length allows it.
 #pragma once
-#include "wunet_elementwise.h"
+#include "wunet_reduce.h"
+#include "wunet_row_piece.h"
 
+// ---------------------------------------------------------------------------- data input: aligned window crops (f4)
+// out[b][j] = flat[starts[b] + j] for the mixture and the clean array alike (the reference's sample_fixed_length_data_aligned,
+// util/utils.py:101-113, for a whole batch).  A window start is any sample, so the loads are dwords (64 consecutive per wave
+// instruction: coalesced, never 16-byte aligned in general); a thread gathers 4 consecutive samples and stores them as one
+// aligned float4 per array when the row length allows it.  HBM-bound: 16 B read + 16 B written per thread.
+static __global__ __launch_bounds__(WUNET_THREADS) void crop_windows_kernel(const float* mix_flat, const float* clean_flat, const long long* starts,
+                                                                            long long total, int length, float* mix, float* clean)
+{
+    const int b = blockIdx.y;
+    long long s0 = starts[b];
+    if (s0 < 0) s0 = 0;                                   // (a corrupt start must not read outside the shard)
+    if (s0 > total - length) s0 = total - length;
+    const int j0 = (blockIdx.x * WUNET_THREADS + threadIdx.x) * 4;
+    if (j0 >= length) return;
+    const float* ms = mix_flat + s0 + j0;
+    const float* cs = clean_flat + s0 + j0;
+    float* md = mix + (size_t)b * length + j0;
+    float* cd = clean + (size_t)b * length + j0;
+    if (j0 + 4 <= length && (length & 3) == 0) {
+        const wunet_f4 m = {ms[0], ms[1], ms[2], ms[3]};
+        const wunet_f4 c = {cs[0], cs[1], cs[2], cs[3]};
+        wunet_st4(md, m);
+        wunet_st4(cd, c);
+    } else {
+        for (int k = 0; k < 4 && j0 + k < length; ++k) { md[k] = ms[k]; cd[k] = cs[k]; }
+    }
+}
+
+// ---------------------------------------------------------------------------- mixtures made on the device
 #define WUNET_MIX_PART 4             // per piece: sum c^2, sum n^2, max|c|, max|n| (all kept as double)
 #define WUNET_MIX_SILENT 1e-12       // mean square below which a window counts as silent (RMS 1e-6)
 

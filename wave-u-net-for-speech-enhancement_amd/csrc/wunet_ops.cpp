@@ -3,6 +3,8 @@
 #include "wunet_host.h"
 #include "wunet_elementwise.h"
 #include "wunet_h3_elem.h"
+#include "wunet_adam.h"
+#include "wunet_loss_mean.h"
 #include "wunet_loss_rows.h"
 #include "wunet_stft.h"
 #include "wunet_cspec.h"
@@ -14,6 +16,12 @@
 #include "wunet_resample.h"
 
 using namespace wunet_host;
+
+// the ones and zeros that stand in for BatchNorm's scale and shift in the single-op entry points (op_conv_split_common, op_wgrad_split_common)
+static __global__ __launch_bounds__(WUNET_THREADS) void fill_kernel(float* p, size_t n, float v)
+{
+    for (size_t i = (size_t)blockIdx.x * WUNET_THREADS + threadIdx.x; i < n; i += (size_t)gridDim.x * WUNET_THREADS) p[i] = v;
+}
 
 extern "C" {
 
@@ -43,7 +51,7 @@ int wunet_loss_backward(int kind, const float* clean, const float* enhanced, con
 // ---------------------------------------------------------------------------- the (row, piece) grids of the row losses and the mixer
 // Pieces per row and samples per piece for `rows` rows of `len` samples: about want_blocks blocks in all, so one long row still fills
 // the device, but never less than min_piece samples per block - many rows get one piece each.  plen is a multiple of 4 (every piece of
-// an aligned row starts aligned) and ppr is recomputed from it: no piece is empty (row_piece in wunet_elementwise.h).
+// an aligned row starts aligned) and ppr is recomputed from it: no piece is empty (row_piece in wunet_row_piece.h).
 static void row_pieces(size_t rows, size_t len, size_t want_blocks, size_t min_piece, size_t& ppr, size_t& plen)
 {
     size_t want = (want_blocks + rows - 1) / rows;
@@ -727,6 +735,49 @@ static void adam_launch_at(int n_tensors, int base, float* const* params, const 
     if (L.bx < 1) L.bx = 1;
 }
 
+// What wunet_adam_step_ex has and wunet_adam_step has not.  on: the _ex entry - an 8-float hyper buffer, always filled by a hyper launch of
+// one whole block; clip: the norm launches run, their partial sums in `scratch`.
+struct AdamOptional {
+    bool on = false, clip = false;
+    double weight_decay = 0.0, max_grad_norm = 0.0;
+    const double* lr_dev = nullptr;
+    void* scratch = nullptr;
+};
+
+// The launches of one step, in order: the norm's (they write their partial sums one behind the other), the hyper launch, the updates.
+// The plain entry without a device counter has no hyper launch: its two scalars come from the host's pow and travel as kernel
+// arguments.  With one it launches ONE thread (no partial sums: no barrier) and the kernels stay inside its 2-float buffer.
+static int adam_enqueue(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                        const size_t* numels, double lr, double beta1, double beta2, double eps, long long step, double grad_scale,
+                        long long* step_dev, float* hyper_dev, const AdamOptional& O, hipStream_t st)
+{
+    AdamLaunch L;
+    int n_part = 0;
+    for (int base = 0; O.clip && base < n_tensors; base += WUNET_ADAM_MAX) {
+        adam_launch_at(n_tensors, base, params, grads, exp_avg, exp_avg_sq, numels, L);
+        WUNET_LAUNCH(grad_sqnorm_partial_kernel, dim3(L.bx, L.cnt), dim3(WUNET_THREADS), 0, st, L.T, (float)grad_scale, (double*)O.scratch + n_part);
+        WUNET_CHECK_LAUNCH();
+        n_part += (int)L.bx * L.cnt;
+    }
+    const bool on_device = O.on || step_dev;          // who computes step_size and bc2_sqrt
+    float step_size = 0.0f, bc2_sqrt = 1.0f;
+    if (on_device) {
+        WUNET_LAUNCH(adam_hyper_kernel, dim3(1), dim3(O.on ? WUNET_THREADS : 1), 0, st, step_dev, step, lr, O.lr_dev, beta1, beta2, O.weight_decay,
+                     O.max_grad_norm, (const double*)O.scratch, n_part, hyper_dev, O.on);
+        WUNET_CHECK_LAUNCH();
+    } else {
+        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+        step_size = (float)(lr / bc1); bc2_sqrt = (float)sqrt(bc2);
+    }
+    for (int base = 0; base < n_tensors; base += WUNET_ADAM_MAX) {
+        adam_launch_at(n_tensors, base, params, grads, exp_avg, exp_avg_sq, numels, L);
+        WUNET_LAUNCH(adam_kernel, dim3(L.bx, L.cnt), dim3(WUNET_THREADS), 0, st, L.T, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                     bc2_sqrt, (float)eps, step_size, (float)grad_scale, (const float*)(on_device ? hyper_dev : nullptr), O.on);
+        WUNET_CHECK_LAUNCH();
+    }
+    return WUNET_OK;
+}
+
 int wunet_adam_step(int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
                     float* const* exp_avg_sq, const size_t* numels, double lr, double beta1, double beta2, double eps,
                     long long step, double grad_scale, long long* step_dev, float* hyper_dev, void* stream)
@@ -736,23 +787,8 @@ int wunet_adam_step(int n_tensors, float* const* params, const float* const* gra
     if (step_dev && !hyper_dev) return fail(WUNET_E_ARG, "a device step counter needs the 2-float hyper buffer");
     for (int k = 0; k < n_tensors; ++k)          // (before anything is enqueued: a refused call leaves the device counter alone)
         if (numels[k] >= (1ull << 32)) return fail(WUNET_E_ARG, "tensor too large");
-    hipStream_t st = (hipStream_t)stream;
-    float step_size = 0.0f, bc2_sqrt = 1.0f;
-    if (step_dev) {
-        WUNET_LAUNCH(adam_hyper_kernel, dim3(1), dim3(1), 0, st, step_dev, lr, beta1, beta2, hyper_dev);
-        WUNET_CHECK_LAUNCH();
-    } else {
-        const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
-        step_size = (float)(lr / bc1); bc2_sqrt = (float)sqrt(bc2);
-    }
-    AdamLaunch L;
-    for (int base = 0; base < n_tensors; base += WUNET_ADAM_MAX) {
-        adam_launch_at(n_tensors, base, params, grads, exp_avg, exp_avg_sq, numels, L);
-        WUNET_LAUNCH(adam_kernel, dim3(L.bx, L.cnt), dim3(WUNET_THREADS), 0, st, L.T, (float)(1.0 - beta1), (float)beta2,
-                     (float)(1.0 - beta2), bc2_sqrt, (float)eps, step_size, (float)grad_scale, (const float*)(step_dev ? hyper_dev : nullptr));
-        WUNET_CHECK_LAUNCH();
-    }
-    return WUNET_OK;
+    return adam_enqueue(n_tensors, params, grads, exp_avg, exp_avg_sq, numels, lr, beta1, beta2, eps, step, grad_scale, step_dev, hyper_dev,
+                        AdamOptional{}, (hipStream_t)stream);
 }
 
 // one double per block of the norm's launches: at most 256 blocks per tensor
@@ -772,26 +808,8 @@ int wunet_adam_step_ex(int n_tensors, float* const* params, const float* const* 
     if (clip && !scratch) return fail(WUNET_E_ARG, "max_grad_norm > 0 needs wunet_adam_scratch_bytes(n_tensors) bytes of scratch");
     for (int k = 0; k < n_tensors; ++k)          // (before anything is enqueued: a refused call leaves the device counter alone)
         if (numels[k] >= (1ull << 32)) return fail(WUNET_E_ARG, "tensor too large");
-    hipStream_t st = (hipStream_t)stream;
-    AdamLaunch L;
-    // the norm first: the launches of the step write their partial sums one behind the other
-    int n_part = 0;
-    for (int base = 0; clip && base < n_tensors; base += WUNET_ADAM_MAX) {
-        adam_launch_at(n_tensors, base, params, grads, exp_avg, exp_avg_sq, numels, L);
-        WUNET_LAUNCH(grad_sqnorm_partial_kernel, dim3(L.bx, L.cnt), dim3(WUNET_THREADS), 0, st, L.T, (float)grad_scale, (double*)scratch + n_part);
-        WUNET_CHECK_LAUNCH();
-        n_part += (int)L.bx * L.cnt;
-    }
-    WUNET_LAUNCH(adam_hyper_ex_kernel, dim3(1), dim3(WUNET_THREADS), 0, st, step_dev, step, lr, lr_dev, beta1, beta2, weight_decay, max_grad_norm,
-                 (const double*)scratch, n_part, hyper_dev);
-    WUNET_CHECK_LAUNCH();
-    for (int base = 0; base < n_tensors; base += WUNET_ADAM_MAX) {
-        adam_launch_at(n_tensors, base, params, grads, exp_avg, exp_avg_sq, numels, L);
-        WUNET_LAUNCH(adam_ex_kernel, dim3(L.bx, L.cnt), dim3(WUNET_THREADS), 0, st, L.T, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
-                     (float)eps, (float)grad_scale, (const float*)hyper_dev);
-        WUNET_CHECK_LAUNCH();
-    }
-    return WUNET_OK;
+    return adam_enqueue(n_tensors, params, grads, exp_avg, exp_avg_sq, numels, lr, beta1, beta2, eps, step, grad_scale, step_dev, hyper_dev,
+                        AdamOptional{true, clip, weight_decay, max_grad_norm, lr_dev, scratch}, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------- profiler

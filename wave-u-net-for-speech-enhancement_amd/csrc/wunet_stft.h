@@ -11,7 +11,7 @@
 //   stft_ola_kernel     overlap-add as a gather: every sample sums its frames' contributions in frame order, the reflected ones too
 // fp32 operands and accumulation, every reduction and coefficient in double, no atomics: bit-identical run to run.
 #pragma once
-#include "wunet_elementwise.h"
+#include "wunet_reduce.h"
 
 #define WUNET_STFT_FM 64             // frames per block (one 16-row MFMA tile per wave)
 #define WUNET_STFT_BN 32             // forward: bins per block (two 16-column tiles, cos and -sin each)

@@ -707,7 +707,8 @@ class Engine:
                   weight_decay=0.0, max_grad_norm=None, lr_dev=None, scratch=None):
         """One fused Adam step over a list of tensors.  step_dev (int64 device scalar) + hyper_dev (2 floats):
         the step count lives on the device and the call increments it (capturable in a hipGraph); otherwise `step` is the host's.
-        Keyword arguments (include/wunet_hip.h: wunet_adam_step_ex; with all of them off the call is wunet_adam_step as before):
+        Keyword arguments (include/wunet_hip.h: wunet_adam_step_ex - the kernels of wunet_adam_step with an 8-float hyper buffer; with
+        all of them off the call is wunet_adam_step, whose hyper buffer has 2 floats or is None):
         weight_decay - decoupled (AdamW); max_grad_norm - clipping by the global norm inside the step, `scratch` then holds
         adam_scratch_bytes(len(params)) bytes (p.grad is NOT modified); lr_dev - a float64 device scalar the learning rate is read from.
         Any of them needs hyper_dev with ADAM_HYPER_FLOATS floats: [2] clip, [3] the norm before clipping, [4] 1 - lr * weight_decay."""

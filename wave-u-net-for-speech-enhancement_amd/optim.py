@@ -13,7 +13,8 @@ launches over all 102 tensors instead of ~10 multi-tensor ATen kernels.
 in double), so forward + loss + backward + step can be captured in one hipGraph and replayed (trainer.Trainer(graph=True));
 the host-side `state["step"]` is kept in step by `advance_host_step()` after every replay.
 
-Opt-in, no reference counterpart (with all of them off the step enqueues exactly the launches above):
+Opt-in, no reference counterpart (with all of them off the step enqueues exactly the launches above; with any of them on, the same
+two kernels - adam_hyper_kernel, adam_kernel of csrc/wunet_adam.h - with the optional slots of the hyper buffer in use):
 `max_grad_norm=<float>`: clipping by the global 2-norm inside the step, the arithmetic of
 `torch.nn.utils.clip_grad_norm_(params, max_grad_norm)` in front of `step()` - one extra read of the gradients (summed in double),
 the factor min(1, max_grad_norm / (norm + 1e-6)) multiplies every gradient inside the update.  `p.grad` is NOT modified
