@@ -498,6 +498,39 @@ int wunet_resample_rows(const float* in, long long in_total,
                         float* out, long long out_total, void* stream);
 long long wunet_resample_tile(int up, int down, int n_taps);
 
+/* Cascades of second-order IIR sections over a batch of windows (no reference counterpart in code: a reference user filters on the host
+ * with scipy.signal.sosfilt; csrc/wunet_sos.h): equalisers, DC blockers, pre-emphasis, band limits - everything recursive, which the FIR
+ * kernels above cannot express.  One launch, one block per row.
+ * Source of row b, rows[b] = (window start ws, item start is, circular length nl, phase ph), all in samples of `flat`:
+ *   linear   (nl <= 0)  x[j] = flat[ws + j] where ws + j >= is, and 0 in front of the item.  ws is clamped into [0, total - length] and
+ *                       is into [0, ws]; nl and ph are ignored.
+ *   circular (nl >= 1)  x[j] = flat[is + ((ph + j) mod nl)], the non-negative modulo (j < 0 wraps backwards).  The item [is, is + nl) is
+ *                       cut to its part inside [0, total) and ph reduced modulo what is left, as the mix entry does with a noise item; if
+ *                       nothing is left the output row is zeros.  ws is ignored.
+ * Lead-in: the filter starts from rest at j = -lead_b and the outputs at j < 0 are dropped, so a window cut out of the middle of a
+ *   recording carries no start-up transient.  lead_b = min(lead, ws - is) for a linear row (never in front of the item), lead for a
+ *   circular one.
+ * Filter: `sections` sections in cascade, coefs[b][s] = (b0, b1, b2, a1, a2) with a0 = 1, each the transposed direct form II recurrence
+ *   of scipy.signal.sosfilt:  o = b0 v + s0;  s0 = b1 v - a1 o + s1;  s1 = b2 v - a2 o.  The float32 coefficients are taken as exact
+ *   values; all state and arithmetic are double; each output is rounded to float32 once.  out[b][0][j] for 0 <= j < length.
+ *   The kernel runs the recurrence in parallel along the row, in chunks whose entry states come from a scan with the chunk's exact
+ *   transition matrix; the result differs from the sequential double recurrence by double rounding only (tests/sos_cases.py).
+ * Nothing outside `flat` or `out` is ever addressed, whatever the tables hold; loads are masked, not multiplied by zero.  A row whose
+ * coefficients are non-finite or unstable yields an unspecified row of its own and leaves every other row's bits alone.
+ * rows: device int64, coefs: device float32; everything ragged is read from device memory, so a captured call follows its tables.  No
+ * atomics: bit-identical run to run.  Caller-owned memory, no allocation, no synchronisation, no alignment required.
+ * -1 with the error text for: a null pointer; batch or length < 1; batch > 65535; length > 2^24; sections outside
+ * [1, WUNET_SOS_MAX_SECTIONS]; lead outside [0, WUNET_SOS_MAX_LEAD]; total < length.
+ * wunet_sos_tile: tile * 65536 + chunk for that count of sections - `tile` the samples (lead-in included) a block owns per trip, `chunk`
+ *   (the low 16 bits) the consecutive samples one thread owns: what the tests put row lengths next to; 0 for a refused count. */
+#define WUNET_SOS_MAX_SECTIONS 8
+#define WUNET_SOS_MAX_LEAD 8192
+int wunet_sos_windows(const float* flat, long long total,
+                      const long long* rows /* [batch][4]: window start, item start, circular length, phase */,
+                      const float* coefs /* [batch][sections][5]: b0 b1 b2 a1 a2 */,
+                      int sections, int lead, int batch, int length, float* out /* [batch][1][length] */, void* stream);
+long long wunet_sos_tile(int sections);
+
 /* Measurement aid (tools/conv_trace.py; no reference counterpart): a device buffer of gridDim.x * 64 uint64 that the DMA-staged
  * conv / data-gradient kernel (conv_h3d_kernel) fills with shader-clock stamps of each block's phases (entry; per K stage: tile
  * landed, W buffer released, MFMAs issued; epilogue done), or NULL (default) to turn the stamps off.  Process-wide. */

@@ -30,6 +30,7 @@ EXPORTS = [
     "wunet_estoi_loss_scratch_bytes", "wunet_estoi_loss_saved_bytes", "wunet_estoi_loss_forward", "wunet_estoi_loss_backward",
     "wunet_mix_scratch_bytes", "wunet_mix_windows", "wunet_apply_level", "wunet_reverb_windows",
     "wunet_chunk_gather", "wunet_chunk_overlap_add", "wunet_resample_rows", "wunet_resample_tile",
+    "wunet_sos_windows", "wunet_sos_tile",
 ]
 
 _vp = ctypes.c_void_p
@@ -140,6 +141,11 @@ def declare(lib):
         lib.wunet_resample_rows.argtypes = [_vp, _ll, _vp, _ll, _ll, _i, _i, _vp, _i, _vp, _ll, _vp]
         lib.wunet_resample_tile.argtypes = [_i, _i, _i]
         lib.wunet_resample_tile.restype = _ll
+    if hasattr(lib, "wunet_sos_windows"):        # (the same)
+        _ll = ctypes.c_longlong
+        lib.wunet_sos_windows.argtypes = [_vp, _ll, _vp, _vp, _i, _i, _i, _i, _vp, _vp]
+        lib.wunet_sos_tile.argtypes = [_i]
+        lib.wunet_sos_tile.restype = _ll
     lib.wunet_comm_unique_id.argtypes = [_vp]
     lib.wunet_comm_create.argtypes = [_vp, _i, _i, ctypes.POINTER(_vp)]
     lib.wunet_comm_allreduce_sum.argtypes = [_vp, _vp, _sz, _vp]

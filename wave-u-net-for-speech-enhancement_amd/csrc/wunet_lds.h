@@ -139,4 +139,24 @@ constexpr Resample resample(int up, int down, int ntaps)
     return {g, ng, tile, (int)resample_span(tile, up, down, ntaps), ntaps};
 }
 
+// ---- sos_windows_kernel<S>, doubles first:  es [chunks + 1][2 S + 1] the entry state of every chunk of the tile (row chunks: the
+// entry state of the next tile) | ms [2 S][2 S] the chunk-to-chunk transition matrix, row-major;  then floats:  xs [tile + tile / 64]
+// the samples of the tile, one float of padding behind every 64.
+// A thread owns kSosChunk = 64 consecutive samples, a block kSosTile = 256 * 64: the row of a 16384-sample window and its lead-in is
+// two trips, and the scan over the chunks (one dependent 2S x 2S product per chunk, the long pole of the kernel) has 256 steps per
+// 16384 samples.  A thread reads its chunk at a stride of 65 floats: lane l on bank (l + k) mod 64, conflict free.  The odd stride of es
+// (2 S + 1 doubles) spreads the 2 S stores of a chunk's final state over the banks the same way.  S = 8: 103 KiB, one block per CU.
+constexpr int kSosChunk = 64;
+constexpr int kSosChunks = 256;                      // chunks of a tile: one per thread (WUNET_THREADS)
+constexpr int kSosTile = kSosChunk * kSosChunks;
+struct Sos {
+    int n;                                           // 2 S, the order of the cascade's state
+    constexpr int es_stride() const { return n + 1; }
+    constexpr int ms() const { return (kSosChunks + 1) * es_stride(); }                 // (doubles)
+    constexpr int xs() const { return 2 * (ms() + n * n); }                             // (floats from here on)
+    constexpr int end() const { return xs() + kSosTile + kSosTile / 64; }
+    constexpr size_t bytes() const { return (size_t)end() * sizeof(float); }
+};
+constexpr Sos sos(int sections) { return {2 * sections}; }
+
 }  // namespace wunet_lds

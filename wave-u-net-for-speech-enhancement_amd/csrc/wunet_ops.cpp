@@ -14,6 +14,7 @@
 #include "wunet_reverb.h"
 #include "wunet_chunks.h"
 #include "wunet_resample.h"
+#include "wunet_sos.h"
 
 using namespace wunet_host;
 
@@ -1031,6 +1032,58 @@ int wunet_resample_rows(const float* in, long long in_total, const long long* ro
     prof_end(st);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
+}
+
+// ---------------------------------------------------------------------------- cascades of second-order sections (wunet_sos.h)
+static int sos_sections_check(int sections)
+{
+    if (sections >= 1 && sections <= WUNET_SOS_MAX_SECTIONS) return 0;
+    return fail(WUNET_E_ARG, "sos: sections must be in [1, %d] (got %d)", WUNET_SOS_MAX_SECTIONS, sections);
+}
+
+long long wunet_sos_tile(int sections)
+{
+    if (sos_sections_check(sections)) return 0;
+    return ((long long)wunet_lds::kSosTile << 16) | (long long)wunet_lds::kSosChunk;
+}
+
+extern "C++" template <int S>
+int sos_launch(const SosArgs& A, int batch, hipStream_t st)
+{
+    constexpr size_t bytes = wunet_lds::sos(S).bytes();
+    if (WUNET_ALLOW_BIG_LDS(sos_windows_kernel<S>, bytes)) return fail(WUNET_E_RUNTIME, "sos: %zu bytes of LDS were not granted", bytes);
+    const double n = (double)batch * ((double)A.lead + A.length);
+    // (the profiler's columns: two passes of 9 flops per sample and section; the samples in and out)
+    prof_begin(st, "sos_windows_kernel", 2.0 * 9.0 * S * n, 4.0 * 2.0 * n);
+    WUNET_LAUNCH(sos_windows_kernel<S>, dim3((unsigned)batch), dim3(WUNET_THREADS), bytes, st, A);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_sos_windows(const float* flat, long long total, const long long* rows, const float* coefs, int sections, int lead, int batch,
+                      int length, float* out, void* stream)
+{
+    if (batch < 1 || length < 1) return fail(WUNET_E_ARG, "sos: batch and length must be >= 1 (got %d x %d)", batch, length);
+    if (batch > 65535 || length > (1 << 24)) return fail(WUNET_E_ARG, "sos: at most 65535 rows of 2^24 samples per call (got %d x %d)", batch, length);
+    if (sos_sections_check(sections)) return WUNET_E_ARG;
+    if (lead < 0 || lead > WUNET_SOS_MAX_LEAD) return fail(WUNET_E_ARG, "sos: lead must be in [0, %d] (got %d)", WUNET_SOS_MAX_LEAD, lead);
+    if (total < length) return fail(WUNET_E_ARG, "sos: the flat array is shorter than one window (total=%lld length=%d)", total, length);
+    if (total >= (1LL << 60)) return fail(WUNET_E_ARG, "sos: array too large");
+    if (!flat || !rows || !coefs || !out) return fail(WUNET_E_ARG, "sos: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    SosArgs A{};
+    A.flat = flat; A.total = total; A.rows = rows; A.coefs = coefs; A.lead = lead; A.length = length; A.out = out;
+    switch (sections) {
+    case 1: return sos_launch<1>(A, batch, st);
+    case 2: return sos_launch<2>(A, batch, st);
+    case 3: return sos_launch<3>(A, batch, st);
+    case 4: return sos_launch<4>(A, batch, st);
+    case 5: return sos_launch<5>(A, batch, st);
+    case 6: return sos_launch<6>(A, batch, st);
+    case 7: return sos_launch<7>(A, batch, st);
+    default: return sos_launch<8>(A, batch, st);
+    }
 }
 
 // ---------------------------------------------------------------------------- single-op entry points

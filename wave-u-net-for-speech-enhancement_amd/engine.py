@@ -888,6 +888,30 @@ class Engine:
                                                      taps.data_ptr(), taps.numel(), out.data_ptr(), out.numel(), self._stream(dev)))
         return out
 
+    # ------------------------------------------------------------------ cascades of second-order sections (wunet_sos_windows)
+    def sos_tile(self, sections):
+        """(tile, chunk) of include/wunet_hip.h: wunet_sos_tile - the samples a block owns per trip and the ones a thread owns."""
+        v = self._sized(int(self.lib.wunet_sos_tile(int(sections))))
+        return v >> 16, v & 0xffff
+
+    def sos_windows(self, flat, rows, coefs, out, lead=0):
+        """include/wunet_hip.h: wunet_sos_windows.  out[b, 0, :] = the window of the flat float32 array `flat` that rows[b] = (window
+        start, item start, circular length, phase) names, run through the cascade coefs[b] = [S, 5] (b0, b1, b2, a1, a2 per section,
+        a0 = 1) from rest at `lead` samples in front of the window (fewer where the item starts later).  One launch, nothing read back,
+        no scratch.  Returns out."""
+        given = self._table_op("sos_windows", "sos_windows tensor", "a float32 array, coefs and output and int64 rows", (flat, rows, coefs, out), rows)
+        if flat.dim() != 1 or out.dim() < 2 or coefs.dim() != 3:
+            raise WunetError("sos_windows: shape mismatch (a flat array, rows [B, 4], coefs [B, S, 5], out [B, ..., L])")
+        B, L, S = out.shape[0], out.shape[-1], coefs.shape[1]
+        if out.numel() != B * L or tuple(rows.shape) != (B, 4) or tuple(coefs.shape) != (B, S, 5):
+            raise WunetError("sos_windows: shape mismatch (a flat array, rows [B, 4], coefs [B, S, 5], out [B, 1, L])")
+        dev = out.device
+        self._same_device("sos_windows", given, dev, "the output's device")
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_sos_windows(flat.data_ptr(), flat.numel(), rows.data_ptr(), coefs.data_ptr(), S, int(lead), B, L,
+                                                   out.data_ptr(), self._stream(dev)))
+        return out
+
 
 class _CtxHold:
     """`with engine._using(shape...) as handle`: the context cannot be evicted while the block runs."""

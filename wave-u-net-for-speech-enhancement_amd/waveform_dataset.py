@@ -294,6 +294,7 @@ def pack_mono_shard(list_file, prefix, limit=None, offset=0, sample_rate=None, e
     return len(names)
 
 
+SOS_MAX_LEAD = 8192                 # WUNET_SOS_MAX_LEAD of include/wunet_hip.h
 RIR_MAX_TAPS = 16384          # include/wunet_hip.h: WUNET_REVERB_MAX_TAPS
 
 
@@ -359,13 +360,30 @@ class MixLoader:
       target="reverberant"  a r: denoising only
     The guard looks at r and the noise; a dry or early target is NOT guarded and can exceed peak_limit where the response attenuates
     (|r| well below |c|).  `last_draw` gains "rir_rows" (int64 [B,4]: window start, item start, RIR start, RIR taps - 0 for a dry row)
-    and "reverberant" (a r, [B,1,L]).  Four launches per batch."""
+    and "reverberant" (a r, [B,1,L]).  Four launches per batch.
+
+    Random spectral shaping (`eq_speech`, `eq_noise`: None, or a dict of filters.random_biquads' keywords sections / spread / p; with
+    both None nothing below applies and the batches, the generator's consumption and the launches are what they were).  Per row a
+    short cascade of random second-order sections (RNNoise's recipe) is drawn for the speech and another for the noise, from the same
+    generator and after all the draws above, the response's included: a seed keeps its rows, params and rir_rows with and without the
+    equalisers.  The speech first, then the noise; each by random_biquads' documented order.  Both are filtered on the device
+    (wunet_sos_windows) before they are mixed, so the SNR and the peak guard apply to the filtered signals, and the target is the
+    filtered speech at the mixture's level: the network is not asked to undo the colouration.
+      without a response  the speech window is filtered out of the clean shard, the filter starting at rest `eq_lead` samples in
+                          front of the window (fewer where the item starts later; never in front of the item), so a window from the
+                          middle of a recording carries no start-up transient; the noise is filtered out of the noise shard along its
+                          circular read, with `eq_lead` samples of lead-in too.  The mix then reads the two staged batches.
+      with a response     the speech equaliser runs on what the reverb staged - the reverberant window and, for a dry or early target,
+                          the direct part, both with the row's one cascade, so the target stays consistent.  These start from rest at
+                          the window start: the staged batch has no past, so the lead-in is 0 there, whatever eq_lead is.
+    eq_noise needs a noise shard of at least sample_length samples in all.  `last_draw` gains "eq_speech" and "eq_noise": the float32
+    [B, S, 6] tables in scipy's layout, or None.  One more launch per filtered batch; still one linear chain."""
 
     TARGETS = ("dry", "early", "reverberant")
 
     def __init__(self, clean_prefix, noise_prefix, batch_size, sample_length=16384, snr_db=(0.0, 20.0), level_db=None, peak_limit=0.99,
                  p_clean=0.0, device="cpu", seed=0, steps_per_epoch=None, engine=None, rir_prefix=None, p_reverb=1.0, target="dry",
-                 early_ms=50.0):
+                 early_ms=50.0, eq_speech=None, eq_noise=None, eq_lead=256):
         self.device = torch.device(device)
         if self.device.type != "cuda" and engine is None:
             raise ValueError("MixLoader mixes on the device: device='cpu' needs an engine (there is no host implementation of the mix)")
@@ -400,6 +418,16 @@ class MixLoader:
         self.rir = None
         if rir_prefix is not None:
             self._init_rir(rir_prefix, p_reverb, target, early_ms)
+        self.eq_speech, self.eq_noise, self.eq_lead = self._eq_spec("eq_speech", eq_speech), self._eq_spec("eq_noise", eq_noise), int(eq_lead)
+        if self.eq_speech is not None or self.eq_noise is not None:
+            from .filters import random_biquads
+            for spec in (self.eq_speech, self.eq_noise):
+                if spec is not None:
+                    random_biquads(1, generator=torch.Generator().manual_seed(0), **spec)      # (its checks, before the first batch)
+            if not 0 <= self.eq_lead <= SOS_MAX_LEAD:
+                raise ValueError(f"eq_lead must be in [0, {SOS_MAX_LEAD}], got {eq_lead}")
+            if self.eq_noise is not None and self.noise.numel() < sample_length:
+                raise ValueError("eq_noise needs a noise shard of at least sample_length samples in all")
 
     UPLOAD_CHUNK = ShardLoader.UPLOAD_CHUNK
     _resident = ShardLoader._resident
@@ -491,14 +519,118 @@ class MixLoader:
         target = reverberant if direct is None else self.engine.apply_level(direct, gains)
         return mixture, target, gains, reverberant
 
+    @staticmethod
+    def _eq_spec(name, spec):
+        if spec is None:
+            return None
+        spec = dict(spec)
+        if set(spec) - {"sections", "spread", "p"}:
+            raise ValueError(f"{name}: a dict of random_biquads' keywords sections, spread, p expected, got {sorted(spec)}")
+        return spec
+
+    def draw_eq(self):
+        """(eq_speech, eq_noise) of the batch just drawn: float32 [B, S, 6] each, or None.  Their draws come after all the others of
+        the batch, the speech's first."""
+        from .filters import random_biquads
+        return tuple(None if spec is None else random_biquads(self.batch_size, generator=self.gen, **spec) for spec in (self.eq_speech, self.eq_noise))
+
+    def _filtered(self, flat, table, coefs, lead):
+        """A staged [B, 1, L] batch: the windows of `flat` that the table [B, 4] names, through the cascades coefs [B, S, 5]."""
+        dev = self.device
+        out = torch.empty(table.shape[0], 1, self.sample_length, dtype=torch.float32, device=dev)
+        return self.engine.sos_windows(flat, table.to(dev, non_blocking=True), coefs.to(dev, non_blocking=True), out, lead=lead)
+
+    def eq_tables(self, speech_table, rows, eq_speech, eq_noise):
+        """The host tables of an equalised batch, a dict: "speech" / "noise" = (rows [B, 4], coefs [B, S, 5]) of the filter launch, or
+        None without that equaliser, and "rows" = the mix's table on what the filters staged.  speech_table: the speech filter's rows.
+        A filtered batch is read by the mix as windows of one flat array: row b's clean window starts at b L, its noise is the item
+        [b L, (b + 1) L) read from phase 0.  A row that is passed clean (noise length 0) keeps its 0 in the mix's table; its staged noise
+        is filtered from one sample and never read."""
+        from .filters import sos_to_coefs
+        B, L = rows.shape[0], self.sample_length
+        at = torch.arange(B, dtype=torch.int64) * L
+        t = {"speech": None, "noise": None}
+        rows = rows.clone()
+        if eq_speech is not None:
+            t["speech"] = (speech_table.contiguous(), sos_to_coefs(eq_speech))
+            rows[:, 0] = at
+        if eq_noise is not None:
+            table = rows.clone()
+            table[:, 2] = torch.clamp(rows[:, 2], min=1)
+            t["noise"] = (table, sos_to_coefs(eq_noise))
+            rows[:, 1] = at
+            rows[:, 2] = torch.where(rows[:, 2] > 0, torch.full_like(at, L), torch.zeros_like(at))
+            rows[:, 3] = 0
+        t["rows"] = rows
+        return t
+
+    def enqueue_equalised(self, clean_src, tables, params, lead):
+        """The launches of an equalised batch on tables that eq_tables made (host or device tensors): a filter launch per equaliser into
+        a staged batch, then the mix's two on the staged arrays - one linear chain.  clean_src: the flat array the speech is read from.
+        Returns (mixture, clean, gains)."""
+        B, L, dev = tables["rows"].shape[0], self.sample_length, self.device
+        if tables["speech"] is not None:
+            clean_src = self._filtered(clean_src, *tables["speech"], lead).view(-1)
+        noise_src = self.noise if tables["noise"] is None else self._filtered(self.noise, *tables["noise"], self.eq_lead).view(-1)
+        mixture = torch.empty(B, 1, L, dtype=torch.float32, device=dev)
+        clean = torch.empty(B, 1, L, dtype=torch.float32, device=dev)
+        gains = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        self.engine.mix_windows(clean_src, noise_src, tables["rows"].to(dev, non_blocking=True), params.to(dev, non_blocking=True), mixture, clean,
+                                gains, peak_limit=self.peak_limit)
+        return mixture, clean, gains
+
+    def mix_equalised(self, pick, rows, params, eq_speech, eq_noise):
+        """mix() with the equalisers: (mixture, target, gains)."""
+        if self.engine is None:
+            from .engine import default_engine
+            self.engine = default_engine()
+        zero = torch.zeros(rows.shape[0], dtype=torch.int64)
+        speech_table = torch.stack([rows[:, 0], self.starts[pick], zero, zero], dim=1)
+        return self.enqueue_equalised(self.clean, self.eq_tables(speech_table, rows, eq_speech, eq_noise), params, self.eq_lead)
+
+    def mix_reverberant_equalised(self, rows, params, rir_rows, eq_speech, eq_noise):
+        """mix_reverberant() with the equalisers: (mixture, target, gains, a r) with r the filtered reverberant window.  The speech
+        equaliser runs on the staged reverberant batch and on the staged direct part, from rest at the window start (lead 0)."""
+        if self.engine is None:
+            from .engine import default_engine
+            self.engine = default_engine()
+        B, L, dev = rows.shape[0], self.sample_length, self.device
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)          # noqa: E731
+        staged = new(B, 1, L)
+        direct = None if self.target == "reverberant" else new(B, 1, L)
+        self.engine.reverb_windows(self.clean, self.rir, rir_rows.to(dev, non_blocking=True), staged, direct, early_taps=self.early_taps)
+        at = torch.arange(B, dtype=torch.int64) * L
+        speech_table = torch.stack([at, at, torch.zeros_like(at), torch.zeros_like(at)], dim=1)
+        staged_rows = rows.clone()
+        staged_rows[:, 0] = at
+        tables = self.eq_tables(speech_table, staged_rows, eq_speech, eq_noise)
+        if direct is not None and eq_speech is not None:
+            direct = self._filtered(direct.view(-1), *tables["speech"], 0)
+        mixture, reverberant, gains = self.enqueue_equalised(staged.view(-1), tables, params, 0)
+        target = reverberant if direct is None else self.engine.apply_level(direct, gains)
+        return mixture, target, gains, reverberant
+
     def __iter__(self):
+        equalised = self.eq_speech is not None or self.eq_noise is not None
         for _ in range(self.steps):
             pick, rows, params = self.draw()
             if self.rir is None:
-                mixture, clean, gains = self.mix(rows, params)
-                self.last_draw = {"rows": rows, "params": params, "gains": gains}
+                if equalised:
+                    eq_s, eq_n = self.draw_eq()
+                    mixture, clean, gains = self.mix_equalised(pick, rows, params, eq_s, eq_n)
+                    self.last_draw = {"rows": rows, "params": params, "gains": gains, "eq_speech": eq_s, "eq_noise": eq_n}
+                else:
+                    mixture, clean, gains = self.mix(rows, params)
+                    self.last_draw = {"rows": rows, "params": params, "gains": gains}
             else:
                 rir_rows = self.draw_rir(pick, rows)
-                mixture, clean, gains, reverberant = self.mix_reverberant(rows, params, rir_rows)
+                if equalised:
+                    eq_s, eq_n = self.draw_eq()
+                    mixture, clean, gains, reverberant = self.mix_reverberant_equalised(rows, params, rir_rows, eq_s, eq_n)
+                else:
+                    eq_s = eq_n = None
+                    mixture, clean, gains, reverberant = self.mix_reverberant(rows, params, rir_rows)
                 self.last_draw = {"rows": rows, "params": params, "gains": gains, "rir_rows": rir_rows, "reverberant": reverberant}
+                if equalised:
+                    self.last_draw.update(eq_speech=eq_s, eq_noise=eq_n)
             yield mixture, clean, [self.names[i] for i in pick.tolist()]
