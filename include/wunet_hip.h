@@ -531,6 +531,34 @@ int wunet_sos_windows(const float* flat, long long total,
                       int sections, int lead, int batch, int length, float* out /* [batch][1][length] */, void* stream);
 long long wunet_sos_tile(int sections);
 
+/* BSS Eval SDR per row (no reference counterpart in code: Wave-U-Net results are reported in it, computed on the host by
+ * mir_eval.separation.bss_eval_sources / museval; csrc/wunet_bss.h): that function for ONE source - the reference padded with
+ * filter_length - 1 zeros, so e_interf = 0 and SDR = SAR; no mean removal, no regularisation.  Per row, with s = clean, e = estimate,
+ * both zero outside [0, len), n = filter_length:
+ *   r[k] = sum_t s[t] s[t + k],  b[k] = sum_t s[t] e[t + k]  (k = 0 .. n - 1),  E = sum e^2,  G = toeplitz(r);  G c = b;
+ *   P = c'b,  R = E - 2 c'b + c'G c,  out_db = 10 log10(P / R)
+ * R is the residual energy of the c that was found, second order in the solver's error.  Unlike SI-SDR the score forgives the
+ * estimate any n-tap filtering (colouring, delay < n) of the reference; n = 1 is SI-SDR without mean removal.
+ * Two launches: correlation partials per (row, segment of wunet_bss_sdr_tile samples) - float x float products are exact in double,
+ * the sums are double - then one block per row adds them in segment order, runs Levinson's recursion in double (n dependent orders,
+ * the latency of the call) and rounds the score to float32 once.  No atomics: bit-identical run to run.
+ * A row whose clean or estimate is all zero inside its length, or whose length is 0, yields NaN in that row (mir_eval raises there)
+ * and leaves every other row's bits alone; nothing is read back.  estimate == clean bit for bit yields +inf (R = 0 exactly).
+ * lengths: NULL (every row has row_len samples) or device int64 [rows], read on the device and clamped to [0, row_len], so a captured
+ * call follows it; samples beyond a row's length are never addressed as data (masked loads).
+ * scratch: wunet_bss_sdr_scratch_bytes(rows, row_len, filter_length) bytes, 8-byte aligned; the waveforms need 4-byte alignment only.
+ * Caller-owned memory, no allocation, no synchronisation, capturable.
+ * -1 with the error text for: a null pointer (lengths excepted); filter_length outside [1, WUNET_BSS_MAX_FILTER]; rows or row_len 0;
+ * rows > 65535; row_len >= 2^31.  wunet_bss_sdr_scratch_bytes answers 0 for the same shapes.
+ * wunet_bss_sdr_tile: the samples of a row one block of the first launch owns - what the tests put row lengths next to; 0 for a
+ * refused filter_length. */
+#define WUNET_BSS_MAX_FILTER 512
+size_t wunet_bss_sdr_scratch_bytes(size_t rows, size_t row_len, int filter_length);
+int wunet_bss_sdr_forward(const float* clean, const float* estimate, size_t rows, size_t row_len,
+                          const long long* lengths /* NULL or device [rows] */, int filter_length,
+                          void* scratch, float* out_db /* [rows] */, void* stream);
+long long wunet_bss_sdr_tile(int filter_length);
+
 /* Measurement aid (tools/conv_trace.py; no reference counterpart): a device buffer of gridDim.x * 64 uint64 that the DMA-staged
  * conv / data-gradient kernel (conv_h3d_kernel) fills with shader-clock stamps of each block's phases (entry; per K stage: tile
  * landed, W buffer released, MFMAs issued; epilogue done), or NULL (default) to turn the stamps off.  Process-wide. */

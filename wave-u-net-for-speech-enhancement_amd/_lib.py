@@ -31,6 +31,7 @@ EXPORTS = [
     "wunet_mix_scratch_bytes", "wunet_mix_windows", "wunet_apply_level", "wunet_reverb_windows",
     "wunet_chunk_gather", "wunet_chunk_overlap_add", "wunet_resample_rows", "wunet_resample_tile",
     "wunet_sos_windows", "wunet_sos_tile",
+    "wunet_bss_sdr_scratch_bytes", "wunet_bss_sdr_forward", "wunet_bss_sdr_tile",
 ]
 
 _vp = ctypes.c_void_p
@@ -146,6 +147,12 @@ def declare(lib):
         lib.wunet_sos_windows.argtypes = [_vp, _ll, _vp, _vp, _i, _i, _i, _i, _vp, _vp]
         lib.wunet_sos_tile.argtypes = [_i]
         lib.wunet_sos_tile.restype = _ll
+    if hasattr(lib, "wunet_bss_sdr_forward"):    # (the same)
+        lib.wunet_bss_sdr_scratch_bytes.argtypes = [_sz, _sz, _i]
+        lib.wunet_bss_sdr_scratch_bytes.restype = _sz
+        lib.wunet_bss_sdr_forward.argtypes = [_vp, _vp, _sz, _sz, _vp, _i, _vp, _vp, _vp]
+        lib.wunet_bss_sdr_tile.argtypes = [_i]
+        lib.wunet_bss_sdr_tile.restype = ctypes.c_longlong
     lib.wunet_comm_unique_id.argtypes = [_vp]
     lib.wunet_comm_create.argtypes = [_vp, _i, _i, ctypes.POINTER(_vp)]
     lib.wunet_comm_allreduce_sum.argtypes = [_vp, _vp, _sz, _vp]

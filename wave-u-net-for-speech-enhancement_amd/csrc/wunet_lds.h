@@ -159,4 +159,32 @@ struct Sos {
 };
 constexpr Sos sos(int sections) { return {2 * sections}; }
 
+// ---- bss_corr_kernel, doubles:  ss [tile + n - 1] the reference under one tile of the row and the n - 1 samples behind it | es the
+// estimate over the same span.  Staged as doubles: the inner loop is one double FMA per 8-byte LDS read, no conversion in it.  Thread t
+// owns the lags t and t + 256: at every sample it reads ss / es at consecutive addresses across the wave (conflict free) and the tile's
+// own sample as a broadcast.  n = 512: 40 KiB, three blocks per CU.
+constexpr int kBssTile = 2048;                       // samples of a row a block owns (its segment)
+constexpr int kBssMaxFilter = 512;                   // WUNET_BSS_MAX_FILTER: two lags per thread
+struct BssCorr {
+    int n;                                           // filter length
+    constexpr int span() const { return kBssTile + n - 1; }
+    constexpr int es() const { return span(); }
+    constexpr int end() const { return 2 * span(); }
+    constexpr size_t bytes() const { return (size_t)end() * sizeof(double); }
+};
+constexpr BssCorr bss_corr(int filter_length) { return {filter_length}; }
+
+// ---- bss_solve_kernel, doubles:  rs [512] the autocorrelation | bs [512] the cross-correlation | as [2][512] the prediction
+// polynomial of Levinson's recursion, the order before and the order being written (afterwards: the solution c in the first half)
+// | red [2 * kWaves] block_sum's hand-over | one double: the estimate's energy.  Sized for the largest filter whatever n is: 16.1 KiB.
+struct BssSolve {
+    constexpr int bs() const { return kBssMaxFilter; }
+    constexpr int as() const { return 2 * kBssMaxFilter; }
+    constexpr int red() const { return 4 * kBssMaxFilter; }
+    constexpr int energy() const { return red() + 2 * kWaves; }
+    constexpr int end() const { return energy() + 1; }
+    constexpr size_t bytes() const { return (size_t)end() * sizeof(double); }
+};
+constexpr BssSolve bss_solve() { return {}; }
+
 }  // namespace wunet_lds

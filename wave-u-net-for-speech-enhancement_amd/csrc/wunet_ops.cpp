@@ -15,6 +15,7 @@
 #include "wunet_chunks.h"
 #include "wunet_resample.h"
 #include "wunet_sos.h"
+#include "wunet_bss.h"
 
 using namespace wunet_host;
 
@@ -1084,6 +1085,53 @@ int wunet_sos_windows(const float* flat, long long total, const long long* rows,
     case 7: return sos_launch<7>(A, batch, st);
     default: return sos_launch<8>(A, batch, st);
     }
+}
+
+// ---------------------------------------------------------------------------- BSS Eval SDR per row (wunet_bss.h)
+static int bss_check(size_t rows, size_t row_len, int filter_length)
+{
+    if (filter_length < 1 || filter_length > WUNET_BSS_MAX_FILTER)
+        return fail(WUNET_E_ARG, "bss_sdr: filter_length must be in [1, %d] (got %d)", WUNET_BSS_MAX_FILTER, filter_length);
+    if (rows == 0 || row_len == 0) return fail(WUNET_E_ARG, "bss_sdr: rows and row_len must be > 0 (got %zu x %zu)", rows, row_len);
+    if (rows > 65535 || row_len >= (1ull << 31))
+        return fail(WUNET_E_ARG, "bss_sdr: at most 65535 rows of fewer than 2^31 samples per call (got %zu x %zu)", rows, row_len);
+    return 0;
+}
+
+static unsigned bss_segments(size_t row_len) { return (unsigned)((row_len + wunet_lds::kBssTile - 1) / wunet_lds::kBssTile); }
+
+long long wunet_bss_sdr_tile(int filter_length)
+{
+    if (bss_check(1, 1, filter_length)) return 0;
+    return wunet_lds::kBssTile;
+}
+
+size_t wunet_bss_sdr_scratch_bytes(size_t rows, size_t row_len, int filter_length)
+{
+    if (bss_check(rows, row_len, filter_length)) return 0;
+    return rows * bss_segments(row_len) * (size_t)(2 * filter_length + 1) * sizeof(double);
+}
+
+int wunet_bss_sdr_forward(const float* clean, const float* estimate, size_t rows, size_t row_len, const long long* lengths, int filter_length,
+                          void* scratch, float* out_db, void* stream)
+{
+    if (bss_check(rows, row_len, filter_length)) return WUNET_E_ARG;
+    if (!clean || !estimate || !scratch || !out_db) return fail(WUNET_E_ARG, "bss_sdr: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    BssArgs A{};
+    A.clean = clean; A.est = estimate; A.row_len = row_len; A.lengths = lengths; A.n = filter_length; A.segs = bss_segments(row_len);
+    A.part = (double*)scratch; A.out = out_db;
+    const double samples = (double)rows * (double)row_len;
+    // (the profiler's columns: two products per lag and sample; both rows in, one partial per segment out)
+    prof_begin(st, "bss_corr_kernel", 2.0 * 2.0 * filter_length * samples, 4.0 * 2.0 * samples);
+    WUNET_LAUNCH(bss_corr_kernel, dim3(A.segs, (unsigned)rows), dim3(WUNET_THREADS), wunet_lds::bss_corr(filter_length).bytes(), st, A);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    prof_begin(st, "bss_solve_kernel", (double)rows * 6.0 * filter_length * filter_length, 8.0 * (double)rows * A.segs * (2.0 * filter_length + 1.0));
+    WUNET_LAUNCH(bss_solve_kernel, dim3((unsigned)rows), dim3(WUNET_THREADS), wunet_lds::bss_solve().bytes(), st, A);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
 }
 
 // ---------------------------------------------------------------------------- single-op entry points

@@ -912,6 +912,36 @@ class Engine:
                                                    out.data_ptr(), self._stream(dev)))
         return out
 
+    # ------------------------------------------------------------------ BSS Eval SDR per row (wunet_bss_sdr_*)
+    def bss_sdr_tile(self, filter_length=512):
+        """include/wunet_hip.h: wunet_bss_sdr_tile - the samples of a row one block of the correlation launch owns."""
+        return self._sized(int(self.lib.wunet_bss_sdr_tile(int(filter_length))))
+
+    def bss_sdr(self, clean, estimate, filter_length=512, lengths=None, out=None):
+        """include/wunet_hip.h: wunet_bss_sdr_forward.  The last dimension is the utterance, all leading ones are flattened.  lengths:
+        None, or an int64 tensor of one entry per row on the waveforms' device (clamped to [0, T] on the device).  Returns float32
+        [rows] in dB (`out`, where given); NaN on a row whose reference or estimate is silent or whose length is 0.  Nothing is read
+        back to the host."""
+        R, T, dev = self._wave_pair("bss_sdr", clean, estimate, "estimate")
+        if out is not None:
+            self._require(out, "out")
+            if out.dtype != torch.float32 or out.numel() != R or out.device != dev:
+                raise WunetError(f"bss_sdr: out must be a float32 tensor of {R} elements on {dev}")
+        if lengths is not None:
+            if not isinstance(lengths, torch.Tensor) or lengths.dtype is not torch.int64:
+                raise WunetError("bss_sdr: lengths must be an int64 tensor")
+            if lengths.device != dev:
+                raise WunetError(f"bss_sdr: lengths lives on {lengths.device}, the waveforms on {dev}")
+            if lengths.numel() != R or not lengths.is_contiguous():
+                raise WunetError(f"bss_sdr: lengths must be contiguous with one entry per row ({R}), got {tuple(lengths.shape)}")
+        n = int(filter_length)
+        scratch = torch.empty(self._sized(self.lib.wunet_bss_sdr_scratch_bytes(R, T, n)) // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(R, dtype=torch.float32, device=dev) if out is None else out
+        with self._device_guard(dev):
+            self._check(self.lib.wunet_bss_sdr_forward(clean.data_ptr(), estimate.data_ptr(), R, T, _ptr(lengths), n, scratch.data_ptr(),
+                                                       out.data_ptr(), self._stream(dev)))
+        return out
+
 
 class _CtxHold:
     """`with engine._using(shape...) as handle`: the context cannot be evicted while the block runs."""

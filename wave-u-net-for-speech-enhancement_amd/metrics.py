@@ -2,6 +2,8 @@
 (trainer/trainer.py:58-143): `stoi` below is that STOI (pystoi, extended=False) as HIP kernels; PESQ (ITU-T P.862, a long procedural
 model) stays a host metric and out of scope - SURVEY.md §2.  `si_sdr` / `snr` are the forward of the row losses (include/wunet_hip.h:
 wunet_loss_rows_forward) with its per-row output: one pass over the pair, sums in double, no backward; float32 [rows] in dB.
+`sdr` is the BSS Eval SDR the Wave-U-Net literature reports (mir_eval.separation.bss_eval_sources for one source; include/wunet_hip.h:
+wunet_bss_sdr_forward).  The scores available on the device are therefore SI-SDR, SNR, BSS Eval SDR, STOI and ESTOI.
 The last dimension is the utterance; all leading dimensions are flattened to rows.  Results live on the inputs' device.
 """
 import torch
@@ -30,6 +32,23 @@ def snr(clean, estimate, zero_mean=True, eps=1e-8, engine=None):
 def si_sdr_improvement(clean, noisy, enhanced, zero_mean=True, eps=1e-8, engine=None):
     """SI-SDR of the enhanced signal minus SI-SDR of the noisy one, per row: what the enhancement gained."""
     return si_sdr(clean, enhanced, zero_mean, eps, engine) - si_sdr(clean, noisy, zero_mean, eps, engine)
+
+
+@torch.no_grad()
+def sdr(clean, estimate, filter_length=512, lengths=None, engine=None):
+    """BSS Eval SDR of `estimate` against `clean`, per row, in dB: mir_eval.separation.bss_eval_sources(clean[None], estimate[None])
+    for one source - the energy of the projection of the estimate onto the reference and its delays 0 .. filter_length - 1 over the
+    energy of the rest; no mean removal.  Unlike SI-SDR it forgives a filter of up to filter_length (1 .. 512) taps; filter_length=1
+    is si_sdr(zero_mean=False, eps=0).  lengths: None, or int64 [rows] on the device - row i counts as its first lengths[i] samples
+    (ragged recordings in one padded slab).  A row whose reference or estimate is silent, or of length 0, scores NaN (mir_eval raises
+    there; nothing is read back here), estimate == clean scores +inf.  Returns float32 [rows]."""
+    engine = engine if engine is not None else default_engine()
+    return engine.bss_sdr(clean.detach().contiguous(), estimate.detach().contiguous(), filter_length, lengths)
+
+
+def sdr_improvement(clean, noisy, enhanced, filter_length=512, lengths=None, engine=None):
+    """BSS Eval SDR of the enhanced signal minus that of the noisy one, per row: what the enhancement gained."""
+    return sdr(clean, enhanced, filter_length, lengths, engine) - sdr(clean, noisy, filter_length, lengths, engine)
 
 
 @torch.no_grad()

@@ -41,6 +41,12 @@ Differences from the reference loop, all on the f2 list:
     recordings the epoch's score (`validation_scores` holds it, "find_max" applies as in the reference).  metrics.stoi at
     `"custom": {"sample_rate": 16000}` (the reference hard-codes 16 kHz); still one device->host read per validation epoch.
     `"stoi_extended": true` beside "stoi" makes both calls ESTOI (metrics.stoi(extended=True)); it needs the "stoi" key and a bool;
+  * BSS Eval SDR, the score Wave-U-Net results are reported in (metrics.sdr: mir_eval's bss_eval_sources for one source), on the
+    device: beside "metric": "si_sdr" the optional key `"sdr": "report"` also appends (mean SDR of the noisy recordings, mean SDR of
+    the enhanced ones) [dB] to `validation_sdr` every validation epoch and leaves the score alone; `"sdr": "score"` makes the mean
+    SDR of the enhanced recordings the epoch's score.  `"sdr_filter_length": n` (default 512) sets the forgiven filter's taps.  The
+    recordings of a pass ("recordings_per_pass") are scored in one call, ragged, through `lengths`; with "model_rate" the score is
+    at the files' rate.  Still one device->host read per validation epoch.  "stoi": "score" and "sdr": "score" together raise;
   * checkpoints keep the reference's names and keys (base_trainer.py:83-124) so either side can resume; only rank 0 writes.
 """
 import os
@@ -137,6 +143,21 @@ class Trainer:
             raise ValueError(f'trainer config "validation.stoi_extended" must be true or false (got {self.validation_stoi_extended!r})')
         if "stoi_extended" in vcfg and self.validation_stoi_mode is None:
             raise ValueError('trainer config "validation.stoi_extended" needs "validation.stoi": "report" or "score" beside it')
+        # "sdr": BSS Eval SDR (metrics.sdr) beside the SI-SDR improvement, reported or as the score; "sdr_filter_length": its taps
+        self.validation_sdr_mode = vcfg.get("sdr")
+        if self.validation_sdr_mode not in (None, "report", "score"):
+            raise ValueError(f'trainer config "validation.sdr" must be "report" or "score" (got {self.validation_sdr_mode!r})')
+        if self.validation_sdr_mode is not None and self.validation_metric != "si_sdr":
+            raise ValueError('trainer config "validation.sdr" needs "validation.metric": "si_sdr" beside it')
+        if self.validation_sdr_mode == "score" and self.validation_stoi_mode == "score":
+            raise ValueError('trainer config "validation.stoi": "score" and "validation.sdr": "score" together: an epoch has one score')
+        n_taps = vcfg.get("sdr_filter_length", 512)
+        if isinstance(n_taps, bool) or not isinstance(n_taps, int) or not 1 <= n_taps <= 512:
+            raise ValueError(f'trainer config "validation.sdr_filter_length" must be an integer in [1, 512] (got {n_taps!r})')
+        if "sdr_filter_length" in vcfg and self.validation_sdr_mode is None:
+            raise ValueError('trainer config "validation.sdr_filter_length" needs "validation.sdr": "report" or "score" beside it')
+        self.validation_sdr_filter_length = n_taps
+        self.validation_sdr = []      # with "validation.sdr": (mean SDR noisy, mean SDR enhanced) [dB] per validation epoch
         self.validation_sample_rate = int((vcfg.get("custom") or {}).get("sample_rate", 16000))
         # "custom.model_rate": the rate the network runs at when the validation files ("custom.sample_rate") are at another one - the
         # recordings are resampled to it, enhanced and resampled back on the device (inference.py); the scores stay at the files' rate
@@ -271,6 +292,20 @@ class Trainer:
             if held:
                 yield from flush(held)
 
+        def sdr_of(group):
+            """float32 [len(group), 2]: BSS Eval SDR of the noisy and of the enhanced recording of every (mixture, clean, enhanced) of
+            `group` - the recordings of one pass, ragged, zero-padded to one slab and told apart by `lengths`: one call."""
+            n, lens = len(group), [cl.shape[-1] for _, cl, _ in group]
+            ref = torch.zeros(2, n, max(lens), dtype=torch.float32, device=self.device)
+            est = torch.zeros_like(ref)
+            for i, (mix, cl, enh) in enumerate(group):
+                ref[:, i, :lens[i]] = cl.reshape(-1)
+                est[0, i, :lens[i]] = mix.reshape(-1)
+                est[1, i, :lens[i]] = enh.reshape(-1)
+            lengths = torch.tensor(lens + lens, dtype=torch.int64).to(self.device, non_blocking=True)
+            return metrics.sdr(ref, est, self.validation_sdr_filter_length, lengths=lengths, engine=engine).reshape(2, n).t()
+
+        sdrs, group = [], []
         try:
             for mixture, clean, enhanced in passes():
                 gains.append(metrics.si_sdr_improvement(clean, mixture, enhanced, engine=engine))
@@ -278,6 +313,13 @@ class Trainer:
                     ext = self.validation_stoi_extended
                     stois.append(torch.cat([metrics.stoi(clean, mixture, sample_rate=fs, engine=engine, extended=ext).reshape(-1),
                                             metrics.stoi(clean, enhanced, sample_rate=fs, engine=engine, extended=ext).reshape(-1)]))
+                if self.validation_sdr_mode is not None:
+                    group.append((mixture, clean, enhanced))
+                    if len(group) == (per_pass or 1):
+                        sdrs.append(sdr_of(group))
+                        group = []
+            if group:
+                sdrs.append(sdr_of(group))
         finally:
             for m, was in modes:                         # exactly the flags of before: a frozen BatchNorm layer stays frozen
                 m.training = was
@@ -286,12 +328,18 @@ class Trainer:
         means = [torch.cat(gains).double().mean()]
         if stois:                                        # [recordings, 2]: noisy, enhanced
             means.extend(torch.stack(stois).double().mean(dim=0))
+        if sdrs:                                         # [recordings, 2]: noisy, enhanced
+            means.extend(torch.cat(sdrs).double().mean(dim=0))
         means = torch.stack(means).tolist()              # the only device->host read of the validation epoch
         score = means[0]
         if stois:
             self.validation_stoi.append((means[1], means[2]))
             if self.validation_stoi_mode == "score":
                 score = means[2]
+        if sdrs:
+            self.validation_sdr.append((means[-2], means[-1]))
+            if self.validation_sdr_mode == "score":
+                score = means[-1]
         self.validation_scores.append(score)
         return score
 
