@@ -237,7 +237,53 @@ int wunet_cspec_backward(const float* saved, size_t saved_bytes, const double* c
                          int n_fft, int hop, int win_length, double compress, double clamp, const float* basis, void* scratch,
                          size_t scratch_bytes, float* grad_enhanced, int accumulate, void* stream);
 
-/* STOI per row (no reference counterpart on the device: the reference's validation epoch calls pystoi on the host per recording,
+/* Multi-scale log-mel spectrogram loss (HiFi-GAN's mel loss; the multi-scale mel loss of DAC / EnCodec-style codecs).  No reference
+ * counterpart.  One resolution (N, H, W) frames and transforms clean = c and enhanced = e exactly as the STFT loss above does (same
+ * window, centring, reflect padding, frames f = 0 .. T / H, bins b = 0 .. N/2, N/2 <= T - 1, and the basis of wunet_stft_basis).  With a
+ * filterbank filt = Phi [n_mels][BP] (BP = N/2 + 1 rounded up to 32; non-negative float32, the padding columns 0, 16-byte aligned; the
+ * library knows nothing of mel scales - any non-negative bank will do):
+ *   P = re^2 + im^2,  Pc = max(P, clamp),  S = Pc^(power / 2),  m[f][j] = sum_b Phi[j][b] S[f][b],  l = ln max(m, floor);
+ *   L_i = mean over rows, frames and j of log_weight |l_c - l_e| + lin_weight |m_c - m_e|;
+ *   loss = (1 / n_res) sum_i L_i.
+ * Gradient with respect to `enhanced` only: autograd's of this graph with torch.clamp and abs - it passes where P_e >= clamp and where
+ * m_e >= floor, sign(0) = 0.  Equal signals give exactly 0 and an all-zero gradient; an all-zero row of Phi adds nothing to the sums
+ * and still counts in the mean.
+ * Supported: the STFT loss's N / H / W, 1 .. WUNET_STFT_MAX_RESOLUTIONS resolutions, 1 <= n_mels <= WUNET_MEL_MAX_FILTERS, power 1 or 2,
+ * clamp and floor finite and > 0 (>= 0 for the call without `clean`), the weights finite and >= 0 and not both 0; anything else is
+ * WUNET_E_ARG with a message.
+ * Arithmetic: fp32 operands and fp32 MFMA accumulation in both GEMMs of either direction; the logs, every reduction and every
+ * coefficient in double; no atomics, every sum has one fixed order: bit-identical run to run.
+ * The calls of one loss (the buffers' byte sizes are passed and checked; scratch and saved 16-byte aligned):
+ *   per resolution:  wunet_mel_forward writes its partial sums and the planes S_e, S_c to `scratch` (scratch_bytes >=
+ *                    wunet_mel_scratch_bytes(..)) and, when `saved` is given (saved_bytes == wunet_mel_saved_bytes(..); else NULL and
+ *                    0), re_e, im_e [rows * F][BP] and m_c, m_e [rows * F][MP] (MP = n_mels rounded up to 16) for the backward; the
+ *                    buffer also holds the plane the backward writes dS to.  mel_out must be NULL.  clean == NULL: the mel spectrogram
+ *                    of `enhanced` alone into mel_out [rows * F][n_mels] - m, or ln max(m, floor) where floor > 0 (saved NULL and 0;
+ *                    scratch as above) - the metric path;
+ *   once:            wunet_mel_finalize over the TABLE of the resolutions' scratch buffers (host arrays of n_res entries, read during
+ *                    the call): the loss, accumulated over the resolutions in double and rounded once, and (coefs != NULL)
+ *                    coefs[n_res][WUNET_MEL_COEFS] = log_weight / (n_res count), lin_weight / (n_res count), the mean of |l_c - l_e|,
+ *                    the mean of |m_c - m_e|, with count = rows F n_mels;
+ *   per resolution:  wunet_mel_backward(saved, .., coefs + i * WUNET_MEL_COEFS, grad_loss, ..): the transposed projection dS = g Phi
+ *                    into `saved`, the adjoint GEMM into `scratch` (scratch_bytes >= wunet_mel_scratch_bytes(.., with_backward = 1); the
+ *                    forward's buffer may be reused after the finalize), then the STFT loss's overlap-add; grad_enhanced =
+ *                    (accumulate ? grad_enhanced : 0) + grad_loss[0] * d loss_i / d e, so several resolutions sum in the order of the
+ *                    calls.  filt, power, clamp and floor: the forward's.
+ * Caller-owned memory, no allocation, no synchronisation, no host read-back: every call can be captured. */
+#define WUNET_MEL_MAX_FILTERS 128
+#define WUNET_MEL_COEFS 4        /* two gradient scales, two term values per resolution, double */
+size_t wunet_mel_scratch_bytes(size_t rows, size_t row_len, int n_fft, int hop, int with_backward);
+size_t wunet_mel_saved_bytes(size_t rows, size_t row_len, int n_fft, int hop, int n_mels);
+int wunet_mel_forward(const float* clean, const float* enhanced, size_t rows, size_t row_len, int n_fft, int hop, int win_length, int n_mels,
+                      const float* filt, int power, double clamp, double floor, const float* basis, void* scratch, size_t scratch_bytes,
+                      float* saved, size_t saved_bytes, float* mel_out, void* stream);
+int wunet_mel_finalize(int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop,
+                       const int* n_mels, double log_weight, double lin_weight, float* loss_out, double* coefs, void* stream);
+int wunet_mel_backward(float* saved, size_t saved_bytes, const double* coefs, const float* grad_loss, size_t rows, size_t row_len, int n_fft,
+                       int hop, int win_length, int n_mels, const float* filt, int power, double clamp, double floor, const float* basis,
+                       void* scratch, size_t scratch_bytes, float* grad_enhanced, int accumulate, void* stream);
+
+/* STOI per row(no reference counterpart on the device: the reference's validation epoch calls pystoi on the host per recording,
  * trainer/trainer.py:128-143, util/utils.py:116-117): Taal et al. 2011 with pystoi's choices for stoi(clean, estimate, fs,
  * extended=False) - resample_poly to 10 kHz with pystoi's Kaiser filter, removal of the frames (256 / hop 128, hanning(258)[1:-1])
  * more than 40 dB below the clean row's loudest, 512-point spectra of the overlap-added rest, 15 third-octave bands from 150 Hz,

@@ -9,4 +9,5 @@ every plugin - by string through importlib (util/utils.py:55-72):
 from .model import Model  # noqa: F401
 from .loss import mse_loss, l1_loss, smooth_l1_loss, si_sdr_loss, snr_loss, stft_loss, stoi_loss, weighted_loss  # noqa: F401
 from .loss import compressed_spectral_loss, HipCompressedSpectralLoss  # noqa: F401
-from .metrics import si_sdr, snr, si_sdr_improvement, stft_magnitude, stoi, sdr, sdr_improvement  # noqa: F401
+from .loss import mel_loss, mel_filterbank, HipMelLoss  # noqa: F401
+from .metrics import si_sdr, snr, si_sdr_improvement, stft_magnitude, stoi, sdr, sdr_improvement, mel_spectrogram  # noqa: F401

@@ -24,6 +24,7 @@ EXPORTS = [
     "wunet_stft_basis_bytes", "wunet_stft_basis", "wunet_stft_scratch_bytes", "wunet_stft_saved_bytes", "wunet_stft_forward",
     "wunet_stft_finalize", "wunet_stft_backward",
     "wunet_cspec_scratch_bytes", "wunet_cspec_saved_bytes", "wunet_cspec_forward", "wunet_cspec_finalize", "wunet_cspec_backward",
+    "wunet_mel_scratch_bytes", "wunet_mel_saved_bytes", "wunet_mel_forward", "wunet_mel_finalize", "wunet_mel_backward",
     "wunet_stoi_tables_bytes", "wunet_stoi_tables_build", "wunet_stoi_scratch_bytes", "wunet_stoi_forward",
     "wunet_stoi_loss_scratch_bytes", "wunet_stoi_loss_saved_bytes", "wunet_stoi_loss_forward", "wunet_stoi_loss_backward",
     "wunet_estoi_scratch_bytes", "wunet_estoi_forward",
@@ -83,6 +84,16 @@ def declare(lib):
         lib.wunet_cspec_forward.argtypes = [_vp, _vp, _sz, _sz, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _sz, _vp, _sz, _vp]
         lib.wunet_cspec_finalize.argtypes = [_i, _vp, _sz, _sz, _vp, _vp, ctypes.c_double, _vp, _vp, _vp]
         lib.wunet_cspec_backward.argtypes = [_vp, _sz, _vp, _vp, _sz, _sz, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _sz, _vp, _i, _vp]
+    if hasattr(lib, "wunet_mel_forward"):        # (saved libraries of earlier versions do not have it)
+        lib.wunet_mel_scratch_bytes.argtypes = [_sz, _sz, _i, _i, _i]
+        lib.wunet_mel_scratch_bytes.restype = _sz
+        lib.wunet_mel_saved_bytes.argtypes = [_sz, _sz, _i, _i, _i]
+        lib.wunet_mel_saved_bytes.restype = _sz
+        lib.wunet_mel_forward.argtypes = [_vp, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _sz, _vp, _sz,
+                                          _vp, _vp]
+        lib.wunet_mel_finalize.argtypes = [_i, _vp, _sz, _sz, _vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]
+        lib.wunet_mel_backward.argtypes = [_vp, _sz, _vp, _vp, _sz, _sz, _i, _i, _i, _i, _vp, _i, ctypes.c_double, ctypes.c_double, _vp, _vp, _sz,
+                                           _vp, _i, _vp]
     if hasattr(lib, "wunet_stoi_forward"):       # (saved libraries of earlier versions do not have it)
         lib.wunet_stoi_tables_bytes.argtypes = [_i]
         lib.wunet_stoi_tables_bytes.restype = _sz

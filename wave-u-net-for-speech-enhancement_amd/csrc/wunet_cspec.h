@@ -93,16 +93,16 @@ static __global__ __launch_bounds__(WUNET_THREADS) void cspec_fwd_kernel(CspecFw
 struct CspecFinalArgs {
     const double* part[WUNET_STFT_MAX_RES];
     unsigned nparts[WUNET_STFT_MAX_RES];
-    double count[WUNET_STFT_MAX_RES];      // rows * F * bins
+    double count[WUNET_STFT_MAX_RES];      // rows * F * bins (wunet_mel.h: rows * F * n_mels)
     int n_res;
-    double lambda;                         // complex_weight
+    double w0, w1;                         // the weights of the two sums: 1 - complex_weight, complex_weight (wunet_mel.h: log_weight, lin_weight)
     float* loss;
     double* coefs;                         // nullptr or [n_res][WUNET_CSPEC_NCOEF]
 };
 
 // ONE block over the table of resolutions, stft_final_kernel's order of sums.  mag = mean (A_c - A_e)^2, cplx = mean |Z_c - Z_e|^2;
-// coefs = (1 - lambda) / (n_res count), lambda / (n_res count), mag, cplx.  The loss is accumulated over the resolutions in double
-// and rounded once.
+// coefs = w0 / (n_res count), w1 / (n_res count), mag, cplx.  The loss is accumulated over the resolutions in double and rounded
+// once.  Also the finalize of the mel loss (wunet_mel.h), whose two sums are |l_c - l_e| and |m_c - m_e|.
 static __global__ __launch_bounds__(WUNET_THREADS) void cspec_final_kernel(CspecFinalArgs A)
 {
     __shared__ double red[2 * WUNET_WAVES];
@@ -116,11 +116,11 @@ static __global__ __launch_bounds__(WUNET_THREADS) void cspec_final_kernel(Cspec
         }
         block_sum<2>(sum, red);
         const double mag = sum[0] / A.count[i], cplx = sum[1] / A.count[i];
-        total += (1.0 - A.lambda) * mag + A.lambda * cplx;
+        total += A.w0 * mag + A.w1 * cplx;
         if (tid == 0 && A.coefs) {
             double* o = A.coefs + (size_t)i * WUNET_CSPEC_NCOEF;
-            o[0] = (1.0 - A.lambda) / ((double)A.n_res * A.count[i]);
-            o[1] = A.lambda / ((double)A.n_res * A.count[i]);
+            o[0] = A.w0 / ((double)A.n_res * A.count[i]);
+            o[1] = A.w1 / ((double)A.n_res * A.count[i]);
             o[2] = mag;
             o[3] = cplx;
         }

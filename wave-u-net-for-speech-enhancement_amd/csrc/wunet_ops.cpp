@@ -8,6 +8,7 @@
 #include "wunet_loss_rows.h"
 #include "wunet_stft.h"
 #include "wunet_cspec.h"
+#include "wunet_mel.h"
 #include "wunet_stoi.h"
 #include "wunet_estoi.h"
 #include "wunet_mix.h"
@@ -149,13 +150,20 @@ int stft_shape(size_t rows, size_t T, int N, int H, int W, StftShape& s)
 }
 inline size_t stft_nparts(const StftShape& s) { return (size_t)s.mtiles * (size_t)(s.BP / WUNET_STFT_BN); }
 
-// ---- one host path for the STFT loss and the compressed spectral loss (wunet_cspec.h); `what` ("stft" / "cspec") starts the messages
-// the resolution of one call (stft_shape's messages say "stft" for both); what == nullptr: a size query, an empty row is 0 without a message
+// ---- one host path for the STFT loss, the compressed spectral loss (wunet_cspec.h) and the mel loss (wunet_mel.h); `what` ("stft" /
+// "cspec" / "mel") starts the messages
+// the resolution of one call (stft_shape's messages say "stft" for all); what == nullptr: a size query, an empty row is 0 without a message
 int spectral_shape(const char* what, size_t rows, size_t row_len, int n_fft, int hop, int win_length, StftShape& s)
 {
     if (row_len == 0) return what ? fail(WUNET_E_ARG, "%s: row_len must be > 0", what) : WUNET_E_ARG;
     return stft_shape(rows, row_len, n_fft, hop, win_length, s);
 }
+int mel_filters(int n_mels)
+{
+    return n_mels < 1 || n_mels > WUNET_MEL_MAX ? fail(WUNET_E_ARG, "mel: n_mels must be in 1 .. %d (got %d)", WUNET_MEL_MAX, n_mels) : 0;
+}
+// the blocks of mel_proj_kernel: WUNET_MEL_FM frames each
+inline unsigned mel_blocks(const StftShape& s) { return (s.M + WUNET_MEL_FM - 1) / WUNET_MEL_FM; }
 // the forward's partials (`fwd` bytes), or with `bwd` the adjoint GEMM's M x n_fft floats where those are more
 inline size_t spectral_scratch(const StftShape& s, size_t fwd, int bwd) { const size_t b = bwd ? (size_t)s.M * s.N * sizeof(float) : 0; return b > fwd ? b : fwd; }
 // StftFwdArgs of one resolution (CspecFwdArgs carries one as .S); returns the forward's grid.  (extern "C++", here and on the two templates
@@ -167,15 +175,20 @@ extern "C++" dim3 fill_fwd_args(StftFwdArgs& A, const StftShape& s, const float*
     A.k0 = s.k0; A.k1 = s.k1; A.clamp = (float)clamp; A.part = (double*)scratch; A.saved = saved; A.mag_out = mag_out;
     return dim3(s.mtiles, (unsigned)(s.BP / WUNET_STFT_BN));
 }
-// part / nparts / count of StftFinalArgs or CspecFinalArgs: one entry per resolution
+// part / nparts / count of StftFinalArgs or CspecFinalArgs: one entry per resolution.  n_mels (the mel loss): one partial per block
+// of mel_proj_kernel, and the mean runs over the mel cells, not the bins
 extern "C++" template <class Args>
-int fill_final_args(Args& A, const char* what, int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop)
+int fill_final_args(Args& A, const char* what, int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop,
+                    const int* n_mels = nullptr)
 {
     for (int i = 0; i < n_res; ++i) {
         StftShape s{};
         if (spectral_shape(what, rows, row_len, n_fft[i], hop[i], 1, s)) return WUNET_E_ARG;
         if (!scratch[i]) return fail(WUNET_E_ARG, "%s: null scratch of resolution %d", what, i);
-        A.part[i] = (const double*)scratch[i]; A.nparts[i] = (unsigned)stft_nparts(s); A.count[i] = (double)s.M * (double)s.bins;
+        if (n_mels && mel_filters(n_mels[i])) return WUNET_E_ARG;
+        A.part[i] = (const double*)scratch[i];
+        A.nparts[i] = n_mels ? mel_blocks(s) : (unsigned)stft_nparts(s);
+        A.count[i] = (double)s.M * (double)(n_mels ? n_mels[i] : s.bins);
     }
     return 0;
 }
@@ -203,6 +216,19 @@ int launch_stft_ola(const StftShape& s, const void* scratch, const float* grad_l
 }
 inline size_t cspec_fwd_bytes(const StftShape& s) { return stft_nparts(s) * 2 * sizeof(double); }
 inline size_t cspec_saved(const StftShape& s) { return (size_t)WUNET_CSPEC_PLANES * s.M * s.BP * sizeof(float); }
+// the mel loss's forward scratch: one partial (two doubles) per block of mel_proj_kernel, then the planes S_e, S_c [M][BP] (mel_spec_kernel -> mel_proj_kernel)
+inline size_t mel_part_bytes(const StftShape& s) { return (size_t)mel_blocks(s) * 2 * sizeof(double); }
+inline size_t mel_fwd_bytes(const StftShape& s) { return mel_part_bytes(s) + (size_t)2 * s.M * s.BP * sizeof(float); }
+inline int mel_padded(int n_mels) { return (n_mels + 15) & ~15; }
+inline size_t mel_saved(const StftShape& s, int n_mels) { return MelLayout(s.M, s.BP, mel_padded(n_mels)).floats() * sizeof(float); }
+// power, clamp and floor of one call; `loss`: the pair (clamp and floor > 0), else the spectrogram alone (>= 0)
+int mel_knobs(int power, double clamp, double floor, bool loss)
+{
+    if (power != 1 && power != 2) return fail(WUNET_E_ARG, "mel: power must be 1 or 2 (got %d)", power);
+    if (!(loss ? clamp > 0.0 : clamp >= 0.0) || clamp > 3.0e38) return fail(WUNET_E_ARG, "mel: clamp must be finite and %s 0 (got %g)", loss ? ">" : ">=", clamp);
+    if (!(loss ? floor > 0.0 : floor >= 0.0) || floor > 3.0e38) return fail(WUNET_E_ARG, "mel: floor must be finite and %s 0 (got %g)", loss ? ">" : ">=", floor);
+    return 0;
+}
 int cspec_knobs(double compress, double clamp)
 {
     if (!(compress > 0.0) || compress > 1.0) return fail(WUNET_E_ARG, "cspec: compress must be in (0, 1] (got %g)", compress);
@@ -344,7 +370,7 @@ int wunet_cspec_finalize(int n_res, const void* const* scratch, size_t rows, siz
     if (!(complex_weight >= 0.0) || complex_weight > 1.0) return fail(WUNET_E_ARG, "cspec: complex_weight must be in [0, 1] (got %g)", complex_weight);
     CspecFinalArgs A{};
     if (fill_final_args(A, "cspec", n_res, scratch, rows, row_len, n_fft, hop)) return WUNET_E_ARG;
-    A.n_res = n_res; A.lambda = complex_weight; A.loss = loss_out; A.coefs = coefs;
+    A.n_res = n_res; A.w0 = 1.0 - complex_weight; A.w1 = complex_weight; A.loss = loss_out; A.coefs = coefs;
     WUNET_LAUNCH(cspec_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, (hipStream_t)stream, A);
     WUNET_CHECK_LAUNCH();
     return WUNET_OK;
@@ -367,6 +393,110 @@ int wunet_cspec_backward(const float* saved, size_t saved_bytes, const double* c
     B.compress = compress; B.hs = 0.5 * (compress - 1.0);
     fill_adjoint_args(B, "cspec_bwd_kernel", WUNET_CSPEC_PLANES, s, saved, coefs, basis, clamp, scratch, st);
     WUNET_LAUNCH(cspec_bwd_kernel, dim3(B.ktiles * s.mtiles), dim3(WUNET_THREADS), 0, st, B);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return launch_stft_ola(s, scratch, grad_loss, grad_enhanced, accumulate, st);
+}
+
+// ---------------------------------------------------------------------------- multi-scale log-mel loss (wunet_mel.h)
+size_t wunet_mel_scratch_bytes(size_t rows, size_t row_len, int n_fft, int hop, int with_backward)
+{
+    StftShape s{};
+    return spectral_shape(nullptr, rows, row_len, n_fft, hop, 1, s) ? 0 : spectral_scratch(s, mel_fwd_bytes(s), with_backward);
+}
+
+size_t wunet_mel_saved_bytes(size_t rows, size_t row_len, int n_fft, int hop, int n_mels)
+{
+    StftShape s{};
+    return spectral_shape(nullptr, rows, row_len, n_fft, hop, 1, s) || mel_filters(n_mels) ? 0 : mel_saved(s, n_mels);
+}
+
+int wunet_mel_forward(const float* clean, const float* enhanced, size_t rows, size_t row_len, int n_fft, int hop, int win_length, int n_mels,
+                      const float* filt, int power, double clamp, double floor, const float* basis, void* scratch, size_t scratch_bytes,
+                      float* saved, size_t saved_bytes, float* mel_out, void* stream)
+{
+    StftShape s{};
+    if (spectral_shape("mel", rows, row_len, n_fft, hop, win_length, s) || mel_filters(n_mels) || mel_knobs(power, clamp, floor, clean != nullptr))
+        return WUNET_E_ARG;
+    if (!enhanced || !basis || !filt || (((size_t)basis | (size_t)filt) & 15))
+        return fail(WUNET_E_ARG, "mel: null argument (or a basis or a filterbank that is not 16-byte aligned)");
+    if (!scratch || ((size_t)scratch & 15) || scratch_bytes < mel_fwd_bytes(s))
+        return fail(WUNET_E_ARG, "mel: the forward needs %zu bytes of 16-byte aligned scratch for this resolution (got %zu)", mel_fwd_bytes(s), scratch_bytes);
+    if (clean) {
+        if (saved ? saved_bytes != mel_saved(s, n_mels) || ((size_t)saved & 15) : saved_bytes != 0)
+            return fail(WUNET_E_ARG, "mel: saved must be the %zu bytes (16-byte aligned) of wunet_mel_saved_bytes for this resolution, or NULL and 0 (got %zu)",
+                        mel_saved(s, n_mels), saved_bytes);
+        if (mel_out) return fail(WUNET_E_ARG, "mel: mel_out belongs to the call without `clean`");
+    } else if (!mel_out || saved || saved_bytes) {
+        return fail(WUNET_E_ARG, "mel: without `clean` the call writes mel_out only (saved NULL and 0)");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const double nsig = clean ? 2.0 : 1.0;
+    MelSpecArgs C{};
+    const dim3 grid = fill_fwd_args(C.S, s, clean, enhanced, clamp, basis, nullptr, saved, nullptr);
+    C.spec = (float*)((char*)scratch + mel_part_bytes(s)); C.power = power;
+    prof_begin(st, clean ? "mel_spec_kernel<pair>" : "mel_spec_kernel<one>", nsig * 2.0 * s.M * (s.k1 - s.k0) * 2.0 * s.BP,
+               4.0 * (nsig * rows * row_len + (double)(s.k1 - s.k0) * 2.0 * s.BP + (nsig + (saved ? 2.0 : 0.0)) * s.M * s.BP));
+    if (clean) {
+        WUNET_LAUNCH(mel_spec_kernel<true>, grid, dim3(WUNET_THREADS), 0, st, C);
+    } else {
+        WUNET_LAUNCH(mel_spec_kernel<false>, grid, dim3(WUNET_THREADS), 0, st, C);
+    }
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    MelProjArgs P{};
+    P.spec = C.spec; P.filt = filt; P.M = s.M; P.BP = s.BP; P.bins = s.bins; P.n_mels = n_mels; P.MP = mel_padded(n_mels); P.floor = floor;
+    P.part = (double*)scratch; P.saved = saved; P.mel_out = mel_out;
+    prof_begin(st, clean ? "mel_proj_kernel<pair>" : "mel_proj_kernel<one>", nsig * 2.0 * s.M * s.bins * n_mels,
+               4.0 * (nsig * s.M * s.BP + (double)n_mels * s.BP + (saved ? 2.0 * s.M * P.MP : 0.0) + (mel_out ? (double)s.M * n_mels : 0.0)));
+    if (clean) {
+        WUNET_LAUNCH(mel_proj_kernel<true>, dim3(mel_blocks(s)), dim3(WUNET_THREADS), 0, st, P);
+    } else {
+        WUNET_LAUNCH(mel_proj_kernel<false>, dim3(mel_blocks(s)), dim3(WUNET_THREADS), 0, st, P);
+    }
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_mel_finalize(int n_res, const void* const* scratch, size_t rows, size_t row_len, const int* n_fft, const int* hop, const int* n_mels,
+                       double log_weight, double lin_weight, float* loss_out, double* coefs, void* stream)
+{
+    if (n_res < 1 || n_res > WUNET_STFT_MAX_RES) return fail(WUNET_E_ARG, "mel: 1 .. %d resolutions per call (got %d)", WUNET_STFT_MAX_RES, n_res);
+    if (!scratch || !n_fft || !hop || !n_mels || !loss_out) return fail(WUNET_E_ARG, "mel: null argument");
+    if (!(log_weight >= 0.0) || !(lin_weight >= 0.0) || log_weight > 1.0e300 || lin_weight > 1.0e300 || log_weight + lin_weight == 0.0)
+        return fail(WUNET_E_ARG, "mel: log_weight and lin_weight must be finite and >= 0, not both 0 (got %g, %g)", log_weight, lin_weight);
+    CspecFinalArgs A{};
+    if (fill_final_args(A, "mel", n_res, scratch, rows, row_len, n_fft, hop, n_mels)) return WUNET_E_ARG;
+    A.n_res = n_res; A.w0 = log_weight; A.w1 = lin_weight; A.loss = loss_out; A.coefs = coefs;
+    WUNET_LAUNCH(cspec_final_kernel, dim3(1), dim3(WUNET_THREADS), 0, (hipStream_t)stream, A);
+    WUNET_CHECK_LAUNCH();
+    return WUNET_OK;
+}
+
+int wunet_mel_backward(float* saved, size_t saved_bytes, const double* coefs, const float* grad_loss, size_t rows, size_t row_len, int n_fft,
+                       int hop, int win_length, int n_mels, const float* filt, int power, double clamp, double floor, const float* basis,
+                       void* scratch, size_t scratch_bytes, float* grad_enhanced, int accumulate, void* stream)
+{
+    StftShape s{};
+    if (spectral_shape("mel", rows, row_len, n_fft, hop, win_length, s) || mel_filters(n_mels) || mel_knobs(power, clamp, floor, true)) return WUNET_E_ARG;
+    if (!saved || !coefs || !grad_loss || !basis || !filt || !grad_enhanced || (((size_t)basis | (size_t)filt | (size_t)saved) & 15))
+        return fail(WUNET_E_ARG, "mel: null argument (or a basis, a filterbank or a saved buffer that is not 16-byte aligned)");
+    if (saved_bytes != mel_saved(s, n_mels))
+        return fail(WUNET_E_ARG, "mel: saved must be the %zu bytes of wunet_mel_saved_bytes for this resolution (got %zu)", mel_saved(s, n_mels), saved_bytes);
+    if (!scratch || scratch_bytes < spectral_scratch(s, 0, 1))
+        return fail(WUNET_E_ARG, "mel: the backward needs %zu bytes of scratch for this resolution (got %zu)", spectral_scratch(s, 0, 1), scratch_bytes);
+    hipStream_t st = (hipStream_t)stream;
+    MelProjBwdArgs P{};
+    P.saved = saved; P.coefs = coefs; P.filt = filt; P.M = s.M; P.BP = s.BP; P.n_mels = n_mels; P.MP = mel_padded(n_mels); P.floor = floor;
+    prof_begin(st, "mel_proj_bwd_kernel", 2.0 * s.M * s.BP * n_mels, 4.0 * (2.0 * s.M * P.MP + (double)n_mels * s.BP + (double)s.M * s.BP));
+    WUNET_LAUNCH(mel_proj_bwd_kernel, dim3(s.mtiles, (unsigned)((s.BP + WUNET_STFT_BWN - 1) / WUNET_STFT_BWN)), dim3(WUNET_THREADS), 0, st, P);
+    prof_end(st);
+    WUNET_CHECK_LAUNCH();
+    MelBwdArgs B{};
+    B.power = power;
+    fill_adjoint_args(B, "mel_bwd_kernel", WUNET_MEL_PLANES, s, saved, coefs, basis, clamp, scratch, st);
+    WUNET_LAUNCH(mel_bwd_kernel, dim3(B.ktiles * s.mtiles), dim3(WUNET_THREADS), 0, st, B);
     prof_end(st);
     WUNET_CHECK_LAUNCH();
     return launch_stft_ola(s, scratch, grad_loss, grad_enhanced, accumulate, st);

@@ -86,20 +86,25 @@ def _load_torch_ext():
 STFT_COEFS = 4                       # WUNET_STFT_COEFS of include/wunet_hip.h: a, b, sc, mag per resolution
 STFT_MAX_RESOLUTIONS = 8             # WUNET_STFT_MAX_RESOLUTIONS
 CSPEC_COEFS = 4                      # WUNET_CSPEC_COEFS: the two gradient scales, the two term values per resolution (wunet_cspec_*)
+MEL_COEFS = 4                        # WUNET_MEL_COEFS: likewise (wunet_mel_*)
+MEL_MAX_FILTERS = 128                # WUNET_MEL_MAX_FILTERS
 
 
 class _SpectralFamily:
-    """What tells the two spectral losses apart on their one host path (Engine._spectral_loss_*): c - the entry points are wunet_<c>_*;
+    """What tells the spectral losses apart on their one host path (Engine._spectral_loss_*): c - the entry points are wunet_<c>_*;
     what - starts the messages; coefs - float64 values per resolution; cspec - wunet_cspec_*'s call shape: scalars (compress, clamp) not
     (clamp,), one finalize weight not two, byte counts behind the scratch and saved pointers (wunet_stft_forward: mag_out); saved_by_dtype
-    - the backward holds saved[i] to float32 and leaves its size to the C call, else it holds its bytes to wunet_<c>_saved_bytes."""
+    - the backward holds saved[i] to float32 and leaves its size to the C call, else it holds its bytes to wunet_<c>_saved_bytes; mel -
+    wunet_mel_*'s call shape: cspec's byte counts, and per resolution a filterbank (n_mels, filt) in front of the scalars (power, clamp,
+    floor), n_mels in the saved-size query and in the finalize's table, two finalize weights."""
 
-    def __init__(self, c, what, coefs, cspec, saved_by_dtype):
-        self.c, self.what, self.coefs, self.cspec, self.saved_by_dtype = c, what, coefs, cspec, saved_by_dtype
+    def __init__(self, c, what, coefs, cspec, saved_by_dtype, mel=False):
+        self.c, self.what, self.coefs, self.cspec, self.saved_by_dtype, self.mel = c, what, coefs, cspec, saved_by_dtype, mel
 
 
 _STFT = _SpectralFamily("stft", "stft loss", STFT_COEFS, False, False)
 _CSPEC = _SpectralFamily("cspec", "compressed spectral loss", CSPEC_COEFS, True, True)
+_MEL = _SpectralFamily("mel", "mel loss", MEL_COEFS, False, True, mel=True)
 
 
 def _ptr(t):
@@ -116,6 +121,61 @@ def check_stft_resolution(n_fft, hop, win_length):
     if win_length < 1 or win_length > n_fft:
         raise ValueError(f"stft: win_length must be in 1 .. n_fft (got {win_length}, n_fft {n_fft})")
     return n_fft, hop, win_length
+
+
+def _hz_to_mel(f, mel_scale):
+    import numpy as np
+    f = np.asarray(f, dtype=np.float64)
+    if mel_scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    return np.where(f < 1000.0, f / (200.0 / 3.0), 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / (np.log(6.4) / 27.0))
+
+
+def _mel_to_hz(m, mel_scale):
+    import numpy as np
+    m = np.asarray(m, dtype=np.float64)
+    if mel_scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m < 15.0, m * (200.0 / 3.0), 1000.0 * np.exp((np.log(6.4) / 27.0) * (np.maximum(m, 15.0) - 15.0)))
+
+
+def mel_filterbank(sample_rate, n_fft, n_mels, fmin=0.0, fmax=None, mel_scale="slaney", norm="slaney"):
+    """The triangular mel filterbank of the mel loss: a float32 [n_mels, n_fft // 2 + 1] CPU tensor, computed in float64 with numpy and
+    rounded once.  n_mels + 2 points equally spaced on the mel axis between mel(fmin) and mel(fmax) (fmax None: sample_rate / 2), mapped
+    back to Hz as p; filter j at the bin frequency f = b sample_rate / n_fft is max(0, min((f - p[j]) / (p[j+1] - p[j]),
+    (p[j+2] - f) / (p[j+2] - p[j+1]))).  mel_scale "htk": mel = 2595 log10(1 + f / 700); "slaney": f / (200 / 3) below 1000 Hz,
+    15 + ln(f / 1000) / (ln 6.4 / 27) from there up.  norm "slaney": row j times 2 / (p[j+2] - p[j]); None: peaks of 1.  These are the
+    formulas of librosa.filters.mel (whose defaults are the ones here); the agreement is by the formulas only - librosa was not at hand
+    to compare against.  A bank with filters that no bin falls under (all-zero rows) is allowed and warned about."""
+    import warnings
+    import numpy as np
+    sample_rate, n_fft, n_mels = float(sample_rate), int(n_fft), int(n_mels)
+    if not (sample_rate > 0.0 and sample_rate < float("inf")):
+        raise ValueError(f"mel_filterbank: sample_rate must be finite and > 0 (got {sample_rate})")
+    if n_fft < 2 or n_fft % 2:
+        raise ValueError(f"mel_filterbank: n_fft must be even and >= 2 (got {n_fft})")
+    if n_mels < 1 or n_mels > MEL_MAX_FILTERS:
+        raise ValueError(f"mel_filterbank: n_mels must be in 1 .. {MEL_MAX_FILTERS} (got {n_mels})")
+    fmax = sample_rate / 2.0 if fmax is None else float(fmax)
+    fmin = float(fmin)
+    if not (0.0 <= fmin < fmax <= sample_rate / 2.0):
+        raise ValueError(f"mel_filterbank: 0 <= fmin < fmax <= sample_rate / 2 (got fmin {fmin}, fmax {fmax}, sample_rate {sample_rate})")
+    if mel_scale not in ("slaney", "htk"):
+        raise ValueError(f"mel_filterbank: mel_scale is 'slaney' or 'htk' (got {mel_scale!r})")
+    if norm not in ("slaney", None):
+        raise ValueError(f"mel_filterbank: norm is 'slaney' or None (got {norm!r})")
+    p = _mel_to_hz(np.linspace(float(_hz_to_mel(fmin, mel_scale)), float(_hz_to_mel(fmax, mel_scale)), n_mels + 2), mel_scale)
+    f = np.arange(n_fft // 2 + 1, dtype=np.float64) * (sample_rate / n_fft)
+    up = (f[None, :] - p[:-2, None]) / (p[1:-1] - p[:-2])[:, None]
+    down = (p[2:, None] - f[None, :]) / (p[2:] - p[1:-1])[:, None]
+    fb = np.maximum(0.0, np.minimum(up, down))
+    if norm == "slaney":
+        fb *= (2.0 / (p[2:] - p[:-2]))[:, None]
+    empty = int((fb.max(axis=1) == 0.0).sum())
+    if empty:
+        warnings.warn(f"mel_filterbank: {empty} of {n_mels} filters have no bin under them at n_fft {n_fft} (all-zero rows): fewer mels or "
+                      "a larger n_fft would fill them")
+    return torch.from_numpy(fb.astype(np.float32))
 
 
 # ---------------------------------------------------------------------- STOI per row (include/wunet_hip.h: wunet_stoi_*)
@@ -182,8 +242,9 @@ class Engine:
         # Bumped by everything that rewrites weights WITHOUT moving a Python version counter: the replay of a captured step graph
         # (FusedAdam.advance_host_step) - part of the eval cache's signature, so an eval forward after N replays re-packs.
         self.weights_generation = 0
-        self._spectral = {}                           # "stft" / "cspec" -> their five C calls in self.lib (_spectral_calls)
+        self._spectral = {}                           # "stft" / "cspec" / "mel" -> their five C calls in self.lib (_spectral_calls)
         self._stft_bases = {}                         # (n_fft, win_length, device) -> windowed DFT basis (stft_basis)
+        self._mel_banks = {}                          # (device, sample_rate, n_fft, n_mels, fmin, fmax, mel_scale, norm) -> filterbank (mel_bank)
         self._stoi_tables_cache = {}                  # (sample rate, device) -> basis | window | resampler taps (stoi_tables)
         self._resample_taps_cache = {}                # (up, down, device) -> the resampling filter on the device (resample_taps)
         # per-step calls marshalled in C++ when the extension is built and this engine drives the HIP library it is linked to
@@ -524,8 +585,9 @@ class Engine:
             self._spectral[fam.c] = tuple(getattr(self.lib, f"wunet_{fam.c}_{n}") for n in ("scratch_bytes", "saved_bytes", "forward", "finalize", "backward"))
         return self._spectral[fam.c]
 
-    def _spectral_loss_forward(self, fam, clean, enhanced, resolutions, knobs, weights, with_backward):
-        """Both spectral losses: per resolution wunet_<c>_forward with the scalars `knobs`, then one wunet_<c>_finalize with `weights`."""
+    def _spectral_loss_forward(self, fam, clean, enhanced, resolutions, knobs, weights, with_backward, banks=None):
+        """Every spectral loss: per resolution wunet_<c>_forward with the scalars `knobs`, then one wunet_<c>_finalize with `weights`.
+        banks (the mel loss): per resolution (n_mels, filterbank on the device)."""
         R, T, dev = self._wave_pair(fam.what, clean, enhanced)
         n = len(resolutions)
         if n < 1 or n > STFT_MAX_RESOLUTIONS:
@@ -537,11 +599,16 @@ class Engine:
         where = str(dev)
         with self._device_guard(dev):
             st = self._stream(dev)
-            for N, H, W in resolutions:
+            for i, (N, H, W) in enumerate(resolutions):
                 basis = self._basis(N, W, dev, where)
                 scr = torch.empty(self._sized(scratch_bytes(R, T, N, H, 0)) // 8, dtype=torch.float64, device=dev)
-                sv = torch.empty(saved_bytes(R, T, N, H) // 4, dtype=torch.float32, device=dev) if with_backward else None
-                if fam.cspec:
+                more = (banks[i][0],) if fam.mel else ()
+                sv = torch.empty(saved_bytes(R, T, N, H, *more) // 4, dtype=torch.float32, device=dev) if with_backward else None
+                if fam.mel:
+                    rc = forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, banks[i][0], banks[i][1].data_ptr(), int(knobs[0]),
+                                 float(knobs[1]), float(knobs[2]), basis.data_ptr(), scr.data_ptr(), scr.numel() * 8, _ptr(sv),
+                                 sv.numel() * 4 if sv is not None else 0, None, st)
+                elif fam.cspec:
                     rc = forward(clean.data_ptr(), enhanced.data_ptr(), R, T, N, H, W, float(knobs[0]), float(knobs[1]), basis.data_ptr(),
                                  scr.data_ptr(), scr.numel() * 8, _ptr(sv), sv.numel() * 4 if sv is not None else 0, st)
                 else:
@@ -550,15 +617,18 @@ class Engine:
                 scratch.append(scr)
                 saved.append(sv)
             ffts, hops = (ctypes.c_int * n)(*[r[0] for r in resolutions]), (ctypes.c_int * n)(*[r[1] for r in resolutions])
-            if fam.cspec:
+            if fam.mel:
+                rc = finalize(n, self._ptrs(scratch), R, T, ffts, hops, (ctypes.c_int * n)(*[b[0] for b in banks]), float(weights[0]),
+                              float(weights[1]), out.data_ptr(), coefs.data_ptr(), st)
+            elif fam.cspec:
                 rc = finalize(n, self._ptrs(scratch), R, T, ffts, hops, float(weights[0]), out.data_ptr(), coefs.data_ptr(), st)
             else:
                 rc = finalize(n, self._ptrs(scratch), R, T, ffts, hops, float(weights[0]), float(weights[1]), out.data_ptr(), coefs.data_ptr(), st)
             self._check(rc)
         return out, coefs, (saved if with_backward else None)
 
-    def _spectral_loss_backward(self, fam, shape, resolutions, coefs, saved, grad_loss, knobs):
-        """Both spectral losses: per resolution wunet_<c>_backward with the scalars `knobs`; the first writes g, the others add to it."""
+    def _spectral_loss_backward(self, fam, shape, resolutions, coefs, saved, grad_loss, knobs, banks=None):
+        """Every spectral loss: per resolution wunet_<c>_backward with the scalars `knobs`; the first writes g, the others add to it."""
         n = len(resolutions)
         if coefs.dtype != torch.float64 or coefs.numel() != n * fam.coefs or not coefs.is_contiguous() or saved is None or len(saved) != n:
             raise WunetError(f"{fam.what}: coefs / saved must be those of {fam.c}_loss_forward over the same {n} resolutions")
@@ -578,7 +648,11 @@ class Engine:
                     raise WunetError(f"{fam.what}: saved[{i}] is not the buffer of resolution {(N, H, W)} on {tuple(shape)}")
                 scr = torch.empty(scratch_bytes(R, T, N, H, 1) // 4, dtype=torch.float32, device=dev)
                 basis = self._basis(N, W, dev, where)
-                if fam.cspec:
+                if fam.mel:
+                    rc = backward(sv.data_ptr(), sv.numel() * 4, coefs.data_ptr() + 8 * fam.coefs * i, gl.data_ptr(), R, T, N, H, W, banks[i][0],
+                                  banks[i][1].data_ptr(), int(knobs[0]), float(knobs[1]), float(knobs[2]), basis.data_ptr(), scr.data_ptr(),
+                                  scr.numel() * 4, g.data_ptr(), 1 if i else 0, st)
+                elif fam.cspec:
                     rc = backward(sv.data_ptr(), sv.numel() * 4, coefs.data_ptr() + 8 * fam.coefs * i, gl.data_ptr(), R, T, N, H, W, float(knobs[0]),
                                   float(knobs[1]), basis.data_ptr(), scr.data_ptr(), scr.numel() * 4, g.data_ptr(), 1 if i else 0, st)
                 else:
@@ -609,6 +683,61 @@ class Engine:
         """d loss / d enhanced (a tensor of `shape`) of the `cspec_loss_forward` that produced `coefs` and `saved`, times grad_loss (a
         scalar tensor).  The resolutions are added in their order: one fixed order of sums."""
         return self._spectral_loss_backward(_CSPEC, shape, resolutions, coefs, saved, grad_loss, (compress, clamp))
+
+    # ------------------------------------------------------------------ multi-scale log-mel loss (wunet_mel_*)
+    def mel_bank(self, device, sample_rate, n_fft, n_mels, fmin=0.0, fmax=None, mel_scale="slaney", norm="slaney"):
+        """(n_mels, filterbank [n_mels, BP] on `device`) of one key: loss.mel_filterbank's float32 rows padded with zeros to the bins
+        rounded up to 32, uploaded once - on the first (eager) call, so that a later graph capture sees no allocation (stft_basis's rule)."""
+        key = (str(device), float(sample_rate), int(n_fft), int(n_mels), float(fmin), None if fmax is None else float(fmax), mel_scale, norm)
+        bank = self._mel_banks.get(key)
+        if bank is None:
+            import warnings
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")          # (empty filters: the warning belongs to the construction of the loss)
+                fb = mel_filterbank(sample_rate, n_fft, n_mels, fmin, fmax, mel_scale, norm)
+            padded = torch.zeros(fb.shape[0], (fb.shape[1] + 31) // 32 * 32, dtype=torch.float32)
+            padded[:, :fb.shape[1]] = fb
+            bank = self._mel_banks[key] = (int(n_mels), padded.to(device))
+        return bank
+
+    def mel_loss_forward(self, clean, enhanced, resolutions, banks, power=1, log_weight=1.0, lin_weight=0.0, clamp=1e-7, floor=1e-5,
+                         with_backward=True):
+        """resolutions: a sequence of (n_fft, hop, win_length); banks: per resolution the pair of `mel_bank`.  The last dimension is the
+        utterance, all leading ones are flattened.  Returns (loss, coefs, saved): loss - device scalar; coefs - float64 [n_res, MEL_COEFS]
+        (the two gradient scales, the two term values per resolution); saved - one float32 buffer per resolution for `mel_loss_backward`
+        (None with with_backward=False)."""
+        if len(banks) != len(resolutions):
+            raise WunetError(f"mel loss: one filterbank per resolution (got {len(banks)} for {len(resolutions)})")
+        return self._spectral_loss_forward(_MEL, clean, enhanced, resolutions, (power, clamp, floor), (log_weight, lin_weight), with_backward, banks)
+
+    def mel_loss_backward(self, shape, resolutions, banks, coefs, saved, grad_loss, power=1, clamp=1e-7, floor=1e-5):
+        """d loss / d enhanced (a tensor of `shape`) of the `mel_loss_forward` that produced `coefs` and `saved`, times grad_loss (a scalar
+        tensor).  The resolutions are added in their order: one fixed order of sums.  The call writes into `saved` (the plane of dS)."""
+        if len(banks) != len(resolutions):
+            raise WunetError(f"mel loss: one filterbank per resolution (got {len(banks)} for {len(resolutions)})")
+        return self._spectral_loss_backward(_MEL, shape, resolutions, coefs, saved, grad_loss, (power, clamp, floor), banks)
+
+    def mel_spectrogram(self, x, bank, n_fft=512, hop=128, win_length=512, power=1, floor=0.0):
+        """The mel spectrogram of every row of x through `bank` (the pair of `mel_bank`; stft_magnitude's conventions, no clamp): float32
+        [rows, F, n_mels] - m, or ln max(m, floor) where floor > 0."""
+        self._require(x, "x")
+        if x.dtype != torch.float32 or x.dim() < 1 or x.numel() == 0:
+            raise WunetError(f"mel: expected a float32 waveform tensor, got {x.dtype} {tuple(x.shape)}")
+        n_fft, hop, win_length = check_stft_resolution(n_fft, hop, win_length)
+        T = x.shape[-1]
+        R = x.numel() // T
+        dev = x.device
+        n_mels, filt = bank
+        if filt.device != dev:
+            raise WunetError(f"mel: the filterbank lives on {filt.device}, x on {dev}")
+        out = torch.empty(R, 1 + T // hop, n_mels, dtype=torch.float32, device=dev)
+        with self._device_guard(dev):
+            basis = self.stft_basis(n_fft, win_length, dev)
+            scr = torch.empty(self._sized(self.lib.wunet_mel_scratch_bytes(R, T, n_fft, hop, 0)) // 8, dtype=torch.float64, device=dev)
+            self._check(self.lib.wunet_mel_forward(None, x.data_ptr(), R, T, n_fft, hop, win_length, n_mels, filt.data_ptr(), int(power), 0.0,
+                                                   float(floor), basis.data_ptr(), scr.data_ptr(), scr.numel() * 8, None, 0, out.data_ptr(),
+                                                   self._stream(dev)))
+        return out
 
     def stft_magnitude(self, x, n_fft=320, hop=160, win_length=320):
         """|STFT| of every row of x (periodic Hann, center=True, reflect padding - torch.stft's conventions): float32 [rows, F, n_fft/2 + 1]."""

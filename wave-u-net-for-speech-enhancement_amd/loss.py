@@ -40,11 +40,19 @@ below `clamp` (on the power) the compression factors are constants, so silence s
 
     "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "weighted_loss",
                       "args": {"terms": [["l1_loss", 1.0], ["compressed_spectral_loss", 0.5, {"compress": 0.3, "complex_weight": 0.3}]]}}
+
+`mel_loss` (no reference counterpart): the multi-scale log-mel spectrogram loss (HiFi-GAN's mel loss; the multi-scale mel loss of DAC /
+EnCodec-style codecs; include/wunet_hip.h: wunet_mel_*) - per resolution the L1 distance between the log-mel spectrograms
+ln max(Phi |S|^power, floor) of the two signals (log_weight) plus that between the mel spectrograms themselves (lin_weight), averaged;
+Phi is `mel_filterbank` (librosa's formulas); gradient with respect to `enhanced` only:
+
+    "loss_function": {"module": "wave-u-net-for-speech-enhancement_amd.loss", "main": "mel_loss", "args": {"sample_rate": 16000}}
+    ["mel_loss", 0.5, {"fft_sizes": [512, 1024], "hop_sizes": [128, 256], "win_lengths": [512, 1024], "n_mels": [40, 80]}]
 """
 import torch
 import torch.nn as nn
 
-from .engine import STFT_MAX_RESOLUTIONS, check_stft_resolution, check_stoi_rate, default_engine
+from .engine import MEL_MAX_FILTERS, STFT_MAX_RESOLUTIONS, check_stft_resolution, check_stoi_rate, default_engine, mel_filterbank  # noqa: F401
 
 
 class _LossFn(torch.autograd.Function):
@@ -213,6 +221,63 @@ def compressed_spectral_loss(fft_sizes=(512,), hop_sizes=(128,), win_lengths=(51
     return HipCompressedSpectralLoss(fft_sizes, hop_sizes, win_lengths, compress, complex_weight, clamp)
 
 
+class HipMelLoss(_EnhancedGradLoss):
+    """loss(clean, enhanced) -> mean over the resolutions of mean [log_weight |ln max(m_c, floor) - ln max(m_e, floor)| + lin_weight
+    |m_c - m_e|] with m = Phi max(P, clamp)^(power / 2), P = re^2 + im^2 of the STFT (stft_loss's conventions) and Phi the
+    `mel_filterbank` of (sample_rate, n_fft, n_mels[i], fmin, fmax, mel_scale, norm); the last dimension is the utterance.  Gradient with
+    respect to `enhanced` only.  The first call on a device uploads the filterbanks: capture a step graph after one eager call, as for
+    stft_loss."""
+    _no_clean_grad = "mel_loss: no gradient with respect to `clean`: detach it"
+
+    def __init__(self, sample_rate=16000, fft_sizes=(512, 1024, 2048), hop_sizes=(128, 256, 512), win_lengths=(512, 1024, 2048),
+                 n_mels=(40, 80, 128), fmin=0.0, fmax=None, mel_scale="slaney", norm="slaney", power=1.0, log_weight=1.0, lin_weight=0.0,
+                 clamp=1e-7, floor=1e-5):
+        super().__init__()
+        name = "mel_loss"
+        triples = _check_resolutions(name, fft_sizes, hop_sizes, win_lengths)
+        n_mels = [n_mels] * len(triples) if isinstance(n_mels, int) else list(n_mels)
+        if len(n_mels) != len(triples):
+            raise ValueError(f"{name}: n_mels must be one int or one per resolution (got {len(n_mels)} for {len(triples)} resolutions)")
+        if any(int(n) != n or n < 1 or n > MEL_MAX_FILTERS for n in n_mels):
+            raise ValueError(f"{name}: n_mels must be integers in 1 .. {MEL_MAX_FILTERS} (got {n_mels})")
+        if power not in (1, 2):
+            raise ValueError(f"{name}: power must be 1 or 2 (got {power})")
+        for what, v in (("log_weight", log_weight), ("lin_weight", lin_weight)):
+            if not (v >= 0.0 and v < float("inf")):
+                raise ValueError(f"{name}: {what} must be finite and >= 0 (got {v})")
+        if log_weight == 0.0 and lin_weight == 0.0:
+            raise ValueError(f"{name}: log_weight and lin_weight must not both be 0")
+        for what, v in (("clamp", clamp), ("floor", floor)):
+            if not (v > 0.0 and v < float("inf")):
+                raise ValueError(f"{name}: {what} must be finite and > 0 (got {v})")
+        self.resolutions = tuple(check_stft_resolution(n, h, w) for n, h, w in triples)
+        self.n_mels = tuple(int(n) for n in n_mels)
+        self.sample_rate, self.fmin, self.fmax, self.mel_scale, self.norm = float(sample_rate), float(fmin), fmax, mel_scale, norm
+        for (n, _, _), nm in zip(self.resolutions, self.n_mels):          # (every ValueError of the bank now, before anything runs)
+            mel_filterbank(self.sample_rate, n, nm, self.fmin, self.fmax, mel_scale, norm)
+        self.power, self.log_weight, self.lin_weight = int(power), float(log_weight), float(lin_weight)
+        self.clamp, self.floor = float(clamp), float(floor)
+
+    def _banks(self, engine, device):
+        return [engine.mel_bank(device, self.sample_rate, n, nm, self.fmin, self.fmax, self.mel_scale, self.norm)
+                for (n, _, _), nm in zip(self.resolutions, self.n_mels)]
+
+    def _loss_forward(self, engine, clean, enhanced):
+        loss, coefs, saved = engine.mel_loss_forward(clean, enhanced, self.resolutions, self._banks(engine, enhanced.device), self.power,
+                                                     self.log_weight, self.lin_weight, self.clamp, self.floor)
+        return loss, (coefs, *saved)
+
+    def _loss_backward(self, engine, shape, saved, grad_loss):
+        return engine.mel_loss_backward(shape, self.resolutions, self._banks(engine, saved[0].device), saved[0], list(saved[1:]), grad_loss,
+                                        self.power, self.clamp, self.floor)
+
+
+def mel_loss(sample_rate=16000, fft_sizes=(512, 1024, 2048), hop_sizes=(128, 256, 512), win_lengths=(512, 1024, 2048), n_mels=(40, 80, 128),
+             fmin=0.0, fmax=None, mel_scale="slaney", norm="slaney", power=1.0, log_weight=1.0, lin_weight=0.0, clamp=1e-7, floor=1e-5):
+    return HipMelLoss(sample_rate, fft_sizes, hop_sizes, win_lengths, n_mels, fmin, fmax, mel_scale, norm, power, log_weight, lin_weight,
+                      clamp, floor)
+
+
 class HipStoiLoss(_EnhancedGradLoss):
     """loss(clean, enhanced) -> -mean over rows of STOI (pystoi, extended=False; ESTOI with extended=True) at `sample_rate`; the last
     dimension is the utterance.  Gradient with respect to `enhanced` only.  The first call on a device builds the rate's tables (shared
@@ -267,7 +332,7 @@ class WeightedLoss(nn.Module):
 
 
 _FACTORIES = ("mse_loss", "l1_loss", "smooth_l1_loss", "si_sdr_loss", "snr_loss", "stft_loss", "stoi_loss")
-_SPECTRAL_FACTORIES = ("compressed_spectral_loss",)       # the factories added since: WeightedLoss consults both tuples
+_SPECTRAL_FACTORIES = ("compressed_spectral_loss", "mel_loss")       # the factories added since: WeightedLoss consults both tuples
 
 
 def weighted_loss(terms):

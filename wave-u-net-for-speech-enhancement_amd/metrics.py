@@ -62,6 +62,22 @@ def stft_magnitude(x, n_fft=320, hop=160, win_length=320, engine=None):
 
 
 @torch.no_grad()
+def mel_spectrogram(x, sample_rate=16000, n_fft=512, hop=128, win_length=512, n_mels=80, fmin=0.0, fmax=None, mel_scale="slaney",
+                    norm="slaney", power=1.0, log=False, floor=1e-5, engine=None):
+    """The mel spectrogram of every row of x on the device: m = Phi |STFT|^power with stft_magnitude's conventions (no clamp) and Phi
+    the `loss.mel_filterbank` of (sample_rate, n_fft, n_mels, fmin, fmax, mel_scale, norm) - the forward of `loss.mel_loss` for one
+    signal (include/wunet_hip.h: wunet_mel_forward without `clean`).  log=True: ln max(m, floor), natural log.
+    Returns float32 [rows, 1 + T // hop, n_mels]."""
+    if power not in (1, 2):
+        raise ValueError(f"mel_spectrogram: power must be 1 or 2 (got {power})")
+    if log and not (floor > 0.0 and floor < float("inf")):
+        raise ValueError(f"mel_spectrogram: floor must be finite and > 0 (got {floor})")
+    engine = engine if engine is not None else default_engine()
+    bank = engine.mel_bank(x.device, sample_rate, n_fft, n_mels, fmin, fmax, mel_scale, norm)
+    return engine.mel_spectrogram(x.detach().contiguous(), bank, n_fft, hop, win_length, int(power), float(floor) if log else 0.0)
+
+
+@torch.no_grad()
 def stoi(clean, estimate, sample_rate=16000, return_frames=False, engine=None, extended=False):
     """Short-time objective intelligibility of `estimate` against `clean`, per row: Taal et al. 2011 as pystoi computes it for
     stoi(clean, estimate, sample_rate, extended=False) - what the reference's validation epoch calls on the host at 16 kHz
