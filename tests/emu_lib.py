@@ -1,12 +1,15 @@
 """TEST INFRASTRUCTURE ONLY.  ctypes access to tests/emu/libwunet_emu.so: the product's kernel and
 host sources compiled against the CPU fiber emulator, with numpy arrays standing in for device memory."""
 import ctypes
+import importlib
 import os
 import subprocess
+import sys
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+_ROOT = os.path.dirname(_HERE)
 _LIB = None
 FP = ctypes.POINTER(ctypes.c_float)
 
@@ -18,11 +21,10 @@ def lib():
         with open(os.path.join(_HERE, "emu", ".build.lock"), "w") as lk:      # pytest-xdist workers must not rebuild concurrently
             fcntl.flock(lk, fcntl.LOCK_EX)
             subprocess.run(["make", "-C", os.path.join(_HERE, "emu"), "-s", "-j8"], check=True)
-        L = ctypes.CDLL(os.path.join(_HERE, "emu", "libwunet_emu.so"))
-        L.wunet_last_error.restype = ctypes.c_char_p
-        L.wunet_workspace_bytes.restype = ctypes.c_size_t
-        L.wunet_loss_scratch_bytes.restype = ctypes.c_size_t
-        _LIB = L
+        if _ROOT not in sys.path:
+            sys.path.insert(0, _ROOT)
+        declare = importlib.import_module("wave-u-net-for-speech-enhancement_amd._lib").declare     # the signatures of include/wunet_hip.h
+        _LIB = declare(ctypes.CDLL(os.path.join(_HERE, "emu", "libwunet_emu.so")))
     return _LIB
 
 

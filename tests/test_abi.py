@@ -17,17 +17,126 @@ def _declared():
     return sorted(set(re.findall(r"\b(wunet_[a-z0-9_]+)\s*\(", src)))
 
 
-def test_header_symbols_are_exported():
+def _built():
     lib_mod = importlib.import_module(PKG_NAME + "._lib")
     if not os.path.exists(lib_mod.LIB_PATH):
         import __graft_entry__
         __graft_entry__.build()
+    return lib_mod
+
+
+def test_header_symbols_are_exported():
+    lib_mod = _built()
     lib = ctypes.CDLL(lib_mod.LIB_PATH)          # HIP runtime initialises lazily: loading needs no GPU
     names = _declared()
     assert len(names) >= 18
     for name in names:
         assert hasattr(lib, name), f"{name} declared in include/wunet_hip.h but not exported"
     assert sorted(lib_mod.EXPORTS) == names, "engine binding list and header disagree"
+
+
+def _defined():
+    """The integer #defines of the header by this file's own regexp (like _declared: a second, independent reading)."""
+    src = open(os.path.join(ROOT, "include", "wunet_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return {name: int(value) for name, value in re.findall(r"#define\s+(WUNET_\w+)\s+\(?(-?\d+)\)?\s*$", src, flags=re.M)}
+
+
+def test_derived_signatures_carry_the_headers_types():
+    """ctypes passes and returns int where nothing is declared: the 64-bit returns and the float / double / long long parameters
+    are where a wrong table would truncate or pass garbage."""
+    c = ctypes
+    P = importlib.import_module(PKG_NAME + "._lib").PROTOTYPES
+    assert len(P) == 86
+    sized = [n for n in P if n.endswith("_bytes")]
+    tiles = [n for n in P if n.endswith("_tile")]
+    assert len(sized) == 20 and len(tiles) == 3
+    other = ["wunet_profile_collect", "wunet_last_error", "wunet_destroy", "wunet_comm_destroy", "wunet_debug_set_conv_trace"]
+    assert sorted(n for n in P if P[n][0] is not c.c_int) == sorted(sized + tiles + other)          # every other return is an int
+    for name in sized:
+        assert P[name][0] is c.c_size_t, name
+    for name in tiles + ["wunet_profile_collect"]:
+        assert P[name][0] is c.c_longlong, name
+    for name in ("wunet_destroy", "wunet_comm_destroy", "wunet_debug_set_conv_trace"):
+        assert P[name][0] is None, name
+    assert P["wunet_last_error"] == (c.c_char_p, [])
+    assert P["wunet_loss_scratch_bytes"] == (c.c_size_t, [])
+    for name, (restype, argtypes) in P.items():
+        assert restype in (c.c_int, c.c_size_t, c.c_longlong, c.c_char_p, None), name
+        assert all(t in (c.c_void_p, c.c_int, c.c_size_t, c.c_double, c.c_float, c.c_longlong) for t in argtypes), name
+        if restype is c.c_char_p:
+            assert name == "wunet_last_error"
+    mix = P["wunet_mix_windows"][1]
+    assert [i for i, t in enumerate(mix) if t is c.c_float] == [6] and c.c_double not in mix
+    assert all(c.c_float not in argtypes for name, (_, argtypes) in P.items() if name != "wunet_mix_windows")
+    adam = P["wunet_adam_step_ex"][1]
+    assert [i for i, t in enumerate(adam) if t is c.c_double] == [6, 7, 8, 9, 11, 12, 13]
+    assert [i for i, t in enumerate(adam) if t is c.c_longlong] == [10]
+    assert len(adam) == 19 and adam[0] is c.c_int and all(adam[i] is c.c_void_p for i in (1, 2, 3, 4, 5, 14, 15, 16, 17, 18))
+    assert P["wunet_create"] == (c.c_int, [c.c_int] * 4 + [c.c_void_p])
+    assert P["wunet_workspace_bytes"] == (c.c_size_t, [c.c_void_p, c.c_int])
+
+
+def test_parser_refuses_what_it_cannot_map(tmp_path):
+    lib_mod = importlib.import_module(PKG_NAME + "._lib")
+    ok, consts = lib_mod.parse_header("#define WUNET_A 3\n#define WUNET_B (-4) /* c */\n#define WUNET_GUARD\ntypedef struct s s;\n"
+                                      "long long wunet_x(const float* const* p /* [n] */,\n    size_t n);\nvoid wunet_y(void);")
+    assert ok == {"wunet_x": (ctypes.c_longlong, [ctypes.c_void_p, ctypes.c_size_t]), "wunet_y": (None, [])}
+    assert consts == {"WUNET_A": 3, "WUNET_B": -4}
+    for text in ("short wunet_x(unsigned n);", "int wunet_x(unsigned n);", "short wunet_x(int n);", "int wunet_x(int n, long m);",
+                 "void wunet_x(int n, char c);", "int wunet_x(int (*callback)(int));", "int wunet_x(int);", "int wunet_count;"):
+        with pytest.raises(TypeError, match="wunet_"):                 # (the message names the prototype)
+            lib_mod.parse_header(text)
+    with pytest.raises(RuntimeError, match="no fallback"):
+        lib_mod.read_header(str(tmp_path / "wunet_hip.h"))
+
+
+def test_python_constants_are_the_headers_defines():
+    mod = lambda name: importlib.import_module(PKG_NAME + "." + name)          # noqa: E731
+    D = _defined()
+    C = mod("_lib").CONSTANTS
+    assert C == D and len(D) == 24
+    assert C["WUNET_E_ARG"] == -1 and C["WUNET_E_RUNTIME"] == -2 and C["WUNET_OK"] == 0
+    eng = mod("engine")
+    assert eng.LOSS_KINDS == {"mse": D["WUNET_LOSS_MSE"], "l1": D["WUNET_LOSS_L1"], "smooth_l1": D["WUNET_LOSS_SMOOTH_L1"]}
+    assert eng.ROW_LOSS_KINDS == {"si_sdr": D["WUNET_LOSS_SI_SDR"], "snr": D["WUNET_LOSS_SNR"]}
+    assert len(set(eng.LOSS_KINDS.values()) | set(eng.ROW_LOSS_KINDS.values())) == 5
+    for m, name, define in [(eng, "LOSS_ROW_COEFS", "WUNET_LOSS_ROW_COEFS"), (eng, "STFT_COEFS", "WUNET_STFT_COEFS"),
+                            (eng, "STFT_MAX_RESOLUTIONS", "WUNET_STFT_MAX_RESOLUTIONS"), (eng, "CSPEC_COEFS", "WUNET_CSPEC_COEFS"),
+                            (eng, "MEL_COEFS", "WUNET_MEL_COEFS"), (eng, "MEL_MAX_FILTERS", "WUNET_MEL_MAX_FILTERS"),
+                            (eng, "ADAM_HYPER_FLOATS", "WUNET_ADAM_HYPER_FLOATS"),
+                            (mod("resample"), "MAX_RATIO", "WUNET_RESAMPLE_MAX_RATIO"), (mod("resample"), "MAX_TAPS", "WUNET_RESAMPLE_MAX_TAPS"),
+                            (mod("waveform_dataset"), "SOS_MAX_LEAD", "WUNET_SOS_MAX_LEAD"),
+                            (mod("waveform_dataset"), "RIR_MAX_TAPS", "WUNET_REVERB_MAX_TAPS"),
+                            (mod("filters"), "MAX_SECTIONS", "WUNET_SOS_MAX_SECTIONS"),
+                            (mod("parallel"), "COMM_ID_BYTES", "WUNET_COMM_ID_BYTES"), (mod("trainer"), "SDR_MAX_FILTER", "WUNET_BSS_MAX_FILTER")]:
+        assert getattr(m, name) == D[define], name
+    rs = mod("resample")
+    assert rs.MAX_TAPS == len(rs.design(rs.MAX_RATIO, 1))                        # the longest filter resample.design makes fits the cap
+    assert D["WUNET_FWD_SAVE"] == 1 and D["WUNET_FWD_PACKS_VALID"] == 2          # bits of one flag word
+
+
+def test_declare_skips_what_a_library_lacks():
+    """Saved libraries of earlier versions lack the newer entry points: declare neither raises nor invents them, and runs twice."""
+    lib_mod = importlib.import_module(PKG_NAME + "._lib")
+
+    class Fn:
+        restype, argtypes = ctypes.c_int, None
+
+    have = ["wunet_last_error", "wunet_workspace_bytes", "wunet_forward", "wunet_destroy"]
+    old = type("OldLibrary", (), {})()
+    for name in have:
+        setattr(old, name, Fn())
+    for _ in range(2):
+        assert lib_mod.declare(old) is old
+        assert sorted(vars(old)) == sorted(have)
+        for name in have:
+            assert (getattr(old, name).restype, getattr(old, name).argtypes) == lib_mod.PROTOTYPES[name]
+    real = ctypes.CDLL(_built().LIB_PATH)
+    assert lib_mod.declare(lib_mod.declare(real)) is real
+    for name in lib_mod.EXPORTS:
+        fn = getattr(real, name)
+        assert (fn.restype, list(fn.argtypes)) == lib_mod.PROTOTYPES[name], name
 
 
 def test_shape_errors_come_back_as_codes_not_crashes():

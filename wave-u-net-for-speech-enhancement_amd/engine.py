@@ -11,9 +11,10 @@ import torch
 
 from . import _lib
 
-LOSS_KINDS = {"mse": 0, "l1": 1, "smooth_l1": 2}
-ROW_LOSS_KINDS = {"si_sdr": 3, "snr": 4}      # WUNET_LOSS_SI_SDR / WUNET_LOSS_SNR: per-row criteria, wunet_loss_rows_* only
-LOSS_ROW_COEFS = 6                             # WUNET_LOSS_ROW_COEFS of include/wunet_hip.h
+_C = _lib.CONSTANTS                            # the #defines of include/wunet_hip.h
+LOSS_KINDS = {k: _C["WUNET_LOSS_" + k.upper()] for k in ("mse", "l1", "smooth_l1")}
+ROW_LOSS_KINDS = {k: _C["WUNET_LOSS_" + k.upper()] for k in ("si_sdr", "snr")}      # per-row criteria, wunet_loss_rows_* only
+LOSS_ROW_COEFS = _C["WUNET_LOSS_ROW_COEFS"]
 
 
 class WunetError(RuntimeError):
@@ -83,11 +84,11 @@ def _load_torch_ext():
 
 
 # ---------------------------------------------------------------------- multi-resolution STFT loss (include/wunet_hip.h: wunet_stft_*)
-STFT_COEFS = 4                       # WUNET_STFT_COEFS of include/wunet_hip.h: a, b, sc, mag per resolution
-STFT_MAX_RESOLUTIONS = 8             # WUNET_STFT_MAX_RESOLUTIONS
-CSPEC_COEFS = 4                      # WUNET_CSPEC_COEFS: the two gradient scales, the two term values per resolution (wunet_cspec_*)
-MEL_COEFS = 4                        # WUNET_MEL_COEFS: likewise (wunet_mel_*)
-MEL_MAX_FILTERS = 128                # WUNET_MEL_MAX_FILTERS
+STFT_COEFS = _C["WUNET_STFT_COEFS"]                       # a, b, sc, mag per resolution
+STFT_MAX_RESOLUTIONS = _C["WUNET_STFT_MAX_RESOLUTIONS"]
+CSPEC_COEFS = _C["WUNET_CSPEC_COEFS"]                     # the two gradient scales, the two term values per resolution (wunet_cspec_*)
+MEL_COEFS = _C["WUNET_MEL_COEFS"]                         # likewise (wunet_mel_*)
+MEL_MAX_FILTERS = _C["WUNET_MEL_MAX_FILTERS"]
 
 
 class _SpectralFamily:
@@ -218,7 +219,7 @@ def check_stoi_rate(sample_rate):
     return fs
 
 
-ADAM_HYPER_FLOATS = 8                # WUNET_ADAM_HYPER_FLOATS of include/wunet_hip.h
+ADAM_HYPER_FLOATS = _C["WUNET_ADAM_HYPER_FLOATS"]
 
 
 class Engine:
@@ -428,7 +429,7 @@ class Engine:
             reuse = cache is not None and cache[0].numel() * 4 >= nbytes
             ws = cache[0] if reuse else torch.empty(nbytes // 4, dtype=torch.float32, device=noisy.device)
             out = torch.empty_like(noisy)
-            flags = (1 if with_backward else 0) | (2 if reuse and cache[1] is not None else 0)          # WUNET_FWD_SAVE | WUNET_FWD_PACKS_VALID
+            flags = (_C["WUNET_FWD_SAVE"] if with_backward else 0) | (_C["WUNET_FWD_PACKS_VALID"] if reuse and cache[1] is not None else 0)
             self._check(self.lib.wunet_forward(h, noisy.data_ptr(), self._ptrs(params), self._ptrs(running),
                                                self._ptrs(nbt), 1 if training else 0, flags, ws.data_ptr(),
                                                out.data_ptr(), self._stream(noisy.device)))

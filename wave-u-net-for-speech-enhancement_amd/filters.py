@@ -8,7 +8,9 @@ There is no host implementation: CPU tensors need an injected engine (the tests'
 import numpy as np
 import torch
 
-MAX_SECTIONS = 8                     # WUNET_SOS_MAX_SECTIONS of include/wunet_hip.h
+from . import _lib
+
+MAX_SECTIONS = _lib.CONSTANTS["WUNET_SOS_MAX_SECTIONS"]
 MAX_ROWS = 65535                     # rows of one call
 
 

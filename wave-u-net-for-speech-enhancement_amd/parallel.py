@@ -13,6 +13,10 @@ import ctypes
 import torch
 import torch.distributed as dist
 
+from . import _lib
+
+COMM_ID_BYTES = _lib.CONSTANTS["WUNET_COMM_ID_BYTES"]         # the RCCL id rank 0 draws
+
 
 class NativeComm:
     """The RCCL communicator behind the C ABI (include/wunet_hip.h: wunet_comm_*): one per process and GPU.  torch.distributed is
@@ -30,7 +34,7 @@ class NativeComm:
         elif rank is None:
             raise ValueError("NativeComm: pass `rank` together with `world`")
         self.world, self.rank = world, rank
-        buf = (ctypes.c_ubyte * 128)()
+        buf = (ctypes.c_ubyte * COMM_ID_BYTES)()
         if comm_id is None:
             box = [None]
             if rank == 0:
@@ -43,7 +47,7 @@ class NativeComm:
                 src = dist.get_global_rank(group, 0) if group is not None else 0
                 dist.broadcast_object_list(box, src=src, group=group)
             comm_id = box[0]
-        buf = (ctypes.c_ubyte * 128)(*comm_id)
+        buf = (ctypes.c_ubyte * COMM_ID_BYTES)(*comm_id)
         self.handle = ctypes.c_void_p()
         self.engine._check(lib.wunet_comm_create(buf, world, rank, ctypes.byref(self.handle)))
 

@@ -13,8 +13,10 @@ import math
 import numpy as np
 import torch
 
-MAX_RATIO = 640                  # WUNET_RESAMPLE_MAX_RATIO of include/wunet_hip.h
-MAX_TAPS = 2 * 10 * MAX_RATIO + 1
+from . import _lib
+
+MAX_RATIO = _lib.CONSTANTS["WUNET_RESAMPLE_MAX_RATIO"]
+MAX_TAPS = _lib.CONSTANTS["WUNET_RESAMPLE_MAX_TAPS"]
 
 
 def _rate(name, v):

@@ -55,6 +55,7 @@ from pathlib import Path
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from .optim import FusedAdam
 from .parallel import GradSync
 
@@ -67,6 +68,7 @@ GRAPH_WARMUP_STEPS = 3
 MAX_RECAPTURES = 3
 MIN_REPLAYS = 16
 REPLAY_CREDIT_S = 0.25e-3
+SDR_MAX_FILTER = _lib.CONSTANTS["WUNET_BSS_MAX_FILTER"]         # the longest forgiven filter of wunet_bss_sdr_forward
 
 
 class Trainer:
@@ -152,8 +154,8 @@ class Trainer:
         if self.validation_sdr_mode == "score" and self.validation_stoi_mode == "score":
             raise ValueError('trainer config "validation.stoi": "score" and "validation.sdr": "score" together: an epoch has one score')
         n_taps = vcfg.get("sdr_filter_length", 512)
-        if isinstance(n_taps, bool) or not isinstance(n_taps, int) or not 1 <= n_taps <= 512:
-            raise ValueError(f'trainer config "validation.sdr_filter_length" must be an integer in [1, 512] (got {n_taps!r})')
+        if isinstance(n_taps, bool) or not isinstance(n_taps, int) or not 1 <= n_taps <= SDR_MAX_FILTER:
+            raise ValueError(f'trainer config "validation.sdr_filter_length" must be an integer in [1, {SDR_MAX_FILTER}] (got {n_taps!r})')
         if "sdr_filter_length" in vcfg and self.validation_sdr_mode is None:
             raise ValueError('trainer config "validation.sdr_filter_length" needs "validation.sdr": "report" or "score" beside it')
         self.validation_sdr_filter_length = n_taps

@@ -35,6 +35,8 @@ import numpy as np
 import torch
 from torch.utils import data
 
+from . import _lib
+
 
 # ---------------------------------------------------------------------------------------------- WAV decoding
 def read_wav(path):
@@ -294,8 +296,8 @@ def pack_mono_shard(list_file, prefix, limit=None, offset=0, sample_rate=None, e
     return len(names)
 
 
-SOS_MAX_LEAD = 8192                 # WUNET_SOS_MAX_LEAD of include/wunet_hip.h
-RIR_MAX_TAPS = 16384          # include/wunet_hip.h: WUNET_REVERB_MAX_TAPS
+SOS_MAX_LEAD = _lib.CONSTANTS["WUNET_SOS_MAX_LEAD"]
+RIR_MAX_TAPS = _lib.CONSTANTS["WUNET_REVERB_MAX_TAPS"]
 
 
 def pack_rir_shard(list_file, prefix, max_taps=8192, limit=None, offset=0, sample_rate=None, engine=None):
